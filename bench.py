@@ -13,6 +13,12 @@ slice of configs[3] and N=8 is configs[3] itself.  `--arch base` gives configs[1
 --batch 16` configs[2].  `python bench.py --gpus N` with N > 1 outside torchrun spawns the N ranks itself.
 Weights are seeded synthetic tensors of the reference architecture (there is no checkpoint / dataset).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline line (images/s, ms_per_step).  `--full` adds
+what costs runs or minutes of its own after the timed steps: the parity canary against the committed oracle golden,
+one instrumented step for the per-kernel table and the roofline figures, and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (dump_outputs below) for output-for-output
+comparisons of two builds; inputs and weights are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -285,6 +291,44 @@ def parity_canary(model, imgs, metas, arch, kind, lora=False, res=None):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, batch):
+    """Writes the per-image results of one step (the pred_instances a caller of test_step receives) as
+    out_dir/image<i>_<field>.npy: floating fields in float32, integer and index fields in float64 (exact).  Instance masks
+    [K, H, W] are too large to store whole; they are written as `<field>_area` (pixels set per instance, float64) and
+    `<field>_sample` (float32 [K, P]: the mask values at P pixel positions drawn once per image from a generator seeded
+    with 0, the same positions for every instance and in every run).  At most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    n_pix = max(256, min(4096, (DUMP_LIMIT_BYTES // 2) // (4 * 100 * max(batch, 1))))   # <= 100 instances per image
+    arrays = {}
+    for i, pi in enumerate(res):
+        for k in pi.keys():
+            v = pi.get(k)
+            if not isinstance(v, torch.Tensor):
+                raise TypeError(f'bench.py --dump-outputs: pred_instances.{k} of image {i} is {type(v).__name__}, not a tensor')
+            if v.dim() == 3:
+                hw = v.shape[1] * v.shape[2]
+                g = torch.Generator(device='cpu')
+                g.manual_seed(0)
+                pos = torch.randperm(hw, generator=g)[:n_pix].to(v.device)
+                flat = v.reshape(v.shape[0], hw)
+                arrays[f'image{i}_{k}_area'] = flat.sum(1, dtype=torch.float64).cpu().numpy()
+                arrays[f'image{i}_{k}_sample'] = flat[:, pos].to(torch.float32).cpu().numpy()
+            elif v.is_floating_point():
+                arrays[f'image{i}_{k}'] = v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+            else:
+                arrays[f'image{i}_{k}'] = v.detach().to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f'bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def _pmc_traffic(arch):
     """HBM bytes per launch of the dominant GEMM from the committed rocprofv3 PMC passes (profiles/r1_pmc/,
     FETCH_SIZE x2 + WRITE_SIZE as MI355X_MICROARCH.md prescribes); the counters cannot be collected inside this
@@ -320,6 +364,84 @@ def _config_tag(args, B, world):
     return ''
 
 
+def full_measurements(args, model, imgs, metas, step, sync, rank, world, num_classes):
+    """--full: everything beyond the headline, after the timed steps -- one more plain step (a profiled --full run keeps
+    the pass count of the committed rocprofv3 statistics, tests/test_bench_contract_cpu.py), the parity canary, one
+    instrumented step (per-kernel HIP events: the kernel table and the roofline figures) and the CPU baseline.  Every rank
+    runs the steps (they contain the result exchange); rank 0 returns the extra keys of the result line, the others None."""
+    step()
+    sync()
+    canary = parity_canary(model, imgs, metas, args.arch, args.model, args.lora) if rank == 0 else None
+
+    # ---- roofline leg: one extra instrumented step, per-kernel HIP events on the launch stream.  Every rank runs
+    # the step (it contains the result gather); only rank 0 records and reports ----
+    from rsprompter_amd import ops
+    prof = ops.Profiler() if rank == 0 else None
+    if prof is not None:
+        prof.shapes = args.shapes
+        ops.set_profiler(prof)
+    step()
+    sync()
+    ops.set_profiler(None)
+    if rank != 0:
+        return None
+    agg = prof.summary()
+    kernels = {k: dict(ms=round(v['ms'], 3), calls=v['calls'],
+                       tflops=round(v['flops'] / v['ms'] / 1e9, 1) if v['ms'] > 0 and v['flops'] else None,
+                       gbps=round(v['bytes'] / v['ms'] / 1e6, 1) if v['ms'] > 0 and v['bytes'] else None)
+               for k, v in sorted(agg.items(), key=lambda kv: -kv[1]['ms'])}
+    # the dominant kernel is the plane-path GEMM: one kernel template whose tile instantiations (128x128,
+    # 256x128, 256x256, ConvTranspose epilogues) the profiler labels separately; the roofline line covers all
+    # of its launches in the step (the per-instantiation rates are in `kernels` and in the rocprofv3 stats)
+    fam = {}
+    for k, v in agg.items():
+        if v['flops'] > 0:
+            f = k.split('<')[0].split(' ')[0]
+            d0 = fam.setdefault(f, dict(ms=0.0, flops=0.0, calls=0))
+            d0['ms'] += v['ms']; d0['flops'] += v['flops']; d0['calls'] += v['calls']
+    dom_name, dom = max(fam.items(), key=lambda kv: kv[1]['ms'])
+    achieved = dom['flops'] / dom['ms'] / 1e9
+    attn = [v for k, v in agg.items() if k.startswith('attn_stream_kernel<vit') or k.startswith('attn_kernel<vit') or
+            k.startswith('attn_global_kernel') or k.startswith('attn_win_kernel<vit')]
+    # the windowed layers' FLOPs are counted for the padded 5 x 5 x 196 tokens of SURVEY section 8(d); the kernel
+    # evaluates only the 64 x 64 real tokens as queries (all 196 keys each): 4096 / 4900 of that figure
+    win_fl = sum(v['flops'] for k, v in agg.items() if k.startswith('attn_win_kernel<vit'))
+    attn_fl_eval = sum(v['flops'] for v in attn) - win_fl * (1.0 - 4096.0 / 4900.0)
+    attn_ms = sum(v['ms'] for v in attn)
+    attn_tf = sum(v['flops'] for v in attn) / attn_ms / 1e9 if attn_ms else None
+    relpos_ms = sum(v['ms'] for k, v in agg.items() if k.startswith('vit_relpos'))
+    attn_tf_rel = sum(v['flops'] for v in attn) / (attn_ms + relpos_ms) / 1e9 if attn_ms else None
+    out = {
+        'roofline': {'bound': 'mfma', 'kernel': dom_name, 'launches_per_step': dom['calls'],
+                     'ms_per_step': round(dom['ms'], 3), 'achieved': round(achieved, 2),
+                     'peak': PEAK_F16_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_F16_MFMA_TFLOPS, 4),
+                     'traffic': (_pmc_traffic(args.arch) or {}).get('bytes_per_launch'), 'traffic_detail': _pmc_traffic(args.arch),
+                     'traffic_measured_in_this_run': False,
+                     'note': 'achieved = algorithmic fp32 FLOPs (2MNK) of all launches of the kernel in one step / '
+                             'their summed HIP-event durations; the kernel issues 3 fp16 MFMA passes per algorithmic '
+                             'FLOP (fp16x3), so its ceiling is peak/3 = 833 TFLOP/s'
+                             + (' (gemm_f16f8: 2 fp16 + 1 fp8 K=64 MFMA per 32 k = 2 units of matrix time, ceiling peak/2)' if args.f8corr else ''),
+                     'frac_of_fp16x3_ceiling': round(achieved / (PEAK_F16_MFMA_TFLOPS / 3), 4)},
+        'roofline_attention': {'bound': 'mfma', 'kernel': 'attn_win_kernel (windowed layers, rel-pos inside) + attn_stream_kernel (global layers)',
+                               'achieved': None if attn_tf is None else round(attn_tf, 2),
+                               'achieved_evaluated_queries': None if not attn_ms else round(attn_fl_eval / attn_ms / 1e9, 2),
+                               'achieved_incl_relpos_kernels': None if attn_tf_rel is None else round(attn_tf_rel, 2),
+                               'ms_per_step': round(attn_ms, 3), 'relpos_ms_per_step': round(relpos_ms, 3),
+                               'peak': PEAK_F16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                               'frac': None if attn_tf is None else round(attn_tf / PEAK_F16_MFMA_TFLOPS, 4),
+                               'attention_gemm_gflop_per_image': ATTN_GEMM_GFLOP_PER_IMAGE[args.arch]},
+        'parity_canary': canary,
+        'kernels': kernels,
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        try:
+            out['cpu_baseline'] = cpu_baseline(args.arch, num_classes, kind=args.model, lora=args.lora)
+        except Exception as e:  # the baseline is context, never a reason to lose the measurement
+            out['cpu_baseline'] = {'value': None, 'unit': 'images/s', 'cores': torch.get_num_threads(),
+                                   'kind': 'port', 'sample': f'failed: {e!r}'}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -332,8 +454,13 @@ def main():
     ap.add_argument('--lora', action='store_true',
                     help='--model query only: LoRA(qkv, r16, alpha32) adapters on the encoder and WHU-shape metas '
                          '(BASELINE.json configs[4]: --model query --arch huge --batch 4 --lora)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--shapes', action='store_true', help='break the kernel table down by GEMM/attention shape')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the parity canary, the instrumented step (per-kernel table, '
+                         'roofline) and the CPU baseline; a plain run reports the headline figures only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the results of the last timed step as DIR/<name>.npy (float32 / float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--shapes', action='store_true', help='--full: break the kernel table down by GEMM/attention shape')
     ap.add_argument('--host-inputs', action='store_true',
                     help='NOT the headline: the tiles start in pinned host memory every step (PCIe-inclusive rate for DESIGN.md)')
     ap.add_argument('--f8corr', nargs='?', const='all', default=None, choices=['all', 'mlp'],
@@ -344,6 +471,8 @@ def main():
                          "BASELINE.json north_star's \"RCCL all-gather of instance results\"; 'gather': rank 0 only (mmengine "
                          "collect_results, what tools/dist_test.sh evaluates)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if not torch.cuda.is_available():
         raise RuntimeError('bench.py needs an MI355X (no CPU fallback)')
@@ -415,54 +544,19 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        res = step()
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t.item())
-    n_dets = sum(len(r.bboxes) for r in step())
-    sync()
-    canary = parity_canary(model, imgs, metas, args.arch, args.model, args.lora) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs, B)
+    n_dets = sum(len(r.bboxes) for r in res)
 
     result = None
-    # ---- roofline leg: one extra instrumented step, per-kernel HIP events on the launch stream.  Every rank runs
-    # the step (it contains the result gather); only rank 0 records and reports ----
-    prof = ops.Profiler() if rank == 0 else None
-    if prof is not None:
-        prof.shapes = args.shapes
-        ops.set_profiler(prof)
-    step()
-    sync()
-    ops.set_profiler(None)
     if rank == 0:
-        agg = prof.summary()
-        kernels = {k: dict(ms=round(v['ms'], 3), calls=v['calls'],
-                           tflops=round(v['flops'] / v['ms'] / 1e9, 1) if v['ms'] > 0 and v['flops'] else None,
-                           gbps=round(v['bytes'] / v['ms'] / 1e6, 1) if v['ms'] > 0 and v['bytes'] else None)
-                   for k, v in sorted(agg.items(), key=lambda kv: -kv[1]['ms'])}
-        # the dominant kernel is the plane-path GEMM: one kernel template whose tile instantiations (128x128,
-        # 256x128, 256x256, ConvTranspose epilogues) the profiler labels separately; the roofline line covers all
-        # of its launches in the step (the per-instantiation rates are in `kernels` and in the rocprofv3 stats)
-        fam = {}
-        for k, v in agg.items():
-            if v['flops'] > 0:
-                f = k.split('<')[0].split(' ')[0]
-                d0 = fam.setdefault(f, dict(ms=0.0, flops=0.0, calls=0))
-                d0['ms'] += v['ms']; d0['flops'] += v['flops']; d0['calls'] += v['calls']
-        dom_name, dom = max(fam.items(), key=lambda kv: kv[1]['ms'])
-        achieved = dom['flops'] / dom['ms'] / 1e9
-        attn = [v for k, v in agg.items() if k.startswith('attn_stream_kernel<vit') or k.startswith('attn_kernel<vit') or
-                k.startswith('attn_global_kernel') or k.startswith('attn_win_kernel<vit')]
-        # the windowed layers' FLOPs are counted for the padded 5 x 5 x 196 tokens of SURVEY section 8(d); the kernel
-        # evaluates only the 64 x 64 real tokens as queries (all 196 keys each): 4096 / 4900 of that figure
-        win_fl = sum(v['flops'] for k, v in agg.items() if k.startswith('attn_win_kernel<vit'))
-        attn_fl_eval = sum(v['flops'] for v in attn) - win_fl * (1.0 - 4096.0 / 4900.0)
-        attn_ms = sum(v['ms'] for v in attn)
-        attn_tf = sum(v['flops'] for v in attn) / attn_ms / 1e9 if attn_ms else None
-        relpos_ms = sum(v['ms'] for k, v in agg.items() if k.startswith('vit_relpos'))
-        attn_tf_rel = sum(v['flops'] for v in attn) / (attn_ms + relpos_ms) / 1e9 if attn_ms else None
         value = world * B * args.steps / elapsed
         result = {
             'metric': 'images/sec (1024x1024 synthetic tiles, rsprompter_%s SAM-ViT-%s%s, full predict path)' % (
@@ -478,36 +572,15 @@ def main():
                        'images_per_gpu_per_step': B, 'detections_per_step_rank0': n_dets,
                        'parallelism': (f'dp{world} (images sharded by batch, result ' + ('gather to rank 0' if args.exchange == 'gather' else 'all-gather') + ' over RCCL)') if world > 1 else 'single GPU',
                        },
-            'roofline': {'bound': 'mfma', 'kernel': dom_name, 'launches_per_step': dom['calls'],
-                         'ms_per_step': round(dom['ms'], 3), 'achieved': round(achieved, 2),
-                         'peak': PEAK_F16_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_F16_MFMA_TFLOPS, 4),
-                         'traffic': (_pmc_traffic(args.arch) or {}).get('bytes_per_launch'), 'traffic_detail': _pmc_traffic(args.arch),
-                         'traffic_measured_in_this_run': False,
-                         'note': 'achieved = algorithmic fp32 FLOPs (2MNK) of all launches of the kernel in one step / '
-                                 'their summed HIP-event durations; the kernel issues 3 fp16 MFMA passes per algorithmic '
-                                 'FLOP (fp16x3), so its ceiling is peak/3 = 833 TFLOP/s'
-                                 + (' (gemm_f16f8: 2 fp16 + 1 fp8 K=64 MFMA per 32 k = 2 units of matrix time, ceiling peak/2)' if args.f8corr else ''),
-                         'frac_of_fp16x3_ceiling': round(achieved / (PEAK_F16_MFMA_TFLOPS / 3), 4)},
-            'roofline_attention': {'bound': 'mfma', 'kernel': 'attn_win_kernel (windowed layers, rel-pos inside) + attn_stream_kernel (global layers)',
-                                   'achieved': None if attn_tf is None else round(attn_tf, 2),
-                                   'achieved_evaluated_queries': None if not attn_ms else round(attn_fl_eval / attn_ms / 1e9, 2),
-                                   'achieved_incl_relpos_kernels': None if attn_tf_rel is None else round(attn_tf_rel, 2),
-                                   'ms_per_step': round(attn_ms, 3), 'relpos_ms_per_step': round(relpos_ms, 3),
-                                   'peak': PEAK_F16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                                   'frac': None if attn_tf is None else round(attn_tf / PEAK_F16_MFMA_TFLOPS, 4),
-                                   'attention_gemm_gflop_per_image': ATTN_GEMM_GFLOP_PER_IMAGE[args.arch]},
             'exchange': None if world == 1 else ('all-gather of instance results (records + COCO RLE strings) to every rank' if args.exchange == 'allgather'
                                                  else 'gather of instance results to rank 0'),
             'rccl_ranks': world if world > 1 else 0,
-            'parity_canary': canary,
-            'kernels': kernels,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                result['cpu_baseline'] = cpu_baseline(args.arch, num_classes, kind=args.model, lora=args.lora)
-            except Exception as e:  # the baseline is context, never a reason to lose the measurement
-                result['cpu_baseline'] = {'value': None, 'unit': 'images/s', 'cores': torch.get_num_threads(),
-                                          'kind': 'port', 'sample': f'failed: {e!r}'}
+    if args.full:
+        full = full_measurements(args, model, imgs, metas, step, sync, rank, world, num_classes)
+        if rank == 0:
+            result.update(full)
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         tdist.barrier()

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
+from _ref_configs import reference_config  # noqa: E402
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def test_cv2_linear_restatement_matches_torch_interpolate():
@@ -36,7 +37,6 @@ def test_rescale_size_and_metainfo_follow_mmcv():
     assert rescale_size((640, 427), (1024, 1024))[0] == (1024, 683)            # 427 * 1.6 = 683.2 -> int(683.7)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 def test_test_pipeline_from_reference_config_on_reference_image(monkeypatch):
     """the pipeline cfg of configs/rsprompter/rsprompter_anchor-nwpu.py applied to the reference's tests/data/color.jpg
     (512 x 288 -> resized to 1024 x 576 -> padded to 1024 x 1024 with the BGR mean)."""
@@ -45,11 +45,11 @@ def test_test_pipeline_from_reference_config_on_reference_image(monkeypatch):
     import rsprompter_amd.apis as apis
     from oracle import pipeline as op
     monkeypatch.setattr(apis, 'ops', mock)
-    cfg = ra.Config.fromfile(os.path.join(REF, 'configs/rsprompter/rsprompter_anchor-nwpu.py'))
+    cfg = reference_config('rsprompter_anchor-nwpu.py')
     pipe = apis.TestPipeline(apis.get_test_pipeline_cfg(cfg), device='cpu')
     assert pipe.scale == (1024, 1024) and pipe.keep_ratio and pipe.pad_size == (1024, 1024)
     assert np.allclose(pipe.pad_val, (0.406 * 255, 0.456 * 255, 0.485 * 255))
-    path = os.path.join(REF, 'tests/data/color.jpg')
+    path = os.path.join(GOLDEN, 'color.jpg')                  # the reference's tests/data/color.jpg
     out = pipe(dict(img_path=path, img_id=7))
     meta = out['data_samples'].metainfo
     assert tuple(out['inputs'].shape) == (3, 1024, 1024)
@@ -132,7 +132,6 @@ def test_checkpoint_formats_round_trip(tmp_path):
         ck.load_checkpoint_into(f3, str(tmp_path / 'extra.pth'), strict=True)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 def test_init_detector_and_inference_detector_host_logic(monkeypatch, tmp_path):
     """init_detector(config file) + a trained-checkpoint load + inference_detector on an ndarray and on a file path,
     with every native op replaced by the torch stand-ins (tiny 'image': the pipeline still pads it to 1024 x 1024)."""
@@ -147,7 +146,10 @@ def test_init_detector_and_inference_detector_host_logic(monkeypatch, tmp_path):
     from rsprompter_amd.synth import synth_state_dict
     for m in (ah, necks, sd, se, det, apis):
         monkeypatch.setattr(m, 'ops', mock)
-    cfg_path = os.path.join(REF, 'configs/rsprompter/rsprompter_anchor-nwpu.py')
+    # configs/rsprompter/rsprompter_anchor-nwpu.py as the loader read it, written back as a config file
+    cfg_path = str(tmp_path / 'rsprompter_anchor-nwpu.py')
+    with open(cfg_path, 'w') as f:
+        f.write(''.join(f'{k} = {v!r}\n' for k, v in reference_config('rsprompter_anchor-nwpu.py').items()))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         donor = apis.init_detector(cfg_path, device='cpu')

@@ -66,3 +66,42 @@ def test_rocprof_summaries_agree_with_the_bench_lines():
         assert abs(passes - round(passes)) < 1e-6 and 5 <= round(passes) <= 8, (name, passes)
         per_step_ms = tot_ns / 1e6 / passes
         assert abs(per_step_ms - r['roofline']['ms_per_step']) < 0.06 * r['roofline']['ms_per_step'], (name, per_step_ms)
+
+
+def test_bench_options_full_and_dump_outputs():
+    """a plain bench run reports the headline only; the canary, kernel table, roofline and CPU baseline sit behind --full"""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True,
+                         check=True).stdout
+    assert '--full' in out and '--dump-outputs' in out
+
+
+def test_dump_outputs_writes_the_step_results_as_float_arrays(tmp_path):
+    """bench.py --dump-outputs: every field of every image's pred_instances as float32 / float64 .npy, instance masks as
+    per-instance areas plus a seeded pixel sample that is the same in every run, at most 64 MB in all"""
+    import numpy as np
+    import torch
+    import bench
+    from rsprompter_amd.structures import InstanceData
+    g = torch.Generator().manual_seed(0)
+    res = [InstanceData(bboxes=torch.rand(k, 4, generator=g) * 1024, scores=torch.rand(k, generator=g),
+                        labels=torch.randint(0, 10, (k,), generator=g), query_indices=torch.arange(k, dtype=torch.int32),
+                        masks=torch.rand(k, 96, 128, generator=g) > 0.5) for k in (3, 0)]
+    names = bench.dump_outputs(res, str(tmp_path / 'a'), len(res))
+    assert bench.dump_outputs(res, str(tmp_path / 'b'), len(res)) == names
+    fields = ('bboxes', 'scores', 'labels', 'query_indices', 'masks_area', 'masks_sample')
+    assert names == sorted(f'image{i}_{f}' for i in range(2) for f in fields)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / f'{n}.npy'), np.load(tmp_path / 'b' / f'{n}.npy')
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    r = res[0]
+    assert np.array_equal(np.load(tmp_path / 'a' / 'image0_labels.npy'), r.labels.double().numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'image0_bboxes.npy'), r.bboxes.numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'image0_masks_area.npy'), r.masks.flatten(1).sum(1).double().numpy())
+    sample = np.load(tmp_path / 'a' / 'image0_masks_sample.npy')
+    assert sample.shape == (3, 4096) and set(np.unique(sample)) <= {0.0, 1.0}
+    assert np.load(tmp_path / 'a' / 'image1_masks_sample.npy').shape == (0, 4096)

@@ -1,11 +1,13 @@
-"""CPU: the reference's own config files build, unchanged, through our registry/config loader
-(only where /root/reference is present, i.e. in the build container)."""
+"""CPU: the reference's own config files build, unchanged, through our registry/config loader (the files as the loader
+read them in the container that has the reference checkout: tests/golden/reference_configs.pt, tests/_ref_configs.py)."""
 import os
+import sys
 import warnings
 
 import pytest
 
-REF = '/root/reference/configs/rsprompter'
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _ref_configs import reference_config  # noqa: E402
 
 
 def _norm(x):
@@ -16,14 +18,13 @@ def _norm(x):
     return x
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 @pytest.mark.parametrize('fname,arch,nc,ps', [('rsprompter_anchor-nwpu.py', 'base', 10, (70, 5)),
                                               ('rsprompter_anchor-ssdd.py', 'base', 1, (30, 5)),
                                               ('rsprompter_anchor-whu.py', 'base', 1, (100, 5))])
 def test_reference_anchor_configs_build(fname, arch, nc, ps):
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import rsprompter_anchor
-    cfg = ra.Config.fromfile(os.path.join(REF, fname))
+    cfg = reference_config(fname)
     ours = rsprompter_anchor(arch, nc, ps)
     assert _norm(cfg.model) == _norm(ours)
     with warnings.catch_warnings():
@@ -43,11 +44,10 @@ def test_reference_anchor_configs_build(fname, arch, nc, ps):
         assert k in keys, k
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 def test_reference_peft512_config_builds_with_peft_key_layout():
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import rsprompter_anchor_peft512
-    cfg = ra.Config.fromfile(os.path.join(REF, 'rsprompter_anchor-nwpu-peft-512.py'))
+    cfg = reference_config('rsprompter_anchor-nwpu-peft-512.py')
     assert _norm(cfg.model) == _norm(rsprompter_anchor_peft512('base', 10, (70, 5)))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -67,14 +67,13 @@ def test_reference_peft512_config_builds_with_peft_key_layout():
     assert tuple(m.backbone.vision_encoder.pos_embed.shape) == (1, 32, 32, 768)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 @pytest.mark.parametrize('fname,nc,ps,mpi', [('rsprompter_query-whu.py', 1, (100, 5), 100),
                                              ('rsprompter_query-nwpu.py', 10, (70, 5), 70),
                                              ('rsprompter_query-ssdd.py', 1, (30, 5), 30)])
 def test_reference_query_configs_build(fname, nc, ps, mpi):
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import rsprompter_query
-    cfg = ra.Config.fromfile(os.path.join(REF, fname))
+    cfg = reference_config(fname)
     assert _norm(cfg.model) == _norm(rsprompter_query('base', nc, ps, max_per_image=mpi))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -91,23 +90,36 @@ def test_reference_query_configs_build(fname, nc, ps, mpi):
         assert k in keys, k
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
-def test_config_loader_base_and_delete():
+def test_config_loader_base_and_delete(tmp_path):
     import rsprompter_amd as ra
-    cfg = ra.Config.fromfile(os.path.join(REF, 'rsprompter_anchor-nwpu-peft-512.py'))
+    cfg = reference_config('rsprompter_anchor-nwpu-peft-512.py')
     assert cfg.model.backbone.type == 'MMPretrainSamVisionEncoder'      # `_delete_=True` replaced the base dict
     assert 'extra_config' not in cfg.model.backbone
     assert cfg.model.neck.feature_aggregator.type == 'PseudoFeatureAggregator'
     assert cfg.model.rpn_head.anchor_generator.strides == [4, 8, 16, 32, 64]   # inherited from _base_
+    # the loader itself on files of the same shape: a `_base_` file and a child that replaces one dict with `_delete_`
+    (tmp_path / '_base_').mkdir()
+    (tmp_path / '_base_' / 'model.py').write_text(
+        "model = dict(backbone=dict(type='MMPretrainSamVisionEncoder', extra_config=dict(depth=12)),\n"
+        "             neck=dict(feature_aggregator=dict(type='RSFeatureAggregator', in_channels=768)),\n"
+        "             rpn_head=dict(anchor_generator=dict(strides=[4, 8, 16, 32, 64])))\n")
+    (tmp_path / 'child.py').write_text(
+        "_base_ = ['_base_/model.py']\n"
+        "model = dict(backbone=dict(_delete_=True, type='MMPretrainSamVisionEncoder', hf_pretrain_name='x'),\n"
+        "             neck=dict(feature_aggregator=dict(type='PseudoFeatureAggregator')))\n")
+    cfg = ra.Config.fromfile(str(tmp_path / 'child.py'))
+    assert cfg.model.backbone == {'type': 'MMPretrainSamVisionEncoder', 'hf_pretrain_name': 'x'}
+    assert 'extra_config' not in cfg.model.backbone
+    assert cfg.model.neck.feature_aggregator == {'type': 'PseudoFeatureAggregator', 'in_channels': 768}
+    assert cfg.model.rpn_head.anchor_generator.strides == [4, 8, 16, 32, 64]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 @pytest.mark.parametrize('fname,nc', [('samseg-maskrcnn-nwpu.py', 10), ('samseg-maskrcnn-ssdd.py', 1), ('samseg-maskrcnn-whu.py', 1)])
 def test_reference_samseg_maskrcnn_configs_build(fname, nc):
     """the SAMSegMaskRCNN sibling model builds from the reference's config files unchanged."""
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import samseg_maskrcnn
-    cfg = ra.Config.fromfile(os.path.join(REF, fname))
+    cfg = reference_config(fname)
     assert _norm(cfg.model) == _norm(samseg_maskrcnn('base', nc))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -121,14 +133,13 @@ def test_reference_samseg_maskrcnn_configs_build(fname, nc):
     assert not any('mask_decoder' in k or 'shared_image_embedding' in k for k in keys)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 @pytest.mark.parametrize('fname,nc,nq', [('samseg-mask2former-nwpu.py', 10, 70), ('samseg-mask2former-ssdd.py', 1, None),
                                          ('samseg-mask2former-whu.py', 1, None)])
 def test_reference_samseg_mask2former_configs_build(fname, nc, nq):
     """the SAMSegMask2Former sibling model builds from the reference's config files unchanged."""
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import samseg_mask2former
-    cfg = ra.Config.fromfile(os.path.join(REF, fname))
+    cfg = reference_config(fname)
     nq = cfg.model.panoptic_head.num_queries
     assert _norm(cfg.model) == _norm(samseg_mask2former('base', nc, nq))
     with warnings.catch_warnings():
@@ -138,13 +149,12 @@ def test_reference_samseg_mask2former_configs_build(fname, nc, nq):
     assert m.panoptic_head.num_transformer_decoder_layers == 9 and m.panoptic_head.pixel_decoder.feat == 256
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not available')
 @pytest.mark.parametrize('fname,nc', [('samdet-nwpu.py', 10), ('samdet-ssdd.py', 1), ('samdet-whu.py', 1)])
 def test_reference_samdet_configs_build(fname, nc):
     """SAMDet (Faster R-CNN R50-FPN + HF SamModel) builds from the reference's config files unchanged."""
     import rsprompter_amd as ra
     from rsprompter_amd.default_configs import samdet
-    cfg = ra.Config.fromfile(os.path.join(REF, fname))
+    cfg = reference_config(fname)
     assert _norm(cfg.model) == _norm(samdet('base', nc))
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')

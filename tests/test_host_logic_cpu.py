@@ -334,24 +334,19 @@ def test_samseg_maskrcnn_end_to_end_host_logic(mocked):
     """SAMSegMaskRCNN.test_step (encoder + RSFPN + RPN(3 anchors) + StandardRoIHead + FCNMaskHead + mask
     paste) through the op stand-ins against oracle/samseg.py; the model is built from the reference's own config file
     when it is present."""
-    import os
     import warnings
     import rsprompter_amd as ra
     from _match import match_detections
     from oracle import glue
     from oracle.samseg import SAMSegMaskRCNNOracle
-    from rsprompter_amd.default_configs import samseg_maskrcnn
     from rsprompter_amd.structures import DetDataSample
     from rsprompter_amd.synth import synth_images, synth_metas, synth_state_dict
-    ref_cfg = '/root/reference/configs/rsprompter/samseg-maskrcnn-nwpu.py'
+    from _ref_configs import reference_config
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        if os.path.exists(ref_cfg):
-            cfg = ra.Config.fromfile(ref_cfg)
-            assert cfg.model.type == 'SAMSegMaskRCNN' and cfg.model.roi_head.mask_head.type == 'FCNMaskHead'
-            model = ra.build_model(cfg)
-        else:
-            model = ra.build_model(samseg_maskrcnn('base', 10))
+        cfg = reference_config('samseg-maskrcnn-nwpu.py')
+        assert cfg.model.type == 'SAMSegMaskRCNN' and cfg.model.roi_head.mask_head.type == 'FCNMaskHead'
+        model = ra.build_model(cfg)
     oracle = SAMSegMaskRCNNOracle('base', 10)
     sd = synth_state_dict(oracle, 0)
     oracle.load_state_dict(sd)
@@ -373,24 +368,19 @@ def test_samseg_maskrcnn_end_to_end_host_logic(mocked):
 def test_samseg_mask2former_end_to_end_host_logic(mocked):
     """SAMSegMask2Former.test_step (encoder + RSFPN + the standard Mask2FormerHead at feat 256 / 9 layers +
     MaskFormerFusionHead) through the op stand-ins against oracle/samseg.py (pinned on the real Mask2FormerHead); the
-    model is built from the reference's own config file when it is present."""
-    import os
+    model is built from the reference's own config file (tests/golden/reference_configs.pt)."""
     import warnings
     import rsprompter_amd as ra
     from oracle import glue
     from oracle.samseg import SAMSegMask2FormerOracle
-    from rsprompter_amd.default_configs import samseg_mask2former
     from rsprompter_amd.structures import DetDataSample
     from rsprompter_amd.synth import synth_images, synth_metas, synth_state_dict
-    ref_cfg = '/root/reference/configs/rsprompter/samseg-mask2former-nwpu.py'
+    from _ref_configs import reference_config
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        if os.path.exists(ref_cfg):
-            cfg = ra.Config.fromfile(ref_cfg)
-            assert cfg.model.type == 'SAMSegMask2Former' and cfg.model.panoptic_head.type == 'Mask2FormerHead'
-            model = ra.build_model(cfg)
-        else:
-            model = ra.build_model(samseg_mask2former('base', 10, 70))
+        cfg = reference_config('samseg-mask2former-nwpu.py')
+        assert cfg.model.type == 'SAMSegMask2Former' and cfg.model.panoptic_head.type == 'Mask2FormerHead'
+        model = ra.build_model(cfg)
     oracle = SAMSegMask2FormerOracle('base', 10, num_queries=70)
     sd = synth_state_dict(oracle, 0)
     oracle.load_state_dict(sd)
@@ -413,25 +403,20 @@ def test_samseg_mask2former_end_to_end_host_logic(mocked):
 def test_samdet_end_to_end_host_logic(mocked):
     """SAMDet.test_step (ResNet-50 + FPN + RPN(3 anchors) + StandardRoIHead(bbox, rescale=True) + the HF
     SamModel prompted with the boxes + mask post-processing) through the op stand-ins against oracle/samdet.py (ResNet /
-    FPN / the predict glue pinned on the real files); built from the reference's own config file when present."""
-    import os
+    FPN / the predict glue pinned on the real files); built from the reference's own config file (tests/golden/reference_configs.pt)."""
     import warnings
     import rsprompter_amd as ra
     from _match import match_detections
     from oracle import glue
     from oracle.samdet import SAMDetOracle
-    from rsprompter_amd.default_configs import samdet
     from rsprompter_amd.structures import DetDataSample
     from rsprompter_amd.synth import synth_images, synth_metas, synth_state_dict
-    ref_cfg = '/root/reference/configs/rsprompter/samdet-nwpu.py'
+    from _ref_configs import reference_config
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        if os.path.exists(ref_cfg):
-            cfg = ra.Config.fromfile(ref_cfg)
-            assert cfg.model.type == 'SAMDet' and cfg.model.detector.backbone.type == 'ResNet'
-            model = ra.build_model(cfg)
-        else:
-            model = ra.build_model(samdet('base', 10))
+        cfg = reference_config('samdet-nwpu.py')
+        assert cfg.model.type == 'SAMDet' and cfg.model.detector.backbone.type == 'ResNet'
+        model = ra.build_model(cfg)
     oracle = SAMDetOracle('base', 10)
     oracle.load_state_dict(synth_state_dict(oracle, 0))
     sd = oracle.state_dict()            # the two tied positional-embedding keys now hold one tensor, as in a checkpoint

@@ -6,8 +6,8 @@
 # Every step writes into gpurun_out/<out-subdir>/ and prints one status line; a failing step does not stop the next.
 #   t:<name>:<pytest args>     python -m pytest -m gpu -q <args>                -> <name>.log      (timeout 1500 s)
 #   n:<name>:<pytest args>     the same under RSP_POISON_EMPTY=1 (tests/conftest.py: torch.empty starts as NaN bytes)
-#   b:<name>:<bench args>      python bench.py <args>                           -> bench_<name>.json / .err
-#   p:<name>:<bench args>      rocprofv3 --kernel-trace --stats -- bench.py ... -> prof_<name>/ + prof_<name>_kernel_stats.csv
+#   b:<name>:<bench args>      python bench.py --full <args>                    -> bench_<name>.json / .err
+#   p:<name>:<bench args>      rocprofv3 --kernel-trace --stats -- bench.py --full ... -> prof_<name>/ + prof_<name>_kernel_stats.csv
 #   x:<name>:<command>         bash -c <command>                                -> <name>.log      (timeout 900 s)
 #   c:<name>:<command>         rocprofv3 --pmc passes of <command> (SQ groups; counters only, one group per pass)
 #   m:<name>:<command>         ... plus the memory-side passes (FETCH_SIZE, WRITE_SIZE, TCC hit / miss)
@@ -24,7 +24,7 @@ for step in "$@"; do
        tail -n 3 "$O/$name.log" | tr '\n' ' ' ;;
     n) eval "RSP_POISON_EMPTY=1 timeout 1500 python -m pytest -m gpu -q $args" > "$O/$name.log" 2>&1; rc=$?
        tail -n 3 "$O/$name.log" | tr '\n' ' ' ;;
-    b) timeout 900 python bench.py $args > "$O/bench_$name.json" 2> "$O/bench_$name.err"; rc=$?
+    b) timeout 900 python bench.py --full $args > "$O/bench_$name.json" 2> "$O/bench_$name.err"; rc=$?
        python - "$O/bench_$name.json" <<'PY'
 import json, sys
 try:
@@ -38,7 +38,7 @@ except Exception as e:
 PY
        ;;
     p) rm -rf "$O/prof_$name"
-       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$O/prof_$name" -o run -- python "$OLDPWD/bench.py" $args --no-cpu-baseline > "$OLDPWD/$O/prof_$name.json" 2> "$OLDPWD/$O/prof_$name.err"); rc=$?
+       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$O/prof_$name" -o run -- python "$OLDPWD/bench.py" --full $args --no-cpu-baseline > "$OLDPWD/$O/prof_$name.json" 2> "$OLDPWD/$O/prof_$name.err"); rc=$?
        f=$(find "$O/prof_$name" -name '*kernel_stats.csv' | head -n 1)
        [ -n "$f" ] && cp "$f" "$O/prof_${name}_kernel_stats.csv" && head -n 6 "$f" | cut -c1-160
        # the trace / database files are large (gpurun copies back at most 64 MiB): keep the summary only

@@ -12,7 +12,7 @@ echo "[probe] rc=$? $(( $(date +%s) - t0 )) s"; cat $O/f16_ovfl_probe.txt
 timeout 400 python -m pytest -m "gpu and quick" -q -x tests > $O/quick.log 2>&1
 echo "[quick tier] rc=$? $(( $(date +%s) - t0 )) s: $(tail -n 1 $O/quick.log)"; grep -E "Error|assert|FAILED" $O/quick.log | head -n 10
 run() {  # name
-  timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --shapes > $O/bench_$1.json 2> $O/bench_$1.err
+  timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --shapes > $O/bench_$1.json 2> $O/bench_$1.err
   python - $O/bench_$1.json $1 <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

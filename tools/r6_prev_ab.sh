@@ -7,7 +7,7 @@ mkdir -p $O
 L=rsprompter_amd/librsp_hip.so
 run() {
   n=$1; shift
-  timeout 400 python bench.py --steps 8 --warmup 2 --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/bench_$n.err
+  timeout 400 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/bench_$n.err
   python - $O/bench_$n.json $n <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
