@@ -1,0 +1,118 @@
+"""CPU (`-m "not gpu"`): the comparisons of the kernel property and decoder-scale tests reject the failures this project has had.
+
+Each test builds a small fp64 reference with the restatements of tests/_kernel_props.py, applies a known failure signature
+to it and asserts that the helper the GPU tests use rejects the result -- at the fault's natural size and at a FAINT size,
+a few times the bound the GPU tests apply (pinned here as FAINT, independently of the helpers' constants), so that a bound
+loosened tenfold makes these tests fail.  The exact reference rounded to fp32 must pass.  The precedent is the emulator's
+`lazy_dma(ignore_waits=True)` self-test."""
+import math
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _kernel_props as kp  # noqa: E402
+
+FAINT = 3 * 2e-5        # the faint signatures' size: 3x the 2e-5 bound of the upscaler (relative) and fold (absolute) checks
+
+
+def _decoder(seed):
+    from rsprompter_amd.sam_decoder import SamMaskDecoderHIP
+    from rsprompter_amd.synth import synth_state_dict
+    dec = SamMaskDecoderHIP()
+    dec.load_state_dict(synth_state_dict(dec, seed))
+    return dec
+
+
+def _scale(ref):
+    return max(1.0, float(ref.abs().max()))
+
+
+def test_upscaler_check_rejects_a_missing_hyper_addend():
+    """round 5: one addend of the 32-channel hyper dot missing for pixels 16-31 of one 32-pixel group in one sub-pixel (the
+    low product of lanes 48-63 lost when two waves shared a SIMD)"""
+    wts = kp.decoder_upscale_weights(_decoder(3), 'cpu')
+    g = torch.Generator().manual_seed(5)
+    R, h, w = 3, 12, 10                                      # 360 pixels: RoIs straddle the 32-pixel groups
+    x = torch.randn(R * h * w, 256, generator=g, dtype=torch.float64) * 1.5
+    hy = torch.randn(R, 32, generator=g, dtype=torch.float64)
+    u = kp.upscale_pre_dot_f64(x.view(R, h, w, 256), *wts)
+    ref = torch.einsum('ryxc,rc->ryx', u, hy)
+    assert torch.allclose(ref, kp.upscale_ref_f64(x, wts, hy, h, w, group=1), rtol=0, atol=1e-12)
+    kp.assert_upscale_close(ref.float(), ref)
+    group, sub, c = 3, 6, 17                                 # pixels 112-127: RoI 0's last rows and RoI 1's first
+    with pytest.raises(AssertionError):
+        kp.assert_upscale_close(kp.drop_hyper_addend(ref, u, hy, h, w, group, sub, c).float(), ref)
+    # faint: the dropped channel's hyper coefficients scaled so that the missing addend is FAINT x the output range
+    bad = kp.drop_hyper_addend(ref, u, hy, h, w, group, sub, c)
+    d = float((bad - ref).abs().max())
+    hy2 = hy.clone()
+    hy2[:, c] *= FAINT * _scale(ref) / d
+    ref2 = torch.einsum('ryxc,rc->ryx', u, hy2)
+    bad2 = kp.drop_hyper_addend(ref2, u, hy2, h, w, group, sub, c)
+    assert 2.0 < float((bad2 - ref2).abs().max()) / (2e-5 * _scale(ref2)) < 5.0
+    with pytest.raises(AssertionError):
+        kp.assert_upscale_close(bad2, ref2)
+
+
+def test_upscaler_check_rejects_a_tile_written_from_the_next_round():
+    """the output of tile t + 256 written into tile t: what a wrong cross-tile prefetch of the persistent upscaler (the next
+    tile's pixel rows requested at chunks 6-7, its first W1 chunk at chunk 7) would produce"""
+    wts = kp.decoder_upscale_weights(_decoder(3), 'cpu')
+    g = torch.Generator().manual_seed(6)
+    R, h, w = 130, 16, 16                                    # 260 tiles of 128 pixels: tiles 0-3 have a next round
+    t = 2
+    x = torch.randn(R * h * w, 256, generator=g, dtype=torch.float64) * 1.5
+    hy = torch.randn(R, 32, generator=g, dtype=torch.float64)
+    ref = kp.upscale_ref_f64(x, wts, hy, h, w)
+    kp.assert_upscale_close(ref.float(), ref)
+    with pytest.raises(AssertionError):
+        kp.assert_upscale_close(kp.tile_written_from(ref, h, w, t, t + 256), ref)
+    # faint: tile t + 256's pixels (and its RoI's hyper vector) equal tile t's up to a small perturbation of the pixels,
+    # sized so that the swap is FAINT x the range
+    a, b = slice(128 * t, 128 * t + 128), slice(128 * (t + 256), 128 * (t + 256) + 128)
+    hy2 = hy.clone()
+    hy2[128 * (t + 256) // (h * w)] = hy[128 * t // (h * w)]
+    noise = torch.randn(128, 256, generator=g, dtype=torch.float64)
+    eps = 1e-3
+    for it in range(4):
+        if it:
+            eps *= FAINT * _scale(ref2) / d
+        x2 = x.clone()
+        x2[b] = x2[a] + eps * noise
+        ref2 = kp.upscale_ref_f64(x2, wts, hy2, h, w)
+        d = float((kp.tile_written_from(ref2, h, w, t, t + 256) - ref2).abs().max())
+    assert 2.0 < d / (2e-5 * _scale(ref2)) < 5.0
+    with pytest.raises(AssertionError):
+        kp.assert_upscale_close(kp.tile_written_from(ref2, h, w, t, t + 256), ref2)
+
+
+def test_fold_check_rejects_a_skipped_key_tile():
+    """one key tile (32 keys) left out of the folded attention's online softmax"""
+    dec = _decoder(21)
+    wts = kp.fold_weights(dec, 'final', 'cpu')
+    g = torch.Generator().manual_seed(7)
+    R, N, T, j = 2, 256, 10, 5
+    keys = torch.randn(R * N, 256, generator=g, dtype=torch.float64) * 1.5
+    pe = torch.randn(N, 256, generator=g, dtype=torch.float64)
+    tq = torch.randn(R * T, 128, generator=g, dtype=torch.float64) * 2.0
+    ref = kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N)
+    kp.assert_fold_close(ref.float(), ref)
+    skip = torch.zeros(N, dtype=torch.float64)
+    skip[kp.FOLD_KEY_TILE * j:kp.FOLD_KEY_TILE * (j + 1)] = -math.inf
+    with pytest.raises(AssertionError):
+        kp.assert_fold_close(kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N, key_bias=skip), ref)
+    # faint: the tile's scores lowered by `b` until its softmax weight moves the output by FAINT
+    bias = torch.zeros(N, dtype=torch.float64)
+    b = 0.0
+    for it in range(6):
+        if it:
+            b += math.log(FAINT / d)
+        bias[kp.FOLD_KEY_TILE * j:kp.FOLD_KEY_TILE * (j + 1)] = b
+        ref2 = kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N, key_bias=bias)
+        d = float((kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N, key_bias=skip) - ref2).abs().max())
+    assert 2.0 < d / 2e-5 < 5.0
+    with pytest.raises(AssertionError):
+        kp.assert_fold_close(kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N, key_bias=skip), ref2)

@@ -16,6 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, 'wave_emu'))
 
+import _kernel_props as kp
+
 DEV = torch.device('cpu')
 
 
@@ -219,34 +221,11 @@ def test_emu_rle_codec_round_trip_property(emu):
     through the DEVICE codec (rsp_mask_rle + rsp_rle_to_string on the emulator) must decode, with the oracle's restatement of
     cocoapi's rleFrString / rleDecode, to the mask again, and the string must be the one pycocotools would write."""
     from hypothesis import given, settings, strategies as st
-    import numpy as np
-    from oracle import rle as orle
-    from rsprompter_amd import rle as prle
 
     @settings(max_examples=120, deadline=None, derandomize=True)
     @given(st.integers(1, 3), st.integers(1, 40), st.integers(1, 45), st.integers(0, 5), st.integers(0, 2 ** 31 - 1))
     def check(k, h, w, kind, seed):
-        g = np.random.default_rng(seed)
-        if kind == 0:
-            m = g.random((k, h, w)) < 0.5                                   # noise: many runs
-        elif kind == 1:
-            m = np.zeros((k, h, w), bool)
-        elif kind == 2:
-            m = np.ones((k, h, w), bool)
-        elif kind == 3:
-            m = np.zeros((k, h, w), bool); m[:, :, ::2] = True               # column stripes (column-major runs of h)
-        elif kind == 4:
-            m = np.zeros((k, h, w), bool); m[:, ::2, :] = True               # row stripes: runs of 1
-        else:
-            m = np.zeros((k, h, w), bool)
-            y0, x0 = int(g.integers(0, h)), int(g.integers(0, w))
-            m[:, y0:y0 + int(g.integers(1, h + 1)), x0:x0 + int(g.integers(1, w + 1))] = True   # a box
-        flat, offs = prle.encode_rle_strings(torch.from_numpy(m), cap=8)     # tiny capacity: the grow-and-retry path
-        buf, o = flat.numpy().tobytes(), offs.tolist()
-        for i in range(k):
-            s_ = buf[o[i]:o[i + 1]]
-            assert s_ == orle.encode(m[i])['counts']
-            assert np.array_equal(orle.rle_decode(orle.rle_from_string(s_), h, w), m[i])
+        kp.check_rle_round_trip(emu, DEV, k, h, w, kind, seed)
     check()
 
 
@@ -289,7 +268,6 @@ def test_emu_gemm_ragged_shapes_property(emu):
     """C = act(A W^T + b) + res for random ragged shapes through whatever kernel the dispatcher picks (fp32 A: the
     register-staged kernel; planes: gemm_f16x3_dma_kernel; hint 40: the persistent kernel) against the fp64 product"""
     from hypothesis import given, settings, strategies as st
-    import torch.nn.functional as F
 
     @settings(max_examples=100, deadline=None, derandomize=True)
     @given(st.integers(1, 300), st.integers(1, 40), st.integers(1, 8), st.sampled_from(['f32', 'planes', 's2']),
@@ -298,28 +276,7 @@ def test_emu_gemm_ragged_shapes_property(emu):
         N, K = 4 * n4, 32 * k32
         if path == 's2':
             K = max(K, 64)                                  # rsp_gemm_s2_eligible: K >= 64 (a forced hint on less is EINVAL)
-        g = torch.Generator().manual_seed(seed)
-        a = torch.randn(M, K, generator=g)
-        w = torch.randn(N, K, generator=g) / K ** 0.5
-        b = torch.randn(N, generator=g) if with_bias else None
-        res = torch.randn(M, N, generator=g) if with_res else None
-        ref = a.double() @ w.double().t()
-        if b is not None:
-            ref = ref + b.double()
-        kw = {}
-        if act == 1 and not with_res:
-            ref, kw['act'] = F.gelu(ref), emu.ACT_GELU
-        elif act == 2:
-            ref, kw['act'] = F.relu(ref), emu.ACT_RELU
-        if res is not None:
-            ref = ref + res.double()
-        pw = emu.PackedWeight(w, b)
-        if path == 'f32':
-            got = emu.gemm(a, pw, res=res, dma=False, **kw)
-        else:
-            got = emu.gemm(emu.to_planes(a), pw, res=res, tile_hint=40 if path == 's2' else 0, **kw)
-        err = float((got.double() - ref).abs().max() / (ref.abs().max() + 1e-30))
-        assert err < 3e-6, (M, N, K, path, with_bias, with_res, act, err)
+        kp.check_gemm_ragged(emu, DEV, M, N, K, path, with_bias, with_res, act, seed)
     check()
 
 
@@ -328,28 +285,12 @@ def test_emu_batched_nms_property(emu):
     counts below the capacity, one to several ids -- against the oracle's restatement of mmcv batched_nms: kept indices in
     the same order"""
     from hypothesis import given, settings, strategies as st
-    from oracle import glue
 
     @settings(max_examples=100, deadline=None, derandomize=True)
     @given(st.integers(0, 400), st.integers(1, 6), st.sampled_from([0.3, 0.5, 0.7]), st.integers(1, 120), st.integers(2, 60),
            st.integers(0, 2 ** 31 - 1))
     def check(n, nid, thr, max_out, levels, seed):
-        g = torch.Generator().manual_seed(seed)
-        cap = max(n + int(torch.randint(0, 50, (1,), generator=g)), 1)
-        xy = (torch.rand(cap, 2, generator=g) * 8).floor() * 16              # a coarse grid: many identical boxes
-        wh = (torch.rand(cap, 2, generator=g) * 4).floor() * 16 + 16
-        boxes = torch.cat([xy, xy + wh], 1)[None].contiguous()
-        scores = ((torch.rand(cap, generator=g) * levels).round() / levels)[None].contiguous()     # few score levels: ties
-        ids = torch.randint(0, nid, (cap,), generator=g, dtype=torch.int32)[None].contiguous()
-        cand = (boxes, scores, ids, torch.arange(cap, dtype=torch.int32)[None].contiguous(), torch.tensor([n], dtype=torch.int32))
-        out = emu.batched_nms(cand, 1, cap, thr, max_out)
-        if n:
-            _, keep = glue.batched_nms(boxes[0, :n], scores[0, :n], ids[0, :n].long(), thr)
-            keep = keep[:max_out]
-        else:
-            keep = torch.zeros(0, dtype=torch.long)
-        k = int(out['count'][0])
-        assert k == keep.numel() and torch.equal(out['keep'][0, :k].long(), keep), (n, nid, thr, max_out)
+        kp.check_batched_nms(emu, DEV, n, nid, thr, max_out, levels, seed)
     check()
 
 
@@ -357,14 +298,11 @@ def test_emu_window_attention_grid_property(emu):
     """rsp_vit_window_attention over random window grids: windows per side 1-3, 1-14 real rows / columns in the last window
     of a row / column (the padded queries are skipped, the padded keys masked), 1-3 heads of 64 or 80, both block counts"""
     from hypothesis import given, settings, strategies as st
-    import test_gpu_kernels as tk
 
     @settings(max_examples=10, deadline=None, derandomize=True)
     @given(st.integers(1, 3), st.integers(1, 14), st.integers(1, 3), st.sampled_from([64, 80]), st.integers(0, 1))
     def check(nw, real, nh, dh, variant):
-        if (nh * dh) % 32:
-            nh += 1                                          # the K | V planes need nh * dh % 32 == 0 (else EINVAL)
-        tk.test_vit_window_attention_fused_relpos(DEV, nw, real, nh, dh, 1, variant)
+        kp.check_window_attention_grid(emu, DEV, nw, real, nh, dh, variant)
     check()
 
 
@@ -372,23 +310,11 @@ def test_emu_layernorm_shapes_property(emu):
     """LayerNorm over random row counts and widths (the four-rows-per-wave kernel for C % 64 == 0 in [256, 1280] with plane
     outputs, the wave-per-row kernel otherwise), fp32 and plane outputs against fp64"""
     from hypothesis import given, settings, strategies as st
-    import torch.nn.functional as F
-    import test_gpu_kernels as tk
 
     @settings(max_examples=70, deadline=None, derandomize=True)
     @given(st.integers(1, 130), st.sampled_from([32, 64, 96, 128, 256, 320, 384, 512, 640, 768, 896, 1024, 1152, 1280, 1408]), st.booleans(), st.integers(0, 2 ** 31 - 1))
     def check(rows, C, planes, seed):
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(rows, C, generator=g) * 3 + 1
-        w, b = torch.randn(C, generator=g), torch.randn(C, generator=g)
-        ref = F.layer_norm(x.double(), (C,), w.double(), b.double(), 1e-6)
-        got = emu.layernorm(x, w, b, 1e-6, planes=planes)
-        if planes:
-            y, pl = got if isinstance(got, tuple) else (None, got)
-            assert float((tk._planes_to_f32(pl) - ref).abs().max()) < 2e-5
-            got = y
-        if got is not None:
-            assert float((got.double() - ref).abs().max()) < 2e-5
+        kp.check_layernorm(emu, DEV, rows, C, planes, seed)
     check()
 
 
@@ -396,18 +322,17 @@ def test_emu_attention_shapes_property(emu):
     """the generic flash attention (token self attention, masked Mask2Former cross attention: rsp_attention) and the fused
     image -> token block over random token / key counts -- ragged last tiles, one key, T below and at the kernels' limits"""
     from hypothesis import given, settings, strategies as st
-    import test_gpu_kernels as tk
 
     @settings(max_examples=25, deadline=None, derandomize=True)
     @given(st.sampled_from([16, 32, 64]), st.integers(1, 70), st.integers(1, 200), st.integers(1, 8))
     def generic(dh, Tq, Tk, nh):
-        tk.test_generic_attention_with_batch_maps(DEV, dh, Tq, Tk, nh)
+        kp.check_generic_attention(emu, DEV, dh, Tq, Tk, nh)
     generic()
 
     @settings(max_examples=16, deadline=None, derandomize=True)
     @given(st.integers(1, 10), st.integers(1, 300), st.booleans(), st.sampled_from(['valu', 'mfma']))
     def i2t(T, N, planes_res, form):
-        tk.test_sam_i2t_fused_matches_composition(DEV, T, N, planes_res, form)
+        kp.check_i2t_fused(emu, DEV, T, N, planes_res, form)
     i2t()
 
 
@@ -417,35 +342,12 @@ def test_emu_rpn_selection_property(emu):
     kernels' rule: score descending, position ascending = the reference's stable sort), nms_pre below and above the level
     sizes, the min-size filter on and off, 1-2 images -- (level, anchor) indices must be identical"""
     from hypothesis import given, settings, strategies as st
-    import torch_ops_mock as mock
-    from rsprompter_amd.anchor_heads import AnchorGenerator, DeltaXYWHBBoxCoder
 
     @settings(max_examples=20, deadline=None, derandomize=True)
     @given(st.integers(1, 2), st.integers(2, 12), st.integers(2, 12), st.sampled_from([5, 40, 300, 1000]), st.integers(1, 60),
            st.sampled_from([-1, 0, 8]), st.integers(1, 12), st.integers(0, 2 ** 31 - 1))
     def check(B, h0, w0, nms_pre, max_per_img, min_size, levels_q, seed):
-        g = torch.Generator().manual_seed(seed)
-        strides = [4, 8, 16]
-        gen = AnchorGenerator(strides=strides, ratios=[0.5, 1.0, 2.0], scales=[8])
-        base = torch.stack(gen.base_anchors, 0)
-        A, LD = 3, 32
-        sizes = [(h0 * 4, w0 * 4), (h0 * 2, w0 * 2), (h0, w0)]
-        heads = []
-        for (H, W) in sizes:
-            hd = torch.zeros(B * H * W, LD)
-            hd[:, :A] = (torch.randn(B * H * W, A, generator=g) * 2 * levels_q).round() / levels_q      # ties
-            hd[:, A:5 * A] = torch.randn(B * H * W, 4 * A, generator=g) * 0.4
-            heads.append(hd.contiguous())
-        img_hw = torch.tensor([[float(16 * h0), float(16 * w0)]] * B)
-        coder = DeltaXYWHBBoxCoder()
-        args = (base, strides, nms_pre, max_per_img, 0.7, min_size, coder, DEV)
-        got = emu.RpnSelector(*args)(heads, sizes, LD, img_hw)
-        ref = mock.RpnSelector(*args)(heads, sizes, LD, img_hw)
-        for b in range(B):
-            k = int(ref['count'][b])
-            assert int(got['count'][b]) == k
-            assert torch.equal(got['ids'][b, :k], ref['ids'][b, :k]) and torch.equal(got['src'][b, :k], ref['src'][b, :k])
-            assert float((got['boxes'][b, :k] - ref['boxes'][b, :k]).abs().max() if k else 0.0) < 1e-3
+        kp.check_rpn_selection(emu, DEV, B, h0, w0, nms_pre, max_per_img, min_size, levels_q, seed)
     check()
 
 
@@ -455,48 +357,17 @@ def test_emu_bbox_post_and_query_topk_property(emu):
     descending, flat index ascending) against the oracle's restatements of BBoxHead._predict_by_feat_single /
     instance_postprocess: same detections (tie-aware matching, tests/_match.py), same flat indices"""
     from hypothesis import given, settings, strategies as st
-    import torch_ops_mock as mock
-    from _match import match_detections
-    from rsprompter_amd.anchor_heads import DeltaXYWHBBoxCoder
 
     @settings(max_examples=25, deadline=None, derandomize=True)
     @given(st.integers(1, 120), st.integers(1, 12), st.sampled_from([0.02, 0.05, 0.3]), st.integers(1, 60), st.integers(0, 2 ** 31 - 1))
     def bbox(n, nc, thr, max_out, seed):
-        g = torch.Generator().manual_seed(seed)
-        xy = torch.rand(n, 2, generator=g) * 300
-        roi = torch.cat([torch.zeros(n, 1), xy, xy + torch.rand(n, 2, generator=g) * 120 + 2], 1)
-        LD = (5 * nc + 1 + 3) // 4 * 4
-        head = torch.zeros(n, LD)
-        head[:, :nc + 1] = torch.randn(n, nc + 1, generator=g) * 2.5
-        head[:, nc + 1:5 * nc + 1] = torch.randn(n, 4 * nc, generator=g)
-        if n > 3:                                            # duplicated RoIs: identical boxes and scores
-            roi[n // 2] = roi[0]; head[n // 2] = head[0]
-        coder = DeltaXYWHBBoxCoder(target_stds=(0.1, 0.1, 0.2, 0.2))
-        args = (head, LD, roi, torch.tensor([0, n]), torch.tensor([[400., 420.]]), nc, thr, coder, 0.5, max_out)
-        got, ref = emu.bbox_post(*args), mock.bbox_post(*args)
-        k = int(ref['count'][0])
-        assert int(got['count'][0]) == k
-        pairs = match_detections(got['boxes'][0, :k], got['scores'][0, :k], got['ids'][0, :k].long(),
-                                 ref['boxes'][0, :k], ref['scores'][0, :k], ref['ids'][0, :k].long())
-        assert len(pairs) == k
+        kp.check_bbox_post(emu, DEV, n, nc, thr, max_out, seed)
     bbox()
 
     @settings(max_examples=25, deadline=None, derandomize=True)
     @given(st.integers(1, 2), st.integers(1, 60), st.integers(1, 10), st.integers(1, 100), st.integers(0, 2 ** 31 - 1))
     def topk(B, Nq, nc, k, seed):
-        g = torch.Generator().manual_seed(seed)
-        k = min(k, Nq * nc)
-        cls = torch.randn(B, Nq, nc + 1, generator=g) * 2
-        if Nq > 2:
-            cls[:, Nq - 1] = cls[:, 0]                        # an exact tie between the first and the last query
-        sc, fl = emu.query_topk(cls.contiguous(), k)
-        rs, rf = mock.query_topk(cls, k)
-        assert float((sc - rs).abs().max()) < 1e-6
-        for b in range(B):                                   # equal up to the order inside runs of (numerically) equal scores
-            bad = (fl[b] != rf[b]).nonzero()[:, 0].tolist()
-            for i in bad:
-                j = (rf[b] == fl[b, i]).nonzero()
-                assert j.numel() == 1 and abs(float(rs[b, int(j[0, 0])]) - float(sc[b, i])) < 2e-7, (b, i)
+        kp.check_query_topk(emu, DEV, B, Nq, nc, k, seed)
     topk()
 
 
@@ -506,54 +377,23 @@ def test_emu_sampling_kernels_property(emu):
     MSDeformAttn with 1-5 levels of random sizes and offsets that leave the maps; GroupNorm with add / ReLU; bilinear
     resizing up and down; the query prompter's attention-mask rule incl. fully blocked rows"""
     from hypothesis import given, settings, strategies as st
-    import torch_ops_mock as mock
 
     @settings(max_examples=15, deadline=None, derandomize=True)
     @given(st.integers(1, 40), st.sampled_from([7, 14]), st.integers(0, 2 ** 31 - 1))
     def roi(K, P, seed):
-        g = torch.Generator().manual_seed(seed)
-        B, C = 2, 8
-        strides, sizes = [4, 8, 16, 32], [(32, 40), (16, 20), (8, 10), (4, 5)]
-        feats = [torch.randn(B, h, w, C, generator=g) for h, w in sizes]
-        pes = [torch.randn(h, w, C, generator=g) if i % 2 == 0 else None for i, (h, w) in enumerate(sizes)]
-        xy = torch.rand(K, 2, generator=g) * 200 - 30                     # some start outside the 128 x 160 image
-        wh = torch.exp(torch.rand(K, 2, generator=g) * 6)                 # 1 .. 400 pixels: every level
-        rois = torch.cat([torch.randint(0, B, (K, 1), generator=g).float(), xy, xy + wh], 1)
-        got, ref = emu.roi_align(feats, pes, rois, P, strides), mock.roi_align(feats, pes, rois, P, strides)
-        assert float((got - ref).abs().max()) < 2e-5
+        kp.check_roi_align(emu, DEV, K, P, seed)
     roi()
 
     @settings(max_examples=15, deadline=None, derandomize=True)
     @given(st.integers(1, 5), st.sampled_from([16, 32]), st.integers(0, 2 ** 31 - 1))
     def msda(L, hd, seed):
-        g = torch.Generator().manual_seed(seed)
-        shapes = [(int(torch.randint(1, 9, (1,), generator=g)), int(torch.randint(1, 9, (1,), generator=g))) for _ in range(L)]
-        ntok, B, D = sum(h * w for h, w in shapes), 2, 8 * hd
-        value = torch.randn(B * ntok, D, generator=g)
-        ow = torch.cat([torch.randn(B * ntok, 8 * L * 4 * 2, generator=g) * 3, torch.randn(B * ntok, 8 * L * 4, generator=g)], 1).contiguous()
-        ref_pts = torch.rand(ntok, 2, generator=g)
-        got = emu.msdeform_attn(value, ow, ref_pts, B, ntok, shapes, head_dim=hd)
-        assert float((got - mock.msdeform_attn(value, ow, ref_pts, B, ntok, shapes, head_dim=hd)).abs().max()) < 2e-5
+        kp.check_msdeform_attn(emu, DEV, L, hd, seed)
     msda()
 
     @settings(max_examples=15, deadline=None, derandomize=True)
     @given(st.integers(1, 3), st.integers(1, 12), st.integers(1, 12), st.integers(1, 20), st.integers(1, 20), st.integers(0, 2 ** 31 - 1))
     def resample(B, h, w, ho, wo, seed):
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(B, h, w, 128, generator=g)
-        assert float((emu.resize_bilinear(x, (ho, wo)) - mock.resize_bilinear(x, (ho, wo))).abs().max()) < 1e-5
-        gam, bet, add = torch.randn(128, generator=g), torch.randn(128, generator=g), torch.randn(B, h * w, 128, generator=g)
-        xs = x.view(B, h * w, 128)
-        assert float((emu.groupnorm(xs, gam, bet, 32, add=add) - mock.groupnorm(xs, gam, bet, 32, add=add)).abs().max()) < 5e-5
-        assert float((emu.groupnorm(xs, gam, bet, 32, relu=True) - mock.groupnorm(xs, gam, bet, 32, relu=True)).abs().max()) < 5e-5
-        mpp = torch.randn(B, 5, h, w, generator=g) * 3
-        mpp[:, 0] = -5.0                                                  # a fully blocked row: cleared (models.py:439-442)
-        a, b = emu.query_attn_mask(mpp.contiguous(), (ho, wo)), mock.query_attn_mask(mpp, (ho, wo))
-        diff = a != b
-        if bool(diff.any()):                                              # only where the resized logit ties with the threshold
-            import torch.nn.functional as F
-            z = F.interpolate(mpp, (ho, wo), mode='bilinear', align_corners=False).flatten(2)
-            assert float(z[diff].abs().max()) < 1e-5
+        kp.check_resample(emu, DEV, B, h, w, ho, wo, seed)
     resample()
 
 
@@ -563,33 +403,19 @@ def test_emu_decoder_tail_kernels_property(emu):
     kernels, and the fused upscaler tail against the two-kernel form for h != w, RoI sizes that are no multiple of the
     128-row tile, and a single RoI smaller than one tile"""
     from hypothesis import given, settings, strategies as st
-    from rsprompter_amd import ops
-    from rsprompter_amd.sam_decoder import SamMaskDecoderHIP
-    from rsprompter_amd.synth import synth_state_dict
-    import test_gpu_kernels as tk
 
     @settings(max_examples=16, deadline=None, derandomize=True)
     @given(st.integers(1, 3), st.sampled_from([32, 64, 96, 160]), st.integers(1, 12))
     def fold(R, N, T):
-        tk.test_sam_t2i_fold_matches_fp64_attention(DEV, R, N, T)
+        kp.check_t2i_fold(emu, DEV, R, N, T)
     fold()
 
-    dec = SamMaskDecoderHIP()
-    dec.load_state_dict(synth_state_dict(dec, 3))
-    dec._pack()
-    P, ln = dec._packed, dec.upscale_layer_norm
+    dec = kp.upscale_decoder(DEV, 3)
 
     @settings(max_examples=30, deadline=None, derandomize=True)
     @given(st.integers(1, 3), st.integers(1, 13), st.integers(1, 13), st.integers(0, 2 ** 31 - 1))
     def upscaler(R, h, w, seed):
-        g = torch.Generator().manual_seed(seed)
-        x = ops.to_planes(torch.randn(R * h * w, 256, generator=g) * 1.5)
-        hy = torch.randn(R, 32, generator=g)
-        up = ops.conv_transpose2x2(x.view(R, h, w, 256), *P['up1'], act=ops.ACT_GELU, ln=(ln.weight, ln.bias, 1e-6))
-        two = ops.conv_transpose2x2(up, *P['up2'], act=ops.ACT_GELU, hyper=hy)
-        one = ops.sam_upscale_fused(x, P['up1'][0], P['up1'][1], ln.weight, ln.bias, 1e-6, P['up2p'][0], P['up2p'][1], hy, h, w)
-        assert one.shape == two.shape == (R, 4 * h, 4 * w)
-        assert float((one - two).abs().max()) < 2e-5 * max(1.0, float(two.abs().max()))
+        kp.check_upscaler(emu, DEV, dec, R, h, w, seed)
     upscaler()
 
 
@@ -598,40 +424,19 @@ def test_emu_query_prompt_kernels_property(emu):
     convolution, + the image embedding of the prompt set's image; models.py:305, HF:569-601) and the row gather, on random
     geometry against the reference's torch calls"""
     from hypothesis import given, settings, strategies as st
-    import torch_ops_mock as mock
 
     @settings(max_examples=12, deadline=None, derandomize=True)
     @given(st.integers(1, 5), st.integers(1, 2), st.integers(1, 10), st.integers(1, 10), st.sampled_from([256, 512]),
            st.integers(0, 2 ** 31 - 1))
     def embed(R, B, he, we, C, seed):
-        g = torch.Generator().manual_seed(seed)
-        rn = lambda *sh: torch.randn(*sh, generator=g)
-        prm = dict(conv1_w=rn(4, 1, 2, 2), conv1_b=rn(4), ln1_w=rn(4), ln1_b=rn(4), conv2_w=rn(16, 4, 2, 2) * 0.5, conv2_b=rn(16),
-                   ln2_w=rn(16), ln2_b=rn(16), conv3_w=rn(C, 16) * 0.3, conv3_b=rn(C))
-        mpp = rn(R, 4 * he, 4 * we) * 4
-        emb = rn(B * he * we, C)
-        roi_img = torch.randint(0, B, (R,), generator=g).to(torch.int32)
-        got, ref = emu.sam_mask_embed(mpp, emb, roi_img, prm, he, we), mock.sam_mask_embed(mpp, emb, roi_img, prm, he, we)
-        assert got.shape == ref.shape and float((got - ref).abs().max()) < 5e-5 * max(1.0, float(ref.abs().max()))
+        kp.check_mask_embed(emu, DEV, R, B, he, we, C, seed)
     embed()
-    # a channel count that would leave lanes out of the output loop's wave shuffle is refused (this test found that
-    # C = 32 gave wrong rows for every pixel beyond the 8th; the reference only has C = 256)
-    g = torch.Generator().manual_seed(0)
-    prm = dict(conv1_w=torch.randn(4, 1, 2, 2), conv1_b=torch.randn(4), ln1_w=torch.randn(4), ln1_b=torch.randn(4),
-               conv2_w=torch.randn(16, 4, 2, 2), conv2_b=torch.randn(16), ln2_w=torch.randn(16), ln2_b=torch.randn(16),
-               conv3_w=torch.randn(32, 16), conv3_b=torch.randn(32))
-    with pytest.raises(RuntimeError):
-        emu.sam_mask_embed(torch.randn(2, 12, 12), torch.randn(9, 32), torch.zeros(2, dtype=torch.int32), prm, 3, 3)
+    kp.check_mask_embed_refuses_narrow_channels(emu, DEV)
 
     @settings(max_examples=20, deadline=None, derandomize=True)
     @given(st.integers(1, 50), st.integers(0, 70), st.sampled_from([4, 32, 100, 256]), st.integers(0, 2 ** 31 - 1))
     def gather(n_src, n_idx, C, seed):
-        g = torch.Generator().manual_seed(seed)
-        src = torch.randn(n_src, C, generator=g)
-        idx = torch.randint(0, n_src, (n_idx,), generator=g).to(torch.int32)
-        if n_idx == 0:
-            return
-        assert torch.equal(emu.gather_rows(src, idx), src[idx.long()])
+        kp.check_gather_rows(emu, DEV, n_src, n_idx, C, seed)
     gather()
 
 
