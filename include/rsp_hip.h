@@ -557,6 +557,43 @@ int rsp_pack_bits(const uint8_t* src, uint8_t* dst, int64_t n_bits, rsp_stream_t
 int rsp_gather_rows(const float* src, const int32_t* idx, float* dst, int64_t rows, int32_t C,
                     rsp_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* COCO evaluation (csrc/cocoeval.hip): the device part of       */
+/* pycocotools COCOeval.evaluate as CocoMetric uses it                       */
+/* ------------------------------------------------------------------------ */
+#define RSP_COCO_IOU_BBOX 0
+#define RSP_COCO_IOU_SEGM 1
+/* One evaluation unit = one (image, category): its dts are [dt0, dt0 + nd) of the per-dt arrays (score-sorted,      */
+/* truncated to maxDets[-1]), its gts [gt0, gt0 + ng) of the per-gt arrays (gt ranges of different units disjoint),    */
+/* its IoU block iou[out0 + d * ng + g]; nwords = 64-bit words of one of its masks (segm).                            */
+typedef struct {
+  int64_t dt0, gt0, out0;
+  int32_t nd, ng, nwords, pad;
+} RspCocoUnit;
+/* cocoapi maskApi.c rleFrString: string i = flat[offs[i] .. offs[i + 1]) (what rsp_rle_to_string writes) -> run      */
+/* counts counts[i, 0 .. n_counts[i]) (uint32, row stride cap); n_counts[i] = -(needed) when cap is too small.        */
+int rsp_rle_from_string(const uint8_t* flat, const int64_t* offs, int32_t k, int32_t cap, uint32_t* counts,
+                        int32_t* n_counts, rsp_stream_t stream);
+/* run counts -> bits: pixel j of the column-major RLE stream of mask i is bit (j & 63) of bits[word_offs[i] + (j >> 6)]  */
+/* (word_offs [k + 1]); area[i] = sum of the odd runs (maskApi rleArea); wrange[2i .. 2i + 1] = words [lo, hi) that hold  */
+/* every set bit ([0, 0) when empty; may be NULL).                                                                      */
+int rsp_rle_to_bits(const uint32_t* counts, const int32_t* n_counts, int32_t k, int32_t cap, const int64_t* word_offs,
+                    uint64_t* bits, int64_t* area, int32_t* wrange, rsp_stream_t stream);
+/* IoU blocks of n_units units (units: DEVICE array).  SEGM: inter = popcount(d & g), union = area_d + area_g - inter   */
+/* (area_d for a crowd gt), 0 when inter == 0, else (double)inter / union (maskApi rleIou).  BBOX: maskApi bbIou in fp64 */
+/* on xywh boxes dt_box [n_dt, 4], gt_box [n_gt, 4].  Arrays of the other mode may be NULL.                             */
+int rsp_coco_iou(const RspCocoUnit* units, int32_t n_units, int32_t mode, const uint64_t* dt_bits, const uint64_t* gt_bits,
+                 const int64_t* dt_woff, const int64_t* gt_woff, const int32_t* dt_wrange, const int32_t* gt_wrange,
+                 const int64_t* dt_area, const int64_t* gt_area, const double* dt_box, const double* gt_box,
+                 const uint8_t* gt_crowd, double* iou, rsp_stream_t stream);
+/* cocoeval.py evaluateImg for every unit x area range (area_rng [A][2], inclusive, A <= 8) x threshold (thrs [T], fp64 */
+/* as the metric holds them).  gt ignore = crowd or area outside the range; dtm [A*T, n_dt] = id of the matched gt (0:    */
+/* none), dtig [A*T, n_dt] as evaluateImg's dtIgnore, npig [n_units, A] = gts not ignored.  gtm_ws: n_gt * A * T bytes.  */
+int rsp_coco_match(const RspCocoUnit* units, int32_t n_units, const double* iou, const double* gt_area,
+                   const uint8_t* gt_crowd, const int64_t* gt_id, const double* dt_area, const double* area_rng, int32_t A,
+                   const double* thrs, int32_t T, int64_t n_dt, uint8_t* gtm_ws, int64_t* dtm, uint8_t* dtig,
+                   int32_t* npig, rsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

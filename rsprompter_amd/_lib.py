@@ -89,6 +89,11 @@ class RspRpnDesc(ctypes.Structure):
     ]
 
 
+class RspCocoUnit(ctypes.Structure):
+    _fields_ = [("dt0", c_int64), ("gt0", c_int64), ("out0", c_int64), ("nd", c_int), ("ng", c_int), ("nwords", c_int),
+                ("pad", c_int)]
+
+
 # name -> (restype, argtypes); the CPU test checks every symbol is exported.
 PROTOTYPES = {
     "rsp_abi_version": (c_int, []),
@@ -186,6 +191,12 @@ PROTOTYPES = {
     "rsp_upsample_nearest_add": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rsp_sam_embed_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p]),
+    "rsp_rle_from_string": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rsp_rle_to_bits": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_coco_iou": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_coco_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                               c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

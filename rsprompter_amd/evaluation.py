@@ -1,0 +1,495 @@
+"""`METRICS` registry and `CocoMetric`: box and mask mAP with mmdet's surface (mmdet/evaluation/metrics/coco_metric.py),
+without pycocotools.  The per-pair and per-(image, category) work of COCOeval.evaluate runs on the device
+(csrc/cocoeval.hip: string decode, bits, IoU, greedy matching); accumulate / summarize stay on the host in float64 numpy
+with pycocotools' arithmetic.
+
+Both ground-truth paths of the reference work and give the reference's (different) numbers:
+  * no `ann_file` (every RSPrompter config): the ground truth of the data samples, converted as `gt_to_coco_json` does
+    (annotation ids from 1, category ids 0..C-1, every instance non-crowd, area = float32 box area w * h);
+  * `ann_file`: the JSON as it is (crowd flags, the JSON's areas and annotation ids).
+"""
+import json
+import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import ops
+from .datasets import ann_to_rle
+from .registry import Registry
+
+METRICS = Registry('metric')
+
+AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)
+AREA_LBL = ('all', 'small', 'medium', 'large')
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+STAT_NAMES = ('mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l', 'AR@100', 'AR@300', 'AR@1000', 'AR_s@1000',
+              'AR_m@1000', 'AR_l@1000')
+
+
+def _get(obj, key, default=None):
+    return obj.get(key, default) if isinstance(obj, dict) else getattr(obj, key, default)
+
+
+def _np(x):
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
+def _flat_strings(strings, device):
+    lens = np.fromiter((len(s) for s in strings), dtype=np.int64, count=len(strings))
+    offs = np.zeros(len(strings) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    flat = np.frombuffer(b''.join(strings), dtype=np.uint8) if offs[-1] else np.zeros(1, dtype=np.uint8)
+    return torch.from_numpy(flat.copy()).to(device), torch.from_numpy(offs).to(device)
+
+
+def _masks_on_device(rles, device):
+    """compressed RLE dicts -> (bits, word_offs, area int64, wrange) on the device (rsp_rle_from_string + rsp_rle_to_bits)"""
+    strings = [r['counts'] if isinstance(r['counts'], bytes) else str(r['counts']).encode() for r in rles]
+    nwords = np.fromiter(((int(r['size'][0]) * int(r['size'][1]) + 63) // 64 for r in rles), dtype=np.int64,
+                         count=len(rles))
+    woff = np.zeros(len(rles) + 1, dtype=np.int64)
+    np.cumsum(nwords, out=woff[1:])
+    flat, offs = _flat_strings(strings, device)
+    counts, n = ops.rle_from_string(flat, offs)
+    woff_d = torch.from_numpy(woff).to(device)
+    bits, area, wrange = ops.rle_to_bits(counts, n, woff_d)
+    return bits, woff_d, area, wrange
+
+
+class CocoEvalResult:
+    """What COCOeval leaves behind that the metric reads: eval['precision'] / ['recall'] and stats."""
+
+    def __init__(self, precision, recall, stats, tables=None):
+        self.eval = dict(precision=precision, recall=recall)
+        self.stats = stats
+        self.tables = tables            # the device's evaluateImg tables (dtm, dtig [A, T, n_dt], npig [units, A], ...)
+
+
+def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, device, timings=None):
+    """COCOeval(gt, dt, iou_type) with params imgIds / catIds / iouThrs / maxDets -> evaluate + accumulate + summarize.
+
+    gt: dict(images, annotations) (annotations with id, image_id, category_id, area, iscrowd, bbox, segmentation);
+    dt: list of loadRes'd detections (id from 1, image_id, category_id, score, area, bbox or segmentation RLE)."""
+    import time
+    t0 = time.perf_counter()
+    img_ids = np.unique(np.asarray(img_ids))
+    cat_ids = np.unique(np.asarray(cat_ids))
+    thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    max_dets = list(max_dets)
+    I, K, A, T, M = len(img_ids), len(cat_ids), len(AREA_RNG), len(thrs), len(max_dets)
+    img_pos = {int(v): i for i, v in enumerate(img_ids.tolist())}
+    cat_pos = {int(v): i for i, v in enumerate(cat_ids.tolist())}
+    img_hw = {im['id']: (im.get('height'), im.get('width')) for im in gt['images']}
+    # ---- units = (category, image), category-major; gts in annotation order, dts by score (stable), truncated
+    gts = [g for g in gt['annotations'] if g['image_id'] in img_pos and g['category_id'] in cat_pos]
+    g_unit = np.fromiter((cat_pos[g['category_id']] * I + img_pos[g['image_id']] for g in gts), dtype=np.int64,
+                         count=len(gts))
+    g_ord = np.argsort(g_unit, kind='mergesort')
+    gts = [gts[i] for i in g_ord]
+    g_unit = g_unit[g_ord]
+    dts = [d for d in dt if d['image_id'] in img_pos and d['category_id'] in cat_pos]
+    d_unit = np.fromiter((cat_pos[d['category_id']] * I + img_pos[d['image_id']] for d in dts), dtype=np.int64,
+                         count=len(dts))
+    d_score = np.fromiter((d['score'] for d in dts), dtype=np.float64, count=len(dts))
+    d_ord = np.lexsort((-d_score, d_unit))                  # per unit: argsort(-score, kind='mergesort')
+    d_unit = d_unit[d_ord]
+    U = K * I
+    nd_all = np.bincount(d_unit, minlength=U)
+    first = np.concatenate([[0], np.cumsum(nd_all)[:-1]])
+    rank = np.arange(len(d_unit)) - first[d_unit] if len(d_unit) else np.zeros(0, dtype=np.int64)
+    keep = rank < max_dets[-1]
+    d_ord, d_unit, rank = d_ord[keep], d_unit[keep], rank[keep]
+    dts = [dts[i] for i in d_ord]
+    d_score = d_score[d_ord]
+    nd = np.bincount(d_unit, minlength=U).astype(np.int64)
+    ng = np.bincount(g_unit, minlength=U).astype(np.int64)
+    dt0 = np.concatenate([[0], np.cumsum(nd)[:-1]]).astype(np.int64)
+    gt0 = np.concatenate([[0], np.cumsum(ng)[:-1]]).astype(np.int64)
+    npair = nd * ng
+    out0 = np.concatenate([[0], np.cumsum(npair)[:-1]]).astype(np.int64)
+    n_iou = int(npair.sum())
+    n_dt, n_gt = len(dts), len(gts)
+    unit_img = np.tile(img_ids, K)
+    nwords = np.array([((img_hw.get(int(i), (0, 0))[0] or 0) * (img_hw.get(int(i), (0, 0))[1] or 0) + 63) // 64
+                       for i in unit_img.tolist()], dtype=np.int64)
+    if iou_type == 'segm':
+        for d in dts:
+            if tuple(d['segmentation']['size']) != tuple(img_hw[d['image_id']]):
+                raise ValueError('segm: a detection mask does not have the size of its image')
+    units = ops.coco_units(dt0, gt0, out0, nd, ng, nwords if iou_type == 'segm' else np.zeros(U, np.int64), device)
+
+    def dev(a, dtype):
+        a = np.asarray(a, dtype=dtype)
+        if a.size == 0:
+            a = np.zeros((1,) + a.shape[1:], dtype=dtype)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    g_crowd = dev([int(bool(g.get('iscrowd', 0))) for g in gts], np.uint8)
+    g_area = dev([g['area'] for g in gts], np.float64)
+    g_id = dev([g['id'] for g in gts], np.int64)
+    t1 = time.perf_counter()
+    if iou_type == 'segm':
+        db, dwo, da, dwr = _masks_on_device([d['segmentation'] for d in dts], device)
+        gb, gwo, ga, gwr = _masks_on_device([g['segmentation'] for g in gts], device)
+        iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
+                           gt_woff=gwo, dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
+        d_area = da.to(torch.float64) if n_dt else dev([0.0], np.float64)
+    else:
+        d_box = dev(np.asarray([d['bbox'] for d in dts], np.float64).reshape(-1, 4), np.float64)
+        g_box = dev(np.asarray([g['bbox'] for g in gts], np.float64).reshape(-1, 4), np.float64)
+        iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_BBOX, gt_crowd=g_crowd, dt_box=d_box, gt_box=g_box)
+        d_area = dev([d['area'] for d in dts], np.float64)
+    if n_iou == 0:
+        iou = torch.zeros((1,), dtype=torch.float64, device=device)
+    dtm, dtig, npig = ops.coco_match(units, iou, g_area, g_crowd, g_id, d_area, dev(AREA_RNG, np.float64),
+                                     dev(thrs, np.float64), n_dt)
+    dtm, dtig, npig = dtm.cpu().numpy(), dtig.cpu().numpy().astype(bool), npig.cpu().numpy()
+    t2 = time.perf_counter()
+    precision, recall = accumulate(dtm, dtig, npig, d_score, d_unit, rank, nd, ng, K, I, thrs, max_dets)
+    stats = summarize(precision, recall, thrs, max_dets)
+    t3 = time.perf_counter()
+    if timings is not None:
+        timings['host_prepare'] = timings.get('host_prepare', 0.0) + (t1 - t0)
+        timings['device'] = timings.get('device', 0.0) + (t2 - t1)
+        timings['host_accumulate'] = timings.get('host_accumulate', 0.0) + (t3 - t2)
+    tables = dict(dtm=dtm, dtig=dtig, npig=npig, dt_ids=np.array([d['id'] for d in dts], dtype=np.int64), dt0=dt0,
+                  nd=nd, ng=ng, n_img=I, n_cat=K)
+    return CocoEvalResult(precision, recall, stats, tables)
+
+
+def accumulate(dtm, dtig, npig, d_score, d_unit, rank, nd, ng, K, I, thrs, max_dets):
+    """COCOeval.accumulate, vectorised over thresholds.  dtm / dtig [A, T, n_dt] in unit order (category-major, images
+    sorted, dts by score within a unit); npig [K * I, A]."""
+    T, R, A, M = len(thrs), len(REC_THRS), len(AREA_RNG), len(max_dets)
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    # a unit that has neither gt nor dt is evaluateImg's None: it contributes nothing either way
+    d_cat = d_unit // I if len(d_unit) else d_unit
+    cat_has = (nd + ng).reshape(K, I).sum(1) > 0
+    for k in range(K):
+        if not cat_has[k]:
+            continue
+        sel_k = np.nonzero(d_cat == k)[0]
+        for m, max_det in enumerate(max_dets):
+            sel = sel_k[rank[sel_k] < max_det]
+            inds = np.argsort(-d_score[sel], kind='mergesort')
+            idx = sel[inds]
+            for a in range(A):
+                n_pos = int(npig[k * I:(k + 1) * I, a].sum())
+                if n_pos == 0:
+                    continue
+                m_ = dtm[a][:, idx] != 0
+                ig = dtig[a][:, idx]
+                tps = np.logical_and(m_, np.logical_not(ig))
+                fps = np.logical_and(np.logical_not(m_), np.logical_not(ig))
+                tp_sum = np.cumsum(tps, axis=1).astype(dtype=np.float64)
+                fp_sum = np.cumsum(fps, axis=1).astype(dtype=np.float64)
+                nd_ = tp_sum.shape[1]
+                for t in range(T):
+                    tp, fp = tp_sum[t], fp_sum[t]
+                    rc = tp / n_pos
+                    pr = tp / (fp + tp + np.spacing(1))
+                    recall[t, k, a, m] = rc[-1] if nd_ else 0
+                    q = np.zeros((R,))
+                    if nd_:
+                        pr = np.maximum.accumulate(pr[::-1])[::-1]
+                        pi = np.searchsorted(rc, REC_THRS, side='left')
+                        ok = pi < nd_
+                        q[ok] = pr[pi[ok]]
+                    precision[t, :, k, a, m] = q
+    return precision, recall
+
+
+def summarize(precision, recall, thrs, max_dets):
+    """COCOeval.summarize / _summarizeDets with mmdet's maxDets = proposal_nums."""
+    thrs = np.asarray(thrs)
+
+    def _s(ap, iou_thr=None, area='all', md=100):
+        aind = [i for i, lbl in enumerate(AREA_LBL) if lbl == area]
+        mind = [i for i, m in enumerate(max_dets) if m == md]
+        if ap == 1:
+            s = precision
+            if iou_thr is not None:
+                s = s[np.where(iou_thr == thrs)[0]]
+            s = s[:, :, :, aind, mind]
+        else:
+            s = recall
+            if iou_thr is not None:
+                s = s[np.where(iou_thr == thrs)[0]]
+            s = s[:, :, aind, mind]
+        return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+
+    md = max_dets
+    stats = np.zeros((12,))
+    stats[0] = _s(1, md=md[2])
+    stats[1] = _s(1, iou_thr=.5, md=md[2])
+    stats[2] = _s(1, iou_thr=.75, md=md[2])
+    stats[3] = _s(1, area='small', md=md[2])
+    stats[4] = _s(1, area='medium', md=md[2])
+    stats[5] = _s(1, area='large', md=md[2])
+    stats[6] = _s(0, md=md[0])
+    stats[7] = _s(0, md=md[1])
+    stats[8] = _s(0, md=md[2])
+    stats[9] = _s(0, area='small', md=md[2])
+    stats[10] = _s(0, area='medium', md=md[2])
+    stats[11] = _s(0, area='large', md=md[2])
+    return stats
+
+
+def load_res(gt, results, iou_type):
+    """COCO.loadRes for a list of result dicts: ids from 1, iscrowd 0, area = w * h (bbox) or the mask area (segm,
+    computed on the device with the IoU's bits; filled in by device_evaluate)."""
+    img_set = {im['id'] for im in gt['images']}
+    out = []
+    for i, r in enumerate(results):
+        if r['image_id'] not in img_set:
+            raise AssertionError('Results do not correspond to current coco set')
+        d = dict(r)
+        d['id'] = i + 1
+        d['iscrowd'] = 0
+        if iou_type == 'bbox':
+            bb = d['bbox']
+            d['area'] = bb[2] * bb[3]
+        out.append(d)
+    return out
+
+
+@METRICS.register_module()
+class CocoMetric:
+    """mmdet CocoMetric (bbox / segm) -- `process`, `compute_metrics`, `evaluate(size)`, `dataset_meta`."""
+    default_prefix = 'coco'
+
+    def __init__(self, ann_file=None, metric='bbox', classwise=False, proposal_nums=(100, 300, 1000), iou_thrs=None,
+                 metric_items=None, format_only=False, outfile_prefix=None, file_client_args=None, backend_args=None,
+                 collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None):
+        self.metrics = metric if isinstance(metric, list) else [metric]
+        for m in self.metrics:
+            if m in ('proposal', 'proposal_fast'):
+                raise NotImplementedError(f'CocoMetric: metric {m!r} is not implemented (bbox and segm are)')
+            if m not in ('bbox', 'segm'):
+                raise KeyError(f"metric should be one of 'bbox', 'segm', 'proposal', 'proposal_fast', but got {m}.")
+        if file_client_args is not None:
+            raise RuntimeError('The `file_client_args` is deprecated, please use `backend_args` instead')
+        if backend_args is not None:
+            raise NotImplementedError('backend_args: only local files are supported (backend_args=None)')
+        self.classwise = classwise
+        self.use_mp_eval = use_mp_eval                      # same numbers: accepted and ignored
+        self.proposal_nums = list(proposal_nums)
+        if iou_thrs is None:
+            iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        self.iou_thrs = iou_thrs
+        self.metric_items = metric_items
+        self.format_only = format_only
+        if format_only:
+            assert outfile_prefix is not None, 'outfile_prefix must be not None when format_only is True'
+        self.outfile_prefix = outfile_prefix
+        self.prefix = prefix or self.default_prefix
+        self.device = device
+        self._coco_api = None
+        if ann_file is not None:
+            with open(ann_file) as f:
+                self._coco_api = json.load(f)
+            self._coco_api.setdefault('annotations', [])
+            if sort_categories:
+                self._coco_api['categories'] = sorted(self._coco_api['categories'], key=lambda c: c['id'])
+        self.cat_ids = None
+        self.img_ids = None
+        self._dataset_meta = None
+        self.results = []
+        self.eval_results = {}                              # iou type -> CocoEvalResult (unrounded stats)
+        self.timings = {}
+
+    @property
+    def dataset_meta(self):
+        return self._dataset_meta
+
+    @dataset_meta.setter
+    def dataset_meta(self, meta):
+        self._dataset_meta = meta
+
+    # ------------------------------------------------------------------ mmengine BaseMetric surface
+    def process(self, data_batch, data_samples):
+        """store (gt, result) per sample as coco_metric.py:346-391; masks may be a device bool tensor (encoded with the
+        device RLE codec) or a list of COCO RLE dicts (what `dist.gather_results` delivers)."""
+        from .rle import encode_mask_results
+        for s in data_samples:
+            pred = _get(s, 'pred_instances')
+            result = dict(img_id=_get(s, 'img_id'), bboxes=_np(_get(pred, 'bboxes')).astype(np.float32).reshape(-1, 4),
+                          scores=_np(_get(pred, 'scores')).astype(np.float32).reshape(-1),
+                          labels=_np(_get(pred, 'labels')).astype(np.int64).reshape(-1))
+            masks = _get(pred, 'masks')
+            if masks is not None:
+                result['masks'] = encode_mask_results(masks) if isinstance(masks, torch.Tensor) else list(masks)
+            ms = _get(pred, 'mask_scores')
+            if ms is not None:
+                result['mask_scores'] = _np(ms).astype(np.float32).reshape(-1)
+            ori = _get(s, 'ori_shape')
+            gt = dict(width=int(ori[1]), height=int(ori[0]), img_id=_get(s, 'img_id'))
+            if self._coco_api is None:
+                gi = _get(s, 'gt_instances')
+                g_masks = _get(gi, 'masks')
+                if isinstance(g_masks, torch.Tensor):
+                    g_masks = encode_mask_results(g_masks)
+                gt['anns'] = [dict(bbox_label=int(lb), bbox=bb, mask=mk) for bb, mk, lb in
+                              zip(_np(_get(gi, 'bboxes')).astype(np.float32).reshape(-1, 4), g_masks,
+                                  _np(_get(gi, 'labels')).reshape(-1))]
+            self.results.append((gt, result))
+
+    def evaluate(self, size):
+        """mmengine BaseMetric.evaluate: the results of `size` samples -> metrics with the `coco/` prefix."""
+        results = self.results[:size]
+        metrics = self.compute_metrics(results)
+        self.results = []
+        return {f'{self.prefix}/{k}': v for k, v in metrics.items()}
+
+    # ------------------------------------------------------------------ conversions
+    def gt_to_coco_json(self, gt_dicts):
+        """coco_metric.py:274-344 (in memory): ids from 1, categories 0..C-1, iscrowd = ignore_flag (never set), area =
+        float32 w * h of the float32 xyxy box."""
+        categories = [dict(id=i, name=n) for i, n in enumerate(self.dataset_meta['classes'])]
+        images, annotations = [], []
+        for idx, g in enumerate(gt_dicts):
+            img_id = g.get('img_id', idx)
+            images.append(dict(id=img_id, width=g['width'], height=g['height'], file_name=''))
+            for ann in g['anns']:
+                bbox = ann['bbox']
+                coco_bbox = [bbox[0], bbox[1], bbox[2] - bbox[0], bbox[3] - bbox[1]]       # float32 arithmetic
+                a = dict(id=len(annotations) + 1, image_id=img_id, bbox=[float(v) for v in coco_bbox],
+                         iscrowd=ann.get('ignore_flag', 0), category_id=int(ann['bbox_label']),
+                         area=float(coco_bbox[2] * coco_bbox[3]))
+                mask = ann.get('mask', None)
+                if mask:
+                    a['segmentation'] = mask
+                annotations.append(a)
+        return dict(images=images, categories=categories, annotations=annotations)
+
+    @staticmethod
+    def xyxy2xywh(bbox):
+        b = bbox.tolist()
+        return [b[0], b[1], b[2] - b[0], b[3] - b[1]]
+
+    def results2json(self, results, outfile_prefix=None):
+        """coco_metric.py:209-272: bbox and segm result lists (written to <prefix>.bbox.json / .segm.json when a prefix
+        is given)."""
+        bbox_json, segm_json = [], []
+        for r in results:
+            image_id = r.get('img_id')
+            labels, bboxes, scores = r['labels'], r['bboxes'], r['scores']
+            for i in range(len(labels)):
+                bbox_json.append(dict(image_id=image_id, bbox=self.xyxy2xywh(bboxes[i]), score=float(scores[i]),
+                                      category_id=self.cat_ids[labels[i]]))
+            if 'masks' not in r:
+                continue
+            mask_scores = r.get('mask_scores', scores)
+            for i in range(len(labels)):
+                m = r['masks'][i]
+                c = m['counts']
+                segm_json.append(dict(image_id=image_id, bbox=self.xyxy2xywh(bboxes[i]), score=float(mask_scores[i]),
+                                      category_id=self.cat_ids[labels[i]],
+                                      segmentation=dict(size=list(m['size']),
+                                                        counts=c.decode() if isinstance(c, bytes) else c)))
+        files = {}
+        if outfile_prefix is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(outfile_prefix)), exist_ok=True)
+            files['bbox'] = f'{outfile_prefix}.bbox.json'
+            with open(files['bbox'], 'w') as f:
+                json.dump(bbox_json, f)
+            if segm_json:
+                files['segm'] = f'{outfile_prefix}.segm.json'
+                with open(files['segm'], 'w') as f:
+                    json.dump(segm_json, f)
+        return dict(bbox=bbox_json, segm=segm_json) if segm_json else dict(bbox=bbox_json), files
+
+    # ------------------------------------------------------------------ metrics
+    def _gt_with_rles(self, coco):
+        """annToRLE of every gt segmentation (polygons rasterised + merged, uncompressed RLE compressed)."""
+        hw = {im['id']: (im['height'], im['width']) for im in coco['images']}
+        anns = []
+        for a in coco['annotations']:
+            a = dict(a)
+            if a['image_id'] in hw and 'segmentation' in a and a['segmentation'] is not None:
+                h, w = hw[a['image_id']]
+                a['segmentation'] = ann_to_rle(a['segmentation'], h, w)
+            anns.append(a)
+        return dict(coco, annotations=anns)
+
+    def compute_metrics(self, results):
+        import time
+        gts, preds = zip(*results) if results else ((), ())
+        coco = self._coco_api if self._coco_api is not None else self.gt_to_coco_json(gts)
+        self.coco_gt = coco                                 # the ground truth the numbers were computed against
+        classes = list(self.dataset_meta['classes'])
+        if self.cat_ids is None:
+            self.cat_ids = [c['id'] for c in coco['categories'] if c['name'] in classes]
+        if self.img_ids is None:
+            self.img_ids = list(dict.fromkeys(im['id'] for im in coco['images']))
+        result_lists, _ = self.results2json(preds, self.outfile_prefix)
+        eval_results = OrderedDict()
+        if self.format_only:
+            return eval_results
+        device = torch.device(self.device) if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        names = {n: i for i, n in enumerate(STAT_NAMES)}
+        gt_rle = None
+        for metric in self.metrics:
+            preds_m = result_lists.get(metric)
+            if preds_m is None:
+                raise KeyError(f'{metric} is not in results')
+            if len(preds_m) == 0:                       # pycocotools loadRes indexes anns[0]: mmdet logs and stops
+                break
+            t0 = time.perf_counter()
+            if metric == 'segm':
+                preds_m = [{k: v for k, v in x.items() if k != 'bbox'} for x in preds_m]
+                if gt_rle is None:
+                    gt_rle = self._gt_with_rles(coco)
+                gt_m = gt_rle
+            else:
+                gt_m = coco
+            dts = load_res(gt_m, preds_m, metric)
+            for d in dts:
+                if metric == 'segm':
+                    c = d['segmentation']['counts']
+                    d['segmentation'] = dict(size=d['segmentation']['size'], counts=c.encode() if isinstance(c, str) else c)
+            tm = {}
+            ev = device_evaluate(gt_m, dts, metric, self.img_ids, self.cat_ids, self.iou_thrs, self.proposal_nums,
+                                 device, timings=tm)
+            tm['total'] = time.perf_counter() - t0
+            self.timings[metric] = tm
+            self.eval_results[metric] = ev
+            if self.metric_items is not None:
+                for item in self.metric_items:
+                    if item not in names:
+                        raise KeyError(f'metric item "{item}" is not supported')
+            if self.classwise:
+                precisions = ev.eval['precision']
+                assert len(self.cat_ids) == precisions.shape[2]
+                cname = {c['id']: c['name'] for c in coco['categories']}
+                for idx, cat_id in enumerate(self.cat_ids):
+                    p = precisions[:, :, idx, 0, -1]
+                    p = p[p > -1]
+                    ap = np.mean(p) if p.size else float('nan')
+                    eval_results[f'{cname[cat_id]}_precision'] = round(ap, 3)
+            items = self.metric_items if self.metric_items is not None else list(STAT_NAMES[:6])
+            for item in items:
+                val = ev.stats[names[item]]
+                eval_results[f'{metric}_{item}'] = float(f'{round(val, 3)}')
+        return eval_results
+
+    def summary_table(self):
+        """mmdet's printed summary: pycocotools' 12 lines per iou type."""
+        lines = []
+        spec = [(1, None, 'all', 2), (1, .5, 'all', 2), (1, .75, 'all', 2), (1, None, 'small', 2), (1, None, 'medium', 2),
+                (1, None, 'large', 2), (0, None, 'all', 0), (0, None, 'all', 1), (0, None, 'all', 2),
+                (0, None, 'small', 2), (0, None, 'medium', 2), (0, None, 'large', 2)]
+        for metric, ev in self.eval_results.items():
+            lines.append(f'Evaluate annotation type *{metric}*')
+            for v, (ap, thr, area, mi) in zip(ev.stats, spec):
+                title = 'Average Precision' if ap == 1 else 'Average Recall'
+                typ = '(AP)' if ap == 1 else '(AR)'
+                iou = '0.50:0.95' if thr is None else f'{thr:0.2f}'
+                lines.append(f' {title:<18} {typ} @[ IoU={iou:<9} | area={area:>6s} | '
+                             f'maxDets={self.proposal_nums[mi]:>3d} ] = {v:0.3f}')
+        return '\n'.join(lines)

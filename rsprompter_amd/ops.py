@@ -1246,6 +1246,90 @@ def rle_to_string(counts, n, k, flat_cap):
     return lens, offs, flat
 
 
+# ----------------------------------------------------------------------------- COCO evaluation (csrc/cocoeval.hip)
+def rle_from_string(flat, offs, cap=1024):
+    """COCO compressed strings flat[offs[i]:offs[i + 1]] (uint8 / int64 device tensors) -> (counts int32 [k, cap'],
+    n int32 [k]) on the device (rsp_rle_from_string); grows `cap` and retries when a string holds more counts."""
+    lib = _lib.load()
+    k = offs.shape[0] - 1
+    dev = offs.device
+    while True:
+        counts = torch.empty((max(k, 1), cap), dtype=torch.int32, device=dev)
+        n = torch.zeros((max(k, 1),), dtype=torch.int32, device=dev)
+        if k <= 0:
+            return counts[:0], n[:0]
+        _lib.check(lib.rsp_rle_from_string(_ptr(flat), offs.data_ptr(), k, cap, counts.data_ptr(), n.data_ptr(),
+                                           _stream()), "rsp_rle_from_string")
+        need = int((-n).max().item())
+        if need <= 0:
+            return counts, n
+        cap = 1 << (need - 1).bit_length()
+
+
+def rle_to_bits(counts, n, word_offs):
+    """run counts (int32 [k, cap], n int32 [k]) -> (bits int64 [word_offs[k]] (64-bit words, mask i at
+    word_offs[i]..word_offs[i + 1]), area int64 [k], wrange int32 [k, 2]) (rsp_rle_to_bits)."""
+    lib = _lib.load()
+    k = n.shape[0]
+    dev = n.device
+    nw = int(word_offs[-1].item()) if k else 0
+    bits = torch.empty((max(nw, 1),), dtype=torch.int64, device=dev)
+    area = torch.empty((max(k, 1),), dtype=torch.int64, device=dev)
+    wrange = torch.empty((max(k, 1), 2), dtype=torch.int32, device=dev)
+    if k:
+        _lib.check(lib.rsp_rle_to_bits(counts.data_ptr(), n.data_ptr(), k, counts.shape[1], word_offs.data_ptr(),
+                                       bits.data_ptr(), area.data_ptr(), wrange.data_ptr(), _stream()), "rsp_rle_to_bits")
+    return bits, area[:k], wrange[:k]
+
+
+COCO_IOU_BBOX, COCO_IOU_SEGM = 0, 1
+COCO_UNIT_BYTES = 40
+
+
+def coco_units(dt0, gt0, out0, nd, ng, nwords, device):
+    """RspCocoUnit records (include/rsp_hip.h) from per-unit numpy columns -> uint8 device tensor."""
+    import numpy as np
+    rec = np.zeros(len(nd), dtype=np.dtype([('dt0', '<i8'), ('gt0', '<i8'), ('out0', '<i8'), ('nd', '<i4'),
+                                             ('ng', '<i4'), ('nwords', '<i4'), ('pad', '<i4')]))
+    rec['dt0'], rec['gt0'], rec['out0'], rec['nd'], rec['ng'], rec['nwords'] = dt0, gt0, out0, nd, ng, nwords
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+
+
+def coco_iou(units, n_iou, mode, *, gt_crowd, dt_box=None, gt_box=None, dt_bits=None, gt_bits=None, dt_woff=None,
+             gt_woff=None, dt_wrange=None, gt_wrange=None, dt_area=None, gt_area=None):
+    """IoU blocks of the units (uint8 device tensor holding RspCocoUnit records, `coco_units`) -> float64 [n_iou]."""
+    lib = _lib.load()
+    dev = units.device
+    iou = torch.zeros((max(n_iou, 1),), dtype=torch.float64, device=dev)
+    nu = units.numel() // COCO_UNIT_BYTES
+    if nu:
+        _lib.check(lib.rsp_coco_iou(units.data_ptr(), nu, mode, _ptr(dt_bits), _ptr(gt_bits), _ptr(dt_woff),
+                                    _ptr(gt_woff), _ptr(dt_wrange), _ptr(gt_wrange), _ptr(dt_area), _ptr(gt_area),
+                                    _ptr(dt_box), _ptr(gt_box), gt_crowd.data_ptr(), iou.data_ptr(), _stream()),
+                   "rsp_coco_iou")
+    return iou[:n_iou]
+
+
+def coco_match(units, iou, gt_area, gt_crowd, gt_id, dt_area, area_rng, thrs, n_dt):
+    """evaluateImg for every unit x area range x threshold (rsp_coco_match) -> (dtm int64 [A, T, n_dt],
+    dtig uint8 [A, T, n_dt], npig int32 [n_units, A]).  Per-dt / per-gt inputs hold at least one element."""
+    lib = _lib.load()
+    dev = units.device
+    nu = units.numel() // COCO_UNIT_BYTES
+    A, T = area_rng.shape[0], thrs.shape[0]
+    n_gt = gt_area.shape[0]
+    ws = torch.empty((max(n_gt * A * T, 1),), dtype=torch.uint8, device=dev)
+    dtm = torch.zeros((A, T, max(n_dt, 1)), dtype=torch.int64, device=dev)
+    dtig = torch.zeros((A, T, max(n_dt, 1)), dtype=torch.uint8, device=dev)
+    npig = torch.zeros((max(nu, 1), A), dtype=torch.int32, device=dev)
+    if nu:
+        _lib.check(lib.rsp_coco_match(units.data_ptr(), nu, iou.data_ptr(), gt_area.data_ptr(), gt_crowd.data_ptr(),
+                                      gt_id.data_ptr(), dt_area.data_ptr(), area_rng.data_ptr(), A, thrs.data_ptr(), T,
+                                      n_dt, ws.data_ptr(), dtm.data_ptr(), dtig.data_ptr(), npig.data_ptr(), _stream()),
+                   "rsp_coco_match")
+    return dtm[:, :, :n_dt], dtig[:, :, :n_dt], npig[:nu]
+
+
 # ----------------------------------------------------------------------------- query prompter ops
 def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, add=None):
     """GroupNorm on channels-last [B, ..., C]; `add` (same shape) is added after the norm."""
