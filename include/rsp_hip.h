@@ -594,6 +594,36 @@ int rsp_coco_match(const RspCocoUnit* units, int32_t n_units, const double* iou,
                    const double* thrs, int32_t T, int64_t n_dt, uint8_t* gtm_ws, int64_t* dtm, uint8_t* dtig,
                    int32_t* npig, rsp_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Sliced inference on large scenes (csrc/large_image.hip)        */
+/* ------------------------------------------------------------------------ */
+/* Tile front end: replaces sahi.slicing.slice_image (host crops, demo/large_image_demo.py:133-141) followed by the     */
+/* test pipeline's Resize + Pad per patch (:146-160 -> inference_detector).  scene: the decoded image [SH, SW, 3]       */
+/* (uint8 or fp32) on the device; origins: DEVICE int32 [B, 2] = (x0, y0) of B tiles of one size (th, tw), clamped into  */
+/* the scene by the kernel; dst [B, 3, Hp, Wp] fp32.  Tile i equals rsp_resize_pad of the contiguous crop                */
+/* scene[y0:y0+th, x0:x0+tw] bit for bit (one interpolation function, csrc/rsp_common.h); the remaining arguments are     */
+/* rsp_resize_pad's.  th == Hn, tw == Wn on a uint8 scene is a pure convert-and-pad (16-byte accesses).  B <= 65535.     */
+int rsp_slice_resize_pad(const void* scene, int32_t src_is_u8, int32_t SH, int32_t SW, const int32_t* origins,
+                         int32_t B, int32_t th, int32_t tw, float* dst, int32_t Hn, int32_t Wn, int32_t Hp, int32_t Wp,
+                         const float* pad3, int32_t normalise, int32_t swap_rb, const float* mean3, const float* std3,
+                         rsp_stream_t stream);
+/* Run-domain shift: replaces sahi.slicing.shift_masks (mmdet/utils/large_image.py:63-65: every instance mask padded to  */
+/* the full scene as a dense array) + encode_mask_results on that array.  counts_in [k, cap_in] / n_in [k]: run counts of */
+/* k masks of ONE tile size (h, w) as rsp_mask_rle writes them; offsets: DEVICE int32 [k, 2] = (ox, oy) per instance,      */
+/* clamped to [0, W - w] x [0, H - h].  counts_out [k, cap_out] / n_out [k]: the COCO run counts of the same masks placed */
+/* at [oy:oy+h, ox:ox+w] of a zero (H, W) canvas, same conventions: n_out = -(needed) when cap_out is too small (the row   */
+/* is then undefined), n_in <= 0 gives n_out = 0.  In the column-major pixel stream: ox*H + oy zeros, the tile's stream    */
+/* with H - h zeros inserted after every tile column (H - h - oy after the last), (W - ox - w)*H zeros; adjacent runs of  */
+/* one value merge.  H * W >= 2^31 is refused (RSP_EINVAL): COCO's counts are 32-bit.                                     */
+int rsp_rle_shift(const uint32_t* counts_in, const int32_t* n_in, int32_t k, int32_t cap_in, const int32_t* offsets,
+                  int32_t h, int32_t w, int32_t H, int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out,
+                  rsp_stream_t stream);
+/* shift_masks itself, for callers who want dense scene masks (mmdet/utils/large_image.py:27-72 shift_predictions):       */
+/* out [k, H, W] bool bytes = masks [k, h, w] at offsets (DEVICE int32 [k, 2] = (ox, oy), clamped), zero elsewhere.       */
+/* k <= 65535.                                                                                                           */
+int rsp_paste_tiles(const uint8_t* masks, const int32_t* offsets, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W,
+                    uint8_t* out, rsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,12 @@ PROTOTYPES = {
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rsp_coco_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_slice_resize_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                     c_int, c_int, ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_float),
+                                     ctypes.POINTER(c_float), c_void_p]),
+    "rsp_rle_shift": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                              c_int, c_void_p]),
+    "rsp_paste_tiles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -78,6 +78,23 @@ class TestPipeline:
             rgb = np.asarray(im.convert('RGB'))
         return np.ascontiguousarray(rgb[:, :, ::-1])                  # BGR like cv2.imread / mmcv.imfrombytes
 
+    def geometry(self, h, w):
+        """resized size (nh, nw), padded size (ph, pw) and the shape metainfo the pipeline gives an [h, w] image"""
+        if self.scale is not None:
+            if self.keep_ratio:
+                (nw, nh), _ = rescale_size((w, h), self.scale)
+            else:
+                nw, nh = int(self.scale[0]), int(self.scale[1])
+        else:
+            nw, nh = w, h
+        pw, ph = self.pad_size if self.pad_size is not None else (nw, nh)
+        pw, ph = max(pw, nw), max(ph, nh)                             # mmcv.impad never crops
+        meta = dict(ori_shape=(h, w),
+                    # Resize sets img_shape to the resized size, mmcv's Pad then overwrites it with the padded one
+                    img_shape=(ph, pw) if self.pad_size is not None else (nh, nw),
+                    scale_factor=(nw / w, nh / h), pad_shape=(ph, pw, 3), keep_ratio=self.keep_ratio)
+        return nh, nw, ph, pw, meta
+
     def __call__(self, data):
         data = dict(data)
         img = data.get('img')
@@ -89,20 +106,9 @@ class TestPipeline:
             raise ValueError('expected an [H, W, 3] image')
         h, w = int(img.shape[0]), int(img.shape[1])
         dimg = img.to(self.device, non_blocking=True)
-        if self.scale is not None:
-            if self.keep_ratio:
-                (nw, nh), _ = rescale_size((w, h), self.scale)
-            else:
-                nw, nh = int(self.scale[0]), int(self.scale[1])
-        else:
-            nw, nh = w, h
-        pw, ph = self.pad_size if self.pad_size is not None else (nw, nh)
-        pw, ph = max(pw, nw), max(ph, nh)                             # mmcv.impad never crops
+        nh, nw, ph, pw, meta = self.geometry(h, w)
         inputs = ops.resize_pad(dimg, (nh, nw), (ph, pw), self.pad_val)
-        meta = dict(img_id=data.get('img_id', 0), img_path=data.get('img_path'), ori_shape=(h, w),
-                    # Resize sets img_shape to the resized size, mmcv's Pad then overwrites it with the padded one
-                    img_shape=(ph, pw) if self.pad_size is not None else (nh, nw),
-                    scale_factor=(nw / w, nh / h), pad_shape=(ph, pw, 3), keep_ratio=self.keep_ratio)
+        meta.update(img_id=data.get('img_id', 0), img_path=data.get('img_path'))
         sample = DetDataSample(metainfo={k: meta[k] for k in self.meta_keys if k in meta})
         return dict(inputs=inputs, data_samples=sample)
 
@@ -195,3 +201,6 @@ class DetInferencer:
             for s in self.model.test_step(data):
                 preds.append(s if return_datasamples else self.pred2dict(s))
         return dict(predictions=preds, visualization=[])
+
+
+from .large_image import inference_large_image  # noqa: E402,F401  (sliced inference on large scenes)

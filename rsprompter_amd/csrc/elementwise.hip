@@ -333,27 +333,7 @@ __global__ __launch_bounds__(256) void resize_pad_kernel(const T* __restrict__ s
        i += (int64_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % Wp), y = (int)(i / Wp);
     float v[3] = {p0, p1, p2};
-    if (y < Hn && x < Wn) {
-      float fx = (float)(((double)x + 0.5) * sx_scale - 0.5);
-      int x0 = (int)floorf(fx);
-      fx -= (float)x0;
-      if (x0 < 0) { x0 = 0; fx = 0.f; }
-      if (x0 >= W - 1) { x0 = W - 1; fx = 0.f; }
-      float fy = (float)(((double)y + 0.5) * sy_scale - 0.5);
-      int y0 = (int)floorf(fy);
-      fy -= (float)y0;
-      if (y0 < 0) { y0 = 0; fy = 0.f; }
-      if (y0 >= H - 1) { y0 = H - 1; fy = 0.f; }
-      const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
-      const T* r0 = src + ((int64_t)y0 * W) * 3;
-      const T* r1 = src + ((int64_t)y1 * W) * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float top = (float)r0[x0 * 3 + c] * (1.f - fx) + (float)r0[x1 * 3 + c] * fx;
-        const float bot = (float)r1[x0 * 3 + c] * (1.f - fx) + (float)r1[x1 * 3 + c] * fx;
-        v[c] = top * (1.f - fy) + bot * fy;
-      }
-    }
+    if (y < Hn && x < Wn) rsp_bilinear_px(src, (int64_t)W * 3, H, W, sx_scale, sy_scale, x, y, v);
     if (normalise) {
       const float a = swap_rb ? v[2] : v[0], b = v[1], c2 = swap_rb ? v[0] : v[2];
       v[0] = (a - m0) / s0; v[1] = (b - m1) / s1; v[2] = (c2 - m2) / s2;

@@ -239,3 +239,32 @@ static inline FastDiv make_fastdiv(int dv) {
   f.sh1 = 1; f.sh2 = l - 1;
   return f;
 }
+
+// One pixel of cv2.resize INTER_LINEAR on an HWC-interleaved 3-channel image (uint8 or fp32): the arithmetic of
+// resize_pad_kernel (elementwise.hip, where it is specified) and of slice_resize_pad_kernel (large_image.hip), which reads
+// a window of a larger image -- `src` then points at the window's first pixel and `pitch` (elements per row) is the
+// scene's.  One function, so that a tile cut by the kernel is bit-identical to the same crop resized on its own.
+// sx_scale = W / Wn, sy_scale = H / Hn in double (cv2's scales); (x, y) inside the resized [Hn, Wn] region.
+template <typename T>
+__device__ __forceinline__ void rsp_bilinear_px(const T* __restrict__ src, int64_t pitch, int H, int W, double sx_scale,
+                                                double sy_scale, int x, int y, float v[3]) {
+  float fx = (float)(((double)x + 0.5) * sx_scale - 0.5);
+  int x0 = (int)floorf(fx);
+  fx -= (float)x0;
+  if (x0 < 0) { x0 = 0; fx = 0.f; }
+  if (x0 >= W - 1) { x0 = W - 1; fx = 0.f; }
+  float fy = (float)(((double)y + 0.5) * sy_scale - 0.5);
+  int y0 = (int)floorf(fy);
+  fy -= (float)y0;
+  if (y0 < 0) { y0 = 0; fy = 0.f; }
+  if (y0 >= H - 1) { y0 = H - 1; fy = 0.f; }
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+  const T* r0 = src + (int64_t)y0 * pitch;
+  const T* r1 = src + (int64_t)y1 * pitch;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float top = (float)r0[x0 * 3 + c] * (1.f - fx) + (float)r0[x1 * 3 + c] * fx;
+    const float bot = (float)r1[x0 * 3 + c] * (1.f - fx) + (float)r1[x1 * 3 + c] * fx;
+    v[c] = top * (1.f - fy) + bot * fy;
+  }
+}

@@ -1,0 +1,310 @@
+"""Sliced inference on large scenes: the reference's `demo/large_image_demo.py` +
+`mmdet/utils/large_image.py` (`shift_predictions`, `merge_results_by_nms`) over `sahi.slicing`
+(`get_slice_bboxes`, `slice_image`, `shift_bboxes`, `shift_masks`) and `mmcv.ops.batched_nms`.
+
+The reference cuts the scene into overlapping patches on the host, runs the detector patch by patch, pads every instance
+mask to the full scene as a dense array and merges with a class-aware NMS.  Here the decoded scene is uploaded once;
+tiles are cut by a kernel straight into the model's input batch (`rsp_slice_resize_pad`); a batch's tile masks are
+reduced to run counts as soon as it is done (`rsp_mask_rle`); the merge is `rsp_batched_nms`; and the scene-sized COCO
+RLE of the kept instances is produced in the run domain from the tile-sized runs (`rsp_rle_shift` ->
+`rsp_rle_to_string`), so a scene-sized dense mask exists only when the caller asks for one.
+
+CLI: `python -m rsprompter_amd.large_image IMG_OR_DIR CONFIG CHECKPOINT --out-dir DIR` writes one `<name>.json` per scene.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from .structures import DetDataSample, InstanceData
+
+# masks='dense' materialises bool [K, H, W]; a request beyond this many bytes is refused with the figure in the message
+# (settable, like ops.NMS_WORKSPACE_LIMIT_BYTES)
+DENSE_MASK_LIMIT_BYTES = 8 << 30
+MAX_PATCH_WIDTH = 8192          # rsp_mask_rle is specified for W <= 8192
+
+
+# ----------------------------------------------------------------------------------------------------------------- host
+def slice_bboxes(height, width, slice_height, slice_width, overlap_height_ratio=0.2, overlap_width_ratio=0.2):
+    """sahi.slicing.get_slice_bboxes(auto_slice_resolution=False): [xmin, ymin, xmax, ymax] per tile, row-major.  A tile
+    that would cross the right / bottom edge is moved back inside, so all tiles have the size
+    (min(slice_height, height), min(slice_width, width))."""
+    slice_bboxes_ = []
+    y_max = y_min = 0
+    y_overlap = int(overlap_height_ratio * slice_height)
+    x_overlap = int(overlap_width_ratio * slice_width)
+    if slice_height <= y_overlap or slice_width <= x_overlap or slice_height <= 0 or slice_width <= 0:
+        raise ValueError('the overlap must be smaller than the slice')
+    while y_max < height:
+        x_min = x_max = 0
+        y_max = y_min + slice_height
+        while x_max < width:
+            x_max = x_min + slice_width
+            if y_max > height or x_max > width:
+                xmax = min(width, x_max)
+                ymax = min(height, y_max)
+                xmin = max(0, xmax - slice_width)
+                ymin = max(0, ymax - slice_height)
+                slice_bboxes_.append([xmin, ymin, xmax, ymax])
+            else:
+                slice_bboxes_.append([x_min, y_min, x_max, y_max])
+            x_min = x_max - x_overlap
+        y_min = y_max - y_overlap
+    return slice_bboxes_
+
+
+def shift_bboxes(bboxes, offset):
+    """sahi.slicing.shift_bboxes: boxes [n, 4] + (ox, oy, ox, oy) in the boxes' dtype (fp32)."""
+    if bboxes.shape[-1] != 4:
+        raise NotImplementedError(f'boxes with {bboxes.shape[-1]} columns (rotated boxes) are not supported')
+    return bboxes + bboxes.new_tensor([offset[0], offset[1], offset[0], offset[1]])
+
+
+def _offsets_tensor(offsets, counts, dev):
+    """per-instance (ox, oy) int32 [sum(counts), 2] on the device from per-tile offsets and per-tile instance counts"""
+    off = torch.tensor([[int(o[0]), int(o[1])] for o in offsets], dtype=torch.int32).reshape(-1, 2)
+    rep = torch.repeat_interleave(off, torch.tensor(list(counts), dtype=torch.int64), dim=0)
+    return rep.to(dev)
+
+
+def shift_predictions(det_data_samples, offsets, src_image_shape):
+    """mmdet/utils/large_image.py:27-72: the patch results moved into the scene and concatenated (tile order, then the
+    tile's own order) -> InstanceData(bboxes, scores, labels[, masks bool [n, H, W] dense, as the reference])."""
+    assert len(det_data_samples) == len(offsets), 'The `results` should has the same length with `offsets`.'
+    insts = [s.pred_instances for s in det_data_samples]
+    for p in insts:
+        if p.bboxes.shape[-1] != 4:
+            raise NotImplementedError(f'boxes with {p.bboxes.shape[-1]} columns (rotated boxes) are not supported')
+    out = InstanceData()
+    out.bboxes = torch.cat([shift_bboxes(p.bboxes, o) for p, o in zip(insts, offsets)], 0)
+    out.scores = torch.cat([p.scores for p in insts], 0)
+    out.labels = torch.cat([p.labels for p in insts], 0)
+    if all('masks' in p and p.masks is not None for p in insts) and insts:
+        shapes = {tuple(p.masks.shape[1:]) for p in insts}
+        if len(shapes) != 1:
+            raise ValueError(f'the patches must have one size, got masks of {sorted(shapes)}')
+        masks = torch.cat([p.masks for p in insts], 0)
+        off = _offsets_tensor(offsets, [len(p.scores) for p in insts], masks.device)
+        H, W = int(src_image_shape[0]), int(src_image_shape[1])
+        _check_dense(masks.shape[0], H, W)
+        out.masks = ops.paste_tiles(masks.to(torch.bool), off, (H, W))
+    return out
+
+
+def _check_nms_cfg(nms_cfg):
+    cfg = dict(nms_cfg)
+    typ = cfg.pop('type', 'nms')
+    if typ != 'nms':
+        raise NotImplementedError(f"merge nms type {typ!r}: only 'nms' (mmcv.ops.nms through batched_nms) is implemented")
+    if cfg.get('class_agnostic', False):
+        raise NotImplementedError('class_agnostic merging is not implemented')
+    return float(cfg.get('iou_threshold', cfg.get('iou_thr', 0.5)))
+
+
+def merge_results_by_nms(results, offsets, src_image_shape, nms_cfg):
+    """mmdet/utils/large_image.py:75-104: shift, then mmcv.ops.batched_nms over all instances of the scene; returns a
+    DetDataSample with the metainfo of results[0] and the kept instances in batched_nms' order (descending score)."""
+    thr = _check_nms_cfg(nms_cfg)
+    inst = shift_predictions(results, offsets, src_image_shape)
+    keep = ops.nms_flat(inst.bboxes, inst.scores, inst.labels, thr)
+    merged = DetDataSample(metainfo=results[0].metainfo)
+    merged.pred_instances = inst[keep]
+    return merged
+
+
+def _check_dense(k, H, W):
+    need = int(k) * int(H) * int(W)
+    if need > DENSE_MASK_LIMIT_BYTES:
+        raise ValueError(f'dense masks of {k} instances on a {H} x {W} scene need {need} bytes (limit '
+                         f'large_image.DENSE_MASK_LIMIT_BYTES = {DENSE_MASK_LIMIT_BYTES}): use masks="rle"')
+
+
+# ------------------------------------------------------------------------------------------------------------- pipeline
+def _encode_tile_masks(masks, cap):
+    """bool [k, h, w] -> (counts int32 [k, max runs], n int32 [k], cap): rsp_mask_rle with one small device-to-host read
+    (the run numbers) that tells whether every mask fit; grows `cap` and re-encodes like rle.encode_rle_strings."""
+    k = int(masks.shape[0])
+    dev = masks.device
+    if k == 0:
+        return torch.zeros((0, 1), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), cap
+    while True:
+        counts = torch.empty((k, cap), dtype=torch.int32, device=dev)
+        ws = torch.empty((k, cap), dtype=torch.int32, device=dev)
+        n = torch.empty((k,), dtype=torch.int32, device=dev)
+        ops.mask_rle_into(masks, counts, ws, n)
+        nh = n.cpu()
+        need = int((-nh).max())
+        if need > 0:
+            cap = 1 << (need - 1).bit_length()
+            continue
+        return counts[:, :int(nh.max())].clone(), n, cap
+
+
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
+    """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
+    k = int(n.shape[0])
+    H, W = scene_hw
+    if k == 0:
+        return []
+    # a column end inside a run adds at most one ones-run and one zero run: n_in + 2 w bounds the scene's runs
+    cap_out = int(counts.shape[1]) + 2 * int(tile_hw[1]) + 2
+    while True:
+        sc, sn = ops.rle_shift(counts, n, offsets, tile_hw, scene_hw, cap_out)
+        need = int((-sn).max().item())
+        if need <= 0:
+            break
+        cap_out = 1 << (need - 1).bit_length()
+    flat_cap = 2 * int(sn.sum().item()) + 16
+    while True:
+        _, offs, flat = ops.rle_to_string(sc, sn, k, flat_cap)
+        offs_h = offs.cpu()
+        if int(offs_h[-1]) <= flat_cap:
+            break
+        flat_cap = int(offs_h[-1])
+    buf, o = flat[:int(offs_h[-1])].cpu().numpy().tobytes(), offs_h.tolist()
+    return [dict(size=[int(H), int(W)], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+
+
+@torch.no_grad()
+def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
+                          batch_size=1, masks='rle', return_patches=False):
+    """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
+    patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
+    labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
+    (masks='rle') or a bool [K, H, W] device tensor (masks='dense').  return_patches=True: (sample, per-tile samples,
+    starting_pixels)."""
+    from .apis import TestPipeline, get_test_pipeline_cfg
+    if merge_nms_type != 'nms':
+        raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms' is implemented (soft_nms and the other "
+                                  'mmcv variants are not)')
+    if masks not in ('rle', 'dense'):
+        raise ValueError("masks must be 'rle' or 'dense'")
+    ph_, pw_ = (int(patch_size), int(patch_size)) if isinstance(patch_size, (int, float)) else (int(patch_size[0]), int(patch_size[1]))
+    if pw_ > MAX_PATCH_WIDTH:
+        raise ValueError(f'a patch {pw_} pixels wide: the tile RLE kernel is specified for widths up to {MAX_PATCH_WIDTH}')
+    dev = next(model.parameters()).device
+    ops.require_device(dev)
+    pipe = TestPipeline(get_test_pipeline_cfg(model.cfg), device=dev)
+    img_path = None
+    if isinstance(img, (str, os.PathLike)):
+        img_path = str(img)
+        img = pipe._decode(img_path)
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError('expected an [H, W, 3] image')
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if H * W >= 2 ** 31:
+        raise ValueError(f'a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
+    scene = img.to(dev).contiguous()                                    # the one upload
+    tiles = slice_bboxes(H, W, ph_, pw_, patch_overlap_ratio, patch_overlap_ratio)
+    starting_pixels = [(t[0], t[1]) for t in tiles]
+    th, tw = min(ph_, H), min(pw_, W)
+    nh, nw, ph, pw, meta = pipe.geometry(th, tw)
+    origins = torch.tensor(starting_pixels, dtype=torch.int32).reshape(-1, 2).to(dev)
+
+    boxes, scores, labels, tile_of, runs, run_n, dense_tiles, patch_samples = [], [], [], [], [], [], [], []
+    cap = 4096
+    for b0 in range(0, len(tiles), batch_size):
+        nb = min(batch_size, len(tiles) - b0)
+        inputs = ops.slice_resize_pad(scene, origins[b0:b0 + nb], (th, tw), (nh, nw), (ph, pw), pipe.pad_val)
+        samples = [DetDataSample(metainfo={k: v for k, v in dict(meta, img_id=b0 + j, img_path=img_path).items()
+                                           if k in pipe.meta_keys}) for j in range(nb)]
+        res = model.test_step(dict(inputs=[inputs[j] for j in range(nb)], data_samples=samples))
+        insts = [r.pred_instances for r in res]
+        for j, p in enumerate(insts):
+            if p.bboxes.shape[-1] != 4:
+                raise NotImplementedError(f'boxes with {p.bboxes.shape[-1]} columns (rotated boxes) are not supported')
+            boxes.append(p.bboxes)
+            scores.append(p.scores)
+            labels.append(p.labels)
+            tile_of.append(torch.full((int(p.scores.shape[0]),), b0 + j, dtype=torch.int64, device=dev))
+        if all('masks' in p and p.masks is not None for p in insts):
+            bm = torch.cat([p.masks for p in insts], 0).to(torch.bool)
+            if masks == 'dense':
+                dense_tiles.append(bm)
+            else:
+                c, n, cap = _encode_tile_masks(bm, cap)                 # the batch's dense masks go once the runs fit
+                runs.append(c)
+                run_n.append(n)
+            del bm
+        if return_patches:
+            patch_samples.extend(res)
+        del res, insts
+
+    cat = (lambda xs, dt: torch.cat(xs, 0) if xs else torch.zeros((0,), dtype=dt, device=dev))
+    tile_of = cat(tile_of, torch.int64)
+    off_all = origins.to(torch.int64)[tile_of]                          # [n, 2] = (ox, oy)
+    all_boxes = (torch.cat(boxes, 0) if boxes else torch.zeros((0, 4), device=dev))
+    all_boxes = all_boxes + torch.cat([off_all, off_all], 1).to(all_boxes.dtype)       # sahi shift_bboxes, fp32
+    all_scores, all_labels = cat(scores, torch.float32), cat(labels, torch.int64)
+    keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
+    out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
+    koff = off_all[keep].to(torch.int32).contiguous()
+    if masks == 'dense' and dense_tiles:
+        _check_dense(keep.shape[0], H, W)
+        out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
+    elif runs:
+        # only the kept instances' runs are gathered, batch by batch, into one [K, widest] array
+        width = max(int(c.shape[1]) for c in runs)
+        kc = torch.zeros((int(keep.shape[0]), width), dtype=torch.int32, device=dev)
+        r0 = 0
+        for c in runs:
+            sel = ((keep >= r0) & (keep < r0 + c.shape[0])).nonzero().view(-1)
+            kc[sel, :c.shape[1]] = c[keep[sel] - r0]
+            r0 += c.shape[0]
+        out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W))
+    sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
+    sample.pred_instances = out
+    sample.keep = keep                                                  # indices into the tile-ordered concatenation
+    if return_patches:
+        return sample, patch_samples, starting_pixels
+    return sample
+
+
+def pred2dict(sample, score_thr=0.0):
+    """DetInferencer.pred2dict form (det_inferencer.py:573-627): labels, scores, bboxes, masks as RLE with `counts` as str"""
+    p = sample.pred_instances
+    sel = (p.scores >= score_thr).nonzero().view(-1).tolist()
+    lab, sc, bb = p.labels.tolist(), p.scores.tolist(), p.bboxes.tolist()
+    out = dict(labels=[lab[i] for i in sel], scores=[sc[i] for i in sel], bboxes=[bb[i] for i in sel])
+    if 'masks' in p and p.masks is not None:
+        rles = p.masks
+        if isinstance(rles, torch.Tensor):
+            from .rle import encode_mask_results
+            rles = encode_mask_results(rles) if rles.shape[0] else []
+        out['masks'] = [dict(size=rles[i]['size'], counts=rles[i]['counts'].decode()) for i in sel]
+    return out
+
+
+def main(argv=None):
+    import argparse
+    from .apis import DetInferencer, init_detector
+    ap = argparse.ArgumentParser(description='Sliced inference on large images (demo/large_image_demo.py without drawing)')
+    ap.add_argument('img', help='Image path or a directory of images')
+    ap.add_argument('config', help='Config file')
+    ap.add_argument('checkpoint', help='Checkpoint file')
+    ap.add_argument('--out-dir', default='./output', help='one <name>.json per scene is written here')
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--score-thr', type=float, default=0.3, help='Bbox score threshold')
+    ap.add_argument('--patch-size', type=int, default=640, help='The size of patches')
+    ap.add_argument('--patch-overlap-ratio', type=float, default=0.25, help='Ratio of overlap between two patches')
+    ap.add_argument('--merge-iou-thr', type=float, default=0.25, help='IoU threshould for merging results')
+    ap.add_argument('--merge-nms-type', default='nms', help='NMS type for merging results')
+    ap.add_argument('--batch-size', type=int, default=1, help='Batch size of patches')
+    a = ap.parse_args(argv)
+    model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
+    os.makedirs(a.out_dir, exist_ok=True)
+    for path in DetInferencer._inputs_to_list(a.img):
+        s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
+                                  a.batch_size)
+        dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + '.json')
+        with open(dst, 'w') as f:
+            json.dump(pred2dict(s, a.score_thr), f)
+        print(f'{path}: {len(s.pred_instances.scores)} instances -> {dst}')
+
+
+if __name__ == '__main__':
+    main()

@@ -1246,6 +1246,93 @@ def rle_to_string(counts, n, k, flat_cap):
     return lens, offs, flat
 
 
+# ----------------------------------------------------------------------------- large scenes (csrc/large_image.hip)
+def slice_resize_pad(scene_hwc, origins, tile_hw, new_hw, pad_hw, pad_val=(0.0, 0.0, 0.0), out=None, normalise=None):
+    """B tiles of a device-resident scene [H, W, 3] (uint8 / fp32) -> fp32 [B, 3, Hp, Wp], one launch
+    (rsp_slice_resize_pad).  origins: int32 [B, 2] = (x0, y0) on the device; tile i is bit-identical to
+    `resize_pad(scene[y0:y0 + th, x0:x0 + tw].contiguous(), new_hw, pad_hw, pad_val, normalise=normalise)`."""
+    import ctypes
+    lib = _lib.load()
+    if scene_hwc.dim() != 3 or scene_hwc.shape[2] != 3 or not _is_device(scene_hwc):
+        raise ValueError('slice_resize_pad expects an [H, W, 3] device tensor')
+    im = scene_hwc.contiguous()
+    if im.dtype != torch.uint8:
+        im = im.to(torch.float32)
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.device != im.device:
+        raise ValueError('origins: int32 [B, 2] = (x0, y0) on the device of the scene')
+    origins = origins.contiguous()
+    B = int(origins.shape[0])
+    SH, SW = int(im.shape[0]), int(im.shape[1])
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    Hn, Wn = int(new_hw[0]), int(new_hw[1])
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=im.device)
+    p3 = (ctypes.c_float * 3)(*[float(v) for v in pad_val])
+    if normalise is None:
+        m3 = s3 = None
+        nrm, swap = 0, 0
+    else:
+        m3 = (ctypes.c_float * 3)(*[float(v) for v in normalise[0]])
+        s3 = (ctypes.c_float * 3)(*[float(v) for v in normalise[1]])
+        nrm, swap = 1, 1 if normalise[2] else 0
+    _lib.check(lib.rsp_slice_resize_pad(im.data_ptr(), 1 if im.dtype == torch.uint8 else 0, SH, SW, origins.data_ptr(), B,
+                                        th, tw, out.data_ptr(), Hn, Wn, Hp, Wp, p3, nrm, swap, m3, s3, _stream()),
+               "rsp_slice_resize_pad")
+    return out
+
+
+def rle_shift(counts, n, offsets, tile_hw, scene_hw, cap_out):
+    """run counts of k tile-sized masks (counts int32 [k, cap], n int32 [k], as mask_rle_into writes them) -> run counts
+    of the same masks placed at offsets (int32 [k, 2] = (ox, oy), device) in an (H, W) scene: (counts_out int32
+    [k, cap_out], n_out int32 [k]); n_out[i] = -(needed) when cap_out is too small.  No host synchronisation."""
+    lib = _lib.load()
+    k = int(n.shape[0])
+    H, W = int(scene_hw[0]), int(scene_hw[1])
+    if H * W >= 2 ** 31:
+        raise ValueError(f'rle_shift: a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
+    dev = n.device
+    counts = counts.contiguous()
+    out = torch.empty((max(k, 1), int(cap_out)), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((max(k, 1),), dtype=torch.int32, device=dev)
+    if k:
+        _lib.check(lib.rsp_rle_shift(counts.data_ptr(), n.contiguous().data_ptr(), k, counts.shape[1],
+                                     offsets.contiguous().data_ptr(), int(tile_hw[0]), int(tile_hw[1]), H, W,
+                                     out.data_ptr(), n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_shift")
+    return out[:k], n_out[:k]
+
+
+def paste_tiles(masks, offsets, scene_hw):
+    """bool [k, h, w] tile masks at offsets (int32 [k, 2] = (ox, oy), device) -> bool [k, H, W] (sahi shift_masks)."""
+    lib = _lib.load()
+    k, h, w = masks.shape
+    H, W = int(scene_hw[0]), int(scene_hw[1])
+    out = torch.empty((k, H, W), dtype=torch.bool, device=masks.device)
+    for i in range(0, k, 65535):
+        m = masks[i:i + 65535].contiguous()
+        _lib.check(lib.rsp_paste_tiles(m.data_ptr(), offsets[i:i + 65535].contiguous().data_ptr(), m.shape[0], h, w, H, W,
+                                       out[i:i + 65535].data_ptr(), _stream()), "rsp_paste_tiles")
+    return out
+
+
+def nms_flat(boxes, scores, labels, iou_thr):
+    """mmcv.ops.batched_nms(boxes [n, 4], scores [n], labels [n], dict(type='nms', iou_threshold=iou_thr)) on flat device
+    tensors through rsp_batched_nms with B = 1: returns keep (int64 [m], indices into the inputs in descending score
+    order).  One host read (the number kept)."""
+    n = int(boxes.shape[0])
+    dev = boxes.device
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.int64, device=dev)
+    if n > NMS_MAX_CANDIDATES:
+        raise ValueError(f'nms_flat: {n} instances, rsp_batched_nms holds {NMS_MAX_CANDIDATES} candidates at most')
+    cand = (boxes.to(torch.float32).contiguous().view(1, n, 4), scores.to(torch.float32).contiguous().view(1, n),
+            labels.to(torch.int32).contiguous().view(1, n), torch.arange(n, dtype=torch.int32, device=dev).view(1, n),
+            torch.full((1,), n, dtype=torch.int32, device=dev))
+    r = batched_nms(cand, 1, n, float(iou_thr), n)
+    m = int(r['count'][0].item())
+    return r['keep'][0, :m].to(torch.int64)
+
+
 # ----------------------------------------------------------------------------- COCO evaluation (csrc/cocoeval.hip)
 def rle_from_string(flat, offs, cap=1024):
     """COCO compressed strings flat[offs[i]:offs[i + 1]] (uint8 / int64 device tensors) -> (counts int32 [k, cap'],
