@@ -624,6 +624,30 @@ int rsp_rle_shift(const uint32_t* counts_in, const int32_t* n_in, int32_t k, int
 int rsp_paste_tiles(const uint8_t* masks, const int32_t* offsets, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W,
                     uint8_t* out, rsp_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */
+/* ------------------------------------------------------------------------ */
+/* HF SamPromptEncoder._embed_points / _embed_boxes / forward (modeling_sam.py:613-698) over SamPositionalEmbedding.forward  */
+/* (:552-566) for R prompt sets: points [R, P, 2] (x, y in input pixels; NULL when P == 0), labels int32 [R, P] (1 / 0: add  */
+/* point_embed1 / point_embed0, -1: the row becomes not_a_point_embed, -10: zeros, anything else: the bare encoding), boxes  */
+/* [R, 4] or NULL, pad = 1 appends the padding point (label -1; HF pads when there is no box, pad with boxes is refused) ->  */
+/* out [R, P + pad + 2 * (boxes != NULL), 2 * num_pos_feats] in HF's order: points, padding point, the two box corners.      */
+/* labels == NULL with points: SamPositionalEmbedding.forward itself (no + 0.5, no type embedding; pass input_h = input_w =   */
+/* 1 for `input_shape=None`).  A boxes-only call returns the bits of rsp_sam_embed_boxes.                                    */
+int rsp_sam_embed_prompts(const float* points, const int32_t* labels, const float* boxes, int32_t R, int32_t P, int32_t pad,
+                          const float* gauss, const float* point_embed0, const float* point_embed1, const float* point_embed2,
+                          const float* point_embed3, const float* not_a_point_embed, float* out, int32_t num_pos_feats,
+                          int32_t input_h, int32_t input_w, rsp_stream_t stream);
+/* HF mask generation's scoring (image_processing_sam: _compute_stability_score, _batched_mask_to_box over                   */
+/* post_process_masks) without the masks: low_res [k, h, w] logits and the geometry of rsp_mask_post_logits.  out int32      */
+/* [k, 7] = number of pixels whose resized value is > t_hi, > t_lo, > t_mid (strict, fp32: the caller forms                  */
+/* float(thr + offset), float(thr - offset), thr), then x0, y0, x1, y1 of the pixels > t_mid (inclusive maxima; 0 0 0 0 for  */
+/* an empty mask).  The value is the one rsp_mask_post_logits thresholds (same device code): the counts are the population  */
+/* counts of its masks.  Integer reductions only: the result is independent of scheduling.  Writes nothing but `out`.       */
+int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
+                       int32_t crop_w, int32_t out_h, int32_t out_w, float t_hi, float t_lo, float t_mid, int32_t* out,
+                       rsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,29 +57,66 @@ __global__ __launch_bounds__(256) void sigmoid_kernel(const float* __restrict__ 
     y[i] = 1.0f / (1.0f + expf(-x[i]));
 }
 
-// `sig` = sigmoid(low-res logits) (models.py:1758); IDENT: crop == output size, so the second
-// interpolation is the identity (src index == dst index, weight 1) and only stage 1 is evaluated.
+// The value of one output pixel of the resize -> crop -> resize chain, shared by the mask kernels below and by the scoring
+// kernel (mask_score_kernel): what is compared against a threshold there is this expression and no other.
+struct MaskScales { float s1h, s1w, s2h, s2w; };
+__device__ __forceinline__ MaskScales mask_scales(const MaskPostP& p) {
+  return MaskScales{(float)p.h / (float)p.Hb, (float)p.w / (float)p.Wb, (float)p.ch / (float)p.oh, (float)p.cw / (float)p.ow};
+}
+__device__ __forceinline__ float mask_stage1(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int Y, int X) {
+  const Lin ay = lin_coef(Y, s.s1h, p.h);
+  const Lin ax = lin_coef(X, s.s1w, p.w);
+  const float v00 = low[ay.i0 * p.w + ax.i0], v01 = low[ay.i0 * p.w + ax.i1];
+  const float v10 = low[ay.i1 * p.w + ax.i0], v11 = low[ay.i1 * p.w + ax.i1];
+  return ay.l0 * (ax.l0 * v00 + ax.l1 * v01) + ay.l1 * (ax.l0 * v10 + ax.l1 * v11);
+}
+// IDENT: crop == output size, so the second interpolation is the identity (src index == dst index, weight 1) and only
+// stage 1 is evaluated.
+template <bool IDENT>
+__device__ __forceinline__ float mask_pixel(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int oy, int ox) {
+  if (IDENT) return mask_stage1(low, p, s, oy, ox);
+  const Lin cy = lin_coef(oy, s.s2h, p.ch), cx = lin_coef(ox, s.s2w, p.cw);
+  const float a00 = mask_stage1(low, p, s, cy.i0, cx.i0), a01 = mask_stage1(low, p, s, cy.i0, cx.i1);
+  const float a10 = mask_stage1(low, p, s, cy.i1, cx.i0), a11 = mask_stage1(low, p, s, cy.i1, cx.i1);
+  return cy.l0 * (cx.l0 * a00 + cx.l1 * a01) + cy.l1 * (cx.l0 * a10 + cx.l1 * a11);
+}
+
+// The identity-crop case with (ow & 3) == 0 as a strip (round 5): a thread owns 4 consecutive output columns and walks down
+// the rows.  The x coefficients are computed once, the two horizontally interpolated source rows only when the source row
+// pair changes (every 4th output row at the usual 256 -> 1024), and a pixel is ay.l0 * h0 + ay.l1 * h1 -- the SAME fp32
+// expression tree as mask_stage1(), so the values are bit-identical.
+struct MaskStrip {
+  Lin ax[4];
+  int r0, r1;
+  float h0[4], h1[4];
+  __device__ __forceinline__ void init(const MaskPostP& p, const MaskScales& s, int ox) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ax[e] = lin_coef(ox + e, s.s1w, p.w);
+    r0 = -1; r1 = -1;
+  }
+  __device__ __forceinline__ void row(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int oy, float v[4]) {
+    const Lin ay = lin_coef(oy, s.s1h, p.h);
+    if (ay.i0 != r0 || ay.i1 != r1) {
+      r0 = ay.i0; r1 = ay.i1;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        h0[e] = ax[e].l0 * low[r0 * p.w + ax[e].i0] + ax[e].l1 * low[r0 * p.w + ax[e].i1];
+        h1[e] = ax[e].l0 * low[r1 * p.w + ax[e].i0] + ax[e].l1 * low[r1 * p.w + ax[e].i1];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = ay.l0 * h0[e] + ay.l1 * h1[e];
+  }
+};
+
+// `sig` = sigmoid(low-res logits) (models.py:1758)
 template <bool IDENT>
 __global__ __launch_bounds__(256) void mask_post_kernel(const MaskPostP p) {
   const int m = blockIdx.y;
   const float* low = p.low + (int64_t)m * p.h * p.w;
-  const float s1h = (float)p.h / (float)p.Hb, s1w = (float)p.w / (float)p.Wb;
-  const float s2h = (float)p.ch / (float)p.oh, s2w = (float)p.cw / (float)p.ow;
+  const MaskScales sc = mask_scales(p);
   const int64_t total = (int64_t)p.oh * p.ow;
-  auto stage1 = [&](int Y, int X) -> float {
-    const Lin ay = lin_coef(Y, s1h, p.h);
-    const Lin ax = lin_coef(X, s1w, p.w);
-    const float v00 = low[ay.i0 * p.w + ax.i0], v01 = low[ay.i0 * p.w + ax.i1];
-    const float v10 = low[ay.i1 * p.w + ax.i0], v11 = low[ay.i1 * p.w + ax.i1];
-    return ay.l0 * (ax.l0 * v00 + ax.l1 * v01) + ay.l1 * (ax.l0 * v10 + ax.l1 * v11);
-  };
-  auto pixel = [&](int oy, int ox) -> float {
-    if (IDENT) return stage1(oy, ox);
-    const Lin cy = lin_coef(oy, s2h, p.ch), cx = lin_coef(ox, s2w, p.cw);
-    const float a00 = stage1(cy.i0, cx.i0), a01 = stage1(cy.i0, cx.i1);
-    const float a10 = stage1(cy.i1, cx.i0), a11 = stage1(cy.i1, cx.i1);
-    return cy.l0 * (cx.l0 * a00 + cx.l1 * a01) + cy.l1 * (cx.l0 * a10 + cx.l1 * a11);
-  };
+  auto pixel = [&](int oy, int ox) -> float { return mask_pixel<IDENT>(low, p, sc, oy, ox); };
   if ((p.ow & 3) == 0) {
     // four pixels of one row per thread: one 32-bit store of the bool mask instead of four byte stores
     const int qw = p.ow >> 2;
@@ -107,48 +144,149 @@ __global__ __launch_bounds__(256) void mask_post_kernel(const MaskPostP p) {
   }
 }
 
-// The identity-crop case (crop == output size: every 1024-px tile) as a strip kernel (round 5): a thread owns 4 consecutive
-// output columns and walks MP_ROWS output rows.  The x coefficients are computed once, the two horizontally interpolated
-// source rows only when the source row pair changes (every 4th output row at the usual 256 -> 1024), and a pixel is
-// ay.l0 * h0 + ay.l1 * h1 -- the SAME fp32 expression tree as stage1() above, so the masks are bit-identical; the generic
+// The identity-crop case (crop == output size: every 1024-px tile) as a strip kernel (MaskStrip above); the generic
 // kernel spends ~40 VALU instructions and four gathers per pixel on it (1.3 ms per ViT-H step for 838 MB of masks).
 constexpr int MP_ROWS = 16;
 __global__ __launch_bounds__(256) void mask_post_strip_kernel(const MaskPostP p) {
   const int m = blockIdx.y;
   const float* low = p.low + (int64_t)m * p.h * p.w;
-  const float s1h = (float)p.h / (float)p.Hb, s1w = (float)p.w / (float)p.Wb;
+  const MaskScales sc = mask_scales(p);
   const int qw = p.ow >> 2;
   const int ntile = (p.oh + MP_ROWS - 1) / MP_ROWS;
   const int64_t total = (int64_t)p.oh * p.ow;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;       // (row tile, column quad): quads fastest -> coalesced rows
   if (i >= ntile * qw) return;
   const int ty = i / qw, ox = (i - ty * qw) << 2;
-  Lin ax[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ax[e] = lin_coef(ox + e, s1w, p.w);
-  int r0 = -1, r1 = -1;
-  float h0[4], h1[4];
+  MaskStrip st;
+  st.init(p, sc, ox);
   const int oy_end = min((ty + 1) * MP_ROWS, p.oh);
   for (int oy = ty * MP_ROWS; oy < oy_end; ++oy) {
-    const Lin ay = lin_coef(oy, s1h, p.h);
-    if (ay.i0 != r0 || ay.i1 != r1) {
-      r0 = ay.i0; r1 = ay.i1;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h0[e] = ax[e].l0 * low[r0 * p.w + ax[e].i0] + ax[e].l1 * low[r0 * p.w + ax[e].i1];
-        h1[e] = ax[e].l0 * low[r1 * p.w + ax[e].i0] + ax[e].l1 * low[r1 * p.w + ax[e].i1];
-      }
-    }
     float v[4];
+    st.row(low, p, sc, oy, v);
     uint32_t bits = 0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[e] = ay.l0 * h0[e] + ay.l1 * h1[e];
-      bits |= ((p.strict ? v[e] > p.thr : v[e] >= p.thr) ? 1u : 0u) << (8 * e);
-    }
+    for (int e = 0; e < 4; ++e) bits |= ((p.strict ? v[e] > p.thr : v[e] >= p.thr) ? 1u : 0u) << (8 * e);
     const int64_t o = (int64_t)m * total + (int64_t)oy * p.ow + ox;
     *reinterpret_cast<uint32_t*>(p.out + o) = bits;
     if (p.prob) *reinterpret_cast<f32x4*>(p.prob + o) = f32x4{v[0], v[1], v[2], v[3]};
+  }
+}
+
+// Scores of K candidate masks without the masks (HF mask generation: _compute_stability_score + _batched_mask_to_box of
+// image_processing_sam over post_process_masks): per mask the number of pixels whose value -- the one the kernels above
+// would threshold, same device functions, same kernel choice per geometry -- is > t_hi, > t_lo and > t_mid, and the extents
+// of the pixels > t_mid.  acc[m] = {n_hi, n_lo, n_mid, min x, min y, max x, max y}; integer sums and extrema only, so the
+// result does not depend on the order in which blocks arrive.  Nothing of size K * oh * ow is written.
+struct MaskScoreP {
+  MaskPostP g;          // geometry + logits (out / prob / thr / strict unused)
+  int32_t* acc;         // [k, 7]
+  float t_hi, t_lo, t_mid;
+};
+
+struct ScoreAcc {
+  int n_hi, n_lo, n_mid, x0, y0, x1, y1;
+  __device__ __forceinline__ void clear() { n_hi = n_lo = n_mid = 0; x0 = y0 = 0x7fffffff; x1 = y1 = -1; }
+  __device__ __forceinline__ void add(const MaskScoreP& q, float v, int oy, int ox) {
+    n_hi += v > q.t_hi ? 1 : 0;
+    n_lo += v > q.t_lo ? 1 : 0;
+    if (v > q.t_mid) {
+      n_mid += 1;
+      x0 = min(x0, ox); x1 = max(x1, ox);
+      y0 = min(y0, oy); y1 = max(y1, oy);
+    }
+  }
+};
+
+// every thread of the block calls this (uniform control flow): wave shuffles, 4 partial rows in LDS, one atomic per value
+__device__ __forceinline__ void score_block_reduce(ScoreAcc a, int32_t* __restrict__ acc) {
+  __shared__ int part[4][7];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    a.n_hi += __shfl_xor(a.n_hi, d, 64);
+    a.n_lo += __shfl_xor(a.n_lo, d, 64);
+    a.n_mid += __shfl_xor(a.n_mid, d, 64);
+    a.x0 = min(a.x0, __shfl_xor(a.x0, d, 64));
+    a.y0 = min(a.y0, __shfl_xor(a.y0, d, 64));
+    a.x1 = max(a.x1, __shfl_xor(a.x1, d, 64));
+    a.y1 = max(a.y1, __shfl_xor(a.y1, d, 64));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[wave][0] = a.n_hi; part[wave][1] = a.n_lo; part[wave][2] = a.n_mid;
+    part[wave][3] = a.x0; part[wave][4] = a.y0; part[wave][5] = a.x1; part[wave][6] = a.y1;
+  }
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j < 7) {
+    const int v0 = part[0][j], v1 = part[1][j], v2 = part[2][j], v3 = part[3][j];
+    if (j < 3) {
+      const int sum = v0 + v1 + v2 + v3;
+      if (sum) atomicAdd(acc + j, sum);
+    } else if (j < 5) {
+      atomicMin(acc + j, min(min(v0, v1), min(v2, v3)));
+    } else {
+      atomicMax(acc + j, max(max(v0, v1), max(v2, v3)));
+    }
+  }
+}
+
+template <bool IDENT>
+__global__ __launch_bounds__(256) void mask_score_kernel(const MaskScoreP q) {
+  const MaskPostP& p = q.g;
+  const int m = blockIdx.y;
+  const float* low = p.low + (int64_t)m * p.h * p.w;
+  const MaskScales sc = mask_scales(p);
+  const int64_t total = (int64_t)p.oh * p.ow;
+  ScoreAcc a;
+  a.clear();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
+    a.add(q, mask_pixel<IDENT>(low, p, sc, oy, ox), oy, ox);
+  }
+  score_block_reduce(a, q.acc + (int64_t)m * 7);
+}
+
+// strip form, taken exactly where launch_mask_post takes mask_post_strip_kernel; a thread walks MS_ROWS rows of its 4 columns
+constexpr int MS_ROWS = 64;
+__global__ __launch_bounds__(256) void mask_score_strip_kernel(const MaskScoreP q) {
+  const MaskPostP& p = q.g;
+  const int m = blockIdx.y;
+  const float* low = p.low + (int64_t)m * p.h * p.w;
+  const MaskScales sc = mask_scales(p);
+  const int qw = p.ow >> 2;
+  const int ntile = (p.oh + MS_ROWS - 1) / MS_ROWS;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  ScoreAcc a;
+  a.clear();
+  if (i < ntile * qw) {
+    const int ty = i / qw, ox = (i - ty * qw) << 2;
+    MaskStrip st;
+    st.init(p, sc, ox);
+    const int oy_end = min((ty + 1) * MS_ROWS, p.oh);
+    for (int oy = ty * MS_ROWS; oy < oy_end; ++oy) {
+      float v[4];
+      st.row(low, p, sc, oy, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a.add(q, v[e], oy, ox + e);
+    }
+  }
+  score_block_reduce(a, q.acc + (int64_t)m * 7);
+}
+
+__global__ __launch_bounds__(256) void mask_score_init_kernel(int32_t* __restrict__ acc, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k * 7) return;
+  const int j = i % 7;
+  acc[i] = j < 3 ? 0 : (j < 5 ? 0x7fffffff : -1);
+}
+
+// an empty mask gets the box [0, 0, 0, 0] (HF _batched_mask_to_box)
+__global__ __launch_bounds__(256) void mask_score_final_kernel(int32_t* __restrict__ acc, int k) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= k) return;
+  if (acc[m * 7 + 2] == 0) {
+#pragma unroll
+    for (int j = 3; j < 7; ++j) acc[m * 7 + j] = 0;
   }
 }
 
@@ -213,6 +351,43 @@ extern "C" int rsp_mask_post_logits(const float* low_res, int32_t k, int32_t h, 
   p.low = low_res; p.out = out_mask; p.prob = out_val; p.k = k; p.h = h; p.w = w; p.Hb = Hb; p.Wb = Wb;
   p.ch = crop_h; p.cw = crop_w; p.oh = out_h; p.ow = out_w; p.thr = thr; p.strict = 1;
   return launch_mask_post(p, (hipStream_t)stream);
+}
+
+
+extern "C" int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
+                                  int32_t crop_w, int32_t out_h, int32_t out_w, float t_hi, float t_lo, float t_mid,
+                                  int32_t* out, rsp_stream_t stream) {
+  if (!low_res || !out || k < 0 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 || crop_h <= 0 || crop_w <= 0 || crop_h > Hb ||
+      crop_w > Wb || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > 0x7fffffffLL || (int64_t)k * 7 > 0x7fffffffLL)
+    return RSP_EINVAL;
+  if (k == 0) return RSP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mask_score_init_kernel, dim3((unsigned)((k * 7 + 255) / 256)), dim3(256), 0, st, out, k);
+  MaskScoreP q;
+  q.g.out = nullptr; q.g.prob = nullptr; q.g.h = h; q.g.w = w; q.g.Hb = Hb; q.g.Wb = Wb;
+  q.g.ch = crop_h; q.g.cw = crop_w; q.g.oh = out_h; q.g.ow = out_w; q.g.thr = t_mid; q.g.strict = 1;
+  q.t_hi = t_hi; q.t_lo = t_lo; q.t_mid = t_mid;
+  const bool ident = crop_h == out_h && crop_w == out_w;
+  for (int32_t m0 = 0; m0 < k; m0 += 65535) {                  // grid.y limit
+    const int32_t km = k - m0 < 65535 ? k - m0 : 65535;
+    q.g.low = low_res + (int64_t)m0 * h * w; q.g.k = km; q.acc = out + (int64_t)m0 * 7;
+    if (ident && (out_w & 3) == 0) {
+      const int64_t nthr = (int64_t)((out_h + MS_ROWS - 1) / MS_ROWS) * (out_w >> 2);
+      hipLaunchKernelGGL(mask_score_strip_kernel, dim3((unsigned)((nthr + 255) / 256), km), dim3(256), 0, st, q);
+    } else {
+      int64_t gx = ((int64_t)out_h * out_w + 255) / 256;
+      // enough blocks per mask to fill the device at small k, few enough that the per-block reduction stays negligible
+      const int64_t cap = k >= 1024 ? 16 : (k >= 64 ? 64 : 1024);
+      if (gx > cap) gx = cap;
+      if (ident)
+        hipLaunchKernelGGL((mask_score_kernel<true>), dim3((unsigned)gx, km), dim3(256), 0, st, q);
+      else
+        hipLaunchKernelGGL((mask_score_kernel<false>), dim3((unsigned)gx, km), dim3(256), 0, st, q);
+    }
+  }
+  hipLaunchKernelGGL(mask_score_final_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, out, k);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
 }
 
 

@@ -1028,6 +1028,69 @@ def sam_embed_boxes(boxes, gauss, pe_top_left, pe_bottom_right, input_size):
     return out
 
 
+def sam_embed_prompts(points, labels, boxes, pad, gauss, point_embed, not_a_point, input_size):
+    """HF SamPromptEncoder.forward's sparse half (HF:613-698) for R prompt sets: points [R, P, 2] or None, labels int
+    [R, P] (None with points: the bare SamPositionalEmbedding.forward, HF:552-566), boxes [R, 4] or None, `pad` appends the
+    padding point (HF: no box given) -> [R, P + pad + 2 * has_boxes, 2F].  point_embed: the four [1, 2F] rows (None in the
+    bare mode), not_a_point [1, 2F]; input_size (h, w)."""
+    lib = _lib.load()
+    if points is None and boxes is None:
+        raise ValueError("sam_embed_prompts needs points or boxes")
+    ref = points if points is not None else boxes
+    R, P = int(ref.shape[0]), 0
+    if points is not None:
+        points = points.contiguous()
+        _chk_f32(points, "points")
+        if points.dim() != 3 or points.shape[2] != 2:
+            raise ValueError("points: expected [R, P, 2]")
+        P = int(points.shape[1])
+        if P == 0:
+            points = None
+    if labels is not None:
+        if points is None or tuple(labels.shape) != (R, P):
+            raise ValueError("labels: expected [R, P] next to points [R, P, 2]")
+        labels = labels.to(torch.int32).contiguous()
+    if boxes is not None:
+        boxes = boxes.contiguous()
+        _chk_f32(boxes, "boxes")
+        if tuple(boxes.shape) != (R, 4):
+            raise ValueError("boxes: expected [R, 4], one box per prompt set")
+    if points is None and boxes is None:
+        raise ValueError("sam_embed_prompts needs at least one point or a box per prompt set")
+    pad = 1 if pad else 0
+    F = gauss.shape[1]
+    T = P + pad + (2 if boxes is not None else 0)
+    out = torch.empty((R, T, 2 * F), dtype=torch.float32, device=ref.device)
+    pe = [None] * 4 if point_embed is None else list(point_embed)
+    _lib.check(lib.rsp_sam_embed_prompts(_ptr(points), _ptr(labels), _ptr(boxes), R, P, pad, gauss.data_ptr(), _ptr(pe[0]),
+                                         _ptr(pe[1]), _ptr(pe[2]), _ptr(pe[3]), _ptr(not_a_point), out.data_ptr(), F,
+                                         int(input_size[0]), int(input_size[1]), _stream()), "rsp_sam_embed_prompts")
+    return out
+
+
+def mask_score_box(low_res, img_shape, crop_hw, out_hw, mask_threshold=0.0, stability_score_offset=1.0):
+    """HF mask generation's scores of k candidate masks without the masks: low_res [k, h, w] logits, the geometry of
+    mask_post_logits -> int32 [k, 7] = pixel counts above thr + offset, thr - offset and thr, then the box x0, y0, x1, y1
+    of the pixels above thr (inclusive maxima, zeros for an empty mask).  The thresholds are rounded to fp32 here, as
+    torch rounds the Python scalar when it compares an fp32 tensor with it."""
+    lib = _lib.load()
+    _chk_f32(low_res, "low_res")
+    if low_res.dim() != 3 or not low_res.is_contiguous():
+        raise ValueError("mask_score_box expects contiguous [k, h, w] logits")
+    k, h, w = low_res.shape
+    out = torch.empty((k, 7), dtype=torch.int32, device=low_res.device)
+    if k == 0:
+        return out
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))             # noqa: E731
+    t_hi, t_lo, t_mid = f32(mask_threshold + stability_score_offset), f32(mask_threshold - stability_score_offset), \
+        f32(mask_threshold)
+    _timed('mask_score_kernel', 0, 4.0 * low_res.numel(),
+           lambda: _lib.check(lib.rsp_mask_score_box(low_res.data_ptr(), k, h, w, img_shape[0], img_shape[1], crop_hw[0],
+                                                     crop_hw[1], out_hw[0], out_hw[1], t_hi, t_lo, t_mid, out.data_ptr(),
+                                                     _stream()), "rsp_mask_score_box"))
+    return out
+
+
 def box_coder(coder):
     """The RspBoxCoder of a DeltaXYWHBBoxCoder-like object (`means`, `stds`, `max_ratio`, `clip_border`, `add_ctr_clamp`,
     `ctr_clamp`: delta_xywh_bbox_coder.py:71-131)."""

@@ -423,26 +423,40 @@ class SamMaskDecoderHIP(HIPModule):
     def forward(self, image_embeddings, image_positional_embeddings, sparse_prompt_embeddings,
                 dense_prompt_embeddings, multimask_output=False, attention_similarity=None,
                 target_embedding=None, output_attentions=None):
-        """HF-compatible signature (HF:461-543) for callers that already repeated the image tensors per
-        prompt set: every batch entry is treated as its own image.  point_batch_size 1, constant dense prompt;
-        multimask_output=True returns the three masks of mask tokens 1..3 (HF:537-542)."""
+        """HF signature (HF:461-543): image_embeddings [B, 256, h, w], sparse_prompt_embeddings [B, Pb, n, 256] (or [B, n, 256]
+        = point_batch_size 1), dense_prompt_embeddings [1 | B, 256, h, w] -- the broadcast `no_mask_embed` or a per-pixel one
+        (SamMaskEmbedding's output).  Every batch entry is its own image and its Pb prompt sets stay mapped to it.  Returns
+        (masks [B, Pb, C, 4h, 4w], iou [B, Pb, C], None) with C = 3 for multimask_output (mask tokens 1..3, HF:537-542)."""
         if attention_similarity is not None or target_embedding is not None:
             raise NotImplementedError('attention_similarity / target_embedding (HF SamAttention hooks) are not implemented')
-        R = image_embeddings.shape[0]
+        B = image_embeddings.shape[0]
         if sparse_prompt_embeddings.dim() == 4:
-            if sparse_prompt_embeddings.shape[1] != 1:
-                raise NotImplementedError('point_batch_size must be 1')
-            sparse = sparse_prompt_embeddings[:, 0]
+            Pb = sparse_prompt_embeddings.shape[1]
+            sparse = sparse_prompt_embeddings.reshape(B * Pb, sparse_prompt_embeddings.shape[2], HID)
         else:
+            Pb = 1
             sparse = sparse_prompt_embeddings
+        dev = image_embeddings.device
+        roi_img = torch.arange(B, dtype=torch.int32, device=dev)
+        if Pb > 1:
+            roi_img = roi_img.repeat_interleave(Pb)
         d = nhwc_view(dense_prompt_embeddings)
-        if d.shape[0] != 1 and not bool((d[0, 0, 0] == d[-1, -1, -1]).all()):
-            raise NotImplementedError('per-pixel dense prompts go through decode_dense()')
-        dense_vec = d[0, 0, 0].contiguous()
-        roi_img = torch.arange(R, dtype=torch.int32, device=image_embeddings.device)
-        masks, iou = self.decode(image_embeddings, image_positional_embeddings, sparse.contiguous(), dense_vec,
-                                 roi_img, multimask_output=bool(multimask_output))
-        return masks.unsqueeze(1), iou.unsqueeze(1), None
+        if d.shape[0] not in (1, B):
+            raise ValueError(f'dense_prompt_embeddings: batch {d.shape[0]} for {B} image embeddings')
+        # a constant dense prompt (every pixel of every entry the same vector) keeps the per-image fast path; one host read
+        const = bool((d == d[:1, :1, :1]).all())
+        if const:
+            masks, iou = self.decode(image_embeddings, image_positional_embeddings, sparse.contiguous(),
+                                     d[0, 0, 0].contiguous(), roi_img, multimask_output=bool(multimask_output))
+        else:
+            emb = nhwc_view(image_embeddings)
+            _, h, w, C = emb.shape
+            # HF:499, one dense source per image (a [1, ..] dense prompt repeats over the batch: row % (h w))
+            src = ops.add_rows(emb.reshape(B * h * w, C).contiguous(), d.reshape(-1, C).contiguous())
+            masks, iou = self.decode(None, image_positional_embeddings, sparse.contiguous(), None, roi_img,
+                                     src_rows=src, hw=(h, w), multimask_output=bool(multimask_output))
+        C, mh, mw = masks.shape[1:]
+        return masks.reshape(B, Pb, C, mh, mw), iou.reshape(B, Pb, C), None
 
 
 @MODELS.register_module()
@@ -499,7 +513,14 @@ class RSSamPositionalEmbedding(HIPModule):
         return self._cache[key]
 
     def forward(self, input_coords, input_shape=None):
-        raise NotImplementedError('only the image-wide table is on the RSPrompter path (models.py:85-95)')
+        """models.py:756-759 -> HF SamPositionalEmbedding.forward (HF:552-566): input_coords [..., 2] (x, y; HF indexes a
+        4-D tensor), divided by input_shape = (h, w) when given, -> [..., 256] on the device (rsp_sam_embed_prompts without
+        labels: no pixel-centre shift, no type embedding)."""
+        c = input_coords.to(torch.float32)
+        lead = tuple(c.shape[:-1])
+        out = ops.sam_embed_prompts(c.reshape(1, -1, 2), None, None, False, self.shared_image_embedding.positional_embedding,
+                                    None, None, (1, 1) if input_shape is None else input_shape)
+        return out.view(*lead, out.shape[-1])
 
 
 class _PromptEncoder(HIPModule):
@@ -526,4 +547,6 @@ class RSSamPromptEncoder(HIPModule):
         self.prompt_encoder = _PromptEncoder()
 
     def forward(self, *args, **kwargs):
-        raise NotImplementedError('RSPrompter only borrows no_mask_embed / mask_embed from the prompt encoder')
+        raise NotImplementedError('RSSamPromptEncoder.forward: this module holds the reduced parameter set RSPrompter '
+                                  'borrows (no_mask_embed / mask_embed); the full prompt encoder (points, boxes, masks) '
+                                  'is SamModelHIP.get_prompt_embeddings (rsprompter_amd/samdet.py)')

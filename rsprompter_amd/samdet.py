@@ -224,8 +224,11 @@ class _SamPromptEncoderFull(_PromptEncoder):
 
 
 class SamModelHIP(HIPModule):
-    """HF `SamModel` (modeling_sam.py:1165-1330) for the call SAMDet makes: `pixel_values` (or `image_embeddings`) +
-    `input_boxes`, `multimask_output=False`.  Points / mask prompts / multimask outputs are not on the reference's path."""
+    """HF `SamModel` (modeling_sam.py:1165-1330): `pixel_values` (or `image_embeddings`) + point / box / mask prompts,
+    one or three masks per prompt set.  The prompt encoder runs as one kernel (ops.sam_embed_prompts), `input_masks` through
+    ops.sam_mask_embed (one dense source per image), and ONE decoder pass serves the B x Pb prompt sets, which stay mapped to
+    their image instead of repeating the image tensors.  `attention_similarity` / `target_embedding` (HF's
+    PerSAM hooks) are not implemented."""
 
     def __init__(self, arch='huge', image_size=1024):
         super().__init__()
@@ -251,34 +254,119 @@ class SamModelHIP(HIPModule):
     def get_image_embeddings(self, pixel_values):
         return self.vision_encoder(pixel_values, output_hidden_states=False)[0]
 
+    def _mask_embed_prm(self):
+        sm = self.prompt_encoder.mask_embed
+        return dict(conv1_w=sm.conv1.weight.detach().contiguous(), conv1_b=sm.conv1.bias.detach(),
+                    ln1_w=sm.layer_norm1.weight.detach(), ln1_b=sm.layer_norm1.bias.detach(),
+                    conv2_w=sm.conv2.weight.detach().contiguous(), conv2_b=sm.conv2.bias.detach(),
+                    ln2_w=sm.layer_norm2.weight.detach(), ln2_b=sm.layer_norm2.bias.detach(),
+                    conv3_w=sm.conv3.weight.detach().reshape(sm.conv3.weight.shape[0], 16).contiguous(),
+                    conv3_b=sm.conv3.bias.detach())
+
+    def embed_sparse(self, input_points=None, input_labels=None, input_boxes=None):
+        """The sparse half of HF `SamPromptEncoder.forward` (HF:676-690) on the device: input_points [B, Pb, P, 2],
+        input_labels [B, Pb, P], input_boxes [B, Pb, 4] -> [B, Pb, P + (1 if no box) + (2 if box), 256]; None without both."""
+        if input_points is None and input_boxes is None:
+            return None
+        if input_points is not None and input_labels is None:
+            raise ValueError('If points are provided, labels must also be provided.')
+        pe = self.prompt_encoder
+        ref = input_points if input_points is not None else input_boxes
+        B, Pb = ref.shape[:2]
+        pts = lab = bx = None
+        if input_points is not None:
+            pts = input_points.reshape(B * Pb, -1, 2).to(torch.float32)
+            lab = input_labels.reshape(B * Pb, -1)
+        if input_boxes is not None:
+            bx = input_boxes.reshape(B * Pb, 4).to(torch.float32)
+        sparse = ops.sam_embed_prompts(pts, lab, bx, input_points is not None and input_boxes is None,
+                                       pe.shared_embedding.positional_embedding,
+                                       [getattr(pe.point_embed, str(i)).weight for i in range(4)],
+                                       pe.not_a_point_embed.weight, (self.image_size, self.image_size))
+        return sparse.view(B, Pb, sparse.shape[1], sparse.shape[2])
+
+    @torch.no_grad()
+    def get_prompt_embeddings(self, input_points=None, input_labels=None, input_boxes=None, input_masks=None):
+        """HF:1158-1188: (sparse [B, Pb, T, 256] or None, dense [B, 256, h, w])."""
+        sparse = self.embed_sparse(input_points, input_labels, input_boxes)
+        g = self.vision_encoder.grid
+        pe = self.prompt_encoder
+        if input_masks is not None:
+            Bm = input_masks.shape[0]
+            m = input_masks.reshape(Bm, input_masks.shape[-2], input_masks.shape[-1]).to(torch.float32).contiguous()
+            zero = torch.zeros((Bm * g * g, 256), dtype=torch.float32, device=m.device)
+            dense = ops.sam_mask_embed(m, zero, torch.arange(Bm, dtype=torch.int32, device=m.device),
+                                       self._mask_embed_prm(), g, g)
+            dense = nchw_view(dense.view(Bm, g, g, 256))
+        else:
+            B = 1 if sparse is None else sparse.shape[0]
+            dense = pe.no_mask_embed.weight.reshape(1, -1, 1, 1).expand(B, -1, g, g)
+        return sparse, dense
+
     @torch.no_grad()
     def forward(self, pixel_values=None, input_points=None, input_labels=None, input_boxes=None, input_masks=None,
                 image_embeddings=None, multimask_output=True, attention_similarity=None, target_embedding=None,
                 output_attentions=None, output_hidden_states=None, return_dict=None, **kwargs):
+        # the argument checks and messages of HF:1286-1334
         if pixel_values is None and image_embeddings is None:
             raise ValueError('Either pixel_values or image_embeddings must be provided.')
         if pixel_values is not None and image_embeddings is not None:
             raise ValueError('Only one of pixel_values and image_embeddings can be provided.')
-        if (input_points is not None or input_labels is not None or input_masks is not None or multimask_output
-                or attention_similarity is not None or target_embedding is not None or input_boxes is None):
-            raise NotImplementedError('SamModel on HIP: only box prompts with multimask_output=False '
-                                      '(the call of SAMDet.predict, models.py:1174-1178)')
-        if input_boxes.dim() != 3 or input_boxes.shape[-1] != 4:
-            raise ValueError('The input_boxes must be a 3D tensor. Of shape `batch_size`, `nb_boxes`, `4`.')
+        if attention_similarity is not None or target_embedding is not None:
+            raise NotImplementedError('SamModel on HIP: attention_similarity / target_embedding (HF SamAttention hooks) '
+                                      'are not implemented')
+        if input_points is not None and len(input_points.shape) != 4:
+            raise ValueError('The input_points must be a 4D tensor. Of shape `batch_size`, `point_batch_size`, '
+                             '`nb_points_per_image`, `2`.', f' got {input_points.shape}.')
+        if input_boxes is not None and len(input_boxes.shape) != 3:
+            raise ValueError('The input_points must be a 3D tensor. Of shape `batch_size`, `nb_boxes`, `4`.',
+                             f' got {input_boxes.shape}.')
+        if input_points is not None and input_boxes is not None:
+            if input_points.shape[1] != input_boxes.shape[1]:
+                raise ValueError('You should provide as many bounding boxes as input points per box. Got '
+                                 f'{input_points.shape[1]} and {input_boxes.shape[1]}.')
         if image_embeddings is None:
             image_embeddings = self.get_image_embeddings(pixel_values)
-        B, nb = input_boxes.shape[:2]
-        if image_embeddings.shape[0] != B:
+        if input_points is not None and input_labels is None:
+            input_labels = torch.ones_like(input_points[:, :, :, 0], dtype=torch.int)
+        B = image_embeddings.shape[0]
+        if input_points is not None and B != input_points.shape[0]:
+            raise ValueError('The batch size of the image embeddings and the input points must be the same. ',
+                             f'Got {B} and {input_points.shape[0]} respectively.',
+                             ' if you want to pass multiple points for the same image, make sure that you passed ',
+                             ' input_points of shape (batch_size, point_batch_size, num_points_per_image, 3) and ',
+                             ' input_labels of shape (batch_size, point_batch_size, num_points_per_image)')
+        if input_boxes is not None and B != input_boxes.shape[0]:
             raise ValueError('You should provide as many bounding boxes as input_points (batch_size)')
+        sparse = self.embed_sparse(input_points, input_labels, input_boxes)
+        dev = image_embeddings.device
+        if sparse is None:
+            # no point and no box: HF decodes the output tokens alone, one prompt set per image (HF:487-495)
+            sparse = torch.zeros((B, 1, 0, 256), dtype=torch.float32, device=dev)
+        Pb = sparse.shape[1]
+        sparse = sparse.reshape(B * Pb, sparse.shape[2], sparse.shape[3])
+        roi_img = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Pb)
         pe = self.prompt_encoder
-        sparse = ops.sam_embed_boxes(input_boxes.reshape(B * nb, 4).to(torch.float32),
-                                     pe.shared_embedding.positional_embedding, getattr(pe.point_embed, '2').weight,
-                                     getattr(pe.point_embed, '3').weight, (self.image_size, self.image_size))
-        roi_img = torch.arange(B, dtype=torch.int32, device=sparse.device).repeat_interleave(nb)
-        masks, iou = self.mask_decoder.decode(image_embeddings, self.get_image_wide_positional_embeddings(), sparse,
-                                              pe.no_mask_embed.weight.reshape(-1), roi_img)
+        multimask_output = bool(multimask_output)
+        if input_masks is not None:
+            # HF:691-692 + HF:499: image_embeddings + mask_embed(input_masks), formed once per image by the kernel of the
+            # query prompter's dense prompt; the prompt sets stay mapped to their image
+            emb = nhwc_view(image_embeddings)
+            _, g, gw, C = emb.shape
+            if input_masks.shape[0] != B or tuple(input_masks.shape[-2:]) != (4 * g, 4 * gw):
+                raise ValueError(f'input_masks: expected [{B}, 1, {4 * g}, {4 * gw}], got {tuple(input_masks.shape)}')
+            m = input_masks.reshape(B, 4 * g, 4 * gw).to(torch.float32).contiguous()
+            src = ops.sam_mask_embed(m, emb.reshape(B * g * gw, C), torch.arange(B, dtype=torch.int32, device=dev),
+                                     self._mask_embed_prm(), g, gw)
+            masks, iou = self.mask_decoder.decode(None, self.get_image_wide_positional_embeddings(), sparse, None, roi_img,
+                                                  src_rows=src, hw=(g, gw), multimask_output=multimask_output)
+        else:
+            masks, iou = self.mask_decoder.decode(image_embeddings, self.get_image_wide_positional_embeddings(), sparse,
+                                                  pe.no_mask_embed.weight.reshape(-1), roi_img,
+                                                  multimask_output=multimask_output)
         h, w = masks.shape[-2:]
-        return SamImageSegmentationOutput(iou.view(B, nb, 1), masks.view(B, nb, 1, h, w))
+        C = masks.shape[1]
+        return SamImageSegmentationOutput(iou.reshape(B, Pb, C), masks.reshape(B, Pb, C, h, w))
 
 
 @MODELS.register_module()
