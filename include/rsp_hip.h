@@ -607,6 +607,16 @@ int rsp_slice_resize_pad(const void* scene, int32_t src_is_u8, int32_t SH, int32
                          int32_t B, int32_t th, int32_t tw, float* dst, int32_t Hn, int32_t Wn, int32_t Hp, int32_t Wp,
                          const float* pad3, int32_t normalise, int32_t swap_rb, const float* mean3, const float* std3,
                          rsp_stream_t stream);
+/* Crop front end of SAM's multi-crop mask generation: replaces the host crop + resize per crop box of HF               */
+/* image_processing_sam._generate_crop_images (`image[top:bottom, left:right]`, then `_get_preprocess_shape` + resize   */
+/* + normalise + pad of every crop).  image: the decoded image [SH, SW, 3] (uint8 or fp32) on the device, uploaded once; */
+/* table: DEVICE int32 [B, 6] = (x0, y0, x1, y1, Hn, Wn) per crop -- crops of DIFFERENT sizes in one launch, each        */
+/* resized to its own (Hn, Wn) and padded to (Hp, Wp); the kernel clamps the box into the image and (Hn, Wn) into the    */
+/* canvas.  dst [B, 3, Hp, Wp] fp32.  Crop i equals rsp_resize_pad of the contiguous crop image[y0:y1, x0:x1] bit for bit */
+/* (one interpolation function, csrc/rsp_common.h); the remaining arguments are rsp_resize_pad's.  B <= 65535.          */
+int rsp_crops_resize_pad(const void* image, int32_t src_is_u8, int32_t SH, int32_t SW, const int32_t* table, int32_t B,
+                         float* dst, int32_t Hp, int32_t Wp, const float* pad3, int32_t normalise, int32_t swap_rb,
+                         const float* mean3, const float* std3, rsp_stream_t stream);
 /* Run-domain shift: replaces sahi.slicing.shift_masks (mmdet/utils/large_image.py:63-65: every instance mask padded to  */
 /* the full scene as a dense array) + encode_mask_results on that array.  counts_in [k, cap_in] / n_in [k]: run counts of */
 /* k masks of ONE tile size (h, w) as rsp_mask_rle writes them; offsets: DEVICE int32 [k, 2] = (ox, oy) per instance,      */
@@ -647,6 +657,20 @@ int rsp_sam_embed_prompts(const float* points, const int32_t* labels, const floa
 int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
                        int32_t crop_w, int32_t out_h, int32_t out_w, float t_hi, float t_lo, float t_mid, int32_t* out,
                        rsp_stream_t stream);
+
+/* rsp_mask_score_box for the candidates of several crops in one call, plus HF image_processing_sam.                     */
+/* _is_box_near_crop_edge (atol = 20) and the shift of the boxes into the image frame (`_pad_masks` / the offset inside    */
+/* _is_box_near_crop_edge).  crop_idx: DEVICE int32 [k], the crop of every candidate (clamped into the table by the        */
+/* kernel); table: DEVICE int32 [n_crops, 12] = (Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H): the geometry */
+/* of rsp_mask_post_logits for that crop, its box in the image, the image size.  max_out_h / max_out_w: the largest out_h  */
+/* and out_w of the table (they size the grid).  out int32 [k, 8]: columns 0-2 are rsp_mask_score_box's counts for that    */
+/* crop's geometry (same device functions, the strip form chosen per crop by the same condition), 3-6 its box + (x0, y0,   */
+/* x0, y0) (the empty-mask box [0, 0, 0, 0] is crop-local and shifted too), 7 = 1 when a coordinate of the shifted box is  */
+/* within 20 of the same coordinate of [x0, y0, x1, y1] and not within 20 of that of [0, 0, W, H].  Integer reductions     */
+/* only.  A table row with a non-positive size scores as an empty mask.                                                  */
+int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t h, int32_t w, const int32_t* crop_idx,
+                             const int32_t* table, int32_t n_crops, int32_t max_out_h, int32_t max_out_w, float t_hi,
+                             float t_lo, float t_mid, int32_t* out, rsp_stream_t stream);
 
 #ifdef __cplusplus
 }

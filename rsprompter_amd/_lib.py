@@ -207,6 +207,11 @@ PROTOTYPES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rsp_mask_score_box": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                    c_float, c_float, c_void_p, c_void_p]),
+    "rsp_crops_resize_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                     ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_float),
+                                     ctypes.POINTER(c_float), c_void_p]),
+    "rsp_mask_score_box_crops": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                         c_float, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

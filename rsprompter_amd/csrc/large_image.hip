@@ -2,6 +2,8 @@
 // (demo/large_image_demo.py:133-170 over sahi.slicing.slice_image / shift_bboxes / shift_masks and
 // mmdet/utils/large_image.py:27-104) as three bandwidth / latency kernels.
 //   rsp_slice_resize_pad : B tiles of the device-resident scene -> the model's input batch, one launch, no crop copy
+//   rsp_crops_resize_pad : the same for B crops of DIFFERENT sizes (the crop layers of SAM's mask generation):
+//                          boxes and resized sizes come from a device table
 //   rsp_rle_shift        : COCO run counts of tile-sized masks -> run counts of the same masks placed in the scene,
 //                          in the run domain (the scene-sized dense mask of sahi's shift_masks never exists)
 //   rsp_paste_tiles      : the dense form of shift_masks, for callers who ask for dense scene masks
@@ -107,6 +109,43 @@ __global__ __launch_bounds__(256) void slice_convert_pad_kernel(const SliceP P) 
         dst[2 * total + oo] = v[2];
       }
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- crop front end
+// B crops of different sizes (SAM's crop layers: the sizes differ between layers, and the last crop of every row and
+// column is clamped to the image), each resized to its own (Hn, Wn) and padded to (Hp, Wp).  Row b of the table is
+// (x0, y0, x1, y1, Hn, Wn); the kernel clamps it so that a crop never reads outside the image or writes outside its canvas.
+struct CropsP {
+  const void* image;
+  const int32_t* table;     // device [B, 6]
+  float* dst;               // [B, 3, Hp, Wp]
+  int SH, SW, Hp, Wp, normalise, swap_rb;
+  float p[3], m[3], s[3];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void crops_resize_pad_kernel(const CropsP P) {
+  const int b = blockIdx.y;
+  const int32_t* t = P.table + 6 * b;
+  const int x0 = min(max(t[0], 0), P.SW - 1), y0 = min(max(t[1], 0), P.SH - 1);
+  const int tw = min(max(t[2], x0 + 1), P.SW) - x0, th = min(max(t[3], y0 + 1), P.SH) - y0;
+  const int Hn = min(max(t[4], 1), P.Hp), Wn = min(max(t[5], 1), P.Wp);
+  const T* src = static_cast<const T*>(P.image) + ((int64_t)y0 * P.SW + x0) * 3;
+  const double sx_scale = (double)tw / (double)Wn, sy_scale = (double)th / (double)Hn;
+  const int64_t total = (int64_t)P.Hp * P.Wp;
+  float* dst = P.dst + (int64_t)b * 3 * total;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % P.Wp), y = (int)(i / P.Wp);
+    float v[3] = {P.p[0], P.p[1], P.p[2]};
+    if (y < Hn && x < Wn) rsp_bilinear_px(src, (int64_t)P.SW * 3, th, tw, sx_scale, sy_scale, x, y, v);
+    if (P.normalise) {
+      const float a = P.swap_rb ? v[2] : v[0], c1 = v[1], c2 = P.swap_rb ? v[0] : v[2];
+      v[0] = (a - P.m[0]) / P.s[0]; v[1] = (c1 - P.m[1]) / P.s[1]; v[2] = (c2 - P.m[2]) / P.s[2];
+    }
+    dst[i] = v[0];
+    dst[total + i] = v[1];
+    dst[2 * total + i] = v[2];
   }
 }
 
@@ -282,6 +321,29 @@ extern "C" int rsp_slice_resize_pad(const void* scene, int32_t src_is_u8, int32_
   } else {
     hipLaunchKernelGGL((slice_resize_pad_kernel<float>), dim3(li_grid(total), B), dim3(256), 0, s, P);
   }
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+extern "C" int rsp_crops_resize_pad(const void* image, int32_t src_is_u8, int32_t SH, int32_t SW, const int32_t* table,
+                                    int32_t B, float* dst, int32_t Hp, int32_t Wp, const float* pad3, int32_t normalise,
+                                    int32_t swap_rb, const float* mean3, const float* std3, rsp_stream_t stream) {
+  if (!image || !table || !dst || !pad3 || B < 0 || B > 65535 || SH <= 0 || SW <= 0 || Hp <= 0 || Wp <= 0) return RSP_EINVAL;
+  if (normalise && (!mean3 || !std3)) return RSP_EINVAL;
+  if (B == 0) return RSP_OK;
+  CropsP P;
+  P.image = image; P.table = table; P.dst = dst;
+  P.SH = SH; P.SW = SW; P.Hp = Hp; P.Wp = Wp; P.normalise = normalise; P.swap_rb = swap_rb;
+  for (int c = 0; c < 3; ++c) {
+    P.p[c] = pad3[c];
+    P.m[c] = normalise ? mean3[c] : 0.f;
+    P.s[c] = normalise ? std3[c] : 1.f;
+  }
+  const int64_t total = (int64_t)Hp * Wp;
+  if (src_is_u8)
+    hipLaunchKernelGGL((crops_resize_pad_kernel<uint8_t>), dim3(li_grid(total), B), dim3(256), 0, (hipStream_t)stream, P);
+  else
+    hipLaunchKernelGGL((crops_resize_pad_kernel<float>), dim3(li_grid(total), B), dim3(256), 0, (hipStream_t)stream, P);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

@@ -290,6 +290,90 @@ __global__ __launch_bounds__(256) void mask_score_final_kernel(int32_t* __restri
   }
 }
 
+// The same scores for candidates of SEVERAL crops in one launch (SAM's crop layers): candidate m belongs to crop
+// crop_idx[m], and row crop_idx[m] of a device table holds that crop's geometry (Hb, Wb, crop_h, crop_w, out_h, out_w), its box
+// in the image (x0, y0, x1, y1) and the image size (W, H).  A block works on ONE candidate, so the table row is wave-uniform
+// (scalar loads) and the form -- strip, identity, generic -- is chosen per crop by launch_mask_post's condition; the pixel
+// value comes from mask_pixel / MaskStrip above, the reduction is score_block_reduce: counts and crop-local box are those of
+// rsp_mask_score_box on that crop's slice.  acc is [k, 8]: the finalising launch shifts the box into the image frame and
+// writes HF's _is_box_near_crop_edge into column 7.
+constexpr int CROP_ROW = 12;
+constexpr int CROP_EDGE_ATOL = 20;      // _is_box_near_crop_edge(atol=20.0); every quantity is an integer
+struct MaskScoreCropsP {
+  const float* low;          // [k, h, w]
+  const int32_t* crop_idx;   // [k]
+  const int32_t* table;      // [n_crops, CROP_ROW]
+  int32_t* acc;              // [k, 8]
+  int k, h, w, n_crops;
+  float t_hi, t_lo, t_mid;
+};
+
+__global__ __launch_bounds__(256) void mask_score_crops_kernel(const MaskScoreCropsP c) {
+  const int m = blockIdx.y;
+  const int32_t* t = c.table + CROP_ROW * min(max(c.crop_idx[m], 0), c.n_crops - 1);   // clamped: never outside the table
+  MaskScoreP q;
+  MaskPostP& p = q.g;
+  p.low = c.low + (int64_t)m * c.h * c.w; p.out = nullptr; p.prob = nullptr; p.k = 1; p.h = c.h; p.w = c.w;
+  p.Hb = t[0]; p.Wb = t[1]; p.ch = t[2]; p.cw = t[3]; p.oh = t[4]; p.ow = t[5]; p.thr = c.t_mid; p.strict = 1;
+  q.acc = c.acc + (int64_t)m * 8; q.t_hi = c.t_hi; q.t_lo = c.t_lo; q.t_mid = c.t_mid;
+  const float* low = p.low;
+  const MaskScales sc = mask_scales(p);
+  ScoreAcc a;
+  a.clear();
+  // a row the host would have refused scores as an empty mask (the loops below never run)
+  const bool ok = p.Hb > 0 && p.Wb > 0 && p.ch > 0 && p.cw > 0 && p.oh > 0 && p.ow > 0 && p.ch <= p.Hb && p.cw <= p.Wb;
+  const bool ident = p.ch == p.oh && p.cw == p.ow;
+  if (ok && ident && (p.ow & 3) == 0) {
+    const int qw = p.ow >> 2;
+    const int nitem = ((p.oh + MS_ROWS - 1) / MS_ROWS) * qw;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nitem; i += gridDim.x * blockDim.x) {
+      const int ty = i / qw, ox = (i - ty * qw) << 2;
+      MaskStrip st;
+      st.init(p, sc, ox);
+      const int oy_end = min((ty + 1) * MS_ROWS, p.oh);
+      for (int oy = ty * MS_ROWS; oy < oy_end; ++oy) {
+        float v[4];
+        st.row(low, p, sc, oy, v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a.add(q, v[e], oy, ox + e);
+      }
+    }
+  } else if (ok) {
+    const int64_t total = (int64_t)p.oh * p.ow;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+      const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
+      a.add(q, ident ? mask_pixel<true>(low, p, sc, oy, ox) : mask_pixel<false>(low, p, sc, oy, ox), oy, ox);
+    }
+  }
+  score_block_reduce(a, q.acc);
+}
+
+__global__ __launch_bounds__(256) void mask_score_crops_init_kernel(int32_t* __restrict__ acc, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k * 8) return;
+  const int j = i & 7;
+  acc[i] = j < 3 ? 0 : (j < 5 ? 0x7fffffff : (j < 7 ? -1 : 0));
+}
+
+// the empty-mask box [0, 0, 0, 0] (crop-local, shifted like any other), the shift by (x0, y0, x0, y0) and the near-edge flag:
+// a coordinate hits when it is within 20 of the crop box's and not within 20 of [0, 0, W, H]'s
+__global__ __launch_bounds__(256) void mask_score_crops_final_kernel(int32_t* __restrict__ acc, const int32_t* __restrict__ crop_idx,
+                                                                     const int32_t* __restrict__ table, int k, int n_crops) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= k) return;
+  const int32_t* t = table + CROP_ROW * min(max(crop_idx[m], 0), n_crops - 1);
+  const int cb[4] = {t[6], t[7], t[8], t[9]}, ob[4] = {0, 0, t[10], t[11]};
+  const bool empty = acc[m * 8 + 2] == 0;
+  int flag = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int v = (empty ? 0 : acc[m * 8 + 3 + j]) + cb[j & 1];
+    flag |= (abs(v - cb[j]) <= CROP_EDGE_ATOL && abs(v - ob[j]) > CROP_EDGE_ATOL) ? 1 : 0;
+    acc[m * 8 + 3 + j] = v;
+  }
+  acc[m * 8 + 7] = flag;
+}
+
 }  // namespace
 
 extern "C" int rsp_hyper_mask(const float* up, const float* hyper, float* out, int32_t R, int32_t npix,
@@ -386,6 +470,33 @@ extern "C" int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, in
     }
   }
   hipLaunchKernelGGL(mask_score_final_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, out, k);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+
+extern "C" int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t h, int32_t w, const int32_t* crop_idx,
+                                        const int32_t* table, int32_t n_crops, int32_t max_out_h, int32_t max_out_w, float t_hi,
+                                        float t_lo, float t_mid, int32_t* out, rsp_stream_t stream) {
+  if (!low_res || !crop_idx || !table || !out || k < 0 || h <= 0 || w <= 0 || n_crops <= 0 || max_out_h <= 0 || max_out_w <= 0 ||
+      (int64_t)max_out_h * max_out_w > 0x7fffffffLL || (int64_t)k * 8 > 0x7fffffffLL)
+    return RSP_EINVAL;
+  if (k == 0) return RSP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mask_score_crops_init_kernel, dim3((unsigned)((k * 8 + 255) / 256)), dim3(256), 0, st, out, k);
+  MaskScoreCropsP c;
+  c.table = table; c.h = h; c.w = w; c.n_crops = n_crops; c.t_hi = t_hi; c.t_lo = t_lo; c.t_mid = t_mid;
+  // blocks per candidate as rsp_mask_score_box sizes them for the largest crop; a smaller crop's blocks find their loops empty
+  int64_t gx = ((int64_t)max_out_h * max_out_w + 255) / 256;
+  const int64_t cap = k >= 1024 ? 16 : (k >= 64 ? 64 : 1024);
+  if (gx > cap) gx = cap;
+  for (int32_t m0 = 0; m0 < k; m0 += 65535) {                  // grid.y limit
+    const int32_t km = k - m0 < 65535 ? k - m0 : 65535;
+    c.low = low_res + (int64_t)m0 * h * w; c.crop_idx = crop_idx + m0; c.acc = out + (int64_t)m0 * 8; c.k = km;
+    hipLaunchKernelGGL(mask_score_crops_kernel, dim3((unsigned)gx, km), dim3(256), 0, st, c);
+  }
+  hipLaunchKernelGGL(mask_score_crops_final_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, out, crop_idx, table, k,
+                     n_crops);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

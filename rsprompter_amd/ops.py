@@ -1091,6 +1091,48 @@ def mask_score_box(low_res, img_shape, crop_hw, out_hw, mask_threshold=0.0, stab
     return out
 
 
+CROP_TABLE_COLS = 12    # rsp_mask_score_box_crops: Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H
+
+
+def mask_score_box_crops(low_res, crop_idx, table, max_out_hw, mask_threshold=0.0, stability_score_offset=1.0,
+                         check_index=True):
+    """mask_score_box for the candidates of several crops in one call (rsp_mask_score_box_crops): low_res [K, h, w] logits,
+    crop_idx int32 [K] (the crop of each candidate) and table int32 [n_crops, 12] = (Hb, Wb, crop_h, crop_w, out_h, out_w,
+    x0, y0, x1, y1, W, H) per crop, both on the device of low_res; max_out_hw: the largest out_h and out_w of the table.
+    Returns int32 [K, 8]: the three counts of mask_score_box on that crop's geometry, its box shifted into the image frame
+    by (x0, y0, x0, y0), and HF `_is_box_near_crop_edge` (atol 20) of that box.  check_index reads crop_idx's extrema on the
+    host and refuses an index outside the table; a caller that built the index itself passes False (no host read; the
+    kernel clamps)."""
+    lib = _lib.load()
+    _chk_f32(low_res, "low_res")
+    if low_res.dim() != 3 or not low_res.is_contiguous():
+        raise ValueError("mask_score_box_crops expects contiguous [K, h, w] logits")
+    K, h, w = low_res.shape
+    dev = low_res.device
+    if crop_idx.dtype != torch.int32 or crop_idx.dim() != 1 or crop_idx.shape[0] != K or crop_idx.device != dev:
+        raise ValueError("crop_idx: int32 [K] on the device of low_res")
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != CROP_TABLE_COLS or table.shape[0] < 1 or \
+            table.device != dev:
+        raise ValueError(f"table: int32 [n_crops, {CROP_TABLE_COLS}] on the device of low_res")
+    out = torch.empty((K, 8), dtype=torch.int32, device=dev)
+    if K == 0:
+        return out
+    n_crops = int(table.shape[0])
+    if check_index:
+        lo, hi = int(crop_idx.min().item()), int(crop_idx.max().item())
+        if lo < 0 or hi >= n_crops:
+            raise ValueError(f"crop_idx holds {lo} .. {hi}, the table has {n_crops} rows")
+    crop_idx, table = crop_idx.contiguous(), table.contiguous()
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))             # noqa: E731
+    t_hi, t_lo, t_mid = f32(mask_threshold + stability_score_offset), f32(mask_threshold - stability_score_offset), \
+        f32(mask_threshold)
+    _timed('mask_score_crops_kernel', 0, 4.0 * low_res.numel(),
+           lambda: _lib.check(lib.rsp_mask_score_box_crops(low_res.data_ptr(), K, h, w, crop_idx.data_ptr(), table.data_ptr(),
+                                                           n_crops, int(max_out_hw[0]), int(max_out_hw[1]), t_hi, t_lo, t_mid,
+                                                           out.data_ptr(), _stream()), "rsp_mask_score_box_crops"))
+    return out
+
+
 def box_coder(coder):
     """The RspBoxCoder of a DeltaXYWHBBoxCoder-like object (`means`, `stds`, `max_ratio`, `clip_border`, `add_ctr_clamp`,
     `ctr_clamp`: delta_xywh_bbox_coder.py:71-131)."""
@@ -1342,6 +1384,40 @@ def slice_resize_pad(scene_hwc, origins, tile_hw, new_hw, pad_hw, pad_val=(0.0, 
     _lib.check(lib.rsp_slice_resize_pad(im.data_ptr(), 1 if im.dtype == torch.uint8 else 0, SH, SW, origins.data_ptr(), B,
                                         th, tw, out.data_ptr(), Hn, Wn, Hp, Wp, p3, nrm, swap, m3, s3, _stream()),
                "rsp_slice_resize_pad")
+    return out
+
+
+def crops_resize_pad(image_hwc, table, pad_hw, pad_val=(0.0, 0.0, 0.0), out=None, normalise=None):
+    """B crops of DIFFERENT sizes of a device-resident image [H, W, 3] (uint8 / fp32) -> fp32 [B, 3, Hp, Wp], one launch
+    (rsp_crops_resize_pad).  table: int32 [B, 6] = (x0, y0, x1, y1, Hn, Wn) on the device; crop i is bit-identical to
+    `resize_pad(image[y0:y1, x0:x1].contiguous(), (Hn, Wn), pad_hw, pad_val, normalise=normalise)`."""
+    import ctypes
+    lib = _lib.load()
+    if image_hwc.dim() != 3 or image_hwc.shape[2] != 3 or not _is_device(image_hwc):
+        raise ValueError('crops_resize_pad expects an [H, W, 3] device tensor')
+    im = image_hwc.contiguous()
+    if im.dtype != torch.uint8:
+        im = im.to(torch.float32)
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 6 or table.device != im.device:
+        raise ValueError('table: int32 [B, 6] = (x0, y0, x1, y1, Hn, Wn) on the device of the image')
+    table = table.contiguous()
+    B = int(table.shape[0])
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=im.device)
+    if B == 0:
+        return out
+    p3 = (ctypes.c_float * 3)(*[float(v) for v in pad_val])
+    if normalise is None:
+        m3 = s3 = None
+        nrm, swap = 0, 0
+    else:
+        m3 = (ctypes.c_float * 3)(*[float(v) for v in normalise[0]])
+        s3 = (ctypes.c_float * 3)(*[float(v) for v in normalise[1]])
+        nrm, swap = 1, 1 if normalise[2] else 0
+    _lib.check(lib.rsp_crops_resize_pad(im.data_ptr(), 1 if im.dtype == torch.uint8 else 0, int(im.shape[0]), int(im.shape[1]),
+                                        table.data_ptr(), B, out.data_ptr(), Hp, Wp, p3, nrm, swap, m3, s3, _stream()),
+               "rsp_crops_resize_pad")
     return out
 
 

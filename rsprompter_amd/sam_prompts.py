@@ -1,5 +1,6 @@
 """Promptable SAM for callers: `SamSession` (one image embedding, any number of point / box / mask prompts),
-`inference_prompts` (the one-shot form) and `generate_masks` (HF's mask-generation pipeline for the whole image).
+`inference_prompts` (the one-shot form), `generate_masks` (HF's mask-generation pipeline for the whole image) and
+`SamMaskGenerator` (the same with crop layers: the image and overlapping crops of it, merged by one NMS).
 
 What it restates: HF `SamImageProcessor` / `SamProcessor` (transformers models/sam/image_processing_sam.py:
 `_get_preprocess_shape`, `_normalize_coordinates`, `post_process_masks`, `_build_point_grid`, `filter_masks`,
@@ -8,6 +9,10 @@ What it restates: HF `SamImageProcessor` / `SamProcessor` (transformers models/s
 `rsp_sam_embed_prompts`, the decoder `SamMaskDecoderHIP.decode`, full-resolution masks `rsp_mask_post_logits`, candidate
 scoring `rsp_mask_score_box` (no full-resolution field is ever stored for a candidate that is not kept), run lengths
 `rsp_mask_rle`, NMS `rsp_batched_nms`.  The host sees prompt coordinates, the kept count and the final results."""
+import contextlib
+import math
+from itertools import product
+
 import numpy as np
 import torch
 
@@ -181,8 +186,8 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     built per kernel call; _stages: a dict that receives the stage tensors (candidate logits, IoU, scores, kept indices,
     boxes) -- the stage-wise parity tests read them."""
     if crop_n_layers:
-        raise NotImplementedError('generate_masks: crop_n_layers > 0 (multi-crop generation) is not implemented; '
-                                  'the image is processed as one crop')
+        raise NotImplementedError('generate_masks: crop_n_layers > 0 (multi-crop generation) is not implemented here, '
+                                  'the image is processed as one crop; use SamMaskGenerator(model, crop_n_layers=...)')
     if output not in ('rle', 'dense'):
         raise ValueError("output must be 'rle' or 'dense'")
     s = session if session is not None else SamSession(model, image)
@@ -218,3 +223,235 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     else:
         res.masks = rles
     return res
+
+
+# --------------------------------------------------------------------------------------------------- crop layers
+def generate_crop_boxes(crop_n_layers, overlap_ratio, hw):
+    """HF `_generate_per_layer_crops`: ([x0, y0, x1, y1] per crop, layer per crop); crop 0 is the image, then per layer
+    `product(x0s, y0s)` -- 2^(l+1) crops per side, the last of every row and column clamped to the image."""
+    H, W = int(hw[0]), int(hw[1])
+    boxes, layers = [[0, 0, W, H]], [0]
+    short = min(H, W)
+    for l in range(crop_n_layers):
+        n = 2 ** (l + 1)
+        overlap = int(overlap_ratio * short * (2 / n))
+        cw = int(math.ceil((overlap * (n - 1) + W) / n))
+        ch = int(math.ceil((overlap * (n - 1) + H) / n))
+        x0s = [int((cw - overlap) * i) for i in range(n)]
+        y0s = [int((ch - overlap) * i) for i in range(n)]
+        for x0, y0 in product(x0s, y0s):
+            boxes.append([x0, y0, min(x0 + cw, W), min(y0 + ch, H)])
+            layers.append(l + 1)
+    return boxes, layers
+
+
+# crops per encoder / decoder / scoring call by the encoder's width (ViT-B / L / H) when crop_batch is None: the smallest value
+# after which the time per image stopped improving by more than the repetitions' spread in the sweep of
+# tools/bench_sam_prompts.py (profiles/sam_prompts/multicrop.json) ...
+DEFAULT_CROP_BATCH = {768: 16, 1024: 8, 1280: 16}
+# ... and never more candidates per batch than the largest batch that sweep ran (4 crops x 32 x 32 points x 3 masks = 16 crops x
+# 16 x 16 x 3; 3.2 GB of low-resolution logits)
+DEFAULT_BATCH_CANDIDATES = 12288
+
+
+class SamMaskGenerator:
+    """SAM's automatic mask generation with crop layers: the image (crop 0) and, per layer l, 2^l x 2^l overlapping crops of
+    it, each resized to the model's input on its own, prompted with its own point grid, filtered (predicted IoU, stability
+    score, HF `_is_box_near_crop_edge`), moved into the image frame and merged by ONE NMS over all crops.
+
+    The semantics are HF's helpers (`_generate_per_layer_crops`, `_build_point_grid`, `filter_masks`,
+    `_is_box_near_crop_edge`, `_pad_masks`, `_mask_to_rle`, `_post_process_for_mask_generation`) composed per crop -- not
+    HF's `MaskGenerationPipeline`, which filters only the first crop, leaves boxes in crop coordinates and scales a crop's
+    grid with the whole image's resize factor.  Not implemented: segment-anything's per-crop box NMS and its
+    preference for smaller crops, `min_mask_region_area`, the PerSAM hooks.
+
+    `sam`: whatever `SamSession` accepts.  `crop_batch`: crops per encoder / decoder / scoring call (all of one layer, so
+    that they share the number of prompts); None picks `DEFAULT_CROP_BATCH` by the encoder's width, capped at
+    `DEFAULT_BATCH_CANDIDATES` candidates per batch.  `generate(image)`
+    returns `InstanceData` in NMS order, everything in IMAGE coordinates: bboxes fp32 [k, 4], scores fp32 [k], masks (list of
+    uncompressed RLE dicts of size [H, W], or bool [k, H, W] with output='dense'), crop_index int64 [k].  With
+    crop_n_layers=0 the result is `generate_masks`' bit for bit."""
+
+    def __init__(self, sam, points_per_side=32, pred_iou_thresh=0.88, stability_score_thresh=0.95, stability_score_offset=1.0,
+                 mask_threshold=0.0, crops_nms_thresh=0.7, crop_n_layers=1, crop_overlap_ratio=512 / 1500,
+                 crop_n_points_downscale_factor=1, crop_batch=None, output='rle', mask_batch=64):
+        if output not in ('rle', 'dense'):
+            raise ValueError("output must be 'rle' or 'dense'")
+        if int(crop_n_layers) < 0:
+            raise ValueError('crop_n_layers must be >= 0')
+        self.sam = _sam_of(sam)
+        self.crop_n_layers, self.crop_overlap_ratio = int(crop_n_layers), float(crop_overlap_ratio)
+        self.grids = []
+        for l in range(self.crop_n_layers + 1):
+            n = int(points_per_side / crop_n_points_downscale_factor ** l)
+            if n < 1:
+                raise ValueError(f'layer {l}: points_per_side={points_per_side} / crop_n_points_downscale_factor='
+                                 f'{crop_n_points_downscale_factor} ** {l} leaves an empty point grid')
+            self.grids.append(point_grid(n))
+        self.pred_iou_thresh, self.stability_score_thresh = pred_iou_thresh, stability_score_thresh
+        self.stability_score_offset, self.mask_threshold = stability_score_offset, mask_threshold
+        self.crops_nms_thresh, self.output, self.mask_batch = crops_nms_thresh, output, int(mask_batch)
+        if crop_batch is not None and int(crop_batch) < 1:
+            raise ValueError('crop_batch must be >= 1')
+        self.crop_batch = None if crop_batch is None else int(crop_batch)
+        self._phase = lambda name: contextlib.nullcontext()      # tools/bench_sam_prompts.py times the phases through this
+
+    def crop_boxes(self, hw):
+        """[x0, y0, x1, y1] of every crop of an (H, W) image; crop 0 is the image."""
+        return generate_crop_boxes(self.crop_n_layers, self.crop_overlap_ratio, hw)[0]
+
+    def _batches(self, layers):
+        """[(first crop, end)]: consecutive crops of ONE layer, crop_batch at a time; with crop_batch=None the default of the
+        encoder's width, capped so that a batch holds at most DEFAULT_BATCH_CANDIDATES candidates"""
+        out, c = [], 0
+        while c < len(layers):
+            nb = self.crop_batch
+            if nb is None:
+                width = getattr(getattr(self.sam, 'vision_encoder', None), 'D', None)
+                nb = max(1, min(DEFAULT_CROP_BATCH.get(width, 8), DEFAULT_BATCH_CANDIDATES // (3 * self.grids[layers[c]].shape[0])))
+            e = c
+            while e < len(layers) and e - c < nb and layers[e] == layers[c]:
+                e += 1
+            out.append((c, e))
+            c = e
+        return out
+
+    def _plan(self, hw):
+        """per crop: box, layer, input size and the prompt points in the crop's input pixels; the two device tables"""
+        S = self.sam.image_size
+        H, W = hw
+        boxes, layers = generate_crop_boxes(self.crop_n_layers, self.crop_overlap_ratio, hw)
+        front, geo, pts = [], [], []
+        for (x0, y0, x1, y1), l in zip(boxes, layers):
+            ch, cw = y1 - y0, x1 - x0
+            nh, nw = preprocess_shape((ch, cw), S)
+            front.append([x0, y0, x1, y1, nh, nw])
+            geo.append([S, S, nh, nw, ch, cw, x0, y0, x1, y1, W, H])
+            # HF _generate_crop_images: grid * (cw, ch) = crop-local pixels; then to the crop's own input size
+            p = self.grids[l] * np.array([[cw, ch]], dtype=np.float64)
+            pts.append(scale_coords(p[:, None, :], (ch, cw), (nh, nw)))
+        return boxes, layers, front, geo, pts
+
+    @torch.no_grad()
+    def generate(self, image, _stages=None):
+        sam, phase = self.sam, self._phase
+        dev = next(sam.parameters()).device
+        ops.require_device(dev)
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if image.dim() != 3 or image.shape[2] != 3:
+            raise ValueError('expected an [H, W, 3] image')
+        H, W = int(image.shape[0]), int(image.shape[1])
+        if H * W >= 2 ** 31:
+            raise ValueError(f'SamMaskGenerator: a {H} x {W} image has {H * W} pixels; run counts are 32-bit (< 2^31 pixels)')
+        S = sam.image_size
+        boxes_c, layers, front, geo, pts = self._plan((H, W))
+        img = image.to(dev)                                            # the decoded image goes up once
+        front_t = torch.tensor(front, dtype=torch.int32).to(dev)
+        geo_t = torch.tensor(geo, dtype=torch.int32).to(dev)
+        max_out = (max(g[4] for g in geo), max(g[5] for g in geo))
+        batches = self._batches(layers)
+        kept_low, kept_iou, kept_box, kept_crop, kept_cand = [], [], [], [], []
+        n_kept, cand0 = 0, 0
+        for c0, c1 in batches:
+            B, Pb = c1 - c0, pts[c0].shape[0]
+            with phase('crop front end'):
+                pv = ops.crops_resize_pad(img, front_t[c0:c1], (S, S), PIXEL_MEAN, normalise=(PIXEL_MEAN, PIXEL_STD, False))
+            with phase('encoder'):
+                emb = sam.get_image_embeddings(pv)
+            with phase('decoder'):
+                p = torch.from_numpy(np.stack(pts[c0:c1], 0)).to(torch.float32).to(dev)                 # [B, Pb, 1, 2]
+                out = sam(image_embeddings=emb, input_points=p, multimask_output=True,
+                          input_labels=torch.ones((B, Pb, 1), dtype=torch.int32, device=dev))
+                low, iou = out.pred_masks, out.iou_scores
+                K = B * Pb * low.shape[2]
+                low, iou = low.reshape(K, low.shape[-2], low.shape[-1]), iou.reshape(K)
+            with phase('scoring'):
+                cidx = torch.arange(c0, c1, dtype=torch.int32, device=dev).repeat_interleave(K // B)
+                score = ops.mask_score_box_crops(low, cidx, geo_t, max_out, self.mask_threshold, self.stability_score_offset,
+                                                 check_index=False)
+            with phase('filter + NMS'):
+                keep = filter_candidates(iou, score, self.pred_iou_thresh, self.stability_score_thresh) & (score[:, 7] == 0)
+                idx = keep.nonzero()[:, 0]                             # compaction; the one host read of the batch (its size)
+                n_kept += int(idx.shape[0])
+                if n_kept > ops.NMS_MAX_CANDIDATES:
+                    raise ValueError(f'SamMaskGenerator: more than {ops.NMS_MAX_CANDIDATES} candidates pass the filters '
+                                     '(ops.NMS_MAX_CANDIDATES, what rsp_batched_nms holds): raise pred_iou_thresh / '
+                                     'stability_score_thresh or lower points_per_side / crop_n_layers')
+                # the kept candidates' logits leave the batch's buffer here; the next batch may reuse it
+                kept_low.append(low[idx]); kept_iou.append(iou[idx]); kept_box.append(score[idx, 3:7].to(torch.float32))
+                kept_crop.append(cidx[idx]); kept_cand.append(idx + cand0)
+            if _stages is not None:
+                _stages.setdefault('batches', []).append(dict(crops=(c0, c1), low_res=low, iou=iou, score=score, kept=idx))
+            cand0 += K
+            del out, low, score, emb, pv
+        low, scores, boxes = torch.cat(kept_low, 0), torch.cat(kept_iou, 0), torch.cat(kept_box, 0)
+        crop, cand = torch.cat(kept_crop, 0), torch.cat(kept_cand, 0)
+        if _stages is not None:
+            _stages.update(kept=cand, kept_crop=crop, boxes=boxes, crop_boxes=boxes_c)
+        res = InstanceData()
+        n = int(boxes.shape[0])                                        # = n_kept, known on the host
+        with phase('filter + NMS'):
+            if n:
+                # one NMS over all crops (candidates are numbered crop-major, then point, then mask: ties go to the lower
+                # number); its count comes to the host together with the survivors' crops, in ONE read
+                r = ops.batched_nms((boxes.view(1, n, 4), scores.view(1, n), torch.zeros((1, n), dtype=torch.int32, device=dev),
+                                     torch.arange(n, dtype=torch.int32, device=dev).view(1, n),
+                                     torch.full((1,), n, dtype=torch.int32, device=dev)), 1, n, float(self.crops_nms_thresh), n)
+                order_all = r['keep'][0].clamp(0, n - 1).to(torch.int64)
+                packed = torch.cat([r['count'].to(torch.int32), crop[order_all]]).cpu()
+                m = int(packed[0])
+                order, crop_h = order_all[:m], packed[1:1 + m].tolist()
+            else:
+                order, crop_h = torch.zeros((0,), dtype=torch.int64, device=dev), []
+        res.bboxes, res.scores, res.crop_index = boxes[order], scores[order], crop[order].to(torch.int64)
+        if _stages is not None:
+            _stages['final'] = cand[order]
+        with phase('masks + run lengths'):
+            res.masks = self._masks(low, order, crop_h, boxes_c, geo, (H, W), dev)
+        return res
+
+    def _masks(self, low, order, crop_h, boxes_c, geo, hw, dev):
+        """full-resolution masks of the NMS survivors, grouped by crop: rsp_mask_post_logits on the crop's geometry, then the
+        run lengths of the crop-sized mask shifted into the image in the run domain (rsp_mask_rle -> rsp_rle_shift), or the
+        dense paste (rsp_paste_tiles); put back in NMS order"""
+        H, W = hw
+        m = len(crop_h)
+        dense = torch.zeros((m, H, W), dtype=torch.bool, device=dev) if self.output == 'dense' else None
+        rles = [None] * m
+        pending = []                                                   # (positions, counts, n) per launched group
+        for c in sorted(set(crop_h)):
+            pos_all = [i for i, cc in enumerate(crop_h) if cc == c]
+            S0, S1, nh, nw, ch, cw, x0, y0 = geo[c][:8]
+            whole = (ch, cw) == (H, W)
+            for b0 in range(0, len(pos_all), self.mask_batch):
+                pos = pos_all[b0:b0 + self.mask_batch]
+                pos_t = torch.tensor(pos, dtype=torch.int64).to(dev)
+                mk = ops.mask_post_logits(low[order[pos_t]].contiguous(), (S0, S1), (nh, nw), (ch, cw), self.mask_threshold)
+                if dense is not None:
+                    if whole:
+                        dense[pos_t] = mk
+                    else:
+                        off = torch.tensor([[x0, y0]] * len(pos), dtype=torch.int32).to(dev)
+                        dense[pos_t] = ops.paste_tiles(mk, off, (H, W))
+                elif whole:
+                    for i, d in zip(pos, _rle_dicts(mk)):
+                        rles[i] = d
+                else:
+                    pending.append((pos, mk, (x0, y0), (ch, cw)))
+        if dense is not None:
+            return dense
+        for pos, mk, (x0, y0), chw in pending:
+            off = torch.tensor([[x0, y0]] * len(pos), dtype=torch.int32).to(dev)
+            counts, n = ops.mask_rle_counts(mk)
+            cap_out = int(counts.shape[1]) + 2 * chw[1] + 2            # a column end inside a run adds at most two runs
+            while True:
+                sc, sn = ops.rle_shift(counts, n, off, chw, (H, W), cap_out)
+                sn_h = sn.cpu().tolist()
+                if min(sn_h) >= 0:
+                    break
+                cap_out = 1 << (-min(sn_h) - 1).bit_length()
+            sc = sc.cpu().numpy()
+            for j, i in enumerate(pos):
+                rles[i] = dict(size=[H, W], counts=sc[j, :sn_h[j]].tolist())
+        return rles

@@ -11,7 +11,16 @@ repetitions after 3 warm-up ones, timed with device events around the whole phas
       scores (the synthetic weights give no mask a stability score near SAM's default 0.95), offset 0.25;
   (c) alternating with (b)'s scoring leg, the same scores the obvious way: ops.mask_post_logits(want_val=True) in batches
       of 64 and three reductions over the fp32 field.
-The scoring kernel's achieved input bytes/s and pixel evaluations/s are derived from the shapes."""
+The scoring kernel's achieved input bytes/s and pixel evaluations/s are derived from the shapes.
+
+  python tools/bench_sam_prompts.py --multicrop [--arch huge] [--reps 5] [--crop-batches 1,2,4,8] [--out .../multicrop.json]
+
+  (d) the crop layers (`SamMaskGenerator`): crop_n_layers 1 and 2 (downscale factor 2 at two layers), points_per_side=32, by
+      phase (crop front end, encoder, decoder, scoring, filter + NMS, masks + run lengths; device events around every phase,
+      summed per name), against -- alternating, same process -- the same work with what existed before the batched path: a
+      host slice per crop, one SamSession per crop, rsp_mask_score_box per crop, a kept-count read per crop, the near-edge rule
+      and the shift as torch expressions; then the sweep of crop_batch.  --multicrop-once runs one generate() per
+      configuration and nothing else (the process to put under rocprofv3 --kernel-trace --stats)."""
 import argparse
 import json
 import os
@@ -39,11 +48,131 @@ def timed(fn, reps, warm=3):
     return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), max_ms=round(max(ms), 3), reps=reps)
 
 
+def _spread(ms):
+    return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), max_ms=round(max(ms), 3), reps=len(ms))
+
+
+class _Phases:
+    """SamMaskGenerator._phase: device events around every phase, summed per name after one synchronisation"""
+
+    def __init__(self):
+        self.ev = []
+
+    def __call__(self, name):
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            yield
+            b.record()
+            self.ev.append((name, a, b))
+        return cm()
+
+    def take(self):
+        torch.cuda.synchronize()
+        out = {}
+        for name, a, b in self.ev:
+            out[name] = out.get(name, 0.0) + a.elapsed_time(b)
+        self.ev = []
+        return out
+
+
+def multicrop(model, img, a):
+    from rsprompter_amd import ops
+    from rsprompter_amd.sam_prompts import SamMaskGenerator, SamSession, filter_candidates, point_grid
+    dev = img.device
+    H, W = int(img.shape[0]), int(img.shape[1])
+    S, off, n = model.image_size, 0.25, 32
+    s0 = SamSession(model, img)
+    low, iou = s0._low_res((point_grid(n) * np.array([[W, H]]))[:, None, :], None, None, None, True)
+    K = low.shape[0] * 3
+    sc = ops.mask_score_box(low.reshape(K, 256, 256), (S, S), s0.input_size, (H, W), 0.0, off)
+    stab = sc[:, 0] / sc[:, 1]
+    t_iou, t_stab = float(iou.median()), float(stab[~stab.isnan()].median())
+    del s0, low, iou, sc
+    out = dict(points_per_side=n, stability_score_offset=off, pred_iou_thresh=t_iou, stability_score_thresh=t_stab, configs={})
+    kw = dict(points_per_side=n, pred_iou_thresh=t_iou, stability_score_thresh=t_stab, stability_score_offset=off)
+
+    def loop_of(gen):
+        """the same work per crop with what existed before rsp_crops_resize_pad / rsp_mask_score_box_crops"""
+        boxes_c, layers, _, geo, _ = gen._plan((H, W))
+
+        def run():
+            host = img.cpu()                                                       # the decoded image is a host array
+            kl, ki, kb, kc = [], [], [], []
+            for ci, ((x0, y0, x1, y1), l) in enumerate(zip(boxes_c, layers)):
+                s = SamSession(model, host[y0:y1, x0:x1].contiguous())              # host slice, upload, resize, encoder
+                ch, cw = y1 - y0, x1 - x0
+                lo, io = s._low_res((gen.grids[l] * np.array([[cw, ch]]))[:, None, :], None, None, None, True)
+                k = lo.shape[0] * 3
+                lo, io = lo.reshape(k, 256, 256), io.reshape(k)
+                score = ops.mask_score_box(lo, (S, S), s.input_size, (ch, cw), 0.0, off)
+                box = score[:, 3:7] + torch.tensor([[x0, y0, x0, y0]], dtype=torch.int32, device=dev)
+                cb = torch.tensor([[x0, y0, x1, y1]], dtype=torch.int32, device=dev)
+                ob = torch.tensor([[0, 0, W, H]], dtype=torch.int32, device=dev)
+                near = (((box - cb).abs() <= 20) & ((box - ob).abs() > 20)).any(1)
+                idx = (filter_candidates(io, score, t_iou, t_stab) & ~near).nonzero()[:, 0]   # the kept-count read of the crop
+                kl.append(lo[idx]); ki.append(io[idx]); kb.append(box[idx].float())
+                kc.append(torch.full((int(idx.shape[0]),), ci, dtype=torch.int32, device=dev))
+            lo, io, bx, cr = torch.cat(kl), torch.cat(ki), torch.cat(kb), torch.cat(kc)
+            order = ops.nms_flat(bx, io, torch.zeros_like(cr), 0.7)
+            return gen._masks(lo, order, cr[order].cpu().tolist(), boxes_c, geo, (H, W), dev), bx[order]
+        return run
+
+    for layers, down in ((1, 1), (2, 2)):
+        gen = SamMaskGenerator(model, crop_n_layers=layers, crop_n_points_downscale_factor=down, crop_batch=a.crop_batch, **kw)
+        if a.multicrop_once:
+            res = gen.generate(img)
+            torch.cuda.synchronize()
+            out['configs'][f'layers{layers}_down{down}'] = dict(instances=len(res.masks))
+            continue
+        loop = loop_of(gen)
+        res = gen.generate(img)
+        lm, lb = loop()
+        same = tuple(res.bboxes.shape) == tuple(lb.shape) and torch.equal(res.bboxes, lb) and res.masks == lm
+        ph = _Phases()
+        bt, lt, phs = [], [], []
+        for r in range(a.reps + 1):                                                  # alternating; the first pair is warm-up
+            t = []
+            for fn in (lambda: gen.generate(img), loop):
+                gen._phase = ph if fn is not loop else (lambda name: __import__('contextlib').nullcontext())
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                t.append(e0.elapsed_time(e1))
+                if fn is not loop:
+                    p = ph.take()
+            if r:
+                bt.append(t[0]); lt.append(t[1]); phs.append(p)
+        cfg = dict(crops=len(gen.crop_boxes((H, W))), crop_batch=gen.crop_batch, batches=gen._batches(gen._plan((H, W))[1]), instances=len(res.masks),
+                   loop_returns_the_same_instances=bool(same),
+                   crop_index_histogram=torch.bincount(res.crop_index.cpu(), minlength=1).tolist(),
+                   batched=_spread(bt), per_crop_loop=_spread(lt),
+                   phases_ms={k: round(statistics.median([p[k] for p in phs]), 3) for k in phs[0]})
+        cfg['batched_minus_loop_ms'] = round(cfg['batched']['median_ms'] - cfg['per_crop_loop']['median_ms'], 3)
+        cfg['loop_spread_ms'] = round(cfg['per_crop_loop']['max_ms'] - cfg['per_crop_loop']['min_ms'], 3)
+        sweep = {}
+        for cb in a.crop_batches:
+            g2 = SamMaskGenerator(model, crop_n_layers=layers, crop_n_points_downscale_factor=down, crop_batch=cb, **kw)
+            sweep[str(cb)] = timed(lambda: g2.generate(img), a.reps, warm=1)
+        cfg['crop_batch_sweep'] = sweep
+        out['configs'][f'layers{layers}_down{down}'] = cfg
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='huge')
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--multicrop', action='store_true', help='the crop-layer phase (d) only')
+    ap.add_argument('--multicrop-once', action='store_true', help='one generate() per configuration (for a kernel trace)')
+    ap.add_argument('--crop-batch', type=int, default=None)
+    ap.add_argument('--crop-batches', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8])
     a = ap.parse_args()
     from rsprompter_amd import ops
     from rsprompter_amd.samdet import SamModelHIP
@@ -57,6 +186,15 @@ def main():
     model = model.to(dev).eval()
     img = synth_images(1)[0].permute(1, 2, 0).contiguous().to(dev)                 # [1024, 1024, 3] uint8
     out = dict(arch=a.arch, device=torch.cuda.get_device_name(0), image=[1024, 1024])
+    if a.multicrop or a.multicrop_once:
+        out['multicrop'] = multicrop(model, img, a)
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write(json.dumps(out, indent=1) + '\n')
+        return
     out['session_setup'] = timed(lambda: SamSession(model, img), max(5, a.reps // 4))
     s = SamSession(model, img)
     g = np.random.RandomState(0)
