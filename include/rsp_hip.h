@@ -277,6 +277,11 @@ int rsp_attention(const RspAttnDesc* desc, rsp_stream_t stream);
 /*  row block of RoI r (NULL: r); out [R,T,128].                                                                      */
 int rsp_sam_t2i_attention(const float* q, const float* kv, const int32_t* kv_map, float* out, int32_t R, int32_t T,
                           int32_t N, float scale, rsp_stream_t stream);
+/*  token -> image with a key bias (HF:260 `attn = attn + attention_similarity` in front of the softmax, as HF:328-330  */
+/*  passes it to cross_attn_token_to_image of both two-way layers -- PerSAM's hook): bias [Rb, N], Rb = 1 (one row for  */
+/*  every RoI) or R; s = q . k * scale + bias[n].  Everything else as rsp_sam_t2i_attention, whose kernels are unchanged. */
+int rsp_sam_t2i_attention_bias(const float* q, const float* kv, const int32_t* kv_map, const float* bias, int32_t Rb,
+                               float* out, int32_t R, int32_t T, int32_t N, float scale, rsp_stream_t stream);
 /*  image -> token: q [Rq*N,128] image-side queries (q_map[r] = row block, NULL: r), k, v [R,T,128] (T <= 16);        */
 /*  result [R*N,128] as fp32 `out` and/or fp16 planes (KB32, value * 2^out_scale_log2).                               */
 int rsp_sam_i2t_attention(const float* q, const int32_t* q_map, const float* k, const float* v, float* out,
@@ -671,6 +676,34 @@ int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, in
 int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t h, int32_t w, const int32_t* crop_idx,
                              const int32_t* table, int32_t n_crops, int32_t max_out_h, int32_t max_out_w, float t_hi,
                              float t_lo, float t_mid, int32_t* out, rsp_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* PerSAM (training-free one-shot segmentation; persam.py of Zhang et al.'s code around SAM)                               */
+/* ------------------------------------------------------------------------ */
+/* `target_feat = ref_feat[ref_mask > 0]; target_embedding = target_feat.mean(0); target_feat = target_embedding /          */
+/* target_embedding.norm()`: emb [N, 256] channels-last embedding rows of the reference, cell_mask [N] bytes (non-zero =     */
+/* selected).  target_embedding, target_feature fp32 [256], count int32 [1] = selected cells, all on the device; with no     */
+/* selected cell both vectors are zero (the caller refuses on the count).  Fixed summation order.                            */
+int rsp_persam_target(const float* emb, const uint8_t* cell_mask, int32_t N, float* target_embedding, float* target_feature,
+                      int32_t* count, rsp_stream_t stream);
+/* `test_feat = test_feat / test_feat.norm(dim=0); sim = target_feat @ test_feat; sim = F.interpolate(sim, scale_factor=4,  */
+/* mode='bilinear')` for B images at once: emb [B * gh * gw, 256] rows (16-byte aligned), target_feature [256].  sim         */
+/* [B, gh * gw] (a zero row scores 0), low_res [B, 4 gh, 4 gw]: the layout rsp_mask_post_logits / rsp_persam_locate take.    */
+int rsp_persam_similarity(const float* emb, const float* target_feature, int32_t B, int32_t gh, int32_t gw, float* sim,
+                          float* low_res, rsp_stream_t stream);
+/* PerSAM's `postprocess_masks(sim)` + `point_selection(sim, topk=1)` + `(sim - sim.mean()) / torch.std(sim)` +             */
+/* `F.interpolate(size=(g, g), mode='bilinear').sigmoid()` without the [k, out_h, out_w] field: low_res [k, h, w] and the    */
+/* geometry of rsp_mask_post_logits (the values are that entry point's `out_val`, same device functions).  stats fp32        */
+/* [k, 4] = maximum, minimum, mean, unbiased standard deviation; xy int32 [k, 5] = x, y of the maximum, x, y of the minimum  */
+/* (the LOWEST flat index y * out_w + x among equal values: torch.argmax / argmin of the flattened field), pixel count;     */
+/* attn_sim fp32 [k, g * g] = sigmoid((D - mean) / std), D the bilinear g x g resampling of the field.  A constant field    */
+/* has std 0 and 0 / 0 := 0 there: attn_sim = 0.5 (PerSAM yields NaN).  Extrema by one 64-bit integer atomic per block,     */
+/* sums as fp64 block partials added in block order: no floating-point atomics, two runs give the same bits.  workspace:   */
+/* rsp_persam_locate_workspace_bytes(k, out_h, out_w) bytes, 8-byte aligned (-1 for arguments the call would refuse).       */
+int64_t rsp_persam_locate_workspace_bytes(int32_t k, int32_t out_h, int32_t out_w);
+int rsp_persam_locate(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
+                      int32_t crop_w, int32_t out_h, int32_t out_w, int32_t g, void* workspace, int64_t workspace_bytes,
+                      float* stats, int32_t* xy, float* attn_sim, rsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -212,6 +212,13 @@ PROTOTYPES = {
                                      ctypes.POINTER(c_float), c_void_p]),
     "rsp_mask_score_box_crops": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                                          c_float, c_float, c_void_p, c_void_p]),
+    "rsp_sam_t2i_attention_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                           c_float, c_void_p]),
+    "rsp_persam_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_persam_similarity": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rsp_persam_locate_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "rsp_persam_locate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -204,4 +204,4 @@ class DetInferencer:
 
 
 from .large_image import inference_large_image  # noqa: E402,F401  (sliced inference on large scenes)
-from .sam_prompts import SamMaskGenerator, SamSession, generate_masks, inference_prompts  # noqa: E402,F401  (promptable SAM)
+from .sam_prompts import PerSam, SamMaskGenerator, SamSession, generate_masks, inference_prompts  # noqa: E402,F401  (promptable SAM)

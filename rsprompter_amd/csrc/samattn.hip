@@ -120,6 +120,112 @@ __global__ __launch_bounds__(512) void sam_t2i_kernel(const float* __restrict__ 
   }
 }
 
+// The same block with a key bias (rsp_sam_t2i_attention_bias; HF:260, PerSAM's attention_similarity): a sibling, not a template
+// parameter of sam_t2i_kernel -- sharing the body through a device function changed hipcc's unrolling of the UNBIASED kernel
+// (2 766 -> 1 281 lines of assembly), and that kernel is on the measured path.
+//   bias [Rb, N]              one additive logit per key: s = q . k * scale + bias[n]; bias_stride = 0 (one row shared by all
+//                             RoIs) or N.  It joins the base-2 softmax as bias * log2(e), AFTER the cross-lane sum of the two
+//                             half dot products, so the product's expression tree is the unbiased kernel's, and the value of the
+//                             NEXT key is requested together with its K | V rows (4 bytes on top of the 1 KiB a key costs)
+template <int TMAX>
+__global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restrict__ q, const float* __restrict__ kv,
+                                                           const int32_t* __restrict__ kv_map, const float* __restrict__ bias,
+                                                           int bias_stride, float* __restrict__ out, int T, int N, float scale) {
+  constexpr int HD = DH / 2;
+  __shared__ __attribute__((aligned(16))) float sQ[TMAX * W];
+  const int r = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int h = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane & 1;
+  for (int i = tid; i < TMAX * W; i += 512)
+    sQ[i] = (i < T * W) ? q[(int64_t)r * T * W + i] * (scale * LOG2E) : 0.f;   // softmax in base 2
+  __syncthreads();
+  const int64_t rb = kv_map ? kv_map[r] : r;
+  const float* kbase = kv + rb * (int64_t)N * (2 * W) + h * DH + half * HD;
+  const float* qbase = &sQ[h * DH + half * HD];
+
+  float m[TMAX], l[TMAX], acc[TMAX][HD];
+#pragma unroll
+  for (int t = 0; t < TMAX; ++t) {
+    m[t] = -INFINITY; l[t] = 0.f;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) acc[t][d] = 0.f;
+  }
+  // the rows of the NEXT key are requested before the current key's 10 x 26 VALU operations: with two waves per SIMD
+  // and four loads per ~2 us of latency the kernel ran at 2.9 TB/s of its K | V stream (round 3); the wave's last
+  // request reads the row of its last key again (clamped: no out-of-range access)
+  int key = lane >> 1;
+  f32x4 k0 = {0.f, 0.f, 0.f, 0.f}, k1 = k0, v0 = k0, v1 = k0;
+  if (key < N) {
+    const float* kr = kbase + (int64_t)key * (2 * W);
+    k0 = *reinterpret_cast<const f32x4*>(kr); k1 = *reinterpret_cast<const f32x4*>(kr + 4);
+    v0 = *reinterpret_cast<const f32x4*>(kr + W); v1 = *reinterpret_cast<const f32x4*>(kr + W + 4);
+  }
+  const float* brow = bias + (int64_t)r * bias_stride;
+  float b0 = (key < N) ? brow[key] * LOG2E : 0.f;
+  for (; key < N; key += 32) {
+    // the loop-invariant q values fit in registers next to the accumulators up to 10 tokens; beyond that they are
+    // re-read from LDS (wave-uniform addresses) every key instead of being hoisted into spills
+    if constexpr (TMAX > 10) asm volatile("" ::: "memory");
+    const float* kn = kbase + (int64_t)min(key + 32, N - 1) * (2 * W);
+    const f32x4 nk0 = *reinterpret_cast<const f32x4*>(kn), nk1 = *reinterpret_cast<const f32x4*>(kn + 4);
+    const f32x4 nv0 = *reinterpret_cast<const f32x4*>(kn + W), nv1 = *reinterpret_cast<const f32x4*>(kn + W + 4);
+    const float nb0 = brow[min(key + 32, N - 1)] * LOG2E;
+#pragma unroll
+    for (int t = 0; t < TMAX; ++t) {
+      const f32x4 q0 = *reinterpret_cast<const f32x4*>(qbase + t * W);
+      const f32x4 q1 = *reinterpret_cast<const f32x4*>(qbase + t * W + 4);
+      float s = q0[0] * k0[0] + q0[1] * k0[1] + q0[2] * k0[2] + q0[3] * k0[3] +
+                q1[0] * k1[0] + q1[1] * k1[1] + q1[2] * k1[2] + q1[3] * k1[3];
+      s += __shfl_xor(s, 1, 64);                               // the other 8 dims of the same key
+      s += b0;
+      const float mn = fmaxf(m[t], s);
+      const float a = __builtin_amdgcn_exp2f(m[t] - mn);      // 0 on the first key (m = -inf)
+      const float p = __builtin_amdgcn_exp2f(s - mn);
+      m[t] = mn;
+      l[t] = l[t] * a + p;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[t][e] = acc[t][e] * a + p * v0[e];
+        acc[t][4 + e] = acc[t][4 + e] * a + p * v1[e];
+      }
+    }
+    k0 = nk0; k1 = nk1; v0 = nv0; v1 = nv1; b0 = nb0;
+  }
+  // merge the 32 per-key-slot states of this (head, dim half) with a butterfly, then slot 0 normalises and stores
+  for (int o = 32; o > 1; o >>= 1) {
+#pragma unroll
+    for (int t = 0; t < TMAX; ++t) {
+      const float mo = __shfl_xor(m[t], o, 64);
+      const float lo = __shfl_xor(l[t], o, 64);
+      const float mn = fmaxf(m[t], mo);
+      const float a = (m[t] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m[t] - mn);
+      const float b = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+      l[t] = l[t] * a + lo * b;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) {
+        const float ao = __shfl_xor(acc[t][d], o, 64);
+        acc[t][d] = acc[t][d] * a + ao * b;
+      }
+      m[t] = mn;
+    }
+  }
+  if (lane < 2) {
+#pragma unroll
+    for (int t = 0; t < TMAX; ++t) {
+      if (t < T) {
+        const float inv = 1.0f / l[t];
+        float* dst = out + ((int64_t)r * T + t) * W + h * DH + half * HD;
+        f32x4 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o0[e] = acc[t][e] * inv; o1[e] = acc[t][4 + e] * inv; }
+        *reinterpret_cast<f32x4*>(dst) = o0;
+        *reinterpret_cast<f32x4*>(dst + 4) = o1;
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // image -> token.  Block = 256 threads = 32 image positions x 8 heads per pass (lane&7 = head: a wave reads 8 whole
 // rows = 4 KiB contiguous), PIX_PER_BLOCK positions per block so that the RoI's K/V (T x 128 each) is staged once.
@@ -654,6 +760,21 @@ extern "C" int rsp_sam_t2i_attention(const float* q, const float* kv, const int3
   if (T <= 8) hipLaunchKernelGGL((sam_t2i_kernel<8>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
   else if (T <= 10) hipLaunchKernelGGL((sam_t2i_kernel<10>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
   else hipLaunchKernelGGL((sam_t2i_kernel<12>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+extern "C" int rsp_sam_t2i_attention_bias(const float* q, const float* kv, const int32_t* kv_map, const float* bias,
+                                          int32_t Rb, float* out, int32_t R, int32_t T, int32_t N, float scale,
+                                          rsp_stream_t stream) {
+  if (!q || !kv || !out || !bias || R < 0 || T <= 0 || T > 12 || N <= 0) return RSP_EINVAL;
+  if (R == 0) return RSP_OK;
+  if (Rb != 1 && Rb != R) return RSP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int bs = Rb == 1 ? 0 : N;
+  if (T <= 8) hipLaunchKernelGGL((sam_t2i_bias_kernel<8>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
+  else if (T <= 10) hipLaunchKernelGGL((sam_t2i_bias_kernel<10>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
+  else hipLaunchKernelGGL((sam_t2i_bias_kernel<12>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

@@ -374,6 +374,172 @@ __global__ __launch_bounds__(256) void mask_score_crops_final_kernel(int32_t* __
   acc[m * 8 + 7] = flag;
 }
 
+// PerSAM's location prior (rsp_persam_locate; PerSAM persam.py `point_selection` + the normalisation of the similarity in
+// front of `attn_sim`): the extrema of the IMAGE-RESOLUTION field with their positions, its mean and unbiased standard
+// deviation, and the g x g resampling of the normalised field -- the field being what the kernels above would write for these
+// logits (same device functions, the strip form where launch_mask_post takes it), and never written.
+//   extrema   one 64-bit integer atomic per block on a packed key (order-preserving image of the value << 32 | index): the
+//             maximum carries ~index, the minimum index, so that among equal values the LOWEST flat index y * ow + x wins
+//             either way (torch.argmax / argmin of the flattened field; a plateau at the extreme is the normal case for a
+//             bilinear up-sampling with clamped borders).  -0 counts as +0, as it does for torch.
+//   sums      fp64, of v - K with K the image's first logit (a constant field sums exact zeros), per thread, then a fixed
+//             tree per block, one partial pair per block in memory, added in block order by the finalising launch: no
+//             floating-point atomic, so two runs give the same bits.
+struct LocateP {
+  MaskPostP g;                 // geometry + logits (out / prob / thr / strict unused)
+  unsigned long long* keys;    // [k, 2] packed maximum, minimum
+  double* part;                // [k, gx, 2] sum, sum of squares of (v - K) per block
+  int gx;
+};
+
+__device__ __forceinline__ uint32_t locate_ord(float v) {
+  const uint32_t u = __float_as_uint(v + 0.0f);           // -0 -> +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float locate_unord(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+struct LocateAcc {
+  unsigned long long kmax, kmin;
+  double s, ss;
+  __device__ __forceinline__ void clear() { kmax = 0ull; kmin = ~0ull; s = 0.0; ss = 0.0; }
+  __device__ __forceinline__ void add(float v, int idx, float K) {
+    const unsigned long long o = (unsigned long long)locate_ord(v) << 32;
+    const unsigned long long a = o | (unsigned long long)(0xffffffffu - (uint32_t)idx), b = o | (unsigned long long)(uint32_t)idx;
+    kmax = a > kmax ? a : kmax;
+    kmin = b < kmin ? b : kmin;
+    const double d = (double)v - (double)K;
+    s += d;
+    ss += d * d;
+  }
+};
+
+// every thread of the block calls this (uniform control flow): a fixed binary tree over the 256 threads in LDS
+__device__ __forceinline__ void locate_block_reduce(LocateAcc a, const LocateP& q, int m) {
+  __shared__ unsigned long long sMax[256], sMin[256];
+  __shared__ double sS[256], sQ[256];
+  const int t = threadIdx.x;
+  sMax[t] = a.kmax; sMin[t] = a.kmin; sS[t] = a.s; sQ[t] = a.ss;
+  __syncthreads();
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (t < d) {
+      sMax[t] = sMax[t + d] > sMax[t] ? sMax[t + d] : sMax[t];
+      sMin[t] = sMin[t + d] < sMin[t] ? sMin[t + d] : sMin[t];
+      sS[t] = sS[t] + sS[t + d];
+      sQ[t] = sQ[t] + sQ[t + d];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    atomicMax(q.keys + (int64_t)m * 2, sMax[0]);
+    atomicMin(q.keys + (int64_t)m * 2 + 1, sMin[0]);
+    double* pp = q.part + ((int64_t)m * q.gx + blockIdx.x) * 2;
+    pp[0] = sS[0]; pp[1] = sQ[0];
+  }
+}
+
+template <bool IDENT>
+__global__ __launch_bounds__(256) void persam_locate_kernel(const LocateP q) {
+  const MaskPostP& p = q.g;
+  const int m = blockIdx.y;
+  const float* low = p.low + (int64_t)m * p.h * p.w;
+  const MaskScales sc = mask_scales(p);
+  const int64_t total = (int64_t)p.oh * p.ow;
+  const float K = low[0];
+  LocateAcc a;
+  a.clear();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
+    a.add(mask_pixel<IDENT>(low, p, sc, oy, ox), (int)i, K);
+  }
+  locate_block_reduce(a, q, m);
+}
+
+// strip form, taken exactly where launch_mask_post takes mask_post_strip_kernel; a thread walks LOC_ROWS rows of its 4 columns
+constexpr int LOC_ROWS = 16;
+__global__ __launch_bounds__(256) void persam_locate_strip_kernel(const LocateP q) {
+  const MaskPostP& p = q.g;
+  const int m = blockIdx.y;
+  const float* low = p.low + (int64_t)m * p.h * p.w;
+  const MaskScales sc = mask_scales(p);
+  const int qw = p.ow >> 2;
+  const int ntile = (p.oh + LOC_ROWS - 1) / LOC_ROWS;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const float K = low[0];
+  LocateAcc a;
+  a.clear();
+  if (i < ntile * qw) {
+    const int ty = i / qw, ox = (i - ty * qw) << 2;
+    MaskStrip st;
+    st.init(p, sc, ox);
+    const int oy_end = min((ty + 1) * LOC_ROWS, p.oh);
+    for (int oy = ty * LOC_ROWS; oy < oy_end; ++oy) {
+      float v[4];
+      st.row(low, p, sc, oy, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a.add(v[e], oy * p.ow + ox + e, K);
+    }
+  }
+  locate_block_reduce(a, q, m);
+}
+
+__global__ __launch_bounds__(256) void persam_locate_init_kernel(unsigned long long* __restrict__ keys, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < k * 2) keys[i] = (i & 1) ? ~0ull : 0ull;
+}
+
+// one thread per image: the block partials in block order, then stats = {max, min, mean, std}, xy = {x+, y+, x-, y-, pixels}.
+// std is torch.std's (unbiased); a constant field (max == min) has std 0 exactly, as has a field of one pixel.
+__global__ __launch_bounds__(64) void persam_locate_final_kernel(const LocateP q, float* __restrict__ stats, int32_t* __restrict__ xy) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= q.g.k) return;
+  const double* pp = q.part + (int64_t)m * q.gx * 2;
+  double s = 0.0, ss = 0.0;
+  for (int b = 0; b < q.gx; ++b) { s += pp[2 * b]; ss += pp[2 * b + 1]; }
+  const double n = (double)q.g.oh * (double)q.g.ow;
+  const double K = (double)q.g.low[(int64_t)m * q.g.h * q.g.w];
+  const unsigned long long kmax = q.keys[(int64_t)m * 2], kmin = q.keys[(int64_t)m * 2 + 1];
+  const uint32_t omax = (uint32_t)(kmax >> 32), omin = (uint32_t)(kmin >> 32);
+  const int imax = (int)(0xffffffffu - (uint32_t)kmax), imin = (int)(uint32_t)kmin;
+  double var = n > 1.0 ? (ss - s * s / n) / (n - 1.0) : 0.0;
+  if (!(var > 0.0) || omax == omin) var = 0.0;
+  stats[m * 4 + 0] = locate_unord(omax);
+  stats[m * 4 + 1] = locate_unord(omin);
+  stats[m * 4 + 2] = (float)(K + s / n);
+  stats[m * 4 + 3] = (float)sqrt(var);
+  xy[m * 5 + 0] = imax % q.g.ow; xy[m * 5 + 1] = imax / q.g.ow;
+  xy[m * 5 + 2] = imin % q.g.ow; xy[m * 5 + 3] = imin / q.g.ow;
+  xy[m * 5 + 4] = q.g.oh * q.g.ow;
+}
+
+// attn_sim[m, cy * g + cx] = sigmoid((D - mean) / std), D = the bilinear g x g resampling of the image-resolution field
+// (F.interpolate(size=(g, g), align_corners=False): four field values per cell, evaluated here).  PerSAM normalises first and
+// resamples then; the normalisation is affine and the weights sum to 1, so the order does not matter.  std == 0: 0 / 0 := 0,
+// i.e. 0.5 everywhere (PerSAM itself would produce NaN).
+__global__ __launch_bounds__(256) void persam_attn_sim_kernel(const MaskPostP p, int g, const float* __restrict__ stats,
+                                                              float* __restrict__ attn) {
+  const int m = blockIdx.y;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= g * g) return;
+  const float* low = p.low + (int64_t)m * p.h * p.w;
+  const MaskScales sc = mask_scales(p);
+  const int cy = c / g, cx = c - cy * g;
+  const Lin ly = lin_coef(cy, (float)p.oh / (float)g, p.oh), lx = lin_coef(cx, (float)p.ow / (float)g, p.ow);
+  float a00, a01, a10, a11;
+  if (p.ch == p.oh && p.cw == p.ow) {
+    a00 = mask_pixel<true>(low, p, sc, ly.i0, lx.i0); a01 = mask_pixel<true>(low, p, sc, ly.i0, lx.i1);
+    a10 = mask_pixel<true>(low, p, sc, ly.i1, lx.i0); a11 = mask_pixel<true>(low, p, sc, ly.i1, lx.i1);
+  } else {
+    a00 = mask_pixel<false>(low, p, sc, ly.i0, lx.i0); a01 = mask_pixel<false>(low, p, sc, ly.i0, lx.i1);
+    a10 = mask_pixel<false>(low, p, sc, ly.i1, lx.i0); a11 = mask_pixel<false>(low, p, sc, ly.i1, lx.i1);
+  }
+  const float D = ly.l0 * (lx.l0 * a00 + lx.l1 * a01) + ly.l1 * (lx.l0 * a10 + lx.l1 * a11);
+  const float mean = stats[m * 4 + 2], sd = stats[m * 4 + 3];
+  const float z = sd > 0.f ? (D - mean) / sd : 0.f;
+  attn[(int64_t)m * g * g + c] = 1.0f / (1.0f + expf(-z));
+}
+
 }  // namespace
 
 extern "C" int rsp_hyper_mask(const float* up, const float* hyper, float* out, int32_t R, int32_t npix,
@@ -501,6 +667,52 @@ extern "C" int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t
   return RSP_OK;
 }
 
+
+namespace {
+// blocks per image of rsp_persam_locate's reduction (also the number of fp64 partial pairs per image in its workspace)
+int locate_gx(int out_h, int out_w, bool strip) {
+  if (strip) return (int)(((int64_t)((out_h + LOC_ROWS - 1) / LOC_ROWS) * (out_w >> 2) + 255) / 256);
+  const int64_t gx = ((int64_t)out_h * out_w + 255) / 256;
+  return (int)(gx > 256 ? 256 : gx);
+}
+}  // namespace
+
+extern "C" int64_t rsp_persam_locate_workspace_bytes(int32_t k, int32_t out_h, int32_t out_w) {
+  if (k < 0 || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > 0x7fffffffLL) return -1;
+  const int gs = locate_gx(out_h, out_w, true), gg = locate_gx(out_h, out_w, false);
+  return (int64_t)k * (16 + 16 * (int64_t)(gs > gg ? gs : gg));
+}
+
+extern "C" int rsp_persam_locate(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
+                                 int32_t crop_w, int32_t out_h, int32_t out_w, int32_t g, void* workspace,
+                                 int64_t workspace_bytes, float* stats, int32_t* xy, float* attn_sim, rsp_stream_t stream) {
+  if (!low_res || !workspace || !stats || !xy || !attn_sim || k < 0 || k > 65535 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 ||
+      crop_h <= 0 || crop_w <= 0 || crop_h > Hb || crop_w > Wb || out_h <= 0 || out_w <= 0 || g <= 0 || g > 4096 ||
+      (int64_t)out_h * out_w > 0x7fffffffLL)
+    return RSP_EINVAL;
+  if (workspace_bytes < rsp_persam_locate_workspace_bytes(k, out_h, out_w) || ((uintptr_t)workspace & 7)) return RSP_EINVAL;
+  if (k == 0) return RSP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool ident = crop_h == out_h && crop_w == out_w;
+  const bool strip = ident && (out_w & 3) == 0;
+  LocateP q;
+  q.g.low = low_res; q.g.out = nullptr; q.g.prob = nullptr; q.g.k = k; q.g.h = h; q.g.w = w; q.g.Hb = Hb; q.g.Wb = Wb;
+  q.g.ch = crop_h; q.g.cw = crop_w; q.g.oh = out_h; q.g.ow = out_w; q.g.thr = 0.f; q.g.strict = 1;
+  q.keys = reinterpret_cast<unsigned long long*>(workspace);
+  q.part = reinterpret_cast<double*>(q.keys + (int64_t)k * 2);
+  q.gx = locate_gx(out_h, out_w, strip);
+  hipLaunchKernelGGL(persam_locate_init_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, q.keys, k);
+  if (strip)
+    hipLaunchKernelGGL(persam_locate_strip_kernel, dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
+  else if (ident)
+    hipLaunchKernelGGL((persam_locate_kernel<true>), dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
+  else
+    hipLaunchKernelGGL((persam_locate_kernel<false>), dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(persam_locate_final_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, q, stats, xy);
+  hipLaunchKernelGGL(persam_attn_sim_kernel, dim3((unsigned)((g * g + 255) / 256), k), dim3(256), 0, st, q.g, g, stats, attn_sim);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // FCNMaskHead._predict_by_feat_single + _do_paste_mask (mmdet/models/roi_heads/mask_heads/fcn_mask_head.py:276-480),

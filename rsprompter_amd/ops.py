@@ -787,6 +787,29 @@ def sam_t2i_attention(q, kv, out, *, R, T, N, scale, kv_map=None):
     return out
 
 
+def sam_t2i_attention_bias(q, kv, bias, out, *, R, T, N, scale, kv_map=None):
+    """sam_t2i_attention with one additive logit per key (HF:260, PerSAM's `attention_similarity`): bias [Rb, N] fp32, Rb = 1
+    (shared by the R prompt sets) or R; softmax(q . k * scale + bias) v."""
+    lib = _lib.load()
+    for t, n in ((q, 'q'), (kv, 'kv'), (out, 'out'), (bias, 'bias')):
+        _chk_f32(t, n)
+        if not t.is_contiguous():
+            raise ValueError(f'sam_t2i_attention_bias: {n} must be contiguous')
+    if q.shape[-1] != 128 or kv.shape[-1] != 256:
+        raise ValueError('sam_t2i_attention_bias expects internal width 128 (q) and fused K|V rows of 256')
+    if bias.dim() != 2 or bias.shape[1] != N or bias.shape[0] not in (1, R):
+        raise ValueError(f'sam_t2i_attention_bias: bias must be [1 | {R}, {N}], got {tuple(bias.shape)}')
+    if T > SAM_T2I_MAX_TOKENS:
+        raise ValueError(f'sam_t2i_attention_bias: at most {SAM_T2I_MAX_TOKENS} tokens')
+    Rb = int(bias.shape[0])
+    _timed('sam_t2i_bias_kernel', 4.0 * R * T * N * 128, 4.0 * R * N * 257,
+           lambda: _lib.check(lib.rsp_sam_t2i_attention_bias(q.data_ptr(), kv.data_ptr(), _ptr(kv_map), bias.data_ptr(), Rb,
+                                                             out.data_ptr(), R, T, N, scale, _stream()),
+                              "rsp_sam_t2i_attention_bias"),
+           detail=f'R={R} T={T} N={N} Rb={Rb}')
+    return out
+
+
 def sam_upscale_fused(x, w1, bias1, gamma, beta, eps, w2p, bias2, hyper, h, w):
     """x Planes [R*h*w, 256] -> masks [R, 4h, 4w] (ConvT + LN + GELU + ConvT + GELU + hyper dot in one kernel, csrc/upscale.hip);
     w1 = PackedWeight [(dy, dx, co), 256], w2p = PackedWeight [(dy2, dx2, c2), 64] with its K columns in the order
@@ -1089,6 +1112,74 @@ def mask_score_box(low_res, img_shape, crop_hw, out_hw, mask_threshold=0.0, stab
                                                      crop_hw[1], out_hw[0], out_hw[1], t_hi, t_lo, t_mid, out.data_ptr(),
                                                      _stream()), "rsp_mask_score_box"))
     return out
+
+
+def persam_target(emb_rows, cell_mask):
+    """PerSAM's target: emb_rows [N, 256] (the reference's channels-last embedding rows), cell_mask bool / uint8 [N] ->
+    (target_embedding fp32 [256] = mean of the selected rows, target_feature fp32 [256] = its unit vector, count int32 [1]),
+    all on the device; zeros with an empty selection."""
+    lib = _lib.load()
+    _chk_f32(emb_rows, "emb_rows")
+    if emb_rows.dim() != 2 or emb_rows.shape[1] != 256 or not emb_rows.is_contiguous():
+        raise ValueError("persam_target expects contiguous [N, 256] embedding rows")
+    N = int(emb_rows.shape[0])
+    if cell_mask.dtype not in (torch.bool, torch.uint8) or cell_mask.numel() != N or cell_mask.device != emb_rows.device:
+        raise ValueError("cell_mask: bool or uint8 [N] on the device of emb_rows")
+    cell = cell_mask.reshape(N).contiguous()
+    dev = emb_rows.device
+    te = torch.empty((256,), dtype=torch.float32, device=dev)
+    tf = torch.empty((256,), dtype=torch.float32, device=dev)
+    cnt = torch.empty((1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_persam_target(emb_rows.data_ptr(), cell.data_ptr(), N, te.data_ptr(), tf.data_ptr(), cnt.data_ptr(),
+                                     _stream()), "rsp_persam_target")
+    return te, tf, cnt
+
+
+def persam_similarity(emb_rows, target_feature, B, gh, gw):
+    """emb_rows [B * gh * gw, 256], target_feature [256] -> (sim [B, gh * gw] = cosine similarity of every cell with the
+    target, low_res [B, 4 gh, 4 gw] = its bilinear x 4 up-sampling: what mask_post_logits / persam_locate take)."""
+    lib = _lib.load()
+    _chk_f32(emb_rows, "emb_rows")
+    _chk_f32(target_feature, "target_feature")
+    if emb_rows.dim() != 2 or emb_rows.shape[1] != 256 or emb_rows.shape[0] != B * gh * gw or not emb_rows.is_contiguous():
+        raise ValueError(f"persam_similarity expects contiguous [{B * gh * gw}, 256] embedding rows")
+    if target_feature.numel() != 256 or not target_feature.is_contiguous():
+        raise ValueError("target_feature: contiguous [256]")
+    dev = emb_rows.device
+    sim = torch.empty((B, gh * gw), dtype=torch.float32, device=dev)
+    low = torch.empty((B, 4 * gh, 4 * gw), dtype=torch.float32, device=dev)
+    _timed('persam_similarity_kernel', 4.0 * B * gh * gw * 256, 4.0 * B * gh * gw * 256,
+           lambda: _lib.check(lib.rsp_persam_similarity(emb_rows.data_ptr(), target_feature.data_ptr(), B, gh, gw, sim.data_ptr(),
+                                                        low.data_ptr(), _stream()), "rsp_persam_similarity"))
+    return sim, low
+
+
+def persam_locate(low_res, img_shape, crop_hw, out_hw, g):
+    """PerSAM's location prior of k similarity fields without the fields: low_res [k, h, w] and the geometry of
+    mask_post_logits -> (stats fp32 [k, 4] = max, min, mean, unbiased std of the [out_h, out_w] field; xy int32 [k, 5] = x, y
+    of the maximum, x, y of the minimum -- lowest flat index among equal values --, pixel count; attn_sim fp32 [k, g * g] =
+    sigmoid((D - mean) / std) with D the bilinear g x g resampling of the field; 0.5 where std == 0)."""
+    lib = _lib.load()
+    _chk_f32(low_res, "low_res")
+    if low_res.dim() != 3 or not low_res.is_contiguous():
+        raise ValueError("persam_locate expects contiguous [k, h, w] fields")
+    k, h, w = low_res.shape
+    dev = low_res.device
+    stats = torch.empty((k, 4), dtype=torch.float32, device=dev)
+    xy = torch.empty((k, 5), dtype=torch.int32, device=dev)
+    attn = torch.empty((k, g * g), dtype=torch.float32, device=dev)
+    if k == 0:
+        return stats, xy, attn
+    nws = int(lib.rsp_persam_locate_workspace_bytes(k, int(out_hw[0]), int(out_hw[1])))
+    if nws < 0:
+        raise ValueError(f"persam_locate: unsupported geometry {tuple(out_hw)} for {k} fields")
+    ws = torch.empty((nws // 8,), dtype=torch.int64, device=dev)
+    _timed('persam_locate_kernel', 0, 4.0 * low_res.numel(),
+           lambda: _lib.check(lib.rsp_persam_locate(low_res.data_ptr(), k, h, w, img_shape[0], img_shape[1], crop_hw[0],
+                                                    crop_hw[1], out_hw[0], out_hw[1], int(g), ws.data_ptr(), nws,
+                                                    stats.data_ptr(), xy.data_ptr(), attn.data_ptr(), _stream()),
+                              "rsp_persam_locate"))
+    return stats, xy, attn
 
 
 CROP_TABLE_COLS = 12    # rsp_mask_score_box_crops: Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H

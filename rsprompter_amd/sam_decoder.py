@@ -60,6 +60,41 @@ def _g(root, dotted):
     return root
 
 
+HOOK_FORMS = ('accepted forms: attention_similarity 4-D [1 | B * Pb, 1, 1, N] (one bias row over the N image positions, shared '
+              'or per prompt set; no per-head, per-token or other shape), with at most ops.SAM_T2I_MAX_TOKENS = 12 tokens; '
+              'target_embedding [..., 256] that broadcasts to [B, Pb, 1, 256] (every other dimension 1 or equal)')
+
+
+def persam_hooks(attention_similarity, target_embedding, B, Pb, N, T):
+    """HF's PerSAM hooks (`SamModel.forward(attention_similarity=, target_embedding=)`, HF:183-187, 386-387) in the forms this
+    decoder takes -> (bias [1 | B * Pb, N] or None, target rows [1 | B * Pb, 256] or None) for `decode`; every other shape
+    raises NotImplementedError naming the accepted ones."""
+    R = B * Pb
+    bias = te = None
+    if attention_similarity is not None:
+        a = attention_similarity
+        if not torch.is_tensor(a) or a.dim() != 4 or a.shape[1] != 1 or a.shape[2] != 1 or a.shape[3] != N or \
+                a.shape[0] not in (1, R):
+            raise NotImplementedError(f'attention_similarity of shape {tuple(getattr(a, "shape", ()))} for B * Pb = {R}, N = {N}; '
+                                      + HOOK_FORMS)
+        if T > ops.SAM_T2I_MAX_TOKENS:
+            raise NotImplementedError(f'attention_similarity with {T} tokens (the generic attention takes no bias); ' + HOOK_FORMS)
+        bias = a.reshape(a.shape[0], N).to(torch.float32).contiguous()     # (on the caller's device, as every other input)
+    if target_embedding is not None:
+        t = target_embedding
+        ok = torch.is_tensor(t) and 1 <= t.dim() <= 4 and t.shape[-1] == HID
+        if ok:
+            b, pb, tk = ((1, 1, 1) + tuple(t.shape[:-1]))[-3:]
+            ok = b in (1, B) and pb in (1, Pb) and tk == 1
+        if not ok:
+            raise NotImplementedError(f'target_embedding of shape {tuple(getattr(t, "shape", ()))} for B = {B}, Pb = {Pb}; '
+                                      + HOOK_FORMS)
+        t = t.to(torch.float32).reshape(b, pb, HID)
+        te = t.reshape(1, HID) if b * pb == 1 else t.expand(B, Pb, HID).reshape(R, HID)
+        te = te.contiguous()
+    return bias, te
+
+
 class SamMaskDecoderHIP(HIPModule):
     """Parameters in HF `SamMaskDecoder` layout."""
 
@@ -166,9 +201,14 @@ class SamMaskDecoderHIP(HIPModule):
         m = _g(self, name)
         return ops.layernorm(x, m.weight, m.bias, eps, planes=planes)
 
-    def _t2i(self, tq, kv, ao, R, T, N, kv_map=None):
-        """tokens -> image attention on the fused [K | V] projection (HF:326-331, 397-400)."""
+    def _t2i(self, tq, kv, ao, R, T, N, kv_map=None, bias=None):
+        """tokens -> image attention on the fused [K | V] projection (HF:326-331, 397-400); bias [1 | R, N]: HF's
+        attention_similarity, added to the scaled logits (HF:260)."""
         d2, dh2 = HID // 2, (HID // 2) // HEADS
+        if bias is not None:
+            if T > ops.SAM_T2I_MAX_TOKENS:
+                raise NotImplementedError(f'attention_similarity with {T} tokens; ' + HOOK_FORMS)
+            return ops.sam_t2i_attention_bias(tq, kv, bias, ao, R=R, T=T, N=N, scale=dh2 ** -0.5, kv_map=kv_map)
         if T <= ops.SAM_T2I_MAX_TOKENS:
             return ops.sam_t2i_attention(tq, kv, ao, R=R, T=T, N=N, scale=dh2 ** -0.5, kv_map=kv_map)
         kvs = (N * 2 * d2, 2 * d2, dh2)
@@ -214,13 +254,14 @@ class SamMaskDecoderHIP(HIPModule):
         return ops.gemm(o, P[pfx + '.out_proj'], res=res)
 
     def decode(self, image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou=True, src_rows=None, hw=None,
-               multimask_output=False, src_is_identity=False):
+               multimask_output=False, src_is_identity=False, attn_bias=None, target_rows=None):
         """The SAM mask decoder over R prompt sets (see _decode_chunk for the arguments).  Round 6: more prompt sets than the
         folded token -> image attention can address (R * N * 512 bytes of key planes < 2^31: 1023 at N = 4096) are decoded in
         chunks of equal size, each on the product path -- BASELINE configs[2] (16 tiles x 100 queries = 1600 prompt sets) used to
         fall back to the round-2 kernel chain (K | V projection GEMMs over all per-RoI keys + sam_t2i_kernel) for that reason.
         src_is_identity: roi_img is arange(R) over `src_rows` (the query variant: one dense-prompted source per prompt set), so a
-        chunk only needs its own rows of `src_rows`."""
+        chunk only needs its own rows of `src_rows`.  attn_bias [1 | R, N] / target_rows [1 | R, 256]: HF's PerSAM hooks
+        (persam_hooks); a per-prompt-set form is sliced with its chunk."""
         R = sparse.shape[0]
         if src_rows is None:
             N = image_embeddings.shape[-2] * image_embeddings.shape[-1]
@@ -229,7 +270,7 @@ class SamMaskDecoderHIP(HIPModule):
         max_r = self.max_prompt_sets or max(1, (2 ** 31 - 1) // (N * 512))
         if R <= max_r or not self.t2i_fold:
             return self._decode_chunk(image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou, src_rows, hw,
-                                      multimask_output)
+                                      multimask_output, attn_bias, target_rows)
         n_chunks = -(-R // max_r)
         per = -(-R // n_chunks)
         masks, ious = [], []
@@ -240,19 +281,26 @@ class SamMaskDecoderHIP(HIPModule):
                 map_c = roi_img[:r1 - r0]                     # arange(r1 - r0)
             else:
                 src_c, map_c = src_rows, roi_img[r0:r1]
+            bias_c = attn_bias if attn_bias is None or attn_bias.shape[0] == 1 else attn_bias[r0:r1].contiguous()
+            te_c = target_rows if target_rows is None or target_rows.shape[0] == 1 else target_rows[r0:r1].contiguous()
             m, i = self._decode_chunk(image_embeddings, image_pe, sparse[r0:r1], dense_vec, map_c, want_iou, src_c, hw,
-                                      multimask_output)
+                                      multimask_output, bias_c, te_c)
             masks.append(m)
             ious.append(i)
         return torch.cat(masks, 0), (torch.cat(ious, 0) if want_iou else None)
 
     def _decode_chunk(self, image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou=True, src_rows=None, hw=None,
-                      multimask_output=False):
+                      multimask_output=False, attn_bias=None, target_rows=None):
         """image_embeddings [B,256,h,w] (logical NCHW, channels-last), image_pe [1|B,256,h,w] (input
         independent; batch entry 0 is used), sparse [R, n_pts, 256], dense_vec [256] (the broadcast
         `no_mask_embed`, models.py:1680), roi_img int32 [R] image index of every RoI (sorted).
         Returns low_res_masks [R, 1, 4h, 4w] (mask token 0) and iou [R, 1]; multimask_output=True: the masks of mask
-        tokens 1..3, [R, 3, 4h, 4w], and iou [R, 3] (HF:537-542)."""
+        tokens 1..3, [R, 3, 4h, 4w], and iou [R, 3] (HF:537-542).
+        attn_bias [1 | R, N]: added to the logits of cross_attn_token_to_image in BOTH layers (HF:328-330), not in the final
+        attention (HF:401); layer 1 then runs unfolded (K | V GEMM + the biased kernel).  target_rows [1 | R, 256]: HF:386-387
+        `queries += target_embedding` is IN PLACE and at layer 0 `queries` IS `point_embeddings`, so the sum is both the
+        initial queries and the token positional term of every layer and of the final attention, and layer 1 starts from
+        q + target once more."""
         if self._packed is None:
             self._pack()
         P = self._packed
@@ -284,6 +332,11 @@ class SamMaskDecoderHIP(HIPModule):
         out_tok = torch.cat([self.iou_token.weight, self.mask_tokens.weight], 0)
         tokens0 = torch.cat([out_tok.unsqueeze(0).expand(R, -1, -1), sparse.reshape(R, npts, HID)], 1)
         tokens0 = tokens0.reshape(R * T, HID).contiguous()
+        te_rows = None
+        if target_rows is not None:
+            te_rows = target_rows if target_rows.shape[0] == 1 else \
+                target_rows.unsqueeze(1).expand(R, T, HID).reshape(R * T, HID).contiguous()
+            tokens0 = ops.add_rows(tokens0, te_rows)
         # keys of layer 0: image embedding + dense prompt, ONE copy per image (HF:499)
         if src_rows is None:
             src = ops.add_rows(emb.reshape(B * N, C), dense_vec.reshape(1, C), vmod=1)
@@ -300,7 +353,7 @@ class SamMaskDecoderHIP(HIPModule):
         kv_img = ops.gemm(src_pl, P['0.cross_attn_token_to_image.kv_proj'], bias=None,
                           res=pe_t['0.cross_attn_token_to_image.kv_proj'], res_mod=N)    # per image, [K | V]
         ao = torch.empty_like(tq)
-        self._t2i(tq, kv_img, ao, R, T, N, kv_map=roi_img)
+        self._t2i(tq, kv_img, ao, R, T, N, kv_map=roi_img, bias=attn_bias)
         q = ops.gemm(ao, P['0.cross_attn_token_to_image.out_proj'], res=q)
         q = self._ln(q, 'transformer.layers.0.layer_norm2')
         hmid = ops.gemm(q, P['0.lin1'], act=ops.ACT_RELU)
@@ -332,6 +385,8 @@ class SamMaskDecoderHIP(HIPModule):
         del qi, kv_img
 
         # ---------------- layer 1 ----------------
+        if te_rows is not None:
+            q = ops.add_rows(q, te_rows)
         qpe = ops.add_rows(q, tokens0)
         q = self._token_attn(qpe, qpe, q, '1.self_attn', R, T, res=q)
         q = self._ln(q, 'transformer.layers.1.layer_norm1')
@@ -340,12 +395,13 @@ class SamMaskDecoderHIP(HIPModule):
         # (the kernel addresses a key plane with 32-bit byte offsets: R * N * 512 < 2^31, i.e. 1023 RoIs at N = 4096)
         fold = self.t2i_fold and T <= ops.SAM_T2I_FOLD_MAX_TOKENS and N % 32 == 0 and R * N * 512 < 2 ** 31
         kv = None
-        if fold:
+        if fold and attn_bias is None:
             ao = self._t2i_folded('1.cross_attn_token_to_image', tq, keys_pl, pe_t, R, T, N)
         else:
+            # (with a similarity: the folded kernel takes no bias, so the K | V GEMM and the biased kernel; free at PerSAM's R = B)
             kv = ops.gemm(keys_pl, P['1.cross_attn_token_to_image.kv_proj'], bias=None,
                           res=pe_t['1.cross_attn_token_to_image.kv_proj'], res_mod=N)
-            self._t2i(tq, kv, ao, R, T, N)
+            self._t2i(tq, kv, ao, R, T, N, bias=attn_bias)
         q = ops.gemm(ao, P['1.cross_attn_token_to_image.out_proj'], res=q)
         q = self._ln(q, 'transformer.layers.1.layer_norm2')
         hmid = ops.gemm(q, P['1.lin1'], act=ops.ACT_RELU)
@@ -374,7 +430,7 @@ class SamMaskDecoderHIP(HIPModule):
             ao = self._t2i_folded('final', tq, keys_pl, pe_t, R, T, N)
         else:
             kv = ops.gemm(keys_pl, P['final.kv_proj'], bias=None, res=pe_t['final.kv_proj'], res_mod=N, out=kv)
-            self._t2i(tq, kv, ao, R, T, N)
+            self._t2i(tq, kv, ao, R, T, N)                       # no similarity here (HF:401)
         q = ops.gemm(ao, P['final.out_proj'], res=q)
         q = self._ln(q, 'transformer.layer_norm_final_attn', eps=1e-5)
         del kv, qi, ai
@@ -427,8 +483,6 @@ class SamMaskDecoderHIP(HIPModule):
         = point_batch_size 1), dense_prompt_embeddings [1 | B, 256, h, w] -- the broadcast `no_mask_embed` or a per-pixel one
         (SamMaskEmbedding's output).  Every batch entry is its own image and its Pb prompt sets stay mapped to it.  Returns
         (masks [B, Pb, C, 4h, 4w], iou [B, Pb, C], None) with C = 3 for multimask_output (mask tokens 1..3, HF:537-542)."""
-        if attention_similarity is not None or target_embedding is not None:
-            raise NotImplementedError('attention_similarity / target_embedding (HF SamAttention hooks) are not implemented')
         B = image_embeddings.shape[0]
         if sparse_prompt_embeddings.dim() == 4:
             Pb = sparse_prompt_embeddings.shape[1]
@@ -436,6 +490,8 @@ class SamMaskDecoderHIP(HIPModule):
         else:
             Pb = 1
             sparse = sparse_prompt_embeddings
+        bias, te = persam_hooks(attention_similarity, target_embedding, B, Pb,
+                                image_embeddings.shape[-2] * image_embeddings.shape[-1], 1 + N_MASK_TOKENS + sparse.shape[1])
         dev = image_embeddings.device
         roi_img = torch.arange(B, dtype=torch.int32, device=dev)
         if Pb > 1:
@@ -447,14 +503,16 @@ class SamMaskDecoderHIP(HIPModule):
         const = bool((d == d[:1, :1, :1]).all())
         if const:
             masks, iou = self.decode(image_embeddings, image_positional_embeddings, sparse.contiguous(),
-                                     d[0, 0, 0].contiguous(), roi_img, multimask_output=bool(multimask_output))
+                                     d[0, 0, 0].contiguous(), roi_img, multimask_output=bool(multimask_output),
+                                     attn_bias=bias, target_rows=te)
         else:
             emb = nhwc_view(image_embeddings)
             _, h, w, C = emb.shape
             # HF:499, one dense source per image (a [1, ..] dense prompt repeats over the batch: row % (h w))
             src = ops.add_rows(emb.reshape(B * h * w, C).contiguous(), d.reshape(-1, C).contiguous())
             masks, iou = self.decode(None, image_positional_embeddings, sparse.contiguous(), None, roi_img,
-                                     src_rows=src, hw=(h, w), multimask_output=bool(multimask_output))
+                                     src_rows=src, hw=(h, w), multimask_output=bool(multimask_output), attn_bias=bias,
+                                     target_rows=te)
         C, mh, mw = masks.shape[1:]
         return masks.reshape(B, Pb, C, mh, mw), iou.reshape(B, Pb, C), None
 

@@ -89,10 +89,14 @@ class SamSession:
             self.image_embeddings = self.sam.get_image_embeddings(self.pixel_values)
         self.device = dev
 
-    def _low_res(self, points, labels, boxes, mask_input, multimask_output):
+    def _low_res(self, points, labels, boxes, mask_input, multimask_output, attention_similarity=None, target_embedding=None):
         dev = self.device
         n = None
         kw = {}
+        if attention_similarity is not None:
+            kw['attention_similarity'] = attention_similarity
+        if target_embedding is not None:
+            kw['target_embedding'] = target_embedding
         if points is not None:
             p = scale_coords(points, self.original_size, self.input_size)
             if p.ndim == 2:
@@ -132,12 +136,13 @@ class SamSession:
 
     @torch.no_grad()
     def predict(self, points=None, labels=None, boxes=None, mask_input=None, multimask_output=True, return_logits=False,
-                mask_threshold=0.0):
+                mask_threshold=0.0, attention_similarity=None, target_embedding=None):
         """points [Pb, P, 2] / labels [Pb, P] (1 foreground, 0 background, -1 padding) / boxes [Pb, 4], all in original pixels;
         mask_input: [256, 256] low-resolution logits of an earlier call (shared by the prompt sets).  Returns
         (masks bool [Pb, C, H, W] -- the fp32 values with return_logits --, iou_scores [Pb, C], low_res_logits
-        [Pb, C, 256, 256]); C = 3 with multimask_output, else 1."""
-        low, iou = self._low_res(points, labels, boxes, mask_input, multimask_output)
+        [Pb, C, 256, 256]); C = 3 with multimask_output, else 1.  attention_similarity [1 | Pb, 1, 1, N] / target_embedding
+        [..., 256]: HF's PerSAM hooks, passed through to `SamModelHIP.forward` (device tensors)."""
+        low, iou = self._low_res(points, labels, boxes, mask_input, multimask_output, attention_similarity, target_embedding)
         Pb, C, h, w = low.shape
         H, W = self.original_size
         flat = low.reshape(Pb * C, h, w)
@@ -225,6 +230,183 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     return res
 
 
+# --------------------------------------------------------------------------------------------------- PerSAM
+class PerSam:
+    """PerSAM's training-free one-shot segmentation (Zhang et al., "Personalize Segment Anything Model with One Shot";
+    persam.py of the paper's code) in HF terms: ONE labelled reference, then `segment` finds that object in other images.
+
+    `sam`: whatever `SamSession` accepts; `ref_image` [H, W, 3] as for `SamSession`; `ref_mask` [H, W], non-zero = object.
+    The reference is embedded once.  Its mask goes through the image's front end as a {0, 1} float image (`rsp_resize_pad`,
+    pad value 0), bilinearly to the embedding grid and `> 0` -- PerSAM's cell selection --; `rsp_persam_target` gives
+    `.target_embedding` [1, 1, 256] (the mean of the selected embedding rows) and `.target_feature` [256] (its unit vector).
+    A mask that selects no cell is a ValueError (the one host read of the constructor).
+
+    `segment(images, batch_size=8, output='rle', cascade=True)`: one image or a list; images of one size go through the
+    encoder and every decoder pass together, `batch_size` at a time, mixed sizes are grouped by size and the results come
+    back in input order.  Per batch: (1) `rsp_persam_similarity` + `rsp_persam_locate`: the cosine similarity of every cell
+    with the target at image resolution is never stored, its peak becomes the positive and its trough the negative point,
+    its normalised g x g resampling the `attention_similarity`; (2) first pass: both points, one mask, both hooks; (3) the
+    same points + the logits of (2) as `input_masks`, three masks, the one with the highest predicted IoU (lowest index on a
+    tie); (4) as (3) + the box of (3)'s mask at original resolution (`rsp_mask_score_box`, inclusive maxima; an EMPTY mask
+    gives that kernel's [0, 0, 0, 0] box where PerSAM itself fails); (5) `rsp_mask_post_logits`, `rsp_mask_rle`,
+    `rsp_mask_score_box`.  cascade=False stops after (2).  Between the upload of a batch and the transfer of its results
+    nothing is read on the host: points, boxes and the best-of-three choices stay device tensors.
+
+    Returns per image a dict: mask (uncompressed COCO RLE dict of size [H, W], or bool [H, W] on the device with
+    output='dense'), score (predicted IoU), bbox [x0, y0, x1, y1] (inclusive maxima, zeros for an empty mask), points
+    [[x+, y+], [x-, y-]] and point_sims [s+, s-] (the field's maximum and minimum), all in original pixels.  A field that
+    is constant has no peak: the points are pixel 0 and the attention similarity 0.5 everywhere (PerSAM yields NaN).
+    Not implemented: PerSAM-F, topk > 1, several references."""
+
+    RLE_CAP = 4096
+
+    def __init__(self, sam, ref_image, ref_mask):
+        self.sam = _sam_of(sam)
+        dev = next(self.sam.parameters()).device
+        ops.require_device(dev)
+        self.device = dev
+        S, g = self.sam.image_size, self.sam.vision_encoder.grid
+        ref_image = self._as_image(ref_image)
+        if isinstance(ref_mask, np.ndarray):
+            ref_mask = torch.from_numpy(np.ascontiguousarray(ref_mask))
+        if ref_mask.dim() != 2 or tuple(ref_mask.shape) != tuple(ref_image.shape[:2]):
+            raise ValueError('ref_mask: expected [H, W], the size of ref_image')
+        hw = (int(ref_image.shape[0]), int(ref_image.shape[1]))
+        nhw = preprocess_shape(hw, S)
+        with torch.no_grad():
+            pv = ops.resize_pad(ref_image.to(dev), nhw, (S, S), PIXEL_MEAN, normalise=(PIXEL_MEAN, PIXEL_STD, False)).unsqueeze(0)
+            emb = self.sam.get_image_embeddings(pv)
+            self.cell_mask = self.cells_of(ref_mask.to(dev), S, g)
+            te, tf, cnt = ops.persam_target(self._rows(emb), self.cell_mask.reshape(-1))
+        self.cells = int(cnt.item())
+        if self.cells == 0:
+            raise ValueError('PerSam: the reference mask selects no cell of the embedding grid')
+        self.target_feature, self.target_embedding = tf, te.view(1, 1, 256)
+        self._phase = lambda name: contextlib.nullcontext()      # tools/bench_sam_prompts.py times the phases through this
+
+    @staticmethod
+    def cells_of(mask, S, g):
+        """PerSAM's cell selection: mask [H, W] on the device (non-zero = object) -> bool [g, g].  The mask goes through the
+        image's front end as a {0, 1} float image (rsp_resize_pad to S x S, pad value 0), bilinearly to g x g
+        (rsp_resize_bilinear_nhwc = F.interpolate(mode='bilinear', align_corners=False)) and `> 0`, which is exact: with
+        non-negative inputs a cell is zero only if every pixel that contributes to it is."""
+        hw = (int(mask.shape[0]), int(mask.shape[1]))
+        m3 = (mask != 0).to(torch.float32).unsqueeze(-1).expand(hw[0], hw[1], 3).contiguous()
+        mS = ops.resize_pad(m3, preprocess_shape(hw, S), (S, S), (0.0, 0.0, 0.0))[0]        # [S, S], values in [0, 1]
+        mg = ops.resize_bilinear(mS.unsqueeze(-1).expand(S, S, 4).contiguous().unsqueeze(0), (g, g))[0, :, :, 0]
+        return mg > 0
+
+    @staticmethod
+    def _as_image(image):
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if image.dim() != 3 or image.shape[2] != 3:
+            raise ValueError('expected an [H, W, 3] image')
+        return image
+
+    @staticmethod
+    def _rows(emb):
+        """[B, 256, g, g] (channels-last memory) -> contiguous rows [B * g * g, 256]"""
+        B, C, gh, gw = emb.shape
+        return emb.permute(0, 2, 3, 1).reshape(B * gh * gw, C).contiguous()
+
+    @torch.no_grad()
+    def segment(self, images, batch_size=8, output='rle', cascade=True, _stages=None):
+        if output not in ('rle', 'dense'):
+            raise ValueError("output must be 'rle' or 'dense'")
+        if int(batch_size) < 1:
+            raise ValueError('batch_size must be >= 1')
+        single = not isinstance(images, (list, tuple))
+        imgs = [self._as_image(im) for im in ([images] if single else images)]
+        groups = {}
+        for i, im in enumerate(imgs):
+            groups.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(i)
+        results = [None] * len(imgs)
+        for hw, idx in groups.items():
+            if hw[0] * hw[1] >= 2 ** 31:
+                raise ValueError(f'PerSam: a {hw[0]} x {hw[1]} image has 2^31 pixels or more')
+            for b0 in range(0, len(idx), int(batch_size)):
+                sel = idx[b0:b0 + int(batch_size)]
+                for i, r in zip(sel, self._batch([imgs[i] for i in sel], hw, output, cascade, _stages)):
+                    results[i] = r
+        return results[0] if single else results
+
+    def _best(self, out):
+        """best of three by predicted IoU (first index on a tie): (logits [B, h, w], iou [B], index [B]) on the device"""
+        iou = out.iou_scores[:, 0]                                                  # [B, 3]
+        best = iou.argmax(1)
+        ar = torch.arange(iou.shape[0], device=iou.device)
+        return out.pred_masks[:, 0][ar, best].contiguous(), iou[ar, best], best
+
+    def _batch(self, imgs, hw, output, cascade, _stages):
+        sam, dev, phase = self.sam, self.device, self._phase
+        S, g = sam.image_size, sam.vision_encoder.grid
+        B = len(imgs)
+        H, W = hw
+        nhw = preprocess_shape(hw, S)
+        with phase('front end'):
+            pv = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+            for b, im in enumerate(imgs):
+                ops.resize_pad(im.to(dev), nhw, (S, S), PIXEL_MEAN, out=pv[b], normalise=(PIXEL_MEAN, PIXEL_STD, False))
+        with phase('encoder'):
+            emb = sam.get_image_embeddings(pv)
+        with phase('similarity'):
+            sim, low0 = ops.persam_similarity(self._rows(emb), self.target_feature, B, g, g)
+        with phase('locate'):
+            stats, xy, attn = ops.persam_locate(low0, (S, S), nhw, hw, g)
+            # HF _normalize_coordinates (float64, then fp32 as the processor's tensors), on the device
+            scale = torch.tensor([nhw[1] / W, nhw[0] / H], dtype=torch.float64).to(dev)
+            pts = (xy[:, :4].reshape(B, 1, 2, 2).to(torch.float64) * scale).to(torch.float32)
+            labels = torch.tensor([[[1, 0]]], dtype=torch.int32).to(dev).expand(B, 1, 2).contiguous()
+        with phase('decoder pass 1'):
+            out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, multimask_output=False,
+                      attention_similarity=attn.view(B, 1, 1, g * g), target_embedding=self.target_embedding)
+            low, iou = out.pred_masks[:, 0, 0].contiguous(), out.iou_scores[:, 0, 0]
+        st = dict(sim=sim, low_sim=low0, stats=stats, xy=xy, attn_sim=attn, points=pts, low1=low, iou1=iou)
+        if cascade:
+            with phase('decoder pass 2'):
+                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_masks=low.unsqueeze(1),
+                          multimask_output=True)
+                low, iou, best2 = self._best(out)
+                st.update(low2=out.pred_masks[:, 0], iou2=out.iou_scores[:, 0], best2=best2)
+            with phase('decoder pass 3'):
+                box = ops.mask_score_box(low, (S, S), nhw, hw)[:, 3:7]
+                bscale = torch.cat([scale, scale])
+                boxes = (box.to(torch.float64) * bscale).to(torch.float32).reshape(B, 1, 4)
+                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_boxes=boxes,
+                          input_masks=low.unsqueeze(1), multimask_output=True)
+                low, iou, best3 = self._best(out)
+                st.update(box2=box, boxes=boxes, low3=out.pred_masks[:, 0], iou3=out.iou_scores[:, 0], best3=best3)
+        with phase('masks + run lengths'):
+            masks = ops.mask_post_logits(low, (S, S), nhw, hw)
+            score = ops.mask_score_box(low, (S, S), nhw, hw)
+            if output == 'rle':
+                counts = torch.empty((B, self.RLE_CAP), dtype=torch.int32, device=dev)
+                ws = torch.empty((B, self.RLE_CAP), dtype=torch.int32, device=dev)
+                n = torch.empty((B,), dtype=torch.int32, device=dev)
+                ops.mask_rle_into(masks, counts, ws, n)
+        st.update(low_final=low, iou_final=iou, masks=masks, score=score)
+        if _stages is not None:
+            _stages.setdefault('batches', []).append(st)
+        # ---- the transfer of the batch's results: the first host reads since the upload ----
+        with phase('transfer'):
+            ints = torch.cat([xy[:, :4], score[:, 3:7]] + ([n.view(B, 1)] if output == 'rle' else []), 1).cpu()
+            flts = torch.cat([stats[:, :2], iou.reshape(B, 1)], 1).cpu()
+            if output == 'rle':
+                nn = ints[:, 8].tolist()
+                if min(nn) < 0:                                # a mask with more runs than RLE_CAP: again with room (rare)
+                    counts, n = ops.mask_rle_counts(masks, cap=1 << (-min(nn) - 1).bit_length())
+                    nn = n.cpu().tolist()
+                counts = counts[:, :max(nn)].cpu().numpy()
+        res = []
+        for b in range(B):
+            r = dict(score=float(flts[b, 2]), bbox=ints[b, 4:8].tolist(), points=ints[b, :4].reshape(2, 2).tolist(),
+                     point_sims=flts[b, :2].tolist())
+            r['mask'] = dict(size=[H, W], counts=counts[b, :nn[b]].tolist()) if output == 'rle' else masks[b]
+            res.append(r)
+        return res
+
+
 # --------------------------------------------------------------------------------------------------- crop layers (DESIGN §15)
 def generate_crop_boxes(crop_n_layers, overlap_ratio, hw):
     """HF `_generate_per_layer_crops`: ([x0, y0, x1, y1] per crop, layer per crop); crop 0 is the image, then per layer
@@ -263,7 +445,7 @@ class SamMaskGenerator:
     `_is_box_near_crop_edge`, `_pad_masks`, `_mask_to_rle`, `_post_process_for_mask_generation`) composed per crop -- not
     HF's `MaskGenerationPipeline`, which filters only the first crop, leaves boxes in crop coordinates and scales a crop's
     grid with the whole image's resize factor.  Not implemented: segment-anything's per-crop box NMS and its
-    preference for smaller crops, `min_mask_region_area`, the PerSAM hooks.
+    preference for smaller crops, `min_mask_region_area`.
 
     `sam`: whatever `SamSession` accepts.  `crop_batch`: crops per encoder / decoder / scoring call (all of one layer, so
     that they share the number of prompts); None picks `DEFAULT_CROP_BATCH` by the encoder's width, capped at

@@ -15,7 +15,7 @@ from .detectors import BaseDetectorHIP, SAMSegMaskRCNN
 from .necks import conv3x3_weight, fold_bn
 from .nnutil import HIPModule, add_param, infer_sam_arch, load_checkpoint_into, nchw_view, nhwc_view
 from .registry import MODELS
-from .sam_decoder import SamMaskDecoderHIP, _PosEmb, _PromptEncoder, image_wide_table
+from .sam_decoder import SamMaskDecoderHIP, _PosEmb, _PromptEncoder, image_wide_table, persam_hooks
 from .sam_encoder import SamVisionEncoderHIP
 from .structures import InstanceData
 
@@ -228,7 +228,8 @@ class SamModelHIP(HIPModule):
     one or three masks per prompt set.  The prompt encoder runs as one kernel (ops.sam_embed_prompts), `input_masks` through
     ops.sam_mask_embed (one dense source per image), and ONE decoder pass serves the B x Pb prompt sets, which stay mapped to
     their image instead of repeating the image tensors.  `attention_similarity` / `target_embedding` (HF's
-    PerSAM hooks) are not implemented."""
+    PerSAM hooks) are taken in the forms `sam_decoder.persam_hooks` names: a key bias row [1 | B * Pb, 1, 1, N] and a target
+    that broadcasts to [B, Pb, 1, 256]."""
 
     def __init__(self, arch='huge', image_size=1024):
         super().__init__()
@@ -312,9 +313,6 @@ class SamModelHIP(HIPModule):
             raise ValueError('Either pixel_values or image_embeddings must be provided.')
         if pixel_values is not None and image_embeddings is not None:
             raise ValueError('Only one of pixel_values and image_embeddings can be provided.')
-        if attention_similarity is not None or target_embedding is not None:
-            raise NotImplementedError('SamModel on HIP: attention_similarity / target_embedding (HF SamAttention hooks) '
-                                      'are not implemented')
         if input_points is not None and len(input_points.shape) != 4:
             raise ValueError('The input_points must be a 4D tensor. Of shape `batch_size`, `point_batch_size`, '
                              '`nb_points_per_image`, `2`.', f' got {input_points.shape}.')
@@ -346,6 +344,9 @@ class SamModelHIP(HIPModule):
         Pb = sparse.shape[1]
         sparse = sparse.reshape(B * Pb, sparse.shape[2], sparse.shape[3])
         roi_img = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Pb)
+        # HF's PerSAM hooks (HF:183-187, 386-387) in the forms persam_hooks names; everything else raises NotImplementedError
+        emb_hw = image_embeddings.shape[-2] * image_embeddings.shape[-1]
+        bias, te = persam_hooks(attention_similarity, target_embedding, B, Pb, emb_hw, 1 + 4 + sparse.shape[1])
         pe = self.prompt_encoder
         multimask_output = bool(multimask_output)
         if input_masks is not None:
@@ -359,11 +360,12 @@ class SamModelHIP(HIPModule):
             src = ops.sam_mask_embed(m, emb.reshape(B * g * gw, C), torch.arange(B, dtype=torch.int32, device=dev),
                                      self._mask_embed_prm(), g, gw)
             masks, iou = self.mask_decoder.decode(None, self.get_image_wide_positional_embeddings(), sparse, None, roi_img,
-                                                  src_rows=src, hw=(g, gw), multimask_output=multimask_output)
+                                                  src_rows=src, hw=(g, gw), multimask_output=multimask_output, attn_bias=bias,
+                                                  target_rows=te)
         else:
             masks, iou = self.mask_decoder.decode(image_embeddings, self.get_image_wide_positional_embeddings(), sparse,
                                                   pe.no_mask_embed.weight.reshape(-1), roi_img,
-                                                  multimask_output=multimask_output)
+                                                  multimask_output=multimask_output, attn_bias=bias, target_rows=te)
         h, w = masks.shape[-2:]
         C = masks.shape[1]
         return SamImageSegmentationOutput(iou.reshape(B, Pb, C), masks.reshape(B, Pb, C, h, w))

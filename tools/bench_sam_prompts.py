@@ -20,7 +20,16 @@ The scoring kernel's achieved input bytes/s and pixel evaluations/s are derived 
       summed per name), against -- alternating, same process -- the same work with what existed before the batched path: a
       host slice per crop, one SamSession per crop, rsp_mask_score_box per crop, a kept-count read per crop, the near-edge rule
       and the shift as torch expressions; then the sweep of crop_batch.  --multicrop-once runs one generate() per
-      configuration and nothing else (the process to put under rocprofv3 --kernel-trace --stats)."""
+      configuration and nothing else (the process to put under rocprofv3 --kernel-trace --stats).
+
+  python tools/bench_sam_prompts.py --persam [--arch huge] [--reps 5] [--out profiles/sam_prompts/persam.json]
+
+  (e) PerSAM (`PerSam.segment`): synthetic 1 024^2 tiles, B = 1 and B = 8, by phase (front end, encoder, similarity, locate,
+      the three decoder passes, masks + run lengths, transfer), against -- alternating, same process -- the same work with what
+      existed before the similarity / locate kernels and the batched flow: per image a SamSession, the similarity as torch
+      expressions, mask_post_logits(want_val=True) for the field, torch argmax / argmin / mean / std / F.interpolate, and the
+      three decoder passes with host-side point, best-of-three and box extraction in between; then rsp_persam_locate and
+      rsp_mask_score_box alone on the same fields (pixel rates).  --persam-once: one segment() per batch size (kernel trace)."""
 import argparse
 import json
 import os
@@ -164,6 +173,85 @@ def multicrop(model, img, a):
     return out
 
 
+def persam(model, a):
+    import torch.nn.functional as F
+    from rsprompter_amd import ops
+    from rsprompter_amd.sam_prompts import PerSam, SamSession, _rle_dicts
+    from rsprompter_amd.synth import synth_images
+    dev = next(model.parameters()).device
+    S, g = model.image_size, model.vision_encoder.grid
+    tiles = [t.permute(1, 2, 0).contiguous() for t in synth_images(9)]                # [1024, 1024, 3] uint8, on the host
+    H, W = int(tiles[0].shape[0]), int(tiles[0].shape[1])
+    ref_mask = torch.zeros(H, W, dtype=torch.bool)
+    ref_mask[300:600, 400:700] = True
+    ps = PerSam(model, tiles[8], ref_mask)
+    tf, te = ps.target_feature, ps.target_embedding
+    out = dict(reference_cells=ps.cells, batches={})
+
+    def parent_means(batch):
+        res = []
+        for img in batch:
+            s = SamSession(model, img)
+            f = s.image_embeddings[0]
+            f = f / f.norm(dim=0, keepdim=True)
+            sim = (tf @ f.reshape(256, g * g)).reshape(1, 1, g, g)
+            low0 = F.interpolate(sim, scale_factor=4, mode='bilinear')[0]
+            val = s.full_res(low0, want_val=True)[1][0]                               # the [H, W] field
+            imax, imin = int(val.argmax()), int(val.argmin())                         # host reads
+            pts = np.array([[[imax % W, imax // W], [imin % W, imin // W]]], dtype=np.float64)
+            lab = np.array([[1, 0]])
+            attn = F.interpolate(((val - val.mean()) / val.std())[None, None], size=(g, g), mode='bilinear').sigmoid()
+            m, iou, low = s.predict(points=pts, labels=lab, multimask_output=False, attention_similarity=attn.reshape(1, 1, 1, g * g),
+                                    target_embedding=te)
+            m, iou, low = s.predict(points=pts, labels=lab, mask_input=low[0, 0], multimask_output=True)
+            b = int(iou[0].argmax())
+            ys, xs = torch.nonzero(m[0, b], as_tuple=True)
+            box = [0, 0, 0, 0] if ys.numel() == 0 else [int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max())]
+            m, iou, low = s.predict(points=pts, labels=lab, boxes=np.array([box], dtype=np.float64), mask_input=low[0, b],
+                                    multimask_output=True)
+            b = int(iou[0].argmax())
+            res.append(dict(mask=_rle_dicts(m[0, b][None])[0], score=float(iou[0, b]), points=pts[0].astype(int).tolist()))
+        return res
+
+    for B in (1, 8):
+        batch = tiles[:B]
+        if a.persam_once:
+            ps.segment(batch, batch_size=B)
+            torch.cuda.synchronize()
+            continue
+        new, old = ps.segment(batch, batch_size=B), parent_means(batch)
+        same = [n['points'] == o['points'] and n['mask'] == o['mask'] for n, o in zip(new, old)]
+        ph = _Phases()
+        bt, lt, phs = [], [], []
+        for r in range(a.reps + 1):                                                    # alternating; the first pair is warm-up
+            t = []
+            for which in (0, 1):
+                ps._phase = ph if which == 0 else (lambda name: __import__('contextlib').nullcontext())
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ps.segment(batch, batch_size=B) if which == 0 else parent_means(batch)
+                e1.record()
+                e1.synchronize()
+                t.append(e0.elapsed_time(e1))
+                if which == 0:
+                    p = ph.take()
+            if r:
+                bt.append(t[0]); lt.append(t[1]); phs.append(p)
+        cfg = dict(batched=_spread(bt), parent_means=_spread(lt), same_points_and_masks=same,
+                   phases_ms={k: round(statistics.median([p[k] for p in phs]), 3) for k in phs[0]})
+        cfg['parent_spread_ms'] = round(cfg['parent_means']['max_ms'] - cfg['parent_means']['min_ms'], 3)
+        out['batches'][str(B)] = cfg
+    if not a.persam_once:
+        low = torch.randn(8, 4 * g, 4 * g, device=dev)
+        loc = timed(lambda: ops.persam_locate(low, (S, S), (S, S), (H, W), g), max(a.reps, 10))
+        sco = timed(lambda: ops.mask_score_box(low, (S, S), (S, S), (H, W)), max(a.reps, 10))
+        out['locate_vs_score_8_fields'] = dict(persam_locate=loc, mask_score_box=sco, pixels=8 * H * W,
+                                               locate_Gpixel_per_s=round(8 * H * W / (loc['median_ms'] * 1e-3) / 1e9, 1),
+                                               score_Gpixel_per_s=round(8 * H * W / (sco['median_ms'] * 1e-3) / 1e9, 1),
+                                               note='whole calls (four and three launches), host launch time included')
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='huge')
@@ -171,6 +259,8 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--multicrop', action='store_true', help='the crop-layer phase (d) only')
     ap.add_argument('--multicrop-once', action='store_true', help='one generate() per configuration (for a kernel trace)')
+    ap.add_argument('--persam', action='store_true', help='the PerSAM phase (e) only')
+    ap.add_argument('--persam-once', action='store_true', help='one segment() per batch size (for a kernel trace)')
     ap.add_argument('--crop-batch', type=int, default=None)
     ap.add_argument('--crop-batches', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8])
     a = ap.parse_args()
@@ -186,8 +276,11 @@ def main():
     model = model.to(dev).eval()
     img = synth_images(1)[0].permute(1, 2, 0).contiguous().to(dev)                 # [1024, 1024, 3] uint8
     out = dict(arch=a.arch, device=torch.cuda.get_device_name(0), image=[1024, 1024])
-    if a.multicrop or a.multicrop_once:
-        out['multicrop'] = multicrop(model, img, a)
+    if a.multicrop or a.multicrop_once or a.persam or a.persam_once:
+        if a.persam or a.persam_once:
+            out['persam'] = persam(model, a)
+        else:
+            out['multicrop'] = multicrop(model, img, a)
         line = json.dumps(out)
         print(line)
         if a.out:
