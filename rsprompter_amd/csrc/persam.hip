@@ -5,6 +5,7 @@
 // one 1 KiB row, read once.  The location prior itself (extrema, statistics, attn_sim of the image-resolution field) is
 // rsp_persam_locate in samdec.hip, next to the mask kernels whose device functions it shares.  No inline assembly.
 #include "rsp_common.h"
+#include "mask_field.h"
 
 namespace {
 
@@ -63,17 +64,10 @@ __global__ __launch_bounds__(256) void persam_up4_kernel(const float* __restrict
   const int oh = 4 * gh, ow = 4 * gw;
   if (i >= oh * ow) return;
   const int oy = i / ow, ox = i - oy * ow;
-  float sy = 0.25f * ((float)oy + 0.5f) - 0.5f, sx = 0.25f * ((float)ox + 0.5f) - 0.5f;
-  sy = sy < 0.f ? 0.f : sy;
-  sx = sx < 0.f ? 0.f : sx;
-  int y0 = (int)sy, x0 = (int)sx;
-  y0 = y0 > gh - 1 ? gh - 1 : y0;
-  x0 = x0 > gw - 1 ? gw - 1 : x0;
-  const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
-  const float ly1 = sy - (float)y0, ly0 = 1.0f - ly1, lx1 = sx - (float)x0, lx0 = 1.0f - lx1;
+  const Lin cy = lin_coef(oy, 0.25f, gh), cx = lin_coef(ox, 0.25f, gw);
   const float* s = sim + (int64_t)b * gh * gw;
-  low[(int64_t)b * oh * ow + i] = ly0 * (lx0 * s[y0 * gw + x0] + lx1 * s[y0 * gw + x1]) +
-                                  ly1 * (lx0 * s[y1 * gw + x0] + lx1 * s[y1 * gw + x1]);
+  low[(int64_t)b * oh * ow + i] = cy.l0 * (cx.l0 * s[cy.i0 * gw + cx.i0] + cx.l1 * s[cy.i0 * gw + cx.i1]) +
+                                  cy.l1 * (cx.l0 * s[cy.i1 * gw + cx.i0] + cx.l1 * s[cy.i1 * gw + cx.i1]);
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 //   class softmax + top-k, mask statistics    maskformer_fusion_head.py:149-176, structures/mask/utils.py:56-77
 // All HBM / latency bound; fp32 arithmetic.
 #include "rsp_common.h"
+#include "mask_field.h"
 
 namespace {
 
@@ -74,19 +75,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------ bilinear resize (NHWC)
-struct Lin2 { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Lin2 lin2(int dst, float scale, int in_size) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  Lin2 c;
-  c.i0 = (int)src;
-  if (c.i0 > in_size - 1) c.i0 = in_size - 1;
-  c.i1 = c.i0 + (c.i0 < in_size - 1 ? 1 : 0);
-  c.l1 = src - (float)c.i0;
-  c.l0 = 1.0f - c.l1;
-  return c;
-}
-
 // y[b, oy, ox, :] = F.interpolate(x, (Ho, Wo), bilinear, align_corners=False)[b, :, oy, ox]   (channels-last)
 __global__ __launch_bounds__(256) void resize_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H,
                                                          int W, int Ho, int Wo, int C) {
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(256) void resize_nhwc_kernel(const float* __restric
     const int ox = (int)(t % Wo); t /= Wo;
     const int oy = (int)(t % Ho);
     const int b = (int)(t / Ho);
-    const Lin2 cy = lin2(oy, sh, H), cx = lin2(ox, sw, W);
+    const Lin cy = lin_coef(oy, sh, H), cx = lin_coef(ox, sw, W);
     const float* base = x + (int64_t)b * H * W * C + c;
     const f32x4 v00 = *reinterpret_cast<const f32x4*>(base + ((int64_t)cy.i0 * W + cx.i0) * C);
     const f32x4 v01 = *reinterpret_cast<const f32x4*>(base + ((int64_t)cy.i0 * W + cx.i1) * C);
@@ -201,7 +189,7 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(const float* __restrict_
   int cnt = 0;
   for (int k = threadIdx.x; k < h * w; k += blockDim.x) {
     const int oy = k / w, ox = k - oy * w;
-    const Lin2 cy = lin2(oy, sh, Hs), cx = lin2(ox, sw, Ws);
+    const Lin cy = lin_coef(oy, sh, Hs), cx = lin_coef(ox, sw, Ws);
     const float v = cy.l0 * (cx.l0 * src[cy.i0 * Ws + cx.i0] + cx.l1 * src[cy.i0 * Ws + cx.i1]) +
                     cy.l1 * (cx.l0 * src[cy.i1 * Ws + cx.i0] + cx.l1 * src[cy.i1 * Ws + cx.i1]);
     const uint8_t blocked = (1.0f / (1.0f + expf(-v))) < 0.5f ? 1 : 0;
@@ -368,7 +356,7 @@ struct QMaskP {
   double* stats;           // [k, 2] (sum sigmoid over positive pixels, positive count)
   int32_t* box;            // [k, 4] xmin, ymin, xmax, ymax (init: INT_MAX, INT_MAX, -1, -1)
   float* logits;           // optional [k, oh, ow]
-  int h, w, Hb, Wb, ch, cw, oh, ow;
+  MaskGeom g;
 };
 
 // models.py:652-656 + :684-695 + maskformer_fusion_head.py:164-176: logits are interpolated (twice when rescale)
@@ -378,23 +366,9 @@ __global__ __launch_bounds__(256) void query_mask_kernel(const QMaskP p) {
   __shared__ double s_sum[4], s_cnt[4];
   __shared__ int s_box[4][4];
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)p.qidx[m] * p.h * p.w;
-  const float s1h = (float)p.h / (float)p.Hb, s1w = (float)p.w / (float)p.Wb;
-  const float s2h = (float)p.ch / (float)p.oh, s2w = (float)p.cw / (float)p.ow;
-  const int64_t total = (int64_t)p.oh * p.ow;
-  auto stage1 = [&](int Y, int X) -> float {
-    const Lin2 ay = lin2(Y, s1h, p.h), ax = lin2(X, s1w, p.w);
-    return ay.l0 * (ax.l0 * low[ay.i0 * p.w + ax.i0] + ax.l1 * low[ay.i0 * p.w + ax.i1]) +
-           ay.l1 * (ax.l0 * low[ay.i1 * p.w + ax.i0] + ax.l1 * low[ay.i1 * p.w + ax.i1]);
-  };
-  double sum = 0.0, cnt = 0.0;
+  const float* low = p.low + (int64_t)p.qidx[m] * p.g.h * p.g.w;
+  const int64_t base = (int64_t)m * p.g.oh * p.g.ow;
   int xmin = 0x7fffffff, ymin = 0x7fffffff, xmax = -1, ymax = -1;
-  auto pixel = [&](int oy, int ox) -> float {
-    if (IDENT) return stage1(oy, ox);
-    const Lin2 cy = lin2(oy, s2h, p.ch), cx = lin2(ox, s2w, p.cw);
-    return cy.l0 * (cx.l0 * stage1(cy.i0, cx.i0) + cx.l1 * stage1(cy.i0, cx.i1)) +
-           cy.l1 * (cx.l0 * stage1(cy.i1, cx.i0) + cx.l1 * stage1(cy.i1, cx.i1));
-  };
   float fsum = 0.f;   // per-thread partial (a thread sees <= a few dozen pixels); widened to double once at the end
   int icnt = 0;
   auto account = [&](float v, int oy, int ox) {
@@ -405,43 +379,25 @@ __global__ __launch_bounds__(256) void query_mask_kernel(const QMaskP p) {
       xmin = min(xmin, ox); xmax = max(xmax, ox); ymin = min(ymin, oy); ymax = max(ymax, oy);
     }
   };
-  if ((p.ow & 3) == 0) {
+  if ((p.g.ow & 3) == 0) {
     // four pixels of one row per thread: one 32-bit store of the bool mask instead of four byte stores
-    const int qw = p.ow >> 2;
-    const int nq = p.oh * qw;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
-      const int oy = i / qw, ox = (i - oy * qw) << 2;
-      float v[4];
-      if (IDENT) {          // the row coefficients are shared by the four pixels
-        const Lin2 ay = lin2(oy, s1h, p.h);
-        const float* r0 = low + ay.i0 * p.w;
-        const float* r1 = low + ay.i1 * p.w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const Lin2 ax = lin2(ox + e, s1w, p.w);
-          v[e] = ay.l0 * (ax.l0 * r0[ax.i0] + ax.l1 * r0[ax.i1]) + ay.l1 * (ax.l0 * r1[ax.i0] + ax.l1 * r1[ax.i1]);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = pixel(oy, ox + e);
-      }
+    mask_each_quad<IDENT>(low, p.g, [&](const float v[4], int oy, int ox) {
       uint32_t bits = 0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) { bits |= (v[e] > 0.f ? 1u : 0u) << (8 * e); account(v[e], oy, ox + e); }
-      const int64_t o = (int64_t)m * total + (int64_t)oy * p.ow + ox;
+      const int64_t o = base + (int64_t)oy * p.g.ow + ox;
       *reinterpret_cast<uint32_t*>(p.out + o) = bits;
       if (p.logits) *reinterpret_cast<f32x4*>(p.logits + o) = f32x4{v[0], v[1], v[2], v[3]};
-    }
+    });
   } else {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-      const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
-      const float v = pixel(oy, ox);
-      p.out[(int64_t)m * total + i] = v > 0.f ? 1 : 0;
-      if (p.logits) p.logits[(int64_t)m * total + i] = v;
+    mask_each_pixel(low, p.g, IDENT, [&](float v, int oy, int ox, int64_t i) {
+      const int64_t o = base + i;
+      p.out[o] = v > 0.f ? 1 : 0;
+      if (p.logits) p.logits[o] = v;
       account(v, oy, ox);
-    }
+    });
   }
-  sum = (double)fsum; cnt = (double)icnt;
+  double sum = (double)fsum, cnt = (double)icnt;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64);
@@ -600,26 +556,22 @@ extern "C" int rsp_query_mask_post(const float* low_res, const int32_t* qidx, co
                                    int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h, int32_t crop_w, int32_t out_h,
                                    int32_t out_w, void* stats_ws, uint8_t* out_mask, float* out_logits, float* det_score,
                                    float* bboxes, rsp_stream_t stream) {
-  if (!low_res || !qidx || !cls_score || !stats_ws || !out_mask || !det_score || !bboxes || k < 0 || h <= 0 || w <= 0 ||
-      crop_h <= 0 || crop_w <= 0 || crop_h > Hb || crop_w > Wb || out_h <= 0 || out_w <= 0)
+  const MaskGeom g{h, w, Hb, Wb, crop_h, crop_w, out_h, out_w};
+  if (!low_res || !qidx || !cls_score || !stats_ws || !out_mask || !det_score || !bboxes || k < 0 || !mask_geom_valid(g))
     return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;
-  QMaskP p;
-  p.low = low_res; p.qidx = qidx; p.out = out_mask; p.logits = out_logits;
-  p.stats = (double*)stats_ws; p.box = (int32_t*)((char*)stats_ws + sizeof(double) * 2 * k);
-  p.h = h; p.w = w; p.Hb = Hb; p.Wb = Wb; p.ch = crop_h; p.cw = crop_w; p.oh = out_h; p.ow = out_w;
+  const QMaskP p{low_res, qidx, out_mask, (double*)stats_ws, (int32_t*)((char*)stats_ws + sizeof(double) * 2 * k), out_logits, g};
   hipLaunchKernelGGL(init_qstats_kernel, dim3((k + 63) / 64), dim3(64), 0, s, p.stats, p.box, k);
-  if ((int64_t)out_h * out_w > 0x7fffffffLL) return RSP_EINVAL;
   int64_t gx = ((int64_t)out_h * out_w / ((out_w & 3) == 0 ? 4 : 1) + 255) / 256;
   // every block ends with 6 atomics on its mask's statistics: with 1024 blocks per mask those same-address atomics
   // (0.6 M per call) were the whole run time; keep the grid just large enough to fill the chip
   const int64_t cap = k >= 64 ? 64 : (k >= 8 ? 256 : 1024);
   if (gx > cap) gx = cap;
-  if (crop_h == out_h && crop_w == out_w)
-    hipLaunchKernelGGL((query_mask_kernel<true>), dim3((unsigned)gx, k), dim3(256), 0, s, p);
+  if (mask_form(g) != MASK_GENERIC)
+    hipLaunchKernelGGL((query_mask_kernel<true>), dim3((unsigned)gx, k), dim3(MASK_BLOCK), 0, s, p);
   else
-    hipLaunchKernelGGL((query_mask_kernel<false>), dim3((unsigned)gx, k), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((query_mask_kernel<false>), dim3((unsigned)gx, k), dim3(MASK_BLOCK), 0, s, p);
   hipLaunchKernelGGL(query_finalize_kernel, dim3((k + 63) / 64), dim3(64), 0, s, cls_score, p.stats, p.box, det_score, bboxes, k);
   RSP_CHECK_LAUNCH();
   return RSP_OK;

@@ -245,6 +245,7 @@ static inline FastDiv make_fastdiv(int dv) {
 // a window of a larger image -- `src` then points at the window's first pixel and `pitch` (elements per row) is the
 // scene's.  One function, so that a tile cut by the kernel is bit-identical to the same crop resized on its own.
 // sx_scale = W / Wn, sy_scale = H / Hn in double (cv2's scales); (x, y) inside the resized [Hn, Wn] region.
+// (Not lin_coef of mask_field.h: that is torch's align_corners=False resize with fp32 scales, a different function.)
 template <typename T>
 __device__ __forceinline__ void rsp_bilinear_px(const T* __restrict__ src, int64_t pitch, int H, int W, double sx_scale,
                                                 double sy_scale, int x, int y, float v[3]) {

@@ -4,6 +4,7 @@
 //   mask post-process           models.py:1746-1784 (sigmoid -> bilinear to batch_input_shape ->
 //                               crop -> bilinear to ori_shape -> >= thr)
 #include "rsp_common.h"
+#include "mask_field.h"
 
 namespace {
 
@@ -29,25 +30,12 @@ __global__ __launch_bounds__(256) void hyper_mask_kernel(const float* __restrict
   }
 }
 
-struct Lin { int i0, i1; float l0, l1; };
-// torch upsample_bilinear2d(align_corners=False) source index / weights
-__device__ __forceinline__ Lin lin_coef(int dst, float scale, int in_size) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  Lin c;
-  c.i0 = (int)src;
-  if (c.i0 > in_size - 1) c.i0 = in_size - 1;
-  c.i1 = c.i0 + (c.i0 < in_size - 1 ? 1 : 0);
-  c.l1 = src - (float)c.i0;
-  c.l0 = 1.0f - c.l1;
-  return c;
-}
-
 struct MaskPostP {
   const float* low;   // [k, h, w] logits
   uint8_t* out;       // [k, oh, ow] bool
   float* prob;        // optional [k, oh, ow]
-  int k, h, w, Hb, Wb, ch, cw, oh, ow;
+  int k;
+  MaskGeom g;
   float thr;
   int strict;         // 1: value > thr (SAMDet, models.py:1206), 0: value >= thr (models.py:1779)
 };
@@ -57,143 +45,71 @@ __global__ __launch_bounds__(256) void sigmoid_kernel(const float* __restrict__ 
     y[i] = 1.0f / (1.0f + expf(-x[i]));
 }
 
-// The value of one output pixel of the resize -> crop -> resize chain, shared by the mask kernels below and by the scoring
-// kernel (mask_score_kernel): what is compared against a threshold there is this expression and no other.
-struct MaskScales { float s1h, s1w, s2h, s2w; };
-__device__ __forceinline__ MaskScales mask_scales(const MaskPostP& p) {
-  return MaskScales{(float)p.h / (float)p.Hb, (float)p.w / (float)p.Wb, (float)p.ch / (float)p.oh, (float)p.cw / (float)p.ow};
-}
-__device__ __forceinline__ float mask_stage1(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int Y, int X) {
-  const Lin ay = lin_coef(Y, s.s1h, p.h);
-  const Lin ax = lin_coef(X, s.s1w, p.w);
-  const float v00 = low[ay.i0 * p.w + ax.i0], v01 = low[ay.i0 * p.w + ax.i1];
-  const float v10 = low[ay.i1 * p.w + ax.i0], v11 = low[ay.i1 * p.w + ax.i1];
-  return ay.l0 * (ax.l0 * v00 + ax.l1 * v01) + ay.l1 * (ax.l0 * v10 + ax.l1 * v11);
-}
-// IDENT: crop == output size, so the second interpolation is the identity (src index == dst index, weight 1) and only
-// stage 1 is evaluated.
-template <bool IDENT>
-__device__ __forceinline__ float mask_pixel(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int oy, int ox) {
-  if (IDENT) return mask_stage1(low, p, s, oy, ox);
-  const Lin cy = lin_coef(oy, s.s2h, p.ch), cx = lin_coef(ox, s.s2w, p.cw);
-  const float a00 = mask_stage1(low, p, s, cy.i0, cx.i0), a01 = mask_stage1(low, p, s, cy.i0, cx.i1);
-  const float a10 = mask_stage1(low, p, s, cy.i1, cx.i0), a11 = mask_stage1(low, p, s, cy.i1, cx.i1);
-  return cy.l0 * (cx.l0 * a00 + cx.l1 * a01) + cy.l1 * (cx.l0 * a10 + cx.l1 * a11);
-}
-
-// The identity-crop case with (ow & 3) == 0 as a strip (round 5): a thread owns 4 consecutive output columns and walks down
-// the rows.  The x coefficients are computed once, the two horizontally interpolated source rows only when the source row
-// pair changes (every 4th output row at the usual 256 -> 1024), and a pixel is ay.l0 * h0 + ay.l1 * h1 -- the SAME fp32
-// expression tree as mask_stage1(), so the values are bit-identical.
-struct MaskStrip {
-  Lin ax[4];
-  int r0, r1;
-  float h0[4], h1[4];
-  __device__ __forceinline__ void init(const MaskPostP& p, const MaskScales& s, int ox) {
+__device__ __forceinline__ bool mask_post_test(const MaskPostP& p, float v) { return p.strict ? v > p.thr : v >= p.thr; }
+// four pixels of one row: one 32-bit store of the bool mask instead of four byte stores
+__device__ __forceinline__ void mask_post_store4(const MaskPostP& p, int64_t o, const float v[4]) {
+  uint32_t bits = 0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ax[e] = lin_coef(ox + e, s.s1w, p.w);
-    r0 = -1; r1 = -1;
-  }
-  __device__ __forceinline__ void row(const float* __restrict__ low, const MaskPostP& p, const MaskScales& s, int oy, float v[4]) {
-    const Lin ay = lin_coef(oy, s.s1h, p.h);
-    if (ay.i0 != r0 || ay.i1 != r1) {
-      r0 = ay.i0; r1 = ay.i1;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h0[e] = ax[e].l0 * low[r0 * p.w + ax[e].i0] + ax[e].l1 * low[r0 * p.w + ax[e].i1];
-        h1[e] = ax[e].l0 * low[r1 * p.w + ax[e].i0] + ax[e].l1 * low[r1 * p.w + ax[e].i1];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ay.l0 * h0[e] + ay.l1 * h1[e];
-  }
-};
+  for (int e = 0; e < 4; ++e) bits |= (mask_post_test(p, v[e]) ? 1u : 0u) << (8 * e);
+  *reinterpret_cast<uint32_t*>(p.out + o) = bits;
+  if (p.prob) *reinterpret_cast<f32x4*>(p.prob + o) = f32x4{v[0], v[1], v[2], v[3]};
+}
 
 // `sig` = sigmoid(low-res logits) (models.py:1758)
 template <bool IDENT>
 __global__ __launch_bounds__(256) void mask_post_kernel(const MaskPostP p) {
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int64_t total = (int64_t)p.oh * p.ow;
-  auto pixel = [&](int oy, int ox) -> float { return mask_pixel<IDENT>(low, p, sc, oy, ox); };
-  if ((p.ow & 3) == 0) {
-    // four pixels of one row per thread: one 32-bit store of the bool mask instead of four byte stores
-    const int qw = p.ow >> 2;
-    const int nq = p.oh * qw;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
-      const int oy = i / qw, ox = (i - oy * qw) << 2;
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = pixel(oy, ox + e);
-      uint32_t bits = 0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bits |= ((p.strict ? v[e] > p.thr : v[e] >= p.thr) ? 1u : 0u) << (8 * e);
-      const int64_t o = (int64_t)m * total + (int64_t)oy * p.ow + ox;
-      *reinterpret_cast<uint32_t*>(p.out + o) = bits;
-      if (p.prob) *reinterpret_cast<f32x4*>(p.prob + o) = f32x4{v[0], v[1], v[2], v[3]};
-    }
+  const float* low = p.low + (int64_t)m * p.g.h * p.g.w;
+  const int64_t base = (int64_t)m * p.g.oh * p.g.ow;
+  if ((p.g.ow & 3) == 0) {
+    mask_each_quad<IDENT>(low, p.g,
+                          [&](const float v[4], int oy, int ox) { mask_post_store4(p, base + (int64_t)oy * p.g.ow + ox, v); });
     return;
   }
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
-    const float val = pixel(oy, ox);
-    p.out[(int64_t)m * total + i] = (p.strict ? val > p.thr : val >= p.thr) ? 1 : 0;
-    if (p.prob) p.prob[(int64_t)m * total + i] = val;
-  }
+  mask_each_pixel(low, p.g, IDENT, [&](float v, int, int, int64_t i) {
+    const int64_t o = base + i;
+    p.out[o] = mask_post_test(p, v) ? 1 : 0;
+    if (p.prob) p.prob[o] = v;
+  });
 }
 
-// The identity-crop case (crop == output size: every 1024-px tile) as a strip kernel (MaskStrip above); the generic
-// kernel spends ~40 VALU instructions and four gathers per pixel on it (1.3 ms per ViT-H step for 838 MB of masks).
+// MASK_STRIP (every 1024-px tile); the generic kernel spends ~40 VALU instructions and four gathers per pixel on it
+// (1.3 ms per ViT-H step for 838 MB of masks).
 constexpr int MP_ROWS = 16;
 __global__ __launch_bounds__(256) void mask_post_strip_kernel(const MaskPostP p) {
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int qw = p.ow >> 2;
-  const int ntile = (p.oh + MP_ROWS - 1) / MP_ROWS;
-  const int64_t total = (int64_t)p.oh * p.ow;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;       // (row tile, column quad): quads fastest -> coalesced rows
-  if (i >= ntile * qw) return;
-  const int ty = i / qw, ox = (i - ty * qw) << 2;
-  MaskStrip st;
-  st.init(p, sc, ox);
-  const int oy_end = min((ty + 1) * MP_ROWS, p.oh);
-  for (int oy = ty * MP_ROWS; oy < oy_end; ++oy) {
-    float v[4];
-    st.row(low, p, sc, oy, v);
-    uint32_t bits = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bits |= ((p.strict ? v[e] > p.thr : v[e] >= p.thr) ? 1u : 0u) << (8 * e);
-    const int64_t o = (int64_t)m * total + (int64_t)oy * p.ow + ox;
-    *reinterpret_cast<uint32_t*>(p.out + o) = bits;
-    if (p.prob) *reinterpret_cast<f32x4*>(p.prob + o) = f32x4{v[0], v[1], v[2], v[3]};
-  }
+  const int64_t base = (int64_t)m * p.g.oh * p.g.ow;
+  mask_each_strip<MP_ROWS, true>(p.low + (int64_t)m * p.g.h * p.g.w, p.g,
+                           [&](const float v[4], int oy, int ox) { mask_post_store4(p, base + (int64_t)oy * p.g.ow + ox, v); });
 }
 
 // Scores of K candidate masks without the masks (HF mask generation: _compute_stability_score + _batched_mask_to_box of
-// image_processing_sam over post_process_masks): per mask the number of pixels whose value -- the one the kernels above
-// would threshold, same device functions, same kernel choice per geometry -- is > t_hi, > t_lo and > t_mid, and the extents
-// of the pixels > t_mid.  acc[m] = {n_hi, n_lo, n_mid, min x, min y, max x, max y}; integer sums and extrema only, so the
-// result does not depend on the order in which blocks arrive.  Nothing of size K * oh * ow is written.
+// image_processing_sam over post_process_masks): per mask the number of pixels of its field that are > t_hi, > t_lo and
+// > t_mid, and the extents of the pixels > t_mid.  acc[m] = {n_hi, n_lo, n_mid, min x, min y, max x, max y}; integer sums and
+// extrema only, so the result does not depend on the order in which blocks arrive.  Nothing of size K * oh * ow is written.
+struct ScoreThr { float t_hi, t_lo, t_mid; };
 struct MaskScoreP {
-  MaskPostP g;          // geometry + logits (out / prob / thr / strict unused)
+  const float* low;     // [k, h, w] logits
+  MaskGeom g;
   int32_t* acc;         // [k, 7]
-  float t_hi, t_lo, t_mid;
+  ScoreThr t;
 };
 
 struct ScoreAcc {
   int n_hi, n_lo, n_mid, x0, y0, x1, y1;
   __device__ __forceinline__ void clear() { n_hi = n_lo = n_mid = 0; x0 = y0 = 0x7fffffff; x1 = y1 = -1; }
-  __device__ __forceinline__ void add(const MaskScoreP& q, float v, int oy, int ox) {
-    n_hi += v > q.t_hi ? 1 : 0;
-    n_lo += v > q.t_lo ? 1 : 0;
-    if (v > q.t_mid) {
+  __device__ __forceinline__ void add(const ScoreThr& t, float v, int oy, int ox) {
+    n_hi += v > t.t_hi ? 1 : 0;
+    n_lo += v > t.t_lo ? 1 : 0;
+    if (v > t.t_mid) {
       n_mid += 1;
       x0 = min(x0, ox); x1 = max(x1, ox);
       y0 = min(y0, oy); y1 = max(y1, oy);
     }
+  }
+  __device__ __forceinline__ void add4(const ScoreThr& t, const float v[4], int oy, int ox) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) add(t, v[e], oy, ox + e);
   }
 };
 
@@ -232,52 +148,30 @@ __device__ __forceinline__ void score_block_reduce(ScoreAcc a, int32_t* __restri
 
 template <bool IDENT>
 __global__ __launch_bounds__(256) void mask_score_kernel(const MaskScoreP q) {
-  const MaskPostP& p = q.g;
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int64_t total = (int64_t)p.oh * p.ow;
   ScoreAcc a;
   a.clear();
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
-    a.add(q, mask_pixel<IDENT>(low, p, sc, oy, ox), oy, ox);
-  }
+  mask_each_pixel(q.low + (int64_t)m * q.g.h * q.g.w, q.g, IDENT, [&](float v, int oy, int ox, int64_t) { a.add(q.t, v, oy, ox); });
   score_block_reduce(a, q.acc + (int64_t)m * 7);
 }
 
-// strip form, taken exactly where launch_mask_post takes mask_post_strip_kernel; a thread walks MS_ROWS rows of its 4 columns
 constexpr int MS_ROWS = 64;
 __global__ __launch_bounds__(256) void mask_score_strip_kernel(const MaskScoreP q) {
-  const MaskPostP& p = q.g;
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int qw = p.ow >> 2;
-  const int ntile = (p.oh + MS_ROWS - 1) / MS_ROWS;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
   ScoreAcc a;
   a.clear();
-  if (i < ntile * qw) {
-    const int ty = i / qw, ox = (i - ty * qw) << 2;
-    MaskStrip st;
-    st.init(p, sc, ox);
-    const int oy_end = min((ty + 1) * MS_ROWS, p.oh);
-    for (int oy = ty * MS_ROWS; oy < oy_end; ++oy) {
-      float v[4];
-      st.row(low, p, sc, oy, v);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) a.add(q, v[e], oy, ox + e);
-    }
-  }
+  mask_each_strip<MS_ROWS, true>(q.low + (int64_t)m * q.g.h * q.g.w, q.g,
+                                 [&](const float v[4], int oy, int ox) { a.add4(q.t, v, oy, ox); });
   score_block_reduce(a, q.acc + (int64_t)m * 7);
 }
 
+// rows of W = 7 (rsp_mask_score_box) or 8 (rsp_mask_score_box_crops: + the near-edge flag) accumulators
+template <int W>
 __global__ __launch_bounds__(256) void mask_score_init_kernel(int32_t* __restrict__ acc, int k) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k * 7) return;
-  const int j = i % 7;
-  acc[i] = j < 3 ? 0 : (j < 5 ? 0x7fffffff : -1);
+  if (i >= k * W) return;
+  const int j = i % W;
+  acc[i] = j < 3 ? 0 : (j < 5 ? 0x7fffffff : (j < 7 ? -1 : 0));
 }
 
 // an empty mask gets the box [0, 0, 0, 0] (HF _batched_mask_to_box)
@@ -293,10 +187,9 @@ __global__ __launch_bounds__(256) void mask_score_final_kernel(int32_t* __restri
 // The same scores for candidates of SEVERAL crops in one launch (SAM's crop layers): candidate m belongs to crop
 // crop_idx[m], and row crop_idx[m] of a device table holds that crop's geometry (Hb, Wb, crop_h, crop_w, out_h, out_w), its box
 // in the image (x0, y0, x1, y1) and the image size (W, H).  A block works on ONE candidate, so the table row is wave-uniform
-// (scalar loads) and the form -- strip, identity, generic -- is chosen per crop by launch_mask_post's condition; the pixel
-// value comes from mask_pixel / MaskStrip above, the reduction is score_block_reduce: counts and crop-local box are those of
-// rsp_mask_score_box on that crop's slice.  acc is [k, 8]: the finalising launch shifts the box into the image frame and
-// writes HF's _is_box_near_crop_edge into column 7.
+// (scalar loads) and mask_form() is evaluated per crop: counts and crop-local box are those of rsp_mask_score_box on that
+// crop's slice.  acc is [k, 8]: the finalising launch shifts the box into the image frame and writes HF's
+// _is_box_near_crop_edge into column 7.
 constexpr int CROP_ROW = 12;
 constexpr int CROP_EDGE_ATOL = 20;      // _is_box_near_crop_edge(atol=20.0); every quantity is an integer
 struct MaskScoreCropsP {
@@ -305,54 +198,25 @@ struct MaskScoreCropsP {
   const int32_t* table;      // [n_crops, CROP_ROW]
   int32_t* acc;              // [k, 8]
   int k, h, w, n_crops;
-  float t_hi, t_lo, t_mid;
+  ScoreThr t;
 };
 
 __global__ __launch_bounds__(256) void mask_score_crops_kernel(const MaskScoreCropsP c) {
   const int m = blockIdx.y;
   const int32_t* t = c.table + CROP_ROW * min(max(c.crop_idx[m], 0), c.n_crops - 1);   // clamped: never outside the table
-  MaskScoreP q;
-  MaskPostP& p = q.g;
-  p.low = c.low + (int64_t)m * c.h * c.w; p.out = nullptr; p.prob = nullptr; p.k = 1; p.h = c.h; p.w = c.w;
-  p.Hb = t[0]; p.Wb = t[1]; p.ch = t[2]; p.cw = t[3]; p.oh = t[4]; p.ow = t[5]; p.thr = c.t_mid; p.strict = 1;
-  q.acc = c.acc + (int64_t)m * 8; q.t_hi = c.t_hi; q.t_lo = c.t_lo; q.t_mid = c.t_mid;
-  const float* low = p.low;
-  const MaskScales sc = mask_scales(p);
+  const MaskGeom g{c.h, c.w, t[0], t[1], t[2], t[3], t[4], t[5]};
+  const float* low = c.low + (int64_t)m * c.h * c.w;
   ScoreAcc a;
   a.clear();
-  // a row the host would have refused scores as an empty mask (the loops below never run)
-  const bool ok = p.Hb > 0 && p.Wb > 0 && p.ch > 0 && p.cw > 0 && p.oh > 0 && p.ow > 0 && p.ch <= p.Hb && p.cw <= p.Wb;
-  const bool ident = p.ch == p.oh && p.cw == p.ow;
-  if (ok && ident && (p.ow & 3) == 0) {
-    const int qw = p.ow >> 2;
-    const int nitem = ((p.oh + MS_ROWS - 1) / MS_ROWS) * qw;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nitem; i += gridDim.x * blockDim.x) {
-      const int ty = i / qw, ox = (i - ty * qw) << 2;
-      MaskStrip st;
-      st.init(p, sc, ox);
-      const int oy_end = min((ty + 1) * MS_ROWS, p.oh);
-      for (int oy = ty * MS_ROWS; oy < oy_end; ++oy) {
-        float v[4];
-        st.row(low, p, sc, oy, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a.add(q, v[e], oy, ox + e);
-      }
-    }
-  } else if (ok) {
-    const int64_t total = (int64_t)p.oh * p.ow;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-      const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
-      a.add(q, ident ? mask_pixel<true>(low, p, sc, oy, ox) : mask_pixel<false>(low, p, sc, oy, ox), oy, ox);
-    }
+  // a row the host would have refused scores as an empty mask (no traversal)
+  if (mask_table_row_ok(g)) {
+    const MaskForm form = mask_form(g);
+    if (form == MASK_STRIP)
+      mask_each_strip<MS_ROWS, false>(low, g, [&](const float v[4], int oy, int ox) { a.add4(c.t, v, oy, ox); });
+    else
+      mask_each_pixel(low, g, form == MASK_IDENT, [&](float v, int oy, int ox, int64_t) { a.add(c.t, v, oy, ox); });
   }
-  score_block_reduce(a, q.acc);
-}
-
-__global__ __launch_bounds__(256) void mask_score_crops_init_kernel(int32_t* __restrict__ acc, int k) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k * 8) return;
-  const int j = i & 7;
-  acc[i] = j < 3 ? 0 : (j < 5 ? 0x7fffffff : (j < 7 ? -1 : 0));
+  score_block_reduce(a, c.acc + (int64_t)m * 8);
 }
 
 // the empty-mask box [0, 0, 0, 0] (crop-local, shifted like any other), the shift by (x0, y0, x0, y0) and the near-edge flag:
@@ -376,8 +240,7 @@ __global__ __launch_bounds__(256) void mask_score_crops_final_kernel(int32_t* __
 
 // PerSAM's location prior (rsp_persam_locate; PerSAM persam.py `point_selection` + the normalisation of the similarity in
 // front of `attn_sim`): the extrema of the IMAGE-RESOLUTION field with their positions, its mean and unbiased standard
-// deviation, and the g x g resampling of the normalised field -- the field being what the kernels above would write for these
-// logits (same device functions, the strip form where launch_mask_post takes it), and never written.
+// deviation, and the g x g resampling of the normalised field.  The field itself is never written.
 //   extrema   one 64-bit integer atomic per block on a packed key (order-preserving image of the value << 32 | index): the
 //             maximum carries ~index, the minimum index, so that among equal values the LOWEST flat index y * ow + x wins
 //             either way (torch.argmax / argmin of the flattened field; a plateau at the extreme is the normal case for a
@@ -386,7 +249,9 @@ __global__ __launch_bounds__(256) void mask_score_crops_final_kernel(int32_t* __
 //             tree per block, one partial pair per block in memory, added in block order by the finalising launch: no
 //             floating-point atomic, so two runs give the same bits.
 struct LocateP {
-  MaskPostP g;                 // geometry + logits (out / prob / thr / strict unused)
+  const float* low;            // [k, h, w] logits
+  MaskGeom g;
+  int k;
   unsigned long long* keys;    // [k, 2] packed maximum, minimum
   double* part;                // [k, gx, 2] sum, sum of squares of (v - K) per block
   int gx;
@@ -441,46 +306,26 @@ __device__ __forceinline__ void locate_block_reduce(LocateAcc a, const LocateP& 
 
 template <bool IDENT>
 __global__ __launch_bounds__(256) void persam_locate_kernel(const LocateP q) {
-  const MaskPostP& p = q.g;
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int64_t total = (int64_t)p.oh * p.ow;
+  const float* low = q.low + (int64_t)m * q.g.h * q.g.w;
   const float K = low[0];
   LocateAcc a;
   a.clear();
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int oy = (int)(i / p.ow), ox = (int)(i - (int64_t)oy * p.ow);
-    a.add(mask_pixel<IDENT>(low, p, sc, oy, ox), (int)i, K);
-  }
+  mask_each_pixel(low, q.g, IDENT, [&](float v, int, int, int64_t i) { a.add(v, (int)i, K); });
   locate_block_reduce(a, q, m);
 }
 
-// strip form, taken exactly where launch_mask_post takes mask_post_strip_kernel; a thread walks LOC_ROWS rows of its 4 columns
 constexpr int LOC_ROWS = 16;
 __global__ __launch_bounds__(256) void persam_locate_strip_kernel(const LocateP q) {
-  const MaskPostP& p = q.g;
   const int m = blockIdx.y;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
-  const int qw = p.ow >> 2;
-  const int ntile = (p.oh + LOC_ROWS - 1) / LOC_ROWS;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const float* low = q.low + (int64_t)m * q.g.h * q.g.w;
   const float K = low[0];
   LocateAcc a;
   a.clear();
-  if (i < ntile * qw) {
-    const int ty = i / qw, ox = (i - ty * qw) << 2;
-    MaskStrip st;
-    st.init(p, sc, ox);
-    const int oy_end = min((ty + 1) * LOC_ROWS, p.oh);
-    for (int oy = ty * LOC_ROWS; oy < oy_end; ++oy) {
-      float v[4];
-      st.row(low, p, sc, oy, v);
+  mask_each_strip<LOC_ROWS, true>(low, q.g, [&](const float v[4], int oy, int ox) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) a.add(v[e], oy * p.ow + ox + e, K);
-    }
-  }
+    for (int e = 0; e < 4; ++e) a.add(v[e], oy * q.g.ow + ox + e, K);
+  });
   locate_block_reduce(a, q, m);
 }
 
@@ -493,12 +338,12 @@ __global__ __launch_bounds__(256) void persam_locate_init_kernel(unsigned long l
 // std is torch.std's (unbiased); a constant field (max == min) has std 0 exactly, as has a field of one pixel.
 __global__ __launch_bounds__(64) void persam_locate_final_kernel(const LocateP q, float* __restrict__ stats, int32_t* __restrict__ xy) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= q.g.k) return;
+  if (m >= q.k) return;
   const double* pp = q.part + (int64_t)m * q.gx * 2;
   double s = 0.0, ss = 0.0;
   for (int b = 0; b < q.gx; ++b) { s += pp[2 * b]; ss += pp[2 * b + 1]; }
   const double n = (double)q.g.oh * (double)q.g.ow;
-  const double K = (double)q.g.low[(int64_t)m * q.g.h * q.g.w];
+  const double K = (double)q.low[(int64_t)m * q.g.h * q.g.w];
   const unsigned long long kmax = q.keys[(int64_t)m * 2], kmin = q.keys[(int64_t)m * 2 + 1];
   const uint32_t omax = (uint32_t)(kmax >> 32), omin = (uint32_t)(kmin >> 32);
   const int imax = (int)(0xffffffffu - (uint32_t)kmax), imin = (int)(uint32_t)kmin;
@@ -516,28 +361,61 @@ __global__ __launch_bounds__(64) void persam_locate_final_kernel(const LocateP q
 // attn_sim[m, cy * g + cx] = sigmoid((D - mean) / std), D = the bilinear g x g resampling of the image-resolution field
 // (F.interpolate(size=(g, g), align_corners=False): four field values per cell, evaluated here).  PerSAM normalises first and
 // resamples then; the normalisation is affine and the weights sum to 1, so the order does not matter.  std == 0: 0 / 0 := 0,
-// i.e. 0.5 everywhere (PerSAM itself would produce NaN).
+// i.e. 0.5 everywhere (PerSAM itself would produce NaN).  Of `p` it reads the logits and the geometry.
 __global__ __launch_bounds__(256) void persam_attn_sim_kernel(const MaskPostP p, int g, const float* __restrict__ stats,
                                                               float* __restrict__ attn) {
   const int m = blockIdx.y;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= g * g) return;
-  const float* low = p.low + (int64_t)m * p.h * p.w;
-  const MaskScales sc = mask_scales(p);
+  const float* low = p.low + (int64_t)m * p.g.h * p.g.w;
+  const MaskScales sc = mask_scales(p.g);
   const int cy = c / g, cx = c - cy * g;
-  const Lin ly = lin_coef(cy, (float)p.oh / (float)g, p.oh), lx = lin_coef(cx, (float)p.ow / (float)g, p.ow);
+  const Lin ly = lin_coef(cy, (float)p.g.oh / (float)g, p.g.oh), lx = lin_coef(cx, (float)p.g.ow / (float)g, p.g.ow);
   float a00, a01, a10, a11;
-  if (p.ch == p.oh && p.cw == p.ow) {
-    a00 = mask_pixel<true>(low, p, sc, ly.i0, lx.i0); a01 = mask_pixel<true>(low, p, sc, ly.i0, lx.i1);
-    a10 = mask_pixel<true>(low, p, sc, ly.i1, lx.i0); a11 = mask_pixel<true>(low, p, sc, ly.i1, lx.i1);
+  if (mask_form(p.g) != MASK_GENERIC) {
+    a00 = mask_pixel<true>(low, p.g, sc, ly.i0, lx.i0); a01 = mask_pixel<true>(low, p.g, sc, ly.i0, lx.i1);
+    a10 = mask_pixel<true>(low, p.g, sc, ly.i1, lx.i0); a11 = mask_pixel<true>(low, p.g, sc, ly.i1, lx.i1);
   } else {
-    a00 = mask_pixel<false>(low, p, sc, ly.i0, lx.i0); a01 = mask_pixel<false>(low, p, sc, ly.i0, lx.i1);
-    a10 = mask_pixel<false>(low, p, sc, ly.i1, lx.i0); a11 = mask_pixel<false>(low, p, sc, ly.i1, lx.i1);
+    a00 = mask_pixel<false>(low, p.g, sc, ly.i0, lx.i0); a01 = mask_pixel<false>(low, p.g, sc, ly.i0, lx.i1);
+    a10 = mask_pixel<false>(low, p.g, sc, ly.i1, lx.i0); a11 = mask_pixel<false>(low, p.g, sc, ly.i1, lx.i1);
   }
   const float D = ly.l0 * (lx.l0 * a00 + lx.l1 * a01) + ly.l1 * (lx.l0 * a10 + lx.l1 * a11);
   const float mean = stats[m * 4 + 2], sd = stats[m * 4 + 3];
   const float z = sd > 0.f ? (D - mean) / sd : 0.f;
   attn[(int64_t)m * g * g + c] = 1.0f / (1.0f + expf(-z));
+}
+
+// ---- launch geometry
+// 256-thread blocks for n work items, at most cap
+unsigned blocks256(int64_t n, int64_t cap) {
+  const int64_t b = (n + 255) / 256;
+  return (unsigned)(b > cap ? cap : b);
+}
+constexpr int64_t NO_CAP = 0x7fffffffLL;
+// blocks per mask of the flat scoring traversal: enough to fill the device at small k, few enough that the per-block
+// reduction stays negligible
+unsigned score_blocks(int32_t k, int out_h, int out_w) {
+  return blocks256((int64_t)out_h * out_w, k >= 1024 ? 16 : (k >= 64 ? 64 : 1024));
+}
+// launch(m0, km) for chunks of at most 65535 masks (the grid.y limit)
+template <typename F>
+void for_mask_chunks(int32_t k, F&& launch) {
+  for (int32_t m0 = 0; m0 < k; m0 += 65535) launch(m0, k - m0 < 65535 ? k - m0 : 65535);
+}
+
+int launch_mask_post(const MaskPostP& p, hipStream_t stream) {
+  const MaskGeom& g = p.g;
+  const unsigned gx = blocks256((int64_t)g.oh * g.ow / ((g.ow & 3) == 0 ? 4 : 1), 4096);
+  switch (mask_form(g)) {
+    case MASK_STRIP:
+      hipLaunchKernelGGL(mask_post_strip_kernel, dim3(blocks256(mask_strip_items(g.oh, g.ow, MP_ROWS), NO_CAP), p.k),
+                         dim3(MASK_BLOCK), 0, stream, p);
+      break;
+    case MASK_IDENT: hipLaunchKernelGGL((mask_post_kernel<true>), dim3(gx, p.k), dim3(MASK_BLOCK), 0, stream, p); break;
+    case MASK_GENERIC: hipLaunchKernelGGL((mask_post_kernel<false>), dim3(gx, p.k), dim3(MASK_BLOCK), 0, stream, p); break;
+  }
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
 }
 
 }  // namespace
@@ -553,93 +431,49 @@ extern "C" int rsp_hyper_mask(const float* up, const float* hyper, float* out, i
   return RSP_OK;
 }
 
-namespace {
-int launch_mask_post(const MaskPostP& p, hipStream_t stream) {
-  if ((int64_t)p.oh * p.ow > 0x7fffffffLL) return RSP_EINVAL;
-  int64_t gx = ((int64_t)p.oh * p.ow / ((p.ow & 3) == 0 ? 4 : 1) + 255) / 256;
-  if (gx > 4096) gx = 4096;
-  if (p.ch == p.oh && p.cw == p.ow && (p.ow & 3) == 0) {
-    const int64_t nthr = (int64_t)((p.oh + MP_ROWS - 1) / MP_ROWS) * (p.ow >> 2);
-    hipLaunchKernelGGL(mask_post_strip_kernel, dim3((unsigned)((nthr + 255) / 256), p.k), dim3(256), 0, stream, p);
-  } else if (p.ch == p.oh && p.cw == p.ow)
-    hipLaunchKernelGGL((mask_post_kernel<true>), dim3((unsigned)gx, p.k), dim3(256), 0, stream, p);
-  else
-    hipLaunchKernelGGL((mask_post_kernel<false>), dim3((unsigned)gx, p.k), dim3(256), 0, stream, p);
-  RSP_CHECK_LAUNCH();
-  return RSP_OK;
-}
-}  // namespace
-
 extern "C" int rsp_mask_post(const float* low_res, float* sig_ws, int32_t k, int32_t h, int32_t w, int32_t Hb,
                              int32_t Wb, int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w, float thr,
                              uint8_t* out_mask, float* out_prob, rsp_stream_t stream) {
-  if (!low_res || !sig_ws || !out_mask || k < 0 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 || crop_h <= 0 || crop_w <= 0 ||
-      crop_h > Hb || crop_w > Wb || out_h <= 0 || out_w <= 0)
-    return RSP_EINVAL;
+  const MaskGeom g{h, w, Hb, Wb, crop_h, crop_w, out_h, out_w};
+  if (!low_res || !sig_ws || !out_mask || k < 0 || !mask_geom_valid(g)) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
-  {
-    const int64_t n = (int64_t)k * h * w;
-    int64_t gs = (n + 255) / 256;
-    if (gs > 4096) gs = 4096;
-    hipLaunchKernelGGL(sigmoid_kernel, dim3((unsigned)gs), dim3(256), 0, (hipStream_t)stream, low_res, sig_ws, n);
-  }
-  MaskPostP p;
-  p.low = sig_ws; p.out = out_mask; p.prob = out_prob; p.k = k; p.h = h; p.w = w; p.Hb = Hb; p.Wb = Wb;
-  p.ch = crop_h; p.cw = crop_w; p.oh = out_h; p.ow = out_w; p.thr = thr; p.strict = 0;
-  return launch_mask_post(p, (hipStream_t)stream);
+  const int64_t n = (int64_t)k * h * w;
+  hipLaunchKernelGGL(sigmoid_kernel, dim3(blocks256(n, 4096)), dim3(256), 0, (hipStream_t)stream, low_res, sig_ws, n);
+  return launch_mask_post(MaskPostP{sig_ws, out_mask, out_prob, k, g, thr, 0}, (hipStream_t)stream);
 }
 
 // SAMDet.predict (models.py:1185-1206): the same resize -> crop -> resize chain on the raw logits, then `> thr` (thr = 0)
 extern "C" int rsp_mask_post_logits(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb,
                                     int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w, float thr,
                                     uint8_t* out_mask, float* out_val, rsp_stream_t stream) {
-  if (!low_res || !out_mask || k < 0 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 || crop_h <= 0 || crop_w <= 0 ||
-      crop_h > Hb || crop_w > Wb || out_h <= 0 || out_w <= 0)
-    return RSP_EINVAL;
+  const MaskGeom g{h, w, Hb, Wb, crop_h, crop_w, out_h, out_w};
+  if (!low_res || !out_mask || k < 0 || !mask_geom_valid(g)) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
-  MaskPostP p;
-  p.low = low_res; p.out = out_mask; p.prob = out_val; p.k = k; p.h = h; p.w = w; p.Hb = Hb; p.Wb = Wb;
-  p.ch = crop_h; p.cw = crop_w; p.oh = out_h; p.ow = out_w; p.thr = thr; p.strict = 1;
-  return launch_mask_post(p, (hipStream_t)stream);
+  return launch_mask_post(MaskPostP{low_res, out_mask, out_val, k, g, thr, 1}, (hipStream_t)stream);
 }
-
 
 extern "C" int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
                                   int32_t crop_w, int32_t out_h, int32_t out_w, float t_hi, float t_lo, float t_mid,
                                   int32_t* out, rsp_stream_t stream) {
-  if (!low_res || !out || k < 0 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 || crop_h <= 0 || crop_w <= 0 || crop_h > Hb ||
-      crop_w > Wb || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > 0x7fffffffLL || (int64_t)k * 7 > 0x7fffffffLL)
-    return RSP_EINVAL;
+  const MaskGeom g{h, w, Hb, Wb, crop_h, crop_w, out_h, out_w};
+  if (!low_res || !out || k < 0 || !mask_geom_valid(g) || (int64_t)k * 7 > 0x7fffffffLL) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mask_score_init_kernel, dim3((unsigned)((k * 7 + 255) / 256)), dim3(256), 0, st, out, k);
-  MaskScoreP q;
-  q.g.out = nullptr; q.g.prob = nullptr; q.g.h = h; q.g.w = w; q.g.Hb = Hb; q.g.Wb = Wb;
-  q.g.ch = crop_h; q.g.cw = crop_w; q.g.oh = out_h; q.g.ow = out_w; q.g.thr = t_mid; q.g.strict = 1;
-  q.t_hi = t_hi; q.t_lo = t_lo; q.t_mid = t_mid;
-  const bool ident = crop_h == out_h && crop_w == out_w;
-  for (int32_t m0 = 0; m0 < k; m0 += 65535) {                  // grid.y limit
-    const int32_t km = k - m0 < 65535 ? k - m0 : 65535;
-    q.g.low = low_res + (int64_t)m0 * h * w; q.g.k = km; q.acc = out + (int64_t)m0 * 7;
-    if (ident && (out_w & 3) == 0) {
-      const int64_t nthr = (int64_t)((out_h + MS_ROWS - 1) / MS_ROWS) * (out_w >> 2);
-      hipLaunchKernelGGL(mask_score_strip_kernel, dim3((unsigned)((nthr + 255) / 256), km), dim3(256), 0, st, q);
-    } else {
-      int64_t gx = ((int64_t)out_h * out_w + 255) / 256;
-      // enough blocks per mask to fill the device at small k, few enough that the per-block reduction stays negligible
-      const int64_t cap = k >= 1024 ? 16 : (k >= 64 ? 64 : 1024);
-      if (gx > cap) gx = cap;
-      if (ident)
-        hipLaunchKernelGGL((mask_score_kernel<true>), dim3((unsigned)gx, km), dim3(256), 0, st, q);
-      else
-        hipLaunchKernelGGL((mask_score_kernel<false>), dim3((unsigned)gx, km), dim3(256), 0, st, q);
+  hipLaunchKernelGGL((mask_score_init_kernel<7>), dim3(blocks256(k * 7, NO_CAP)), dim3(256), 0, st, out, k);
+  const MaskForm form = mask_form(g);
+  const unsigned gx = form == MASK_STRIP ? blocks256(mask_strip_items(out_h, out_w, MS_ROWS), NO_CAP) : score_blocks(k, out_h, out_w);
+  for_mask_chunks(k, [&](int32_t m0, int32_t km) {
+    const MaskScoreP q{low_res + (int64_t)m0 * h * w, g, out + (int64_t)m0 * 7, ScoreThr{t_hi, t_lo, t_mid}};
+    switch (form) {
+      case MASK_STRIP: hipLaunchKernelGGL(mask_score_strip_kernel, dim3(gx, km), dim3(MASK_BLOCK), 0, st, q); break;
+      case MASK_IDENT: hipLaunchKernelGGL((mask_score_kernel<true>), dim3(gx, km), dim3(MASK_BLOCK), 0, st, q); break;
+      case MASK_GENERIC: hipLaunchKernelGGL((mask_score_kernel<false>), dim3(gx, km), dim3(MASK_BLOCK), 0, st, q); break;
     }
-  }
-  hipLaunchKernelGGL(mask_score_final_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, out, k);
+  });
+  hipLaunchKernelGGL(mask_score_final_kernel, dim3(blocks256(k, NO_CAP)), dim3(256), 0, st, out, k);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }
-
 
 extern "C" int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t h, int32_t w, const int32_t* crop_idx,
                                         const int32_t* table, int32_t n_crops, int32_t max_out_h, int32_t max_out_w, float t_hi,
@@ -649,31 +483,23 @@ extern "C" int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t
     return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mask_score_crops_init_kernel, dim3((unsigned)((k * 8 + 255) / 256)), dim3(256), 0, st, out, k);
-  MaskScoreCropsP c;
-  c.table = table; c.h = h; c.w = w; c.n_crops = n_crops; c.t_hi = t_hi; c.t_lo = t_lo; c.t_mid = t_mid;
+  hipLaunchKernelGGL((mask_score_init_kernel<8>), dim3(blocks256(k * 8, NO_CAP)), dim3(256), 0, st, out, k);
   // blocks per candidate as rsp_mask_score_box sizes them for the largest crop; a smaller crop's blocks find their loops empty
-  int64_t gx = ((int64_t)max_out_h * max_out_w + 255) / 256;
-  const int64_t cap = k >= 1024 ? 16 : (k >= 64 ? 64 : 1024);
-  if (gx > cap) gx = cap;
-  for (int32_t m0 = 0; m0 < k; m0 += 65535) {                  // grid.y limit
-    const int32_t km = k - m0 < 65535 ? k - m0 : 65535;
-    c.low = low_res + (int64_t)m0 * h * w; c.crop_idx = crop_idx + m0; c.acc = out + (int64_t)m0 * 8; c.k = km;
-    hipLaunchKernelGGL(mask_score_crops_kernel, dim3((unsigned)gx, km), dim3(256), 0, st, c);
-  }
-  hipLaunchKernelGGL(mask_score_crops_final_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, out, crop_idx, table, k,
-                     n_crops);
+  const unsigned gx = score_blocks(k, max_out_h, max_out_w);
+  for_mask_chunks(k, [&](int32_t m0, int32_t km) {
+    const MaskScoreCropsP c{low_res + (int64_t)m0 * h * w, crop_idx + m0, table, out + (int64_t)m0 * 8, km, h, w, n_crops,
+                            ScoreThr{t_hi, t_lo, t_mid}};
+    hipLaunchKernelGGL(mask_score_crops_kernel, dim3(gx, km), dim3(MASK_BLOCK), 0, st, c);
+  });
+  hipLaunchKernelGGL(mask_score_crops_final_kernel, dim3(blocks256(k, NO_CAP)), dim3(256), 0, st, out, crop_idx, table, k, n_crops);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }
 
-
 namespace {
 // blocks per image of rsp_persam_locate's reduction (also the number of fp64 partial pairs per image in its workspace)
 int locate_gx(int out_h, int out_w, bool strip) {
-  if (strip) return (int)(((int64_t)((out_h + LOC_ROWS - 1) / LOC_ROWS) * (out_w >> 2) + 255) / 256);
-  const int64_t gx = ((int64_t)out_h * out_w + 255) / 256;
-  return (int)(gx > 256 ? 256 : gx);
+  return (int)(strip ? blocks256(mask_strip_items(out_h, out_w, LOC_ROWS), NO_CAP) : blocks256((int64_t)out_h * out_w, 256));
 }
 }  // namespace
 
@@ -686,30 +512,25 @@ extern "C" int64_t rsp_persam_locate_workspace_bytes(int32_t k, int32_t out_h, i
 extern "C" int rsp_persam_locate(const float* low_res, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h,
                                  int32_t crop_w, int32_t out_h, int32_t out_w, int32_t g, void* workspace,
                                  int64_t workspace_bytes, float* stats, int32_t* xy, float* attn_sim, rsp_stream_t stream) {
-  if (!low_res || !workspace || !stats || !xy || !attn_sim || k < 0 || k > 65535 || h <= 0 || w <= 0 || Hb <= 0 || Wb <= 0 ||
-      crop_h <= 0 || crop_w <= 0 || crop_h > Hb || crop_w > Wb || out_h <= 0 || out_w <= 0 || g <= 0 || g > 4096 ||
-      (int64_t)out_h * out_w > 0x7fffffffLL)
+  const MaskGeom geom{h, w, Hb, Wb, crop_h, crop_w, out_h, out_w};
+  if (!low_res || !workspace || !stats || !xy || !attn_sim || k < 0 || k > 65535 || !mask_geom_valid(geom) || g <= 0 || g > 4096)
     return RSP_EINVAL;
   if (workspace_bytes < rsp_persam_locate_workspace_bytes(k, out_h, out_w) || ((uintptr_t)workspace & 7)) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool ident = crop_h == out_h && crop_w == out_w;
-  const bool strip = ident && (out_w & 3) == 0;
-  LocateP q;
-  q.g.low = low_res; q.g.out = nullptr; q.g.prob = nullptr; q.g.k = k; q.g.h = h; q.g.w = w; q.g.Hb = Hb; q.g.Wb = Wb;
-  q.g.ch = crop_h; q.g.cw = crop_w; q.g.oh = out_h; q.g.ow = out_w; q.g.thr = 0.f; q.g.strict = 1;
-  q.keys = reinterpret_cast<unsigned long long*>(workspace);
-  q.part = reinterpret_cast<double*>(q.keys + (int64_t)k * 2);
-  q.gx = locate_gx(out_h, out_w, strip);
-  hipLaunchKernelGGL(persam_locate_init_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, q.keys, k);
-  if (strip)
-    hipLaunchKernelGGL(persam_locate_strip_kernel, dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
-  else if (ident)
-    hipLaunchKernelGGL((persam_locate_kernel<true>), dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
-  else
-    hipLaunchKernelGGL((persam_locate_kernel<false>), dim3((unsigned)q.gx, k), dim3(256), 0, st, q);
+  const MaskForm form = mask_form(geom);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);
+  const LocateP q{low_res, geom, k, keys, reinterpret_cast<double*>(keys + (int64_t)k * 2),
+                  locate_gx(out_h, out_w, form == MASK_STRIP)};
+  hipLaunchKernelGGL(persam_locate_init_kernel, dim3(blocks256(k * 2, NO_CAP)), dim3(256), 0, st, q.keys, k);
+  switch (form) {
+    case MASK_STRIP: hipLaunchKernelGGL(persam_locate_strip_kernel, dim3((unsigned)q.gx, k), dim3(MASK_BLOCK), 0, st, q); break;
+    case MASK_IDENT: hipLaunchKernelGGL((persam_locate_kernel<true>), dim3((unsigned)q.gx, k), dim3(MASK_BLOCK), 0, st, q); break;
+    case MASK_GENERIC: hipLaunchKernelGGL((persam_locate_kernel<false>), dim3((unsigned)q.gx, k), dim3(MASK_BLOCK), 0, st, q); break;
+  }
   hipLaunchKernelGGL(persam_locate_final_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, q, stats, xy);
-  hipLaunchKernelGGL(persam_attn_sim_kernel, dim3((unsigned)((g * g + 255) / 256), k), dim3(256), 0, st, q.g, g, stats, attn_sim);
+  const MaskPostP field{low_res, nullptr, nullptr, k, geom, 0.f, 1};      // persam_attn_sim_kernel: logits + geometry
+  hipLaunchKernelGGL(persam_attn_sim_kernel, dim3(blocks256(g * g, NO_CAP), k), dim3(256), 0, st, field, g, stats, attn_sim);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

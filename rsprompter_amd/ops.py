@@ -969,6 +969,26 @@ def hyper_mask(up, hyper):
     return out
 
 
+def _mask_logits(low_res, who, what="logits", f32=True):
+    """(k, h, w) of contiguous fp32 [k, h, w] logits; anything else is a ValueError that names the caller."""
+    if f32:
+        _chk_f32(low_res, "low_res")
+    if low_res.dim() != 3 or not low_res.is_contiguous():
+        raise ValueError(f"{who} expects contiguous [k, h, w] {what}")
+    return low_res.shape
+
+
+def _mask_geometry(img_shape, crop_hw, out_hw):
+    """Hb, Wb, crop_h, crop_w, out_h, out_w: the geometry arguments of the mask-field entry points."""
+    return tuple(int(v) for hw in (img_shape, crop_hw, out_hw) for v in hw[:2])
+
+
+def _score_thresholds(mask_threshold, stability_score_offset):
+    """t_hi, t_lo, t_mid rounded to fp32, as torch rounds the Python scalar when it compares an fp32 tensor with it."""
+    return tuple(float(torch.tensor(v, dtype=torch.float32)) for v in
+                 (mask_threshold + stability_score_offset, mask_threshold - stability_score_offset, mask_threshold))
+
+
 def mask_post(low_res, batch_input_shape, crop_hw, out_hw, thr, want_prob=False):
     """low_res [k, h, w] logits -> bool [k, out_h, out_w] (+ optional probabilities)."""
     lib = _lib.load()
@@ -976,23 +996,19 @@ def mask_post(low_res, batch_input_shape, crop_hw, out_hw, thr, want_prob=False)
     out = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.bool, device=low_res.device)
     prob = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.float32, device=low_res.device) if want_prob else None
     ws = torch.empty_like(low_res)
-    _lib.check(lib.rsp_mask_post(low_res.data_ptr(), ws.data_ptr(), k, h, w, batch_input_shape[0], batch_input_shape[1],
-                                 crop_hw[0], crop_hw[1], out_hw[0], out_hw[1], thr, out.data_ptr(), _ptr(prob),
-                                 _stream()), "rsp_mask_post")
+    _lib.check(lib.rsp_mask_post(low_res.data_ptr(), ws.data_ptr(), k, h, w, *_mask_geometry(batch_input_shape, crop_hw, out_hw),
+                                 thr, out.data_ptr(), _ptr(prob), _stream()), "rsp_mask_post")
     return (out, prob) if want_prob else out
 
 
 def mask_post_logits(low_res, img_shape, crop_hw, out_hw, thr=0.0, want_val=False):
     """SAMDet.predict (models.py:1185-1206): low_res [k, h, w] logits -> bool [k, out_h, out_w] = resized logits > thr."""
     lib = _lib.load()
-    k, h, w = low_res.shape
-    if not low_res.is_contiguous():
-        raise ValueError("mask_post_logits expects contiguous logits")
+    k, h, w = _mask_logits(low_res, "mask_post_logits", f32=False)      # the dtype is the caller's business here, as it always was
     out = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.bool, device=low_res.device)
     val = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.float32, device=low_res.device) if want_val else None
-    _lib.check(lib.rsp_mask_post_logits(low_res.data_ptr(), k, h, w, img_shape[0], img_shape[1], crop_hw[0], crop_hw[1],
-                                        out_hw[0], out_hw[1], thr, out.data_ptr(), _ptr(val), _stream()),
-               "rsp_mask_post_logits")
+    _lib.check(lib.rsp_mask_post_logits(low_res.data_ptr(), k, h, w, *_mask_geometry(img_shape, crop_hw, out_hw), thr,
+                                        out.data_ptr(), _ptr(val), _stream()), "rsp_mask_post_logits")
     return (out, val) if want_val else out
 
 
@@ -1094,23 +1110,16 @@ def sam_embed_prompts(points, labels, boxes, pad, gauss, point_embed, not_a_poin
 def mask_score_box(low_res, img_shape, crop_hw, out_hw, mask_threshold=0.0, stability_score_offset=1.0):
     """HF mask generation's scores of k candidate masks without the masks: low_res [k, h, w] logits, the geometry of
     mask_post_logits -> int32 [k, 7] = pixel counts above thr + offset, thr - offset and thr, then the box x0, y0, x1, y1
-    of the pixels above thr (inclusive maxima, zeros for an empty mask).  The thresholds are rounded to fp32 here, as
-    torch rounds the Python scalar when it compares an fp32 tensor with it."""
+    of the pixels above thr (inclusive maxima, zeros for an empty mask)."""
     lib = _lib.load()
-    _chk_f32(low_res, "low_res")
-    if low_res.dim() != 3 or not low_res.is_contiguous():
-        raise ValueError("mask_score_box expects contiguous [k, h, w] logits")
-    k, h, w = low_res.shape
+    k, h, w = _mask_logits(low_res, "mask_score_box")
     out = torch.empty((k, 7), dtype=torch.int32, device=low_res.device)
     if k == 0:
         return out
-    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))             # noqa: E731
-    t_hi, t_lo, t_mid = f32(mask_threshold + stability_score_offset), f32(mask_threshold - stability_score_offset), \
-        f32(mask_threshold)
+    thr = _score_thresholds(mask_threshold, stability_score_offset)
     _timed('mask_score_kernel', 0, 4.0 * low_res.numel(),
-           lambda: _lib.check(lib.rsp_mask_score_box(low_res.data_ptr(), k, h, w, img_shape[0], img_shape[1], crop_hw[0],
-                                                     crop_hw[1], out_hw[0], out_hw[1], t_hi, t_lo, t_mid, out.data_ptr(),
-                                                     _stream()), "rsp_mask_score_box"))
+           lambda: _lib.check(lib.rsp_mask_score_box(low_res.data_ptr(), k, h, w, *_mask_geometry(img_shape, crop_hw, out_hw),
+                                                     *thr, out.data_ptr(), _stream()), "rsp_mask_score_box"))
     return out
 
 
@@ -1160,25 +1169,21 @@ def persam_locate(low_res, img_shape, crop_hw, out_hw, g):
     of the maximum, x, y of the minimum -- lowest flat index among equal values --, pixel count; attn_sim fp32 [k, g * g] =
     sigmoid((D - mean) / std) with D the bilinear g x g resampling of the field; 0.5 where std == 0)."""
     lib = _lib.load()
-    _chk_f32(low_res, "low_res")
-    if low_res.dim() != 3 or not low_res.is_contiguous():
-        raise ValueError("persam_locate expects contiguous [k, h, w] fields")
-    k, h, w = low_res.shape
+    k, h, w = _mask_logits(low_res, "persam_locate", "fields")
+    geom = _mask_geometry(img_shape, crop_hw, out_hw)
     dev = low_res.device
     stats = torch.empty((k, 4), dtype=torch.float32, device=dev)
     xy = torch.empty((k, 5), dtype=torch.int32, device=dev)
     attn = torch.empty((k, g * g), dtype=torch.float32, device=dev)
     if k == 0:
         return stats, xy, attn
-    nws = int(lib.rsp_persam_locate_workspace_bytes(k, int(out_hw[0]), int(out_hw[1])))
+    nws = int(lib.rsp_persam_locate_workspace_bytes(k, geom[4], geom[5]))
     if nws < 0:
         raise ValueError(f"persam_locate: unsupported geometry {tuple(out_hw)} for {k} fields")
     ws = torch.empty((nws // 8,), dtype=torch.int64, device=dev)
     _timed('persam_locate_kernel', 0, 4.0 * low_res.numel(),
-           lambda: _lib.check(lib.rsp_persam_locate(low_res.data_ptr(), k, h, w, img_shape[0], img_shape[1], crop_hw[0],
-                                                    crop_hw[1], out_hw[0], out_hw[1], int(g), ws.data_ptr(), nws,
-                                                    stats.data_ptr(), xy.data_ptr(), attn.data_ptr(), _stream()),
-                              "rsp_persam_locate"))
+           lambda: _lib.check(lib.rsp_persam_locate(low_res.data_ptr(), k, h, w, *geom, int(g), ws.data_ptr(), nws, stats.data_ptr(),
+                                                    xy.data_ptr(), attn.data_ptr(), _stream()), "rsp_persam_locate"))
     return stats, xy, attn
 
 
@@ -1195,10 +1200,7 @@ def mask_score_box_crops(low_res, crop_idx, table, max_out_hw, mask_threshold=0.
     host and refuses an index outside the table; a caller that built the index itself passes False (no host read; the
     kernel clamps)."""
     lib = _lib.load()
-    _chk_f32(low_res, "low_res")
-    if low_res.dim() != 3 or not low_res.is_contiguous():
-        raise ValueError("mask_score_box_crops expects contiguous [K, h, w] logits")
-    K, h, w = low_res.shape
+    K, h, w = _mask_logits(low_res, "mask_score_box_crops")
     dev = low_res.device
     if crop_idx.dtype != torch.int32 or crop_idx.dim() != 1 or crop_idx.shape[0] != K or crop_idx.device != dev:
         raise ValueError("crop_idx: int32 [K] on the device of low_res")
@@ -1214,13 +1216,11 @@ def mask_score_box_crops(low_res, crop_idx, table, max_out_hw, mask_threshold=0.
         if lo < 0 or hi >= n_crops:
             raise ValueError(f"crop_idx holds {lo} .. {hi}, the table has {n_crops} rows")
     crop_idx, table = crop_idx.contiguous(), table.contiguous()
-    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))             # noqa: E731
-    t_hi, t_lo, t_mid = f32(mask_threshold + stability_score_offset), f32(mask_threshold - stability_score_offset), \
-        f32(mask_threshold)
+    thr = _score_thresholds(mask_threshold, stability_score_offset)
     _timed('mask_score_crops_kernel', 0, 4.0 * low_res.numel(),
            lambda: _lib.check(lib.rsp_mask_score_box_crops(low_res.data_ptr(), K, h, w, crop_idx.data_ptr(), table.data_ptr(),
-                                                           n_crops, int(max_out_hw[0]), int(max_out_hw[1]), t_hi, t_lo, t_mid,
-                                                           out.data_ptr(), _stream()), "rsp_mask_score_box_crops"))
+                                                           n_crops, int(max_out_hw[0]), int(max_out_hw[1]), *thr, out.data_ptr(),
+                                                           _stream()), "rsp_mask_score_box_crops"))
     return out
 
 
@@ -1736,7 +1736,7 @@ def query_mask_post(low_res, qidx, cls_score, batch_input_shape, crop_hw, out_hw
     ws = torch.empty((max(k, 1) * 32,), dtype=torch.uint8, device=dev)
     _timed('query_mask_kernel', 0, 1.0 * masks.numel(),
            lambda: _lib.check(lib.rsp_query_mask_post(low_res.data_ptr(), qidx.data_ptr(), cls_score.data_ptr(), k, h, w,
-                                                      batch_input_shape[0], batch_input_shape[1], crop_hw[0], crop_hw[1],
-                                                      out_hw[0], out_hw[1], ws.data_ptr(), masks.data_ptr(), _ptr(logits),
-                                                      det.data_ptr(), boxes.data_ptr(), _stream()), "rsp_query_mask_post"))
+                                                      *_mask_geometry(batch_input_shape, crop_hw, out_hw), ws.data_ptr(),
+                                                      masks.data_ptr(), _ptr(logits), det.data_ptr(), boxes.data_ptr(),
+                                                      _stream()), "rsp_query_mask_post"))
     return (masks, det, boxes, logits) if want_logits else (masks, det, boxes)

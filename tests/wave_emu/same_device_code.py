@@ -29,6 +29,12 @@ def device_asm(src, out):
     return [ln.rstrip() for ln in t.splitlines() if ln.strip()]
 
 
+def headers_at(rev):
+    """the headers a source of that revision may include (a header added since does not exist there)"""
+    names = subprocess.check_output(['git', '-C', ROOT, 'ls-tree', '--name-only', rev, 'rsprompter_amd/csrc/']).decode().split()
+    return ['include/rsp_hip.h'] + [n for n in names if n.endswith('.h')]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rev', default='HEAD')
@@ -39,8 +45,7 @@ def main():
         csrc = os.path.join(tmp, 'rsprompter_amd', 'csrc')
         os.makedirs(csrc)
         os.makedirs(os.path.join(tmp, 'include'))
-        for rel in ['include/rsp_hip.h'] + ['rsprompter_amd/csrc/' + f for f in os.listdir(os.path.join(ROOT, 'rsprompter_amd', 'csrc'))
-                                            if f.endswith('.h')]:
+        for rel in headers_at(a.rev):
             open(os.path.join(tmp, rel), 'wb').write(subprocess.check_output(['git', '-C', ROOT, 'show', f'{a.rev}:{rel}']))
         for name in a.sources:
             rel = 'rsprompter_amd/csrc/' + name

@@ -3,7 +3,8 @@ revision the same in the working tree, when the file has GAINED kernels (so that
 
     python tools/same_kernel_code.py [--rev HEAD] samattn.hip samdec.hip
 
-Splits both assemblies into functions (label ... .Lfunc_end) and compares the instruction lines of every function of the
+For every kernel that differs it prints the instruction count and the register / scratch / LDS fields of the kernel descriptor
+on both sides.  Splits both assemblies into functions (label ... .Lfunc_end) and compares the instruction lines of every function of the
 revision with the function of the same symbol in the working tree.  Labels of basic blocks and function-end markers are
 numbered per file, so they are renumbered per function in order of first appearance before comparing."""
 import argparse
@@ -15,7 +16,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tests', 'wave_emu'))
-from same_device_code import device_asm  # noqa: E402
+from same_device_code import device_asm, headers_at  # noqa: E402
 
 
 def functions(lines):
@@ -39,6 +40,29 @@ def functions(lines):
     return out
 
 
+RES = ('next_free_vgpr', 'next_free_sgpr', 'private_segment_fixed_size', 'group_segment_fixed_size')
+
+
+def resources(lines):
+    """{symbol: the RES fields of its .amdhsa_kernel descriptor}"""
+    out, name = {}, None
+    for ln in lines:
+        w = ln.split()
+        if w[0] == '.amdhsa_kernel':
+            name = w[1]
+            out[name] = {}
+        elif name and w[0].startswith('.amdhsa_') and w[0][8:] in RES:
+            out[name][w[0][8:]] = w[1]
+    return out
+
+
+def row(fn, res, k):
+    if k not in fn:
+        return 'absent'
+    n = sum(1 for b in fn[k] if not b.endswith(':') and not b.lstrip().startswith('.'))
+    return f'{n} instructions, ' + ', '.join(f'{r} {res[k].get(r)}' for r in RES)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rev', default='HEAD')
@@ -49,22 +73,26 @@ def main():
         csrc = os.path.join(tmp, 'rsprompter_amd', 'csrc')
         os.makedirs(csrc)
         os.makedirs(os.path.join(tmp, 'include'))
-        for rel in ['include/rsp_hip.h'] + ['rsprompter_amd/csrc/' + f for f in os.listdir(os.path.join(ROOT, 'rsprompter_amd', 'csrc'))
-                                            if f.endswith('.h')]:
+        for rel in headers_at(a.rev):
             open(os.path.join(tmp, rel), 'wb').write(subprocess.check_output(['git', '-C', ROOT, 'show', f'{a.rev}:{rel}']))
         for name in a.sources:
             rel = 'rsprompter_amd/csrc/' + name
             open(os.path.join(tmp, rel), 'wb').write(subprocess.check_output(['git', '-C', ROOT, 'show', f'{a.rev}:{rel}']))
-            old = functions(device_asm(os.path.join(tmp, rel), os.path.join(tmp, name + '.old.s')))
-            new = functions(device_asm(os.path.join(ROOT, rel), os.path.join(tmp, name + '.new.s')))
+            old_asm = device_asm(os.path.join(tmp, rel), os.path.join(tmp, name + '.old.s'))
+            new_asm = device_asm(os.path.join(ROOT, rel), os.path.join(tmp, name + '.new.s'))
+            old, new = functions(old_asm), functions(new_asm)
+            old_res, new_res = resources(old_asm), resources(new_asm)
             bad = [k for k in old if old[k] != new.get(k)]
             added = [k for k in new if k not in old]
             print(f'{name}: {len(old)} kernels at {a.rev}, {len(old) - len(bad)} instruction-identical in the working tree, '
                   f'{len(bad)} different or missing, {len(added)} new')
             for k in bad:
                 print('  DIFFERENT:', k)
+                print(f'    {a.rev}: {row(old, old_res, k)}')
+                print(f'    tree: {row(new, new_res, k)}')
             for k in added:
                 print('  new:', k)
+                print(f'    tree: {row(new, new_res, k)}')
             rc |= 1 if bad or not old else 0
     return rc
 
