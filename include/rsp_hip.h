@@ -705,6 +705,26 @@ int rsp_persam_locate(const float* low_res, int32_t k, int32_t h, int32_t w, int
                       int32_t crop_w, int32_t out_h, int32_t out_w, int32_t g, void* workspace, int64_t workspace_bytes,
                       float* stats, int32_t* xy, float* attn_sim, rsp_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Small-region cleanup of masks (segment-anything utils/amg.py `remove_small_regions`, used by                            */
+/* automatic_mask_generator.py `postprocess_small_regions`; there cv2.connectedComponentsWithStats on the host)           */
+/* ------------------------------------------------------------------------ */
+/* masks uint8 [k, H, W] (non-zero = set: what rsp_mask_post_logits writes) -> out uint8 [k, H, W] of 0 / 1, a buffer     */
+/* distinct from `masks`.  mode 1 ("holes"): the 8-connected components of the ZEROS with fewer than min_area pixels are   */
+/* set (the background is a component like any other); mode 2 ("islands"): the 8-connected components of the ONES with     */
+/* fewer than min_area pixels are cleared -- when every component is that small the largest stays, among equals the one   */
+/* that holds the lowest pixel index y * W + x (segment-anything leaves that to OpenCV's label order); mode 3: holes, then */
+/* islands of the filled mask.  A mask without a small component is copied (as 0 / 1).  info int32 [k, 8] = changed by    */
+/* the holes pass, changed by the islands pass (0 / 1: a small component existed), x0, y0, x1, y1 of the result (inclusive */
+/* maxima, 0 0 0 0 when empty), its population count, status (non-zero: a find / union loop reached its step cap -- the    */
+/* result is then invalid; a correct run never does).  A component's label is the minimum pixel index of its members and   */
+/* every size, box and count an integer reduction: the result does not depend on scheduling.  workspace:                  */
+/* rsp_mask_regions_workspace_bytes(k, H, W) bytes, 16-byte aligned (-1 for arguments the call would refuse).  RSP_EINVAL: */
+/* mode outside 1..3, min_area < 0, H * W >= 2^31, a non-positive size; k = 0 does nothing.                                */
+int64_t rsp_mask_regions_workspace_bytes(int32_t k, int32_t H, int32_t W);
+int rsp_mask_remove_small_regions(const uint8_t* masks, int32_t k, int32_t H, int32_t W, int32_t min_area, int32_t mode,
+                                  void* workspace, uint8_t* out, int32_t* info, rsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,9 @@ PROTOTYPES = {
     "rsp_persam_locate_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "rsp_persam_locate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                   c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_mask_regions_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "rsp_mask_remove_small_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
 }
 
 _lib = None

@@ -205,3 +205,16 @@ class DetInferencer:
 
 from .large_image import inference_large_image  # noqa: E402,F401  (sliced inference on large scenes)
 from .sam_prompts import PerSam, SamMaskGenerator, SamSession, generate_masks, inference_prompts  # noqa: E402,F401  (promptable SAM)
+
+
+def remove_small_regions(masks, min_area, mode='both'):
+    """segment-anything's `remove_small_regions` for masks that come from elsewhere (`SamSession.predict`,
+    `PerSam(output='dense')`, a detector's results): masks bool / uint8 [k, H, W] or [H, W] on the device; mode 'holes'
+    (8-connected components of the background with fewer than min_area pixels are filled), 'islands' (components of the mask
+    that small are removed; if all are, the largest stays) or 'both' (holes first).  Returns (masks bool of the input's
+    shape, changed bool [k] or a bool).  One host read (the labelling's status)."""
+    single = masks.dim() == 2
+    out, info = ops.remove_small_regions(masks[None] if single else masks, min_area, mode)
+    ops.check_region_status(info[:, 7].cpu().tolist())
+    changed = (info[:, 0] | info[:, 1]) != 0
+    return (out[0], bool(changed[0])) if single else (out, changed)

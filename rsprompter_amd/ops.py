@@ -1545,6 +1545,61 @@ def paste_tiles(masks, offsets, scene_hw):
     return out
 
 
+MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
+MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
+# the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call
+# stays under this (64 masks of 1024 x 1024 are 512 MiB); a single mask larger than that gets its workspace all the same.
+MASK_REGIONS_WORKSPACE_LIMIT_BYTES = 1 << 30
+
+
+def remove_small_regions(masks, min_area, mode='both'):
+    """segment-anything `remove_small_regions` for k masks on the device (rsp_mask_remove_small_regions): masks bool / uint8
+    [k, H, W] (non-zero = set), mode 'holes' (8-connected components of the zeros smaller than min_area are set), 'islands'
+    (components of the ones smaller than min_area are cleared; if all are, the largest stays -- among equals the one with
+    the lowest first pixel) or 'both' (holes, then islands of the filled mask).  Returns (out bool [k, H, W], info int32
+    [k, 8] = changed by holes, changed by islands, x0, y0, x1, y1 (inclusive maxima; zeros when empty), population count,
+    status).  No host read: whoever reads `info` checks that status is 0 (`check_region_status`)."""
+    lib = _lib.load()
+    if mode not in MASK_REGION_MODES:
+        raise ValueError(f"remove_small_regions: mode must be one of {sorted(MASK_REGION_MODES)}, got {mode!r}")
+    if not isinstance(masks, torch.Tensor) or masks.dtype not in (torch.bool, torch.uint8) or masks.dim() != 3:
+        raise ValueError("remove_small_regions: masks must be a bool or uint8 [k, H, W] tensor")
+    if not _is_device(masks):
+        raise ValueError(f"remove_small_regions: masks must be on the HIP device, got {masks.device}")
+    if int(min_area) != min_area or int(min_area) < 0 or int(min_area) >= 2 ** 31:
+        raise ValueError(f"remove_small_regions: min_area must be an integer in [0, 2^31), got {min_area!r}")
+    k, H, W = (int(s) for s in masks.shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"remove_small_regions: empty masks ({H} x {W})")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"remove_small_regions: a {H} x {W} mask has {H * W} pixels; labels are 32-bit (< 2^31 pixels)")
+    if not masks.is_contiguous():
+        raise ValueError("remove_small_regions: masks must be contiguous")
+    dev = masks.device
+    out = torch.empty((k, H, W), dtype=torch.bool, device=dev)
+    info = torch.empty((k, 8), dtype=torch.int32, device=dev)
+    if k == 0:
+        return out, info
+    per = int(lib.rsp_mask_regions_workspace_bytes(1, H, W))
+    step = max(1, min(k, MASK_REGIONS_WORKSPACE_LIMIT_BYTES // per))
+    ws = torch.empty((int(lib.rsp_mask_regions_workspace_bytes(step, H, W)) // 8,), dtype=torch.int64, device=dev)
+    for i in range(0, k, step):
+        kc = min(step, k - i)
+        _lib.check(lib.rsp_mask_remove_small_regions(masks[i:i + kc].data_ptr(), kc, H, W, int(min_area),
+                                                     MASK_REGION_MODES[mode], ws.data_ptr(), out[i:i + kc].data_ptr(),
+                                                     info[i:i + kc].data_ptr(), _stream()), "rsp_mask_remove_small_regions")
+    return out, info
+
+
+def check_region_status(status):
+    """`status` = column 7 of remove_small_regions' info, ON THE HOST (list / array / tensor): non-zero means that a find /
+    union loop of the labelling reached its step cap and the result is invalid"""
+    bad = [i for i, s in enumerate(list(status)) if int(s) != 0]
+    if bad:
+        raise RuntimeError(f"rsp_mask_remove_small_regions: the labelling of mask(s) {bad[:8]} reached its iteration cap "
+                           "(status != 0); the result is invalid")
+
+
 def nms_flat(boxes, scores, labels, iou_thr):
     """mmcv.ops.batched_nms(boxes [n, 4], scores [n], labels [n], dict(type='nms', iou_threshold=iou_thr)) on flat device
     tensors through rsp_batched_nms with B = 1: returns keep (int64 [m], indices into the inputs in descending score

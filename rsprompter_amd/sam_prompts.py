@@ -178,15 +178,43 @@ def _rle_dicts(masks):
     return [dict(size=[H, W], counts=counts[i, :n[i]].tolist()) for i in range(k)]
 
 
+def _check_region_area(min_mask_region_area):
+    if int(min_mask_region_area) != min_mask_region_area or int(min_mask_region_area) < 0:
+        raise ValueError(f'min_mask_region_area must be a non-negative integer, got {min_mask_region_area!r}')
+    return int(min_mask_region_area)
+
+
+def _region_nms(info, offsets, nms_thresh):
+    """segment-anything `postprocess_small_regions` after the masks were cleaned: info int32 [m, 8] of
+    ops.remove_small_regions (mode 'both') for the m survivors of the first NMS in their order, offsets int32 [m, 2] = (x0, y0)
+    of every survivor's crop in the image.  A second NMS over the boxes of the CLEANED masks with score 1 for an unchanged and
+    0 for a changed mask (equal scores: the lower index wins, rsp_batched_nms' rule), so that a mask which cleaning made a
+    duplicate of an untouched one gives way.  Returns (sel: the kept positions ASCENDING as a host list -- a stable filter of
+    the previous order, where segment-anything reorders by the 0 / 1 score --, boxes fp32 [m, 4] of the cleaned masks in the
+    image frame, changed bool [m]).  One host read: the NMS's count, the kept list and the labelling's status together."""
+    m = int(info.shape[0])
+    dev = info.device
+    changed = (info[:, 0] | info[:, 1]) != 0
+    boxes = (info[:, 2:6] + torch.cat([offsets, offsets], 1)).to(torch.float32)
+    r = ops.batched_nms((boxes.view(1, m, 4).contiguous(), (~changed).to(torch.float32).view(1, m),
+                         torch.zeros((1, m), dtype=torch.int32, device=dev), torch.arange(m, dtype=torch.int32, device=dev).view(1, m),
+                         torch.full((1,), m, dtype=torch.int32, device=dev)), 1, m, float(nms_thresh), m)
+    packed = torch.cat([r['count'].to(torch.int32).view(1), r['keep'][0].to(torch.int32), info[:, 7]]).cpu().tolist()
+    ops.check_region_status(packed[1 + m:])
+    return sorted(packed[1:1 + packed[0]]), boxes, changed
+
+
 @torch.no_grad()
 def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stability_score_thresh=0.95,
                    stability_score_offset=1.0, mask_threshold=0.0, crops_nms_thresh=0.7, crop_n_layers=0, output='rle',
-                   mask_batch=64, session=None, _stages=None):
+                   mask_batch=64, session=None, _stages=None, min_mask_region_area=0):
     """HF's mask generation (`MaskGenerationPipeline` over `SamImageProcessor.generate_crop_boxes` / `filter_masks` /
     `post_process_for_mask_generation`) for the whole image as one crop: a points_per_side^2 grid of single-point prompts,
     three masks each, filtered by predicted IoU and stability score, NMS on the mask boxes.  Returns `InstanceData` in NMS
     order: bboxes fp32 [k, 4] (x0, y0, x1, y1, inclusive maxima as HF's `_batched_mask_to_box`), scores fp32 [k] (predicted
     IoU), masks = list of uncompressed RLE dicts (output='rle') or bool [k, H, W] (output='dense').
+    min_mask_region_area > 0: segment-anything's `postprocess_small_regions` on the NMS's survivors, as in `SamMaskGenerator`
+    (holes and islands smaller than that are removed, a second NMS drops what became a duplicate; `region_changed` bool [k]).
     session: an existing `SamSession` of the image (then `model` / `image` are not read); mask_batch: full-resolution masks
     built per kernel call; _stages: a dict that receives the stage tensors (candidate logits, IoU, scores, kept indices,
     boxes) -- the stage-wise parity tests read them."""
@@ -195,6 +223,7 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
                                   'the image is processed as one crop; use SamMaskGenerator(model, crop_n_layers=...)')
     if output not in ('rle', 'dense'):
         raise ValueError("output must be 'rle' or 'dense'")
+    area = _check_region_area(min_mask_region_area)
     s = session if session is not None else SamSession(model, image)
     H, W = s.original_size
     S = s.sam.image_size
@@ -216,9 +245,26 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     sel = idx[order]
     res = InstanceData()
     res.bboxes, res.scores = boxes[order], scores[order]
+    if area and int(sel.shape[0]):
+        # first pass over the survivors: only the 8 integers per cleaned mask are kept; the kept ones are built again below
+        info = torch.cat([ops.remove_small_regions(s.full_res(low[sel[i:i + mask_batch]], mask_threshold), area)[1]
+                          for i in range(0, int(sel.shape[0]), mask_batch)], 0)
+        kept, boxes2, changed = _region_nms(info, torch.zeros((int(sel.shape[0]), 2), dtype=torch.int32, device=low.device),
+                                            crops_nms_thresh)
+        kept = torch.tensor(kept, dtype=torch.int64).to(low.device)
+        sel = sel[kept]
+        res.region_changed = changed[kept]
+        res.bboxes = torch.where(res.region_changed[:, None], boxes2[kept], res.bboxes[kept])
+        res.scores = res.scores[kept]
+    elif area:
+        res.region_changed = torch.zeros((0,), dtype=torch.bool, device=low.device)
+    if _stages is not None:
+        _stages['final'] = sel
     dense, rles = [], []
     for i in range(0, int(sel.shape[0]), mask_batch):
         m = s.full_res(low[sel[i:i + mask_batch]], mask_threshold)
+        if area:
+            m = ops.remove_small_regions(m, area)[0]
         if output == 'dense':
             dense.append(m)
         else:
@@ -445,7 +491,14 @@ class SamMaskGenerator:
     `_is_box_near_crop_edge`, `_pad_masks`, `_mask_to_rle`, `_post_process_for_mask_generation`) composed per crop -- not
     HF's `MaskGenerationPipeline`, which filters only the first crop, leaves boxes in crop coordinates and scales a crop's
     grid with the whole image's resize factor.  Not implemented: segment-anything's per-crop box NMS and its
-    preference for smaller crops, `min_mask_region_area`.
+    preference for smaller crops.
+
+    `min_mask_region_area` > 0 is segment-anything's `postprocess_small_regions` on the survivors of that NMS: in every mask
+    first the holes, then the islands with fewer pixels are removed (`rsp_mask_remove_small_regions`, 8-connected, on the
+    crop-sized mask), the boxes of the cleaned masks go through a second NMS in which an unchanged mask beats a changed one,
+    and the survivors keep their order (segment-anything moves the unchanged ones to the front).  A kept mask that was
+    changed gets its cleaned mask and that mask's box; `scores` stay the predicted IoUs; `region_changed` bool [k] tells.
+    With 0 (the default) none of this runs.
 
     `sam`: whatever `SamSession` accepts.  `crop_batch`: crops per encoder / decoder / scoring call (all of one layer, so
     that they share the number of prompts); None picks `DEFAULT_CROP_BATCH` by the encoder's width, capped at
@@ -456,11 +509,12 @@ class SamMaskGenerator:
 
     def __init__(self, sam, points_per_side=32, pred_iou_thresh=0.88, stability_score_thresh=0.95, stability_score_offset=1.0,
                  mask_threshold=0.0, crops_nms_thresh=0.7, crop_n_layers=1, crop_overlap_ratio=512 / 1500,
-                 crop_n_points_downscale_factor=1, crop_batch=None, output='rle', mask_batch=64):
+                 crop_n_points_downscale_factor=1, crop_batch=None, output='rle', mask_batch=64, min_mask_region_area=0):
         if output not in ('rle', 'dense'):
             raise ValueError("output must be 'rle' or 'dense'")
         if int(crop_n_layers) < 0:
             raise ValueError('crop_n_layers must be >= 0')
+        self.min_mask_region_area = _check_region_area(min_mask_region_area)
         self.sam = _sam_of(sam)
         self.crop_n_layers, self.crop_overlap_ratio = int(crop_n_layers), float(crop_overlap_ratio)
         self.grids = []
@@ -587,19 +641,37 @@ class SamMaskGenerator:
             else:
                 order, crop_h = torch.zeros((0,), dtype=torch.int64, device=dev), []
         res.bboxes, res.scores, res.crop_index = boxes[order], scores[order], crop[order].to(torch.int64)
+        if self.min_mask_region_area:
+            with phase('small regions'):
+                if crop_h:
+                    # first pass over the crop groups: the masks are cleaned and only their 8 integers kept; the second NMS
+                    # decides who stays, and _masks below builds (and cleans) those again for their run lengths
+                    info = self._masks(low, order, crop_h, boxes_c, geo, (H, W), dev, info_only=True)
+                    kept, boxes2, changed = _region_nms(info, geo_t[crop[order].to(torch.int64), 6:8], self.crops_nms_thresh)
+                    crop_h = [crop_h[i] for i in kept]
+                    kept = torch.tensor(kept, dtype=torch.int64).to(dev)
+                    order = order[kept]
+                    res.region_changed = changed[kept]
+                    res.bboxes = torch.where(res.region_changed[:, None], boxes2[kept], res.bboxes[kept])
+                    res.scores, res.crop_index = res.scores[kept], res.crop_index[kept]
+                else:
+                    res.region_changed = torch.zeros((0,), dtype=torch.bool, device=dev)
         if _stages is not None:
             _stages['final'] = cand[order]
         with phase('masks + run lengths'):
             res.masks = self._masks(low, order, crop_h, boxes_c, geo, (H, W), dev)
         return res
 
-    def _masks(self, low, order, crop_h, boxes_c, geo, hw, dev):
-        """full-resolution masks of the NMS survivors, grouped by crop: rsp_mask_post_logits on the crop's geometry, then the
-        run lengths of the crop-sized mask shifted into the image in the run domain (rsp_mask_rle -> rsp_rle_shift), or the
-        dense paste (rsp_paste_tiles); put back in NMS order"""
+    def _masks(self, low, order, crop_h, boxes_c, geo, hw, dev, info_only=False):
+        """full-resolution masks of the NMS survivors, grouped by crop: rsp_mask_post_logits on the crop's geometry (cleaned by
+        rsp_mask_remove_small_regions with min_mask_region_area > 0), then the run lengths of the crop-sized mask shifted into
+        the image in the run domain (rsp_mask_rle -> rsp_rle_shift), or the dense paste (rsp_paste_tiles); put back in NMS
+        order.  info_only: nothing but the cleaning's info int32 [m, 8] per survivor (crop-local boxes), no host read"""
         H, W = hw
         m = len(crop_h)
-        dense = torch.zeros((m, H, W), dtype=torch.bool, device=dev) if self.output == 'dense' else None
+        area = self.min_mask_region_area
+        info = torch.zeros((m, 8), dtype=torch.int32, device=dev) if info_only else None
+        dense = torch.zeros((m, H, W), dtype=torch.bool, device=dev) if self.output == 'dense' and not info_only else None
         rles = [None] * m
         pending = []                                                   # (positions, counts, n) per launched group
         for c in sorted(set(crop_h)):
@@ -610,6 +682,11 @@ class SamMaskGenerator:
                 pos = pos_all[b0:b0 + self.mask_batch]
                 pos_t = torch.tensor(pos, dtype=torch.int64).to(dev)
                 mk = ops.mask_post_logits(low[order[pos_t]].contiguous(), (S0, S1), (nh, nw), (ch, cw), self.mask_threshold)
+                if area:
+                    mk, inf = ops.remove_small_regions(mk, area)
+                    if info_only:
+                        info[pos_t] = inf
+                        continue
                 if dense is not None:
                     if whole:
                         dense[pos_t] = mk
@@ -621,6 +698,8 @@ class SamMaskGenerator:
                         rles[i] = d
                 else:
                     pending.append((pos, mk, (x0, y0), (ch, cw)))
+        if info_only:
+            return info
         if dense is not None:
             return dense
         for pos, mk, (x0, y0), chw in pending:

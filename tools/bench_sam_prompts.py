@@ -29,7 +29,14 @@ The scoring kernel's achieved input bytes/s and pixel evaluations/s are derived 
       existed before the similarity / locate kernels and the batched flow: per image a SamSession, the similarity as torch
       expressions, mask_post_logits(want_val=True) for the field, torch argmax / argmin / mean / std / F.interpolate, and the
       three decoder passes with host-side point, best-of-three and box extraction in between; then rsp_persam_locate and
-      rsp_mask_score_box alone on the same fields (pixel rates).  --persam-once: one segment() per batch size (kernel trace)."""
+      rsp_mask_score_box alone on the same fields (pixel rates).  --persam-once: one segment() per batch size (kernel trace).
+
+  python tools/bench_sam_prompts.py --regions [--arch huge] [--reps 20] [--out profiles/mask_regions/regions.json]
+
+  (f) `min_mask_region_area`: ops.remove_small_regions on 64 masks of 1024 x 1024 (thresholded smooth noise plus speckle) per
+      mode, after the encoder has run (warm clocks); the bytes the design moves per pixel against norm.hip's streaming rate;
+      the same cleaning the host way (device -> host, scipy.ndimage.label per mask, host -> device); SamMaskGenerator.generate
+      (one crop layer) with min_mask_region_area 0 and 100, alternating.  --regions-once: one call per mode (kernel trace)."""
 import argparse
 import json
 import os
@@ -252,6 +259,112 @@ def persam(model, a):
     return out
 
 
+# bytes per pixel and pass of rsp_mask_remove_small_regions as designed (regions.hip): label 1 (mask) + 4 + 4 (parent, cnt written);
+# flatten 4 (cnt read); reduce 4 (parent read); write 1 + 4 + 1 (mask, parent, result) -- the reads behind a tile-local root
+# (its parent, the root's size) hit a few lines per tile and are not counted, nor is the seam kernel (1 / 32 of the pixels)
+REGION_BYTES_PER_PIXEL_PASS = 23
+NORM_STREAM_TB_S = 4.8            # what norm.hip's plane-producing LayerNorm reaches here
+
+
+def regions_fixture(k, hw, dev, seed=0):
+    """thresholded smooth noise plus speckle: bool [k, H, W] on the device"""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.nn.functional.interpolate(torch.randn(k, 1, 24, 24, generator=g), size=hw, mode='bicubic', align_corners=False)[:, 0]
+    m = z > 0
+    flip = torch.rand(k, hw[0], hw[1], generator=g) < 0.002                            # pinholes and detached specks
+    return (m ^ flip).to(dev).contiguous()
+
+
+def regions(model, img, a):
+    from rsprompter_amd import ops
+    from rsprompter_amd.sam_prompts import SamMaskGenerator, SamSession, point_grid
+    dev = img.device
+    k, hw, area = 64, (1024, 1024), 100
+    masks = regions_fixture(k, hw, dev)
+    out = dict(masks=k, size=list(hw), min_area=area, modes={})
+    if a.regions_once:
+        for mode in ('holes', 'islands', 'both'):
+            ops.remove_small_regions(masks, area, mode)
+        torch.cuda.synchronize()
+        return out
+    for _ in range(3):                                                                 # the encoder leg: clocks are warm after it
+        SamSession(model, img)
+    npx = k * hw[0] * hw[1]
+    for mode, passes in (('holes', 1), ('islands', 1), ('both', 2)):
+        t = timed(lambda: ops.remove_small_regions(masks, area, mode), max(a.reps, 20))
+        floor_ms = npx * REGION_BYTES_PER_PIXEL_PASS * passes / (NORM_STREAM_TB_S * 1e12) * 1e3
+        _, info = ops.remove_small_regions(masks, area, mode)
+        info = info.cpu()
+        t.update(bytes_floor_ms=round(floor_ms, 3), times_the_floor=round(t['median_ms'] / floor_ms, 2),
+                 Gpixel_per_s=round(npx / (t['median_ms'] * 1e-3) / 1e9, 2), masks_changed=int((info[:, :2].sum(1) > 0).sum()),
+                 status_nonzero=int((info[:, 7] != 0).sum()))
+        out['modes'][mode] = t
+    out['bytes_floor'] = dict(bytes_per_pixel_per_pass=REGION_BYTES_PER_PIXEL_PASS, stream_TB_per_s=NORM_STREAM_TB_S,
+                              formula='masks * H * W * bytes_per_pixel_per_pass * passes / stream rate; passes = 2 for both')
+    # the host route this replaces: masks to the host, scipy per mask, results back
+    from scipy import ndimage
+    eight = np.ones((3, 3), dtype=np.int32)
+
+    def host_clean(m, holes):
+        w = ~m if holes else m
+        lab, n = ndimage.label(w, structure=eight)
+        if n == 0:
+            return m
+        sizes = np.bincount(lab.ravel(), minlength=n + 1)[1:]
+        small = sizes < area
+        if not small.any():
+            return m
+        if holes:
+            return m | np.isin(lab, np.nonzero(small)[0] + 1)
+        keep = np.nonzero(~small)[0] + 1
+        return np.isin(lab, keep if len(keep) else [int(np.argmax(sizes)) + 1])
+
+    def host_route():
+        h = masks.cpu().numpy()
+        res = np.stack([host_clean(host_clean(m, True), False) for m in h])
+        return torch.from_numpy(res).to(dev)
+    import time
+    ts = []
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        want = host_route()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    out['host_route_both'] = dict(ms=[round(t, 1) for t in ts], equal_to_the_device_result=bool(torch.equal(want, ops.remove_small_regions(masks, area)[0])),
+                                  note='device -> host, scipy.ndimage.label twice per mask (one thread), host -> device')
+    # the generator with and without the step, alternating in this process
+    H, W = int(img.shape[0]), int(img.shape[1])
+    S, off, n = model.image_size, 0.25, 32
+    s0 = SamSession(model, img)
+    low, iou = s0._low_res((point_grid(n) * np.array([[W, H]]))[:, None, :], None, None, None, True)
+    sc = ops.mask_score_box(low.reshape(low.shape[0] * 3, 256, 256), (S, S), s0.input_size, (H, W), 0.0, off)
+    stab = sc[:, 0] / sc[:, 1]
+    kw = dict(points_per_side=n, pred_iou_thresh=float(iou.median()), stability_score_thresh=float(stab[~stab.isnan()].median()),
+              stability_score_offset=off, crop_n_layers=1, crop_batch=a.crop_batch)
+    del s0, low, iou, sc
+    gens = {0: SamMaskGenerator(model, **kw), area: SamMaskGenerator(model, min_mask_region_area=area, **kw)}
+    res = {ar: g.generate(img) for ar, g in gens.items()}
+    ts = {ar: [] for ar in gens}
+    ph, phs = _Phases(), []
+    for r in range(max(3, a.reps // 4)):
+        for ar, g in gens.items():
+            g._phase = ph
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.generate(img)
+            e1.record()
+            e1.synchronize()
+            ts[ar].append(e0.elapsed_time(e1))
+            p = ph.take()
+            if ar:
+                phs.append(p)
+    out['generate_layers1'] = {f'min_mask_region_area_{ar}': dict(_spread(t), instances=len(res[ar].masks)) for ar, t in ts.items()}
+    out['generate_layers1']['changed'] = int(res[area].region_changed.sum())
+    out['generate_layers1'][f'phases_ms_area_{area}'] = {k_: round(statistics.median([p[k_] for p in phs]), 3) for k_ in phs[0]}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='huge')
@@ -261,6 +374,8 @@ def main():
     ap.add_argument('--multicrop-once', action='store_true', help='one generate() per configuration (for a kernel trace)')
     ap.add_argument('--persam', action='store_true', help='the PerSAM phase (e) only')
     ap.add_argument('--persam-once', action='store_true', help='one segment() per batch size (for a kernel trace)')
+    ap.add_argument('--regions', action='store_true', help='the min_mask_region_area phase (f) only')
+    ap.add_argument('--regions-once', action='store_true', help='one remove_small_regions call per mode (for a kernel trace)')
     ap.add_argument('--crop-batch', type=int, default=None)
     ap.add_argument('--crop-batches', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8])
     a = ap.parse_args()
@@ -276,8 +391,10 @@ def main():
     model = model.to(dev).eval()
     img = synth_images(1)[0].permute(1, 2, 0).contiguous().to(dev)                 # [1024, 1024, 3] uint8
     out = dict(arch=a.arch, device=torch.cuda.get_device_name(0), image=[1024, 1024])
-    if a.multicrop or a.multicrop_once or a.persam or a.persam_once:
-        if a.persam or a.persam_once:
+    if a.multicrop or a.multicrop_once or a.persam or a.persam_once or a.regions or a.regions_once:
+        if a.regions or a.regions_once:
+            out['regions'] = regions(model, img, a)
+        elif a.persam or a.persam_once:
             out['persam'] = persam(model, a)
         else:
             out['multicrop'] = multicrop(model, img, a)
