@@ -45,6 +45,12 @@ __host__ __device__ inline int64_t mask_strip_items(int oh, int ow, int rows) {
   return (int64_t)((oh + rows - 1) / rows) * (ow >> 2);
 }
 
+// launch(m0, km) for chunks of at most 65535 masks (the grid.y limit): every launcher with a mask per blockIdx.y goes through it
+template <typename F>
+inline void for_mask_chunks(int32_t k, F&& launch) {
+  for (int32_t m0 = 0; m0 < k; m0 += 65535) launch(m0, k - m0 < 65535 ? k - m0 : 65535);
+}
+
 struct MaskScales { float s1h, s1w, s2h, s2w; };
 __device__ __forceinline__ MaskScales mask_scales(const MaskGeom& g) {
   return MaskScales{(float)g.h / (float)g.Hb, (float)g.w / (float)g.Wb, (float)g.ch / (float)g.oh, (float)g.cw / (float)g.ow};

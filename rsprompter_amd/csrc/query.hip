@@ -568,10 +568,19 @@ extern "C" int rsp_query_mask_post(const float* low_res, const int32_t* qidx, co
   // (0.6 M per call) were the whole run time; keep the grid just large enough to fill the chip
   const int64_t cap = k >= 64 ? 64 : (k >= 8 ? 256 : 1024);
   if (gx > cap) gx = cap;
-  if (mask_form(g) != MASK_GENERIC)
-    hipLaunchKernelGGL((query_mask_kernel<true>), dim3((unsigned)gx, k), dim3(MASK_BLOCK), 0, s, p);
-  else
-    hipLaunchKernelGGL((query_mask_kernel<false>), dim3((unsigned)gx, k), dim3(MASK_BLOCK), 0, s, p);
+  const bool ident = mask_form(g) != MASK_GENERIC;
+  for_mask_chunks(k, [&](int32_t m0, int32_t km) {
+    QMaskP c = p;      // `low` stays: qidx indexes the whole [Nq, h, w]
+    c.qidx += m0;
+    c.out += (int64_t)m0 * out_h * out_w;
+    c.stats += (int64_t)m0 * 2;
+    c.box += (int64_t)m0 * 4;
+    if (c.logits) c.logits += (int64_t)m0 * out_h * out_w;
+    if (ident)
+      hipLaunchKernelGGL((query_mask_kernel<true>), dim3((unsigned)gx, km), dim3(MASK_BLOCK), 0, s, c);
+    else
+      hipLaunchKernelGGL((query_mask_kernel<false>), dim3((unsigned)gx, km), dim3(MASK_BLOCK), 0, s, c);
+  });
   hipLaunchKernelGGL(query_finalize_kernel, dim3((k + 63) / 64), dim3(64), 0, s, cls_score, p.stats, p.box, det_score, bboxes, k);
   RSP_CHECK_LAUNCH();
   return RSP_OK;

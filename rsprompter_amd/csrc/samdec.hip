@@ -397,23 +397,24 @@ constexpr int64_t NO_CAP = 0x7fffffffLL;
 unsigned score_blocks(int32_t k, int out_h, int out_w) {
   return blocks256((int64_t)out_h * out_w, k >= 1024 ? 16 : (k >= 64 ? 64 : 1024));
 }
-// launch(m0, km) for chunks of at most 65535 masks (the grid.y limit)
-template <typename F>
-void for_mask_chunks(int32_t k, F&& launch) {
-  for (int32_t m0 = 0; m0 < k; m0 += 65535) launch(m0, k - m0 < 65535 ? k - m0 : 65535);
-}
 
 int launch_mask_post(const MaskPostP& p, hipStream_t stream) {
   const MaskGeom& g = p.g;
-  const unsigned gx = blocks256((int64_t)g.oh * g.ow / ((g.ow & 3) == 0 ? 4 : 1), 4096);
-  switch (mask_form(g)) {
-    case MASK_STRIP:
-      hipLaunchKernelGGL(mask_post_strip_kernel, dim3(blocks256(mask_strip_items(g.oh, g.ow, MP_ROWS), NO_CAP), p.k),
-                         dim3(MASK_BLOCK), 0, stream, p);
-      break;
-    case MASK_IDENT: hipLaunchKernelGGL((mask_post_kernel<true>), dim3(gx, p.k), dim3(MASK_BLOCK), 0, stream, p); break;
-    case MASK_GENERIC: hipLaunchKernelGGL((mask_post_kernel<false>), dim3(gx, p.k), dim3(MASK_BLOCK), 0, stream, p); break;
-  }
+  const MaskForm form = mask_form(g);
+  const unsigned gx = form == MASK_STRIP ? blocks256(mask_strip_items(g.oh, g.ow, MP_ROWS), NO_CAP)
+                                         : blocks256((int64_t)g.oh * g.ow / ((g.ow & 3) == 0 ? 4 : 1), 4096);
+  for_mask_chunks(p.k, [&](int32_t m0, int32_t km) {
+    MaskPostP c = p;
+    c.low += (int64_t)m0 * g.h * g.w;
+    c.out += (int64_t)m0 * g.oh * g.ow;
+    if (c.prob) c.prob += (int64_t)m0 * g.oh * g.ow;
+    c.k = km;
+    switch (form) {
+      case MASK_STRIP: hipLaunchKernelGGL(mask_post_strip_kernel, dim3(gx, km), dim3(MASK_BLOCK), 0, stream, c); break;
+      case MASK_IDENT: hipLaunchKernelGGL((mask_post_kernel<true>), dim3(gx, km), dim3(MASK_BLOCK), 0, stream, c); break;
+      case MASK_GENERIC: hipLaunchKernelGGL((mask_post_kernel<false>), dim3(gx, km), dim3(MASK_BLOCK), 0, stream, c); break;
+    }
+  });
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

@@ -992,7 +992,7 @@ def _score_thresholds(mask_threshold, stability_score_offset):
 def mask_post(low_res, batch_input_shape, crop_hw, out_hw, thr, want_prob=False):
     """low_res [k, h, w] logits -> bool [k, out_h, out_w] (+ optional probabilities)."""
     lib = _lib.load()
-    k, h, w = low_res.shape
+    k, h, w = _mask_logits(low_res, "mask_post")
     out = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.bool, device=low_res.device)
     prob = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.float32, device=low_res.device) if want_prob else None
     ws = torch.empty_like(low_res)
@@ -1781,9 +1781,11 @@ def query_topk(cls, k):
 def query_mask_post(low_res, qidx, cls_score, batch_input_shape, crop_hw, out_hw, want_logits=False):
     """low_res [Nq, h, w] logits of one image; qidx int32 [k]; returns (masks bool [k,oh,ow], det_scores, bboxes)."""
     lib = _lib.load()
-    k = qidx.numel()
-    _, h, w = low_res.shape
+    _, h, w = _mask_logits(low_res, "query_mask_post")
     dev = low_res.device
+    if qidx.dtype != torch.int32 or qidx.dim() != 1 or not qidx.is_contiguous() or qidx.device != dev:
+        raise ValueError("qidx: contiguous int32 [k] on the device of low_res")
+    k = qidx.numel()
     masks = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.bool, device=dev)
     logits = torch.empty((k, out_hw[0], out_hw[1]), dtype=torch.float32, device=dev) if want_logits else None
     det = torch.empty((k,), dtype=torch.float32, device=dev)

@@ -116,3 +116,50 @@ def test_fold_check_rejects_a_skipped_key_tile():
     assert 2.0 < d / 2e-5 < 5.0
     with pytest.raises(AssertionError):
         kp.assert_fold_close(kp.t2i_ref_f64(tq, keys, pe, wts, R, T, N, key_bias=skip), ref2)
+
+
+# ------------------------------------------------------------------------------------------------------- the mask-field checks
+import _mask_field_props as mf  # noqa: E402
+
+# the smaller exact cases: every form, both quad / pixel paths, strips below and beyond the row tile
+_MF_CASES = tuple(c for c in mf.EXACT_CASES if mf.pixels(c) <= 4096)
+
+
+def test_mask_field_fake_reproduces_the_oracle():
+    """the stand-in's written-out bilinear resize is F.interpolate in fp64, and the unmutated stand-in passes every exact case"""
+    g = torch.Generator().manual_seed(1)
+    for c in mf.EXACT_CASES + mf.TOL_CASES[:1]:
+        low = torch.randn(2, *c.hw, generator=g)
+        f, seen = mf.FakeOps()._field(low, c.img, c.crop, c.out)
+        assert bool(seen.all()) and float((f - mf.field_f64(low, c.img, c.crop, c.out)).abs().max()) < 1e-12, c
+    for c in mf.EXACT_CASES:
+        mf.check_exact_field(mf.FakeOps(), 'cpu', c, seed=101)
+    # the crop tables: of all the cases, and of the pool the mutation below is run with -- an assertion that fails there
+    # whatever `ops` does would count the mutation as rejected
+    for cases in (mf.EXACT_CASES, _MF_CASES):
+        for hw in mf.crop_groups(cases):
+            mf.check_exact_crops(mf.FakeOps(), 'cpu', hw, seed=101, cases=cases)
+
+
+@pytest.mark.parametrize('mutation', mf.MUTATIONS)
+def test_exact_field_check_rejects(mutation):
+    """check_exact_field raises AssertionError on at least one exact case for every mutation of the stand-in: `>=` for `>` at
+    the logits threshold and the reverse in mask_post, stage 1 without the half-pixel offset, stage 2 skipped, the strip's row
+    pair not refreshed, the last quad of a row / the rows beyond the last full tile not written, the highest index winning a
+    tie, qidx ignored, the box maximum off by one"""
+    fake = mf.FakeOps(mutation)
+    rejected = []
+    for c in _MF_CASES:
+        try:
+            mf.check_exact_field(fake, 'cpu', c, seed=101)
+        except AssertionError:
+            rejected.append(c)
+    assert rejected, mutation
+    # the threshold and index mutations change no value: only ties show them, and every case has ties
+    if mutation in ('ge_at_the_logits_threshold', 'gt_in_mask_post', 'qidx_ignored', 'box_max_off_by_one'):
+        assert len(rejected) == len(_MF_CASES), (mutation, len(rejected))
+    # every box is shifted by its row's origin, so the crop table shows the box mutation at every (h, w)
+    if mutation == 'box_max_off_by_one':
+        for hw in mf.crop_groups(_MF_CASES):
+            with pytest.raises(AssertionError):
+                mf.check_exact_crops(fake, 'cpu', hw, seed=101, cases=_MF_CASES)
