@@ -400,6 +400,26 @@ int rsp_sam_upscale_fused(const uint16_t* x_hi, const uint16_t* x_lo, int64_t x_
                           const uint16_t* w2_lo, int32_t w2_scale_log2, const float* bias2, const float* hyper,
                           float* out, int64_t rows, int32_t rows_per_roi, int32_t W, rsp_stream_t stream);
 
+/* SAM-HQ's mask branch in one kernel (HF transformers models/sam_hq/modeling_sam_hq.py:1007-1037; csrc/sam_hq.hip):          */
+/*   out[r, p] = < hyper[r], mask_conv2(GELU(LN2d_64(mask_conv1(U_r))))[p] + feat[feat_map[r], p] >,                            */
+/*   U_r = GELU(ConvTranspose2d(64 -> 32, k2 s2)(up_r)),  both convolutions 3 x 3 with zero padding 1.                         */
+/* up: planes of [up_rows >= n_up (2g)^2, 64], the [n_up, 2g, 2g, 64] upscaler planes; U_r is formed from block up_map[r]    */
+/* (int32 [R], clamped to [0, n_up); null: block r, n_up == R).  w2: planes of the packed upscale_conv2 weight                */
+/* [(dy, dx, c2), 64], bias2 [128] (tiled x4); w1: planes of mask_conv1 as [64, (tap = 3 ky + kx, ci) = 288], bias1 [64];     */
+/* gamma / beta / eps: mask_norm; wf: mask_conv2 as fp32 [tap][ci = 64][c = 32], biasf [32]; hyper [R, 32]; feat              */
+/* [n_feat, 4g, 4g, 32] fp32 with feat_map int32 [R] (clamped to [0, n_feat)); out fp32 [R, 4g, 4g].  Optionally SAM's own    */
+/* masks from the same U tile (HF:1032, 1065): hyper_sam [R, n_sam <= 3, 32] -> out_sam[r, t] = < hyper_sam[r, t], U_r > +    */
+/* out[r], fp32 [R, n_sam, 4g, 4g] (both null with n_sam == 0).  Nothing else is written.  mask_conv2 and the hyper product   */
+/* are folded into one 3 x 3 filter per prompt set (another summation order than HF's).                                       */
+/* RSP_EINVAL: a null pointer, g % 4 != 0, R (4g)^2 >= 2^31, up_rows < n_up (2g)^2, n_sam outside 0..3.                       */
+int rsp_sam_hq_mask(const uint16_t* up_hi, const uint16_t* up_lo, int64_t up_rows, int32_t up_scale_log2,
+                    const int32_t* up_map, int32_t n_up,
+                    const uint16_t* w2_hi, const uint16_t* w2_lo, int32_t w2_scale_log2, const float* bias2,
+                    const uint16_t* w1_hi, const uint16_t* w1_lo, int32_t w1_scale_log2, const float* bias1,
+                    const float* gamma, const float* beta, float eps, const float* wf, const float* biasf,
+                    const float* hyper, const float* feat, const int32_t* feat_map, int32_t n_feat, float* out,
+                    const float* hyper_sam, float* out_sam, int32_t n_sam, int32_t R, int32_t g, rsp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* SAM decoder tail / mask post-process                                        */
 /* ------------------------------------------------------------------------ */

@@ -7,7 +7,9 @@ converted with `zero_to_fp32.py` before evaluation).  What arrives on disk:
 
   * HuggingFace SAM weights: `pytorch_model.bin` (pickle) or `model.safetensors`, a flat state_dict whose vision keys
     carry the `vision_encoder.` prefix (stripped by the reference's revise_keys), possibly sharded with an
-    `*.index.json` (`weight_map`: key -> shard file);
+    `*.index.json` (`weight_map`: key -> shard file); HF `SamHQModel` files are the same format with the HQ decoder's
+    extra keys (`mask_decoder.hq_token`, `.hq_mask_mlp`, `.compress_vit_*`, `.encoder_*`, `.mask_conv*`) and load into a
+    `SamHQModelHIP` as they are -- the ORIGINAL SAM-HQ `.pth` naming (`mask_decoder.hf_token`, `.hf_mlp`, ...) is not mapped;
   * mmengine checkpoints: dict(meta=..., state_dict=..., [optimizer, message_hub, ...]);
   * `zero_to_fp32.py` output: a flat fp32 state_dict, keys possibly prefixed `module.` (DeepSpeed engine wrapper) --
     the same rewrite mmengine applies by default (`revise_keys=[(r'^module\\.', '')]`);

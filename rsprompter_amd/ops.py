@@ -830,6 +830,56 @@ def sam_upscale_fused(x, w1, bias1, gamma, beta, eps, w2p, bias2, hyper, h, w):
     return out
 
 
+def sam_hq_mask(up, w2, bias2, w1, bias1, gamma, beta, eps, wf, biasf, hyper, feat, feat_map, up_map=None, hyper_sam=None):
+    """SAM-HQ's mask branch in one kernel (csrc/sam_hq.hip, HF sam_hq:1007-1037): up Planes [S, 2g, 2g, 64] (the upscaler's
+    planes after LayerNorm + GELU; prompt set r reads block up_map[r], int32 [R] -- None: S == R, block r), w2 = PackedWeight
+    [(dy, dx, c2), 64] of upscale_conv2 with bias2 [128], w1 = PackedWeight [64, (tap, ci) = 288] of mask_conv1 with bias1
+    [64], gamma / beta / eps of mask_norm, wf fp32 [9, 64, 32] = mask_conv2 as [tap][ci][c] with biasf [32], hyper [R, 32],
+    feat fp32 [n, 4g, 4g, 32] and feat_map int32 [R] -> mask_hq fp32 [R, 4g, 4g].  hyper_sam [R, n <= 3, 32]: also SAM's masks
+    from the same upscaled embedding, + mask_hq: returns (mask_hq, fp32 [R, n, 4g, 4g])."""
+    lib = _lib.load()
+    if not isinstance(up, Planes) or up.f8 or len(up.shape) != 4 or up.shape[-1] != 64 or up.shape[1] != up.shape[2]:
+        raise ValueError('sam_hq_mask: up must be fp16 planes of logical shape [S, 2g, 2g, 64]')
+    S, g2 = up.shape[0], up.shape[1]
+    R = hyper.shape[0]
+    G = 2 * g2
+    if g2 % 8:
+        raise ValueError(f'sam_hq_mask: the embedding grid must be a multiple of 4, got {g2 // 2}')
+    if w2.N != 128 or w2.K != 64 or w1.N != 64 or w1.K != 288 or tuple(wf.shape) != (9, 64, 32):
+        raise ValueError('sam_hq_mask: weight shapes')
+    if feat.dim() != 4 or tuple(feat.shape[1:]) != (G, G, 32) or tuple(hyper.shape) != (R, 32) or feat_map.numel() != R:
+        raise ValueError(f'sam_hq_mask: feat {tuple(feat.shape)} / hyper {tuple(hyper.shape)} for R = {R}, 4g = {G}')
+    if (up_map is None and S != R) or (up_map is not None and up_map.numel() != R):
+        raise ValueError(f'sam_hq_mask: {S} blocks of up for {R} prompt sets need up_map int32 [{R}]')
+    n_sam = 0
+    if hyper_sam is not None:
+        if hyper_sam.dim() != 3 or hyper_sam.shape[0] != R or not 1 <= hyper_sam.shape[1] <= 3 or hyper_sam.shape[2] != 32:
+            raise ValueError(f'sam_hq_mask: hyper_sam {tuple(hyper_sam.shape)}, expected [{R}, 1..3, 32]')
+        n_sam = hyper_sam.shape[1]
+    for t, name in ((bias2, 'bias2'), (bias1, 'bias1'), (gamma, 'gamma'), (beta, 'beta'), (wf, 'wf'), (biasf, 'biasf'),
+                    (hyper, 'hyper'), (feat, 'feat')) + (((hyper_sam, 'hyper_sam'),) if n_sam else ()):
+        _chk_f32(t, name)
+        if not t.is_contiguous():
+            raise ValueError(f'sam_hq_mask: {name} must be contiguous')
+    for t, name in ((feat_map, 'feat_map'), (up_map, 'up_map')):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f'sam_hq_mask: {name} must be contiguous int32')
+    out = torch.empty((R, G, G), dtype=torch.float32, device=up.device)
+    out_sam = torch.empty((R, n_sam, G, G), dtype=torch.float32, device=up.device) if n_sam else None
+    npx = float(R) * G * G
+    _timed('sam_hq_mask_kernel', 2.0 * npx * (1.56 * 32 * 64 + 1.27 * 288 * 64 + 576 + 32 * (1 + n_sam)),
+           4.0 * R * g2 * g2 * 64 + 4.0 * npx * (33 + n_sam),
+           lambda: _lib.check(lib.rsp_sam_hq_mask(up.hi.data_ptr(), up.lo.data_ptr(), up.rows, up.scale_log2, _ptr(up_map), S,
+                                                  w2.hi.data_ptr(), w2.lo.data_ptr(), w2.scale_log2, bias2.data_ptr(),
+                                                  w1.hi.data_ptr(), w1.lo.data_ptr(), w1.scale_log2, bias1.data_ptr(),
+                                                  gamma.data_ptr(), beta.data_ptr(), float(eps), wf.data_ptr(),
+                                                  biasf.data_ptr(), hyper.data_ptr(), feat.data_ptr(), feat_map.data_ptr(),
+                                                  feat.shape[0], out.data_ptr(), _ptr(hyper_sam), _ptr(out_sam), n_sam, R,
+                                                  g2 // 2, _stream()), "rsp_sam_hq_mask"),
+           detail=f'R={R} S={S} g={g2 // 2} n_sam={n_sam}')
+    return out if not n_sam else (out, out_sam)
+
+
 SAM_T2I_FOLD_MAX_TOKENS = 12    # 8 heads x T query columns fit the kernel's 96
 
 

@@ -127,6 +127,9 @@ class SamMaskDecoderHIP(HIPModule):
         _add_linear(self, 'iou_prediction_head.layers.0', HID, HID)
         _add_linear(self, 'iou_prediction_head.proj_out', N_MASK_TOKENS, HID)
         self._pe_cache = {}
+        # output tokens in front of the sparse prompts: iou + the mask tokens (SamHQMaskDecoderHIP appends its hq token)
+        self.n_mask_tokens = N_MASK_TOKENS
+        self.n_output_tokens = 1 + N_MASK_TOKENS
         # token -> image attention of layer 1 / final with the K | V projections folded in (csrc/t2i_fold.hip)
         self.t2i_fold = True
         # the upscaler tail in one kernel (csrc/upscale.hip, sam_upscale_fused_kernel)
@@ -178,7 +181,7 @@ class SamMaskDecoderHIP(HIPModule):
 
     def _pe_terms(self, pe_rows):
         """pe @ W^T + b for every image-side projection that consumes keys + pe (HF:326-343, 397-400)."""
-        key = (pe_rows.data_ptr(), tuple(pe_rows.shape))
+        key = self._pe_key(pe_rows)
         if key not in self._pe_cache:
             P = self._packed
             t = {}
@@ -193,8 +196,18 @@ class SamMaskDecoderHIP(HIPModule):
                 t[pre + '.kv_proj'] = torch.cat([t[pre + '.k_proj'], vb.unsqueeze(0).expand(pe_rows.shape[0], -1)],
                                                 1).contiguous()
                 t[pre + '.pek_planes'] = ops.to_planes(t[pre + '.k_proj'])       # PEK of the folded token -> image form
+            # the entry keeps the table it was computed from: while it is cached its memory cannot be handed to another tensor,
+            # so an equal (pointer, shape, version) key means the same values.  The key is the table's NHWC rows: the models'
+            # own tables are channels-last and hit on every call; a foreign NCHW-contiguous `image_pe` is copied to NHWC per
+            # call (nhwc_view), so it misses every time and pays the five small pe GEMMs + to_planes again -- pass such a
+            # table as `.contiguous(memory_format=torch.channels_last)` once
+            t['_table'] = pe_rows
             self._pe_cache = {key: t}
         return self._pe_cache[key]
+
+    @staticmethod
+    def _pe_key(pe_rows):
+        return (pe_rows.data_ptr(), tuple(pe_rows.shape), pe_rows._version)
 
     # ------------------------------------------------------------------ pieces
     def _ln(self, x, name, eps=1e-6, planes=False):
@@ -254,14 +267,15 @@ class SamMaskDecoderHIP(HIPModule):
         return ops.gemm(o, P[pfx + '.out_proj'], res=res)
 
     def decode(self, image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou=True, src_rows=None, hw=None,
-               multimask_output=False, src_is_identity=False, attn_bias=None, target_rows=None):
+               multimask_output=False, src_is_identity=False, attn_bias=None, target_rows=None, **head_kw):
         """The SAM mask decoder over R prompt sets (see _decode_chunk for the arguments).  Round 6: more prompt sets than the
         folded token -> image attention can address (R * N * 512 bytes of key planes < 2^31: 1023 at N = 4096) are decoded in
         chunks of equal size, each on the product path -- BASELINE configs[2] (16 tiles x 100 queries = 1600 prompt sets) used to
         fall back to the round-2 kernel chain (K | V projection GEMMs over all per-RoI keys + sam_t2i_kernel) for that reason.
         src_is_identity: roi_img is arange(R) over `src_rows` (the query variant: one dense-prompted source per prompt set), so a
         chunk only needs its own rows of `src_rows`.  attn_bias [1 | R, N] / target_rows [1 | R, 256]: HF's PerSAM hooks
-        (persam_hooks); a per-prompt-set form is sliced with its chunk."""
+        (persam_hooks); a per-prompt-set form is sliced with its chunk.  head_kw: further keyword arguments of `_heads` (none
+        here; SamHQMaskDecoderHIP: hq_features, hq_token_only), the same for every chunk."""
         R = sparse.shape[0]
         if src_rows is None:
             N = image_embeddings.shape[-2] * image_embeddings.shape[-1]
@@ -270,7 +284,7 @@ class SamMaskDecoderHIP(HIPModule):
         max_r = self.max_prompt_sets or max(1, (2 ** 31 - 1) // (N * 512))
         if R <= max_r or not self.t2i_fold:
             return self._decode_chunk(image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou, src_rows, hw,
-                                      multimask_output, attn_bias, target_rows)
+                                      multimask_output, attn_bias, target_rows, **head_kw)
         n_chunks = -(-R // max_r)
         per = -(-R // n_chunks)
         masks, ious = [], []
@@ -284,13 +298,13 @@ class SamMaskDecoderHIP(HIPModule):
             bias_c = attn_bias if attn_bias is None or attn_bias.shape[0] == 1 else attn_bias[r0:r1].contiguous()
             te_c = target_rows if target_rows is None or target_rows.shape[0] == 1 else target_rows[r0:r1].contiguous()
             m, i = self._decode_chunk(image_embeddings, image_pe, sparse[r0:r1], dense_vec, map_c, want_iou, src_c, hw,
-                                      multimask_output, bias_c, te_c)
+                                      multimask_output, bias_c, te_c, **head_kw)
             masks.append(m)
             ious.append(i)
         return torch.cat(masks, 0), (torch.cat(ious, 0) if want_iou else None)
 
     def _decode_chunk(self, image_embeddings, image_pe, sparse, dense_vec, roi_img, want_iou=True, src_rows=None, hw=None,
-                      multimask_output=False, attn_bias=None, target_rows=None):
+                      multimask_output=False, attn_bias=None, target_rows=None, **head_kw):
         """image_embeddings [B,256,h,w] (logical NCHW, channels-last), image_pe [1|B,256,h,w] (input
         independent; batch entry 0 is used), sparse [R, n_pts, 256], dense_vec [256] (the broadcast
         `no_mask_embed`, models.py:1680), roi_img int32 [R] image index of every RoI (sorted).
@@ -317,9 +331,9 @@ class SamMaskDecoderHIP(HIPModule):
             dev = src_rows.device
         N = h * w
         R, npts = sparse.shape[0], sparse.shape[1]
-        T = 1 + N_MASK_TOKENS + npts
+        T = self.n_output_tokens + npts
         pe_rows = nhwc_view(image_pe[:1]).reshape(N, C)
-        if (pe_rows.data_ptr(), tuple(pe_rows.shape)) not in self._pe_cache and image_pe.shape[0] > 1:
+        if self._pe_key(pe_rows) not in self._pe_cache and image_pe.shape[0] > 1:
             # the image-wide positional embedding is ONE table repeated over the batch (models.py:85-95, 1685); its
             # projections are folded into broadcast terms below, so a caller with per-image tables must not get a
             # silently wrong answer (checked once per new table, not per step)
@@ -329,7 +343,7 @@ class SamMaskDecoderHIP(HIPModule):
         d2, dh2 = HID // 2, (HID // 2) // HEADS
 
         # tokens = [iou, mask x4, sparse prompts] (HF:489-496)
-        out_tok = torch.cat([self.iou_token.weight, self.mask_tokens.weight], 0)
+        out_tok = self._output_tokens()
         tokens0 = torch.cat([out_tok.unsqueeze(0).expand(R, -1, -1), sparse.reshape(R, npts, HID)], 1)
         tokens0 = tokens0.reshape(R * T, HID).contiguous()
         te_rows = None
@@ -436,6 +450,36 @@ class SamMaskDecoderHIP(HIPModule):
         del kv, qi, ai
         q3 = q.view(R, T, HID)
         stages = dict(keys=keys_pl, tokens=q3, up=None, hyper=[]) if self.keep_stages else None
+        hold = [keys_pl]                       # (handed over: _heads frees the keys as soon as the first ConvTranspose has read them)
+        del keys_pl
+        return self._heads(q3, hold, R, h, w, multimask_output, want_iou, stages, roi_img, src, **head_kw)
+
+    def _output_tokens(self):
+        """[iou, mask x4] (HF:489)"""
+        return torch.cat([self.iou_token.weight, self.mask_tokens.weight], 0)
+
+    def _hyper(self, q3, i, name=None):
+        """hyper-network MLP `name` (default: output_hypernetworks_mlps.i -> packed 'hyper{i}') on output token 1 + i"""
+        P = self._packed
+        name = name or f'hyper{i}'
+        mt = q3[:, 1 + i, :].contiguous()
+        hy = ops.gemm(mt, P[name + '.proj_in'], act=ops.ACT_RELU)
+        hy = ops.gemm(hy, P[name + '.layers.0'], act=ops.ACT_RELU)
+        return ops.gemm(hy, P[name + '.proj_out'])
+
+    def _iou_head(self, q3):
+        P = self._packed
+        it = q3[:, 0, :].contiguous()
+        io = ops.gemm(it, P['iou.proj_in'], act=ops.ACT_RELU)
+        io = ops.gemm(io, P['iou.layers.0'], act=ops.ACT_RELU)
+        return ops.gemm(io, P['iou.proj_out'])
+
+    def _heads(self, q3, hold, R, h, w, multimask_output, want_iou, stages, roi_img, src):
+        """upscaling + hyper-networks + IoU head (HF:513-542) on the transformer's tokens q3 [R, T, 256] and the keys
+        (planes, the only element of the list `hold`); roi_img: the prompt sets' image / source index into src
+        [sources * h * w, 256] = image embedding + dense prompt (not read here)"""
+        P = self._packed
+        keys_pl = hold.pop()
 
         # ---------------- upscaling + hyper-network (HF:513-531) ----------------
         # mask token 0 is the only mask kept with multimask_output=False, tokens 1..3 otherwise (HF:537-542)
@@ -451,10 +495,7 @@ class SamMaskDecoderHIP(HIPModule):
                 stages['up'] = up
         outs = []
         for i in toks:
-            mt = q3[:, 1 + i, :].contiguous()
-            hy = ops.gemm(mt, P[f'hyper{i}.proj_in'], act=ops.ACT_RELU)
-            hy = ops.gemm(hy, P[f'hyper{i}.layers.0'], act=ops.ACT_RELU)
-            hy = ops.gemm(hy, P[f'hyper{i}.proj_out'])
+            hy = self._hyper(q3, i)
             if stages is not None:
                 stages['hyper'].append(hy)
             if fused_up:
@@ -469,16 +510,13 @@ class SamMaskDecoderHIP(HIPModule):
         self._last_stages = stages
         iou = None
         if want_iou:
-            it = q3[:, 0, :].contiguous()
-            io = ops.gemm(it, P['iou.proj_in'], act=ops.ACT_RELU)
-            io = ops.gemm(io, P['iou.layers.0'], act=ops.ACT_RELU)
-            io = ops.gemm(io, P['iou.proj_out'])
+            io = self._iou_head(q3)
             iou = io[:, 1:4].contiguous() if multimask_output else io[:, 0:1]
         return masks, iou
 
     def forward(self, image_embeddings, image_positional_embeddings, sparse_prompt_embeddings,
                 dense_prompt_embeddings, multimask_output=False, attention_similarity=None,
-                target_embedding=None, output_attentions=None):
+                target_embedding=None, output_attentions=None, **head_kw):
         """HF signature (HF:461-543): image_embeddings [B, 256, h, w], sparse_prompt_embeddings [B, Pb, n, 256] (or [B, n, 256]
         = point_batch_size 1), dense_prompt_embeddings [1 | B, 256, h, w] -- the broadcast `no_mask_embed` or a per-pixel one
         (SamMaskEmbedding's output).  Every batch entry is its own image and its Pb prompt sets stay mapped to it.  Returns
@@ -491,7 +529,7 @@ class SamMaskDecoderHIP(HIPModule):
             Pb = 1
             sparse = sparse_prompt_embeddings
         bias, te = persam_hooks(attention_similarity, target_embedding, B, Pb,
-                                image_embeddings.shape[-2] * image_embeddings.shape[-1], 1 + N_MASK_TOKENS + sparse.shape[1])
+                                image_embeddings.shape[-2] * image_embeddings.shape[-1], self.n_output_tokens + sparse.shape[1])
         dev = image_embeddings.device
         roi_img = torch.arange(B, dtype=torch.int32, device=dev)
         if Pb > 1:
@@ -504,7 +542,7 @@ class SamMaskDecoderHIP(HIPModule):
         if const:
             masks, iou = self.decode(image_embeddings, image_positional_embeddings, sparse.contiguous(),
                                      d[0, 0, 0].contiguous(), roi_img, multimask_output=bool(multimask_output),
-                                     attn_bias=bias, target_rows=te)
+                                     attn_bias=bias, target_rows=te, **head_kw)
         else:
             emb = nhwc_view(image_embeddings)
             _, h, w, C = emb.shape
@@ -512,9 +550,152 @@ class SamMaskDecoderHIP(HIPModule):
             src = ops.add_rows(emb.reshape(B * h * w, C).contiguous(), d.reshape(-1, C).contiguous())
             masks, iou = self.decode(None, image_positional_embeddings, sparse.contiguous(), None, roi_img,
                                      src_rows=src, hw=(h, w), multimask_output=bool(multimask_output), attn_bias=bias,
-                                     target_rows=te)
+                                     target_rows=te, **head_kw)
         C, mh, mw = masks.shape[1:]
-        return masks.reshape(B, Pb, C, mh, mw), iou.reshape(B, Pb, C), None
+        return masks.reshape(B, Pb, C, mh, mw), iou.reshape(B, Pb, iou.shape[1]), None
+
+
+def hq_conv_weights(conv1_w, conv2_w):
+    """SAM-HQ's two 3 x 3 convolutions in the forms rsp_sam_hq_mask takes: mask_conv1 [64, 32, 3, 3] -> PackedWeight
+    [64, (tap = 3 ky + kx, ci) = 288]; mask_conv2 [32, 64, 3, 3] -> fp32 [tap, ci, c] = [9, 64, 32]"""
+    w1 = ops.PackedWeight(conv1_w.detach().permute(0, 2, 3, 1).reshape(conv1_w.shape[0], -1))
+    wf = conv2_w.detach().to(torch.float32).permute(2, 3, 1, 0).reshape(9, conv2_w.shape[1], conv2_w.shape[0]).contiguous()
+    return w1, wf
+
+
+class SamHQMaskDecoderHIP(SamMaskDecoderHIP):
+    """HF `SamHQMaskDecoder` (transformers models/sam_hq/modeling_sam_hq.py:869-1067, "HQ:" below) in its parameter layout:
+    SAM's decoder with one more output token (tokens = [iou, mask x4, hq, sparse...]) whose hyper-network vector multiplies
+    `mask_conv2(GELU(LN(mask_conv1(upscaled)))) + hq_features`.  The whole tail -- second ConvTranspose, both 3 x 3
+    convolutions, LayerNorm, GELUs, the HQ product and SAM's own mask products -- is one kernel launch per decode
+    (csrc/sam_hq.hip); nothing of shape [R, 4g, 4g, 32 | 64] is stored.  `hq_features` [B, 4g, 4g, 32] depend on the image
+    alone (four ConvTransposes over the image embedding and the early ViT feature, HQ:964-975): `hq_features()`, once per
+    image.  What is upscaled follows HF's code, not SAM's: see `_heads` ("SAM-HQ")."""
+
+    def __init__(self, vit_dim=768):
+        super().__init__()
+        self.vit_dim = vit_dim
+        add_param(self, 'hq_token.weight', (1, HID))
+        for l in ('proj_in', 'layers.0'):
+            _add_linear(self, 'hq_mask_mlp.' + l, HID, HID)
+        _add_linear(self, 'hq_mask_mlp.proj_out', HID // 8, HID)
+        for name, cin, cmid in (('compress_vit', vit_dim, HID), ('encoder', HID, HID // 4)):
+            add_param(self, f'{name}_conv1.weight', (cin, cmid, 2, 2))
+            add_param(self, f'{name}_conv1.bias', (cmid,))
+            _add_ln(self, f'{name}_norm', cmid)
+            add_param(self, f'{name}_conv2.weight', (cmid, HID // 8, 2, 2))
+            add_param(self, f'{name}_conv2.bias', (HID // 8,))
+        add_param(self, 'mask_conv1.weight', (HID // 4, HID // 8, 3, 3))
+        add_param(self, 'mask_conv1.bias', (HID // 4,))
+        _add_ln(self, 'mask_norm', HID // 4)
+        add_param(self, 'mask_conv2.weight', (HID // 8, HID // 4, 3, 3))
+        add_param(self, 'mask_conv2.bias', (HID // 8,))
+        self.n_output_tokens = 2 + N_MASK_TOKENS
+        self.hq_feature_calls = 0            # tests: how often the per-image features were computed
+
+    def _pack(self):
+        from .necks import convt_weights4
+        super()._pack()
+        P = self._packed
+        for l in ('proj_in', 'layers.0', 'proj_out'):
+            P[f'hq.{l}'] = self._pw(f'hq_mask_mlp.{l}')
+        for key, name in (('enc1', 'encoder_conv1'), ('enc2', 'encoder_conv2'), ('vit1', 'compress_vit_conv1'),
+                          ('vit2', 'compress_vit_conv2')):
+            m = getattr(self, name)
+            P[key] = convt_weights4(m.weight, m.bias)
+        P['hq_w1'], P['hq_wf'] = hq_conv_weights(self.mask_conv1.weight, self.mask_conv2.weight)
+
+    def _output_tokens(self):
+        """[iou, mask x4, hq] (HQ:977)"""
+        return torch.cat([self.iou_token.weight, self.mask_tokens.weight, self.hq_token.weight], 0)
+
+    @torch.no_grad()
+    def hq_features(self, image_embeddings, vit_features=None):
+        """HQ:964-975: encoder_conv2(GELU(LN(encoder_conv1(image_embeddings)))) [+ the same chain of compress_vit_* over
+        vit_features [B, g, g, vit_dim], the ViT's hidden state after its first global-attention layer] -> fp32 [B, 4g, 4g, 32].
+        image_embeddings [B, 256, g, g] WITHOUT the dense prompt."""
+        if self._packed is None:
+            self._pack()
+        P = self._packed
+        self.hq_feature_calls += 1
+        emb = nhwc_view(image_embeddings)
+        B, h, w, _ = emb.shape
+        e = ops.conv_transpose2x2(emb, *P['enc1'], act=ops.ACT_GELU, ln=(self.encoder_norm.weight, self.encoder_norm.bias, 1e-6))
+        f = ops.conv_transpose2x2(e, *P['enc2'])
+        if vit_features is not None:
+            if tuple(vit_features.shape) != (B, h, w, self.vit_dim):
+                raise ValueError(f'intermediate embedding: expected [{B}, {h}, {w}, {self.vit_dim}], got {tuple(vit_features.shape)}')
+            c = ops.conv_transpose2x2(vit_features.to(torch.float32).contiguous(), *P['vit1'])
+            c = ops.layernorm(c.view(B * 4 * h * w, HID), self.compress_vit_norm.weight, self.compress_vit_norm.bias, 1e-6,
+                              act=ops.ACT_GELU, planes=True, f32=False)
+            c = ops.conv_transpose2x2(c.view(B, 2 * h, 2 * w, HID), *P['vit2'])
+            f = ops.add_rows(f.view(-1, HID // 8), c.view(-1, HID // 8)).view(B, 4 * h, 4 * w, HID // 8)
+        return f
+
+    def decode(self, *args, hq_features=None, hq_token_only=False, src_is_identity=False, **kw):
+        """`SamMaskDecoderHIP.decode` + hq_features fp32 [B | sources, 4h, 4w, 32] (row = the prompt set's `roi_img` entry) and
+        hq_token_only.  Returns (masks, iou): masks_sam + mask_hq [R, 3 | 1, 4h, 4w], or mask_hq alone [R, 1, 4h, 4w] with
+        hq_token_only; with multimask_output the three SAM masks and iou [R, 3] are ordered by predicted IoU, descending (HQ:1042-1055)."""
+        if hq_features is None:
+            raise ValueError('SamHQMaskDecoderHIP.decode needs hq_features (see hq_features())')
+        if src_is_identity:
+            # (a chunk of that form renumbers its sources from 0, which would index hq_features with chunk-local rows)
+            raise NotImplementedError('SamHQMaskDecoderHIP.decode: src_is_identity (one source per prompt set) is not taken')
+        return super().decode(*args, hq_features=hq_features, hq_token_only=bool(hq_token_only), **kw)
+
+    def _heads(self, q3, hold, R, h, w, multimask_output, want_iou, stages, roi_img, src, hq_features=None, hq_token_only=False):
+        """HQ:999-1065.  What is upscaled is NOT the transformer's keys: HF's HQ decoder binds the transformer's second result
+        to a name it overwrites (HQ:989, 996), so HQ:999-1005 upscale the tensor the transformer was GIVEN -- image embedding
+        + dense prompt, repeated per prompt set -- after `transpose(2, 3).reshape(.., h, w)`, which on that 4-D tensor is a
+        spatial transpose (on SAM's [.., N, C] keys the same line restores NCHW).  Both are reproduced: this decoder computes
+        what `SamHQModel` computes.  The upscaled embedding therefore depends on the SOURCE (image + dense prompt) alone; its
+        first stage runs once per source and the kernel reads it through the prompt set -> source map."""
+        P = self._packed
+        hold.pop()                                                                      # the keys are not read (see above)
+        feat, hq_only = hq_features, hq_token_only
+        if h != w:
+            raise NotImplementedError(f'SamHQMaskDecoderHIP: a {h} x {w} embedding grid (HQ:999 is a spatial transpose only '
+                                      'for a square grid)')
+        if tuple(feat.shape[1:]) != (4 * h, 4 * w, HID // 8):
+            raise ValueError(f'hq_features: expected [*, {4 * h}, {4 * w}, {HID // 8}], got {tuple(feat.shape)}')
+        S = src.shape[0] // (h * w)
+        src_t = src.view(S, h, w, HID).transpose(1, 2).contiguous()
+        up = ops.conv_transpose2x2(src_t, *P['up1'], act=ops.ACT_GELU,
+                                   ln=(self.upscale_layer_norm.weight, self.upscale_layer_norm.bias, 1e-6))   # [S, 2h, 2w, 64] planes
+        io = self._iou_head(q3)                                                         # [R, 4]
+        hy_hq = self._hyper(q3, N_MASK_TOKENS, 'hq')
+        if multimask_output:
+            # HQ:1042-1055: tokens 1..3 by predicted IoU, descending (a tie goes to the lower token).  The ORDER is applied to the
+            # hyper-network vectors, so the masks are produced in their final places: no gather over [R, 3, 4h, 4w], no host read
+            iou, order = torch.sort(io[:, 1:4], dim=1, descending=True, stable=True)
+            hy = torch.stack([self._hyper(q3, i) for i in (1, 2, 3)], 1)
+            hy = torch.gather(hy, 1, order.unsqueeze(-1).expand(-1, -1, hy.shape[-1])).contiguous()
+        else:
+            iou = io[:, 0:1]
+            hy = self._hyper(q3, 0).unsqueeze(1).contiguous()
+        if stages is not None:
+            stages.update(up=up, hyper_hq=hy_hq, hyper=[hy[:, j] for j in range(hy.shape[1])])
+        self._last_stages = stages
+        rmap = roi_img.to(torch.int32).contiguous()
+        # one launch: mask_hq, and (unless hq_token_only) SAM's masks + mask_hq from the same upscaled tile (HQ:1032-1065)
+        res = ops.sam_hq_mask(up, P['up2'][0], P['up2'][1], P['hq_w1'], self.mask_conv1.bias, self.mask_norm.weight,
+                              self.mask_norm.bias, 1e-6, P['hq_wf'], self.mask_conv2.bias, hy_hq, feat.contiguous(), rmap,
+                              up_map=rmap, hyper_sam=None if hq_only else hy)
+        masks = res.view(R, 1, 4 * h, 4 * w) if hq_only else res[1]
+        return masks, (iou if want_iou else None)
+
+    def forward(self, image_embeddings, image_positional_embeddings, sparse_prompt_embeddings, dense_prompt_embeddings,
+                multimask_output=False, hq_token_only=False, intermediate_embeddings=None, attention_similarity=None,
+                target_embedding=None, hq_features=None):
+        """HF signature (HQ:915-926) + hq_features: the result of `hq_features()` for these embeddings, when the caller kept it.
+        Returns (masks [B, Pb, C, 4h, 4w], iou [B, Pb, 3 | 1], None)."""
+        if hq_features is None:
+            vit = intermediate_embeddings[0] if intermediate_embeddings is not None and len(intermediate_embeddings) > 0 else None
+            hq_features = self.hq_features(image_embeddings, vit)
+        return super().forward(image_embeddings, image_positional_embeddings, sparse_prompt_embeddings,
+                               dense_prompt_embeddings, multimask_output=multimask_output,
+                               attention_similarity=attention_similarity, target_embedding=target_embedding,
+                               hq_features=hq_features, hq_token_only=bool(hq_token_only))
 
 
 @MODELS.register_module()

@@ -209,8 +209,22 @@ class SamVisionEncoderHIP(HIPModule):
         want_hidden = bool(self.output_hidden_states if output_hidden_states is None else output_hidden_states)
         return self._run(pixel_values, want_hidden)
 
-    def _run(self, pixel_values, want_hidden):
-        """the launch sequence: no host synchronisation, no host-side decision that depends on device data"""
+    def forward_with_intermediate(self, pixel_values):
+        """(image embeddings [B, 256, g, g], the hidden state after the FIRST global-attention layer as NHWC [B, g, g, D], before
+        the neck) -- SAM-HQ's `intermediate_embeddings[0]` (transformers models/sam_hq/modeling_sam_hq.py:567-581).  The
+        tensor is the layer's own output, kept by reference: no copy, no launch."""
+        if pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or pixel_values.shape[2] != self.image_size or \
+                pixel_values.shape[3] != self.image_size:
+            return self.forward(pixel_values), None                  # (raises forward()'s messages)
+        if self._packed is None:
+            self._pack()
+        keep = []
+        out = self._run(pixel_values, False, keep)
+        return out[0], keep[0]
+
+    def _run(self, pixel_values, want_hidden, keep_first_global=None):
+        """the launch sequence: no host synchronisation, no host-side decision that depends on device data.
+        keep_first_global: a list that receives the hidden state after the first global-attention layer, [B, g, g, D]"""
         P = self._packed
         B = pixel_values.shape[0]
         g, D, nh, dh = self.grid, self.D, self.heads, self.dh
@@ -268,6 +282,8 @@ class SamVisionEncoderHIP(HIPModule):
             del hmid, xn2, x1
             if want_hidden:
                 hidden.append(x)
+            if keep_first_global is not None and S == g and not keep_first_global:
+                keep_first_global.append(x.view(B, g, g, D))
         # neck (HF:985-992): 1x1 conv -> LN over C -> 3x3 conv -> LN over C, all NHWC
         y = ops.gemm(x, P['neck1'], bias=None)
         y = ops.layernorm(y, P['nln1'][0], P['nln1'][1], 1e-6)

@@ -25,7 +25,7 @@ PIXEL_STD = (0.229 * 255, 0.224 * 255, 0.225 * 255)
 
 
 def _sam_of(model):
-    """`SamModelHIP` of a SamModelHIP / RSSamModel / SAMDet."""
+    """`SamModelHIP` (or `SamHQModelHIP`) of a SamModelHIP / SamHQModelHIP / RSSamModel / SAMDet."""
     for path in ((), ('sam_model',), ('segmentor', 'sam_model'), ('segmentor',)):
         m = model
         for p in path:
@@ -34,7 +34,26 @@ def _sam_of(model):
                 break
         if m is not None and hasattr(m, 'mask_decoder') and hasattr(m, 'prompt_encoder') and hasattr(m, 'vision_encoder'):
             return m
-    raise TypeError(f'{type(model).__name__}: expected a SamModelHIP, an RSSamModel or a SAMDet')
+    raise TypeError(f'{type(model).__name__}: expected a SamModelHIP, a SamHQModelHIP, an RSSamModel or a SAMDet')
+
+
+def _is_hq(sam):
+    """a `SamHQModelHIP`: its decoder carries the HQ branch"""
+    return hasattr(sam.mask_decoder, 'hq_features')
+
+
+def _embed(sam, pixel_values):
+    """(image embeddings, SAM-HQ's intermediate list or None) of either model kind"""
+    emb = sam.get_image_embeddings(pixel_values)
+    return emb if isinstance(emb, tuple) else (emb, None)
+
+
+def _hq_kwargs(sam, intermediate, hq_token_only):
+    if not _is_hq(sam):
+        if hq_token_only:
+            raise ValueError('hq_token_only needs a SamHQModelHIP')
+        return {}
+    return dict(intermediate_embeddings=intermediate, hq_token_only=bool(hq_token_only))
 
 
 def preprocess_shape(hw, longest_edge):
@@ -68,10 +87,14 @@ class SamSession:
     geometry and arithmetic -- longest side to `image_size` with `_get_preprocess_shape`'s rounding, ImageNet mean / std,
     zero padding at the bottom / right -- but this package's resampling filter: `rsp_resize_pad` interpolates bilinearly
     with cv2's arithmetic (as `inference_detector` does), not with PIL's antialiased filter, so `pixel_values` differ from
-    HF's processor where the image is strongly minified."""
+    HF's processor where the image is strongly minified.
+    With a `SamHQModelHIP` the session also keeps the ViT's early feature, and the per-image HQ features are computed by the
+    first `predict` and reused by every later one; hq_token_only=True returns the HQ mask alone (one mask per prompt set)."""
 
-    def __init__(self, model, image):
+    def __init__(self, model, image, hq_token_only=False):
         self.sam = _sam_of(model)
+        self.hq_token_only = bool(hq_token_only)
+        _hq_kwargs(self.sam, None, hq_token_only)
         dev = next(self.sam.parameters()).device
         ops.require_device(dev)
         if isinstance(image, np.ndarray):
@@ -86,7 +109,7 @@ class SamSession:
         self.pixel_values = ops.resize_pad(img, self.input_size, (S, S), PIXEL_MEAN,
                                            normalise=(PIXEL_MEAN, PIXEL_STD, False)).unsqueeze(0)
         with torch.no_grad():
-            self.image_embeddings = self.sam.get_image_embeddings(self.pixel_values)
+            self.image_embeddings, self.intermediate_embeddings = _embed(self.sam, self.pixel_values)
         self.device = dev
 
     def _low_res(self, points, labels, boxes, mask_input, multimask_output, attention_similarity=None, target_embedding=None):
@@ -124,6 +147,7 @@ class SamSession:
         if mask_input is not None:
             m = torch.as_tensor(mask_input, dtype=torch.float32).to(dev)
             kw['input_masks'] = m.reshape(1, 1, m.shape[-2], m.shape[-1])
+        kw.update(_hq_kwargs(self.sam, self.intermediate_embeddings, self.hq_token_only))
         out = self.sam(image_embeddings=self.image_embeddings, multimask_output=multimask_output, **kw)
         return out.pred_masks[0], out.iou_scores[0]                       # [Pb, C, 256, 256], [Pb, C]
 
@@ -140,7 +164,10 @@ class SamSession:
         """points [Pb, P, 2] / labels [Pb, P] (1 foreground, 0 background, -1 padding) / boxes [Pb, 4], all in original pixels;
         mask_input: [256, 256] low-resolution logits of an earlier call (shared by the prompt sets).  Returns
         (masks bool [Pb, C, H, W] -- the fp32 values with return_logits --, iou_scores [Pb, C], low_res_logits
-        [Pb, C, 256, 256]); C = 3 with multimask_output, else 1.  attention_similarity [1 | Pb, 1, 1, N] / target_embedding
+        [Pb, C, 256, 256]); C = 3 with multimask_output, else 1.  ORDER with multimask_output: SAM's mask tokens 1, 2, 3 for a
+        `SamModelHIP`; for a `SamHQModelHIP` the three masks and scores are sorted by predicted IoU, descending (HF
+        `SamHQMaskDecoder`), and with the session's hq_token_only the masks are the ONE HQ mask per prompt set ([Pb, 1, ..])
+        while iou_scores stays [Pb, 3].  attention_similarity [1 | Pb, 1, 1, N] / target_embedding
         [..., 256]: HF's PerSAM hooks, passed through to `SamModelHIP.forward` (device tensors)."""
         low, iou = self._low_res(points, labels, boxes, mask_input, multimask_output, attention_similarity, target_embedding)
         Pb, C, h, w = low.shape
@@ -153,9 +180,9 @@ class SamSession:
         return masks.view(Pb, C, H, W), iou, low
 
 
-def inference_prompts(model, image, **prompts):
-    """One-shot `SamSession(model, image).predict(**prompts)`."""
-    return SamSession(model, image).predict(**prompts)
+def inference_prompts(model, image, hq_token_only=False, **prompts):
+    """One-shot `SamSession(model, image, hq_token_only).predict(**prompts)`."""
+    return SamSession(model, image, hq_token_only=hq_token_only).predict(**prompts)
 
 
 def filter_candidates(iou, score, pred_iou_thresh, stability_score_thresh):
@@ -207,7 +234,7 @@ def _region_nms(info, offsets, nms_thresh):
 @torch.no_grad()
 def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stability_score_thresh=0.95,
                    stability_score_offset=1.0, mask_threshold=0.0, crops_nms_thresh=0.7, crop_n_layers=0, output='rle',
-                   mask_batch=64, session=None, _stages=None, min_mask_region_area=0):
+                   mask_batch=64, session=None, _stages=None, min_mask_region_area=0, hq_token_only=False):
     """HF's mask generation (`MaskGenerationPipeline` over `SamImageProcessor.generate_crop_boxes` / `filter_masks` /
     `post_process_for_mask_generation`) for the whole image as one crop: a points_per_side^2 grid of single-point prompts,
     three masks each, filtered by predicted IoU and stability score, NMS on the mask boxes.  Returns `InstanceData` in NMS
@@ -215,7 +242,9 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     IoU), masks = list of uncompressed RLE dicts (output='rle') or bool [k, H, W] (output='dense').
     min_mask_region_area > 0: segment-anything's `postprocess_small_regions` on the NMS's survivors, as in `SamMaskGenerator`
     (holes and islands smaller than that are removed, a second NMS drops what became a duplicate; `region_changed` bool [k]).
-    session: an existing `SamSession` of the image (then `model` / `image` are not read); mask_batch: full-resolution masks
+    hq_token_only (a `SamHQModelHIP`): ONE candidate per point, the HQ mask, scored with the highest of the three predicted
+    IoUs (the first: they come sorted); default: the three SAM + HQ masks in that order.
+    session: an existing `SamSession` of the image (then `model` / `image` / hq_token_only are not read); mask_batch: full-resolution masks
     built per kernel call; _stages: a dict that receives the stage tensors (candidate logits, IoU, scores, kept indices,
     boxes) -- the stage-wise parity tests read them."""
     if crop_n_layers:
@@ -224,12 +253,13 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
     if output not in ('rle', 'dense'):
         raise ValueError("output must be 'rle' or 'dense'")
     area = _check_region_area(min_mask_region_area)
-    s = session if session is not None else SamSession(model, image)
+    s = session if session is not None else SamSession(model, image, hq_token_only=hq_token_only)
     H, W = s.original_size
     S = s.sam.image_size
     # HF _generate_crop_boxes: grid * (W, H) of the crop (= the image), then _normalize_coordinates inside predict
     pts = point_grid(points_per_side) * np.array([[W, H]], dtype=np.float64)
     low, iou = s._low_res(pts[:, None, :], None, None, None, True)
+    iou = iou[:, :low.shape[1]]                                    # (hq_token_only: one mask, the best score)
     K = low.shape[0] * low.shape[1]
     low = low.reshape(K, low.shape[-2], low.shape[-1])
     iou = iou.reshape(K)
@@ -308,6 +338,9 @@ class PerSam:
 
     def __init__(self, sam, ref_image, ref_mask):
         self.sam = _sam_of(sam)
+        if _is_hq(self.sam):
+            raise NotImplementedError('PerSam with a SamHQModelHIP: PerSam feeds the decoder image embeddings it has built '
+                                      'itself (batched, without the ViT\'s early feature the HQ branch needs); use a SamModelHIP')
         dev = next(self.sam.parameters()).device
         ops.require_device(dev)
         self.device = dev
@@ -505,17 +538,20 @@ class SamMaskGenerator:
     `DEFAULT_BATCH_CANDIDATES` candidates per batch.  `generate(image)`
     returns `InstanceData` in NMS order, everything in IMAGE coordinates: bboxes fp32 [k, 4], scores fp32 [k], masks (list of
     uncompressed RLE dicts of size [H, W], or bool [k, H, W] with output='dense'), crop_index int64 [k].  With
-    crop_n_layers=0 the result is `generate_masks`' bit for bit."""
+    crop_n_layers=0 the result is `generate_masks`' bit for bit.  hq_token_only (a `SamHQModelHIP`): as in `generate_masks`."""
 
     def __init__(self, sam, points_per_side=32, pred_iou_thresh=0.88, stability_score_thresh=0.95, stability_score_offset=1.0,
                  mask_threshold=0.0, crops_nms_thresh=0.7, crop_n_layers=1, crop_overlap_ratio=512 / 1500,
-                 crop_n_points_downscale_factor=1, crop_batch=None, output='rle', mask_batch=64, min_mask_region_area=0):
+                 crop_n_points_downscale_factor=1, crop_batch=None, output='rle', mask_batch=64, min_mask_region_area=0,
+                 hq_token_only=False):
         if output not in ('rle', 'dense'):
             raise ValueError("output must be 'rle' or 'dense'")
         if int(crop_n_layers) < 0:
             raise ValueError('crop_n_layers must be >= 0')
         self.min_mask_region_area = _check_region_area(min_mask_region_area)
         self.sam = _sam_of(sam)
+        self.hq_token_only = bool(hq_token_only)          # a SamHQModelHIP: one candidate per point (see generate_masks)
+        _hq_kwargs(self.sam, None, hq_token_only)
         self.crop_n_layers, self.crop_overlap_ratio = int(crop_n_layers), float(crop_overlap_ratio)
         self.grids = []
         for l in range(self.crop_n_layers + 1):
@@ -594,12 +630,13 @@ class SamMaskGenerator:
             with phase('crop front end'):
                 pv = ops.crops_resize_pad(img, front_t[c0:c1], (S, S), PIXEL_MEAN, normalise=(PIXEL_MEAN, PIXEL_STD, False))
             with phase('encoder'):
-                emb = sam.get_image_embeddings(pv)
+                emb, inter = _embed(sam, pv)
             with phase('decoder'):
                 p = torch.from_numpy(np.stack(pts[c0:c1], 0)).to(torch.float32).to(dev)                 # [B, Pb, 1, 2]
                 out = sam(image_embeddings=emb, input_points=p, multimask_output=True,
-                          input_labels=torch.ones((B, Pb, 1), dtype=torch.int32, device=dev))
-                low, iou = out.pred_masks, out.iou_scores
+                          input_labels=torch.ones((B, Pb, 1), dtype=torch.int32, device=dev),
+                          **_hq_kwargs(sam, inter, self.hq_token_only))
+                low, iou = out.pred_masks, out.iou_scores[..., :out.pred_masks.shape[2]]
                 K = B * Pb * low.shape[2]
                 low, iou = low.reshape(K, low.shape[-2], low.shape[-1]), iou.reshape(K)
             with phase('scoring'):

@@ -15,7 +15,7 @@ from .detectors import BaseDetectorHIP, SAMSegMaskRCNN
 from .necks import conv3x3_weight, fold_bn
 from .nnutil import HIPModule, add_param, infer_sam_arch, load_checkpoint_into, nchw_view, nhwc_view
 from .registry import MODELS
-from .sam_decoder import SamMaskDecoderHIP, _PosEmb, _PromptEncoder, image_wide_table, persam_hooks
+from .sam_decoder import SamHQMaskDecoderHIP, SamMaskDecoderHIP, _PosEmb, _PromptEncoder, image_wide_table, persam_hooks
 from .sam_encoder import SamVisionEncoderHIP
 from .structures import InstanceData
 
@@ -255,6 +255,14 @@ class SamModelHIP(HIPModule):
     def get_image_embeddings(self, pixel_values):
         return self.vision_encoder(pixel_values, output_hidden_states=False)[0]
 
+    def _embed_for_forward(self, pixel_values, call_kw):
+        """image embeddings of a forward() given pixel_values; call_kw: forward's further keyword arguments (may be updated)"""
+        return self.get_image_embeddings(pixel_values)
+
+    def _decode_extra(self, image_embeddings, call_kw):
+        """further keyword arguments of `mask_decoder.decode` (SamHQModelHIP: the per-image HQ features)"""
+        return {}
+
     def _mask_embed_prm(self):
         sm = self.prompt_encoder.mask_embed
         return dict(conv1_w=sm.conv1.weight.detach().contiguous(), conv1_b=sm.conv1.bias.detach(),
@@ -324,7 +332,7 @@ class SamModelHIP(HIPModule):
                 raise ValueError('You should provide as many bounding boxes as input points per box. Got '
                                  f'{input_points.shape[1]} and {input_boxes.shape[1]}.')
         if image_embeddings is None:
-            image_embeddings = self.get_image_embeddings(pixel_values)
+            image_embeddings = self._embed_for_forward(pixel_values, kwargs)
         if input_points is not None and input_labels is None:
             input_labels = torch.ones_like(input_points[:, :, :, 0], dtype=torch.int)
         B = image_embeddings.shape[0]
@@ -346,7 +354,9 @@ class SamModelHIP(HIPModule):
         roi_img = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Pb)
         # HF's PerSAM hooks (HF:183-187, 386-387) in the forms persam_hooks names; everything else raises NotImplementedError
         emb_hw = image_embeddings.shape[-2] * image_embeddings.shape[-1]
-        bias, te = persam_hooks(attention_similarity, target_embedding, B, Pb, emb_hw, 1 + 4 + sparse.shape[1])
+        bias, te = persam_hooks(attention_similarity, target_embedding, B, Pb, emb_hw,
+                                self.mask_decoder.n_output_tokens + sparse.shape[1])
+        extra = self._decode_extra(image_embeddings, kwargs)
         pe = self.prompt_encoder
         multimask_output = bool(multimask_output)
         if input_masks is not None:
@@ -361,14 +371,78 @@ class SamModelHIP(HIPModule):
                                      self._mask_embed_prm(), g, gw)
             masks, iou = self.mask_decoder.decode(None, self.get_image_wide_positional_embeddings(), sparse, None, roi_img,
                                                   src_rows=src, hw=(g, gw), multimask_output=multimask_output, attn_bias=bias,
-                                                  target_rows=te)
+                                                  target_rows=te, **extra)
         else:
             masks, iou = self.mask_decoder.decode(image_embeddings, self.get_image_wide_positional_embeddings(), sparse,
                                                   pe.no_mask_embed.weight.reshape(-1), roi_img,
-                                                  multimask_output=multimask_output, attn_bias=bias, target_rows=te)
+                                                  multimask_output=multimask_output, attn_bias=bias, target_rows=te, **extra)
         h, w = masks.shape[-2:]
         C = masks.shape[1]
-        return SamImageSegmentationOutput(iou.reshape(B, Pb, C), masks.reshape(B, Pb, C, h, w))
+        return SamImageSegmentationOutput(iou.reshape(B, Pb, iou.shape[1]), masks.reshape(B, Pb, C, h, w))
+
+
+class SamHQModelHIP(SamModelHIP):
+    """HF `SamHQModel` (transformers models/sam_hq/modeling_sam_hq.py:1230-1487, "HQ:" below): `SamModelHIP` with the HQ mask
+    decoder (`SamHQMaskDecoderHIP`, csrc/sam_hq.hip) and the ViT's early feature.  Same call as `SamModelHIP.forward` plus
+    `hq_token_only` (only the HQ mask instead of SAM's masks + the HQ mask) and `intermediate_embeddings` (with
+    `image_embeddings`: the second item of `get_image_embeddings`).  With multimask_output the three masks and scores come
+    ordered by predicted IoU, descending (HQ:1042-1055) -- unlike `SamModel`.
+    The per-image HQ features (four ConvTransposes, HQ:964-975) are kept for the embedding they were computed from: calls
+    that pass the same `image_embeddings` / `intermediate_embeddings` tensors again (a `SamSession`) reuse them."""
+
+    def __init__(self, arch='huge', image_size=1024):
+        super().__init__(arch=arch, image_size=image_size)
+        from .nnutil import SAM_ARCH
+        self.mask_decoder = SamHQMaskDecoderHIP(vit_dim=SAM_ARCH[arch]['hidden'])
+        self._hq_cache = None                 # (packed weights, image_embeddings, intermediate | None, features)
+
+    def _apply(self, fn, *a, **kw):
+        self._hq_cache = None
+        return super()._apply(fn, *a, **kw)
+
+    def get_image_embeddings(self, pixel_values):
+        """HQ:1281-1282: (image_embeddings [B, 256, g, g], [the hidden state after the first global-attention layer, [B, g, g, D]])"""
+        emb, inter = self.vision_encoder.forward_with_intermediate(pixel_values)
+        return emb, [inter]
+
+    def _embed_for_forward(self, pixel_values, call_kw):
+        emb, call_kw['intermediate_embeddings'] = self.get_image_embeddings(pixel_values)     # (HQ:1456-1459: the encoder's own)
+        return emb
+
+    @staticmethod
+    def _same(a, b):
+        if a is None or b is None:
+            return a is b
+        return a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+                          and a._version == b._version)
+
+    def hq_features(self, image_embeddings, intermediate=None):
+        """`SamHQMaskDecoderHIP.hq_features`, once per (weights, embedding): the cache holds its key tensors, so a hit means
+        the same memory in the same version."""
+        dec = self.mask_decoder
+        if dec._packed is None:
+            dec._pack()
+        c = self._hq_cache
+        if c is not None and c[0] is dec._packed and self._same(c[1], image_embeddings) and self._same(c[2], intermediate):
+            return c[3]
+        f = dec.hq_features(image_embeddings, intermediate)
+        self._hq_cache = (dec._packed, image_embeddings, intermediate, f)
+        return f
+
+    def _decode_extra(self, image_embeddings, call_kw):
+        inter = call_kw.get('intermediate_embeddings')
+        inter = inter[0] if inter is not None and len(inter) > 0 else None
+        return dict(hq_features=self.hq_features(image_embeddings, inter), hq_token_only=bool(call_kw.get('hq_token_only', False)))
+
+    @torch.no_grad()
+    def forward(self, pixel_values=None, input_points=None, input_labels=None, input_boxes=None, input_masks=None,
+                image_embeddings=None, multimask_output=True, hq_token_only=False, attention_similarity=None,
+                target_embedding=None, intermediate_embeddings=None, **kwargs):
+        return super().forward(pixel_values=pixel_values, input_points=input_points, input_labels=input_labels,
+                               input_boxes=input_boxes, input_masks=input_masks, image_embeddings=image_embeddings,
+                               multimask_output=multimask_output, attention_similarity=attention_similarity,
+                               target_embedding=target_embedding, hq_token_only=hq_token_only,
+                               intermediate_embeddings=intermediate_embeddings, **kwargs)
 
 
 @MODELS.register_module()
