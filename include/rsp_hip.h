@@ -725,6 +725,34 @@ int rsp_persam_locate(const float* low_res, int32_t k, int32_t h, int32_t w, int
                       int32_t crop_w, int32_t out_h, int32_t out_w, int32_t g, void* workspace, int64_t workspace_bytes,
                       float* stats, int32_t* xy, float* attn_sim, rsp_stream_t stream);
 
+/* PerSAM-F (persam_f.py of the same code): `logits_high = (logits_high * weights).sum(0)`, `dice_loss + focal_loss` of it     */
+/* against the reference mask, `loss.backward(); optimizer.step(); scheduler.step()` -- without autograd and without an        */
+/* image-sized tensor.  low_res [k, 3, h, w]: per problem the three low-resolution logit maps of ONE decoder pass; the        */
+/* geometry is rsp_mask_post_logits' and F_j(i) below is that entry point's `out_val` of map j (same device functions).  gt    */
+/* uint8 [k, out_h, out_w], t = (gt != 0).  With w0 = 1 - w1 - w2, z = sum_j w_j F_j, p = sigmoid(z):                           */
+/*   loss = 1 - (2 sum p t + 1) / (sum p + sum t + 1)                                         (dice)                          */
+/*        + mean(alpha_t * BCEWithLogits(z, t) * (1 - p_t)^2)                                  (focal, gamma = 2)              */
+/* and g_j = d loss / d w_j for j = 1, 2, from nine sums over the field ("PerSAM-F").  z in fp64, the rest  */
+/* of a pixel in fp32 (precise expf / log1pf), sums as fp64 block partials added in block order: no floating-point atomics,  */
+/* two runs give the same bits.  The k problems share one geometry and are independent.                                      */
+/* rsp_persam_f_loss_grad: one evaluation at weights fp32 [k, 2] = (w1, w2); out fp64 [k, 3] = loss, g1, g2.                   */
+/* rsp_persam_f_fit: the whole fit, enqueued on the stream (2 launches per epoch, no host read): w1 = w2 = fp32 1 / 3, then  */
+/* `epochs` steps of torch.optim.AdamW(lr, betas, eps, weight_decay) (decoupled decay, bias-corrected, denom =                */
+/* sqrt(v) / sqrt(bc2) + eps) under CosineAnnealingLR(T_max = epochs): step e uses lr / 2 (1 + cos(pi e / epochs)); the      */
+/* optimiser state is fp64 on the device.  weights fp32 [k, 3] = w0, w1, w2 after the last step; history fp64                 */
+/* [k, epochs, 3] or NULL = the loss and gradient each step was taken from (row 0: rsp_persam_f_loss_grad at 1 / 3).          */
+/* workspace: rsp_persam_f_workspace_bytes(k, out_h, out_w, epochs) bytes, 8-byte aligned (-1 for arguments the calls would   */
+/* refuse).  RSP_EINVAL: k < 1, epochs < 1, an invalid geometry, out_h * out_w >= 2^31, a null pointer (history excepted), a   */
+/* workspace that is too small.                                                                                              */
+int64_t rsp_persam_f_workspace_bytes(int32_t k, int32_t out_h, int32_t out_w, int32_t epochs);
+int rsp_persam_f_loss_grad(const float* low_res, const uint8_t* gt, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb,
+                           int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w, const float* weights, float alpha,
+                           void* workspace, int64_t workspace_bytes, double* out, rsp_stream_t stream);
+int rsp_persam_f_fit(const float* low_res, const uint8_t* gt, int32_t k, int32_t h, int32_t w, int32_t Hb, int32_t Wb,
+                     int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w, int32_t epochs, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, float alpha, void* workspace, int64_t workspace_bytes,
+                     float* weights, double* history, rsp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* Small-region cleanup of masks (segment-anything utils/amg.py `remove_small_regions`, used by                            */
 /* automatic_mask_generator.py `postprocess_small_regions`; there cv2.connectedComponentsWithStats on the host)           */

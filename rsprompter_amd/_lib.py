@@ -13,6 +13,7 @@ c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_int64 = ctypes.c_int64
 c_float = ctypes.c_float
+c_double = ctypes.c_double
 
 
 class RspGemmDesc(ctypes.Structure):
@@ -222,6 +223,12 @@ PROTOTYPES = {
     "rsp_persam_locate_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "rsp_persam_locate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                   c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rsp_persam_f_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "rsp_persam_f_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rsp_persam_f_fit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_double, c_double, c_double, c_double, c_double, c_float, c_void_p, c_int64, c_void_p, c_void_p,
+                                 c_void_p]),
     "rsp_mask_regions_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "rsp_mask_remove_small_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),

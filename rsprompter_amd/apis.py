@@ -204,7 +204,7 @@ class DetInferencer:
 
 
 from .large_image import inference_large_image  # noqa: E402,F401  (sliced inference on large scenes)
-from .sam_prompts import PerSam, SamMaskGenerator, SamSession, generate_masks, inference_prompts  # noqa: E402,F401  (promptable SAM)
+from .sam_prompts import PerSam, PerSamF, SamMaskGenerator, SamSession, generate_masks, inference_prompts  # noqa: E402,F401  (promptable SAM)
 from .samdet import SamHQModelHIP  # noqa: E402,F401  (HF SamHQModel on HIP kernels, DESIGN §15 "SAM-HQ")
 
 

@@ -1237,6 +1237,65 @@ def persam_locate(low_res, img_shape, crop_hw, out_hw, g):
     return stats, xy, attn
 
 
+PERSAM_F_ALPHA = 0.25                      # the focal loss's alpha; gamma = 2 is fixed in the kernel
+PERSAM_F_ADAMW = dict(beta1=0.9, beta2=0.999, eps=1e-4, weight_decay=0.01)
+
+
+def _persam_f_args(low_res, gt, img_shape, crop_hw, out_hw, epochs, who):
+    """(k, h, w, geometry, gt as uint8, workspace, bytes) of the PerSAM-F entry points"""
+    lib = _lib.load()
+    _chk_f32(low_res, "low_res")
+    if low_res.dim() != 4 or low_res.shape[1] != 3 or not low_res.is_contiguous() or low_res.shape[0] < 1:
+        raise ValueError(f"{who} expects contiguous [k, 3, h, w] logits, k >= 1")
+    k, _, h, w = low_res.shape
+    geom = _mask_geometry(img_shape, crop_hw, out_hw)
+    if gt.dtype not in (torch.bool, torch.uint8) or tuple(gt.shape) != (k, geom[4], geom[5]) or gt.device != low_res.device:
+        raise ValueError(f"gt: bool or uint8 [{k}, {geom[4]}, {geom[5]}] on the device of low_res")
+    gt = gt.contiguous()
+    gt = gt.view(torch.uint8) if gt.dtype == torch.bool else gt
+    nws = int(lib.rsp_persam_f_workspace_bytes(k, geom[4], geom[5], int(epochs)))
+    if nws < 0:
+        raise ValueError(f"{who}: unsupported geometry {tuple(out_hw)} / {epochs} epochs for {k} problems")
+    ws = torch.empty((nws // 8,), dtype=torch.int64, device=low_res.device)
+    return lib, k, h, w, geom, gt, ws, nws
+
+
+def persam_f_loss_grad(low_res, gt, img_shape, crop_hw, out_hw, weights, alpha=PERSAM_F_ALPHA):
+    """PerSAM-F's loss and its gradient at given weights: low_res [k, 3, h, w] (the three logit maps of one decoder pass per
+    problem), gt bool / uint8 [k, out_h, out_w], the geometry of mask_post_logits, weights fp32 [k, 2] = (w1, w2) with
+    w0 = 1 - w1 - w2 -> fp64 [k, 3] = dice + focal loss of sigmoid(sum_j w_j field_j) against gt, d loss / d w1, d loss / d w2."""
+    lib, k, h, w, geom, gt, ws, nws = _persam_f_args(low_res, gt, img_shape, crop_hw, out_hw, 1, "persam_f_loss_grad")
+    _chk_f32(weights, "weights")
+    if tuple(weights.shape) != (k, 2) or not weights.is_contiguous():
+        raise ValueError(f"weights: contiguous [{k}, 2]")
+    out = torch.empty((k, 3), dtype=torch.float64, device=low_res.device)
+    _timed('persam_f_sums_kernel', 0, 12.0 * k * h * w + 1.0 * gt.numel(),
+           lambda: _lib.check(lib.rsp_persam_f_loss_grad(low_res.data_ptr(), gt.data_ptr(), k, h, w, *geom, weights.data_ptr(),
+                                                         float(alpha), ws.data_ptr(), nws, out.data_ptr(), _stream()),
+                              "rsp_persam_f_loss_grad"))
+    return out
+
+
+def persam_f_fit(low_res, gt, img_shape, crop_hw, out_hw, epochs=1000, lr=1e-3, alpha=PERSAM_F_ALPHA, want_history=False):
+    """PerSAM-F's fit of the mask weights, enqueued whole (nothing is read on the host): from w1 = w2 = 1 / 3, `epochs` steps
+    of AdamW(lr, betas=(0.9, 0.999), eps=1e-4, weight_decay=0.01) under CosineAnnealingLR(T_max=epochs) on
+    persam_f_loss_grad's loss.  -> weights fp32 [k, 3] = w0, w1, w2 (and, with want_history, fp64 [k, epochs, 3] = the loss
+    and gradient each step was taken from)."""
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError("persam_f_fit: epochs must be >= 1")
+    lib, k, h, w, geom, gt, ws, nws = _persam_f_args(low_res, gt, img_shape, crop_hw, out_hw, epochs, "persam_f_fit")
+    dev = low_res.device
+    weights = torch.empty((k, 3), dtype=torch.float32, device=dev)
+    hist = torch.empty((k, epochs, 3), dtype=torch.float64, device=dev) if want_history else None
+    o = PERSAM_F_ADAMW
+    _timed('persam_f_fit', 0, epochs * (12.0 * k * h * w + 1.0 * gt.numel()),
+           lambda: _lib.check(lib.rsp_persam_f_fit(low_res.data_ptr(), gt.data_ptr(), k, h, w, *geom, epochs, float(lr), o['beta1'],
+                                                   o['beta2'], o['eps'], o['weight_decay'], float(alpha), ws.data_ptr(), nws,
+                                                   weights.data_ptr(), _ptr(hist), _stream()), "rsp_persam_f_fit"))
+    return (weights, hist) if want_history else weights
+
+
 CROP_TABLE_COLS = 12    # rsp_mask_score_box_crops: Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H
 
 

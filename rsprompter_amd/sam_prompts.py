@@ -332,7 +332,7 @@ class PerSam:
     output='dense'), score (predicted IoU), bbox [x0, y0, x1, y1] (inclusive maxima, zeros for an empty mask), points
     [[x+, y+], [x-, y-]] and point_sims [s+, s-] (the field's maximum and minimum), all in original pixels.  A field that
     is constant has no peak: the points are pixel 0 and the attention similarity 0.5 everywhere (PerSAM yields NaN).
-    Not implemented: PerSAM-F, topk > 1, several references."""
+    The fine-tuned variant of the paper, PerSAM-F, is `PerSamF`.  Not implemented: topk > 1, several references."""
 
     RLE_CAP = 4096
 
@@ -417,12 +417,52 @@ class PerSam:
         ar = torch.arange(iou.shape[0], device=iou.device)
         return out.pred_masks[:, 0][ar, best].contiguous(), iou[ar, best], best
 
+    N_POINTS = 2                 # the peak and the trough of the similarity field
+
+    def _prompts(self, xy, scale, B):
+        """(input_points [B, 1, P, 2] in input pixels, input_labels [B, 1, P]) of locate's xy: HF _normalize_coordinates
+        (float64, then fp32 as the processor's tensors), on the device"""
+        P = self.N_POINTS
+        pts = (xy[:, :2 * P].reshape(B, 1, P, 2).to(torch.float64) * scale).to(torch.float32)
+        labels = torch.tensor([[[1, 0][:P]]], dtype=torch.int32).to(xy.device).expand(B, 1, P).contiguous()
+        return pts, labels
+
+    def _box_prompt(self, low, geo, scale):
+        """(box int32 [B, 4] of the mask of `low` at original resolution, the same as input_boxes [B, 1, 4])"""
+        box = ops.mask_score_box(low, *geo)[:, 3:7]
+        bscale = torch.cat([scale, scale])
+        return box, (box.to(torch.float64) * bscale).to(torch.float32).reshape(low.shape[0], 1, 4)
+
+    def _decode(self, emb, pts, labels, attn, geo, scale, cascade, st):
+        """PerSAM's decoder passes: (logits [B, h, w], predicted IoU [B]) of the final mask; the stages go into `st`"""
+        sam, phase = self.sam, self._phase
+        B, g = emb.shape[0], sam.vision_encoder.grid
+        with phase('decoder pass 1'):
+            out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, multimask_output=False,
+                      attention_similarity=attn.view(B, 1, 1, g * g), target_embedding=self.target_embedding)
+            low, iou = out.pred_masks[:, 0, 0].contiguous(), out.iou_scores[:, 0, 0]
+        st.update(low1=low, iou1=iou)
+        if cascade:
+            with phase('decoder pass 2'):
+                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_masks=low.unsqueeze(1),
+                          multimask_output=True)
+                low, iou, best2 = self._best(out)
+                st.update(low2=out.pred_masks[:, 0], iou2=out.iou_scores[:, 0], best2=best2)
+            with phase('decoder pass 3'):
+                box, boxes = self._box_prompt(low, geo, scale)
+                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_boxes=boxes,
+                          input_masks=low.unsqueeze(1), multimask_output=True)
+                low, iou, best3 = self._best(out)
+                st.update(box2=box, boxes=boxes, low3=out.pred_masks[:, 0], iou3=out.iou_scores[:, 0], best3=best3)
+        return low, iou
+
     def _batch(self, imgs, hw, output, cascade, _stages):
         sam, dev, phase = self.sam, self.device, self._phase
         S, g = sam.image_size, sam.vision_encoder.grid
-        B = len(imgs)
+        B, P = len(imgs), self.N_POINTS
         H, W = hw
         nhw = preprocess_shape(hw, S)
+        geo = ((S, S), nhw, hw)
         with phase('front end'):
             pv = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
             for b, im in enumerate(imgs):
@@ -432,33 +472,14 @@ class PerSam:
         with phase('similarity'):
             sim, low0 = ops.persam_similarity(self._rows(emb), self.target_feature, B, g, g)
         with phase('locate'):
-            stats, xy, attn = ops.persam_locate(low0, (S, S), nhw, hw, g)
-            # HF _normalize_coordinates (float64, then fp32 as the processor's tensors), on the device
+            stats, xy, attn = ops.persam_locate(low0, *geo, g)
             scale = torch.tensor([nhw[1] / W, nhw[0] / H], dtype=torch.float64).to(dev)
-            pts = (xy[:, :4].reshape(B, 1, 2, 2).to(torch.float64) * scale).to(torch.float32)
-            labels = torch.tensor([[[1, 0]]], dtype=torch.int32).to(dev).expand(B, 1, 2).contiguous()
-        with phase('decoder pass 1'):
-            out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, multimask_output=False,
-                      attention_similarity=attn.view(B, 1, 1, g * g), target_embedding=self.target_embedding)
-            low, iou = out.pred_masks[:, 0, 0].contiguous(), out.iou_scores[:, 0, 0]
-        st = dict(sim=sim, low_sim=low0, stats=stats, xy=xy, attn_sim=attn, points=pts, low1=low, iou1=iou)
-        if cascade:
-            with phase('decoder pass 2'):
-                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_masks=low.unsqueeze(1),
-                          multimask_output=True)
-                low, iou, best2 = self._best(out)
-                st.update(low2=out.pred_masks[:, 0], iou2=out.iou_scores[:, 0], best2=best2)
-            with phase('decoder pass 3'):
-                box = ops.mask_score_box(low, (S, S), nhw, hw)[:, 3:7]
-                bscale = torch.cat([scale, scale])
-                boxes = (box.to(torch.float64) * bscale).to(torch.float32).reshape(B, 1, 4)
-                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_boxes=boxes,
-                          input_masks=low.unsqueeze(1), multimask_output=True)
-                low, iou, best3 = self._best(out)
-                st.update(box2=box, boxes=boxes, low3=out.pred_masks[:, 0], iou3=out.iou_scores[:, 0], best3=best3)
+            pts, labels = self._prompts(xy, scale, B)
+        st = dict(sim=sim, low_sim=low0, stats=stats, xy=xy, attn_sim=attn, points=pts)
+        low, iou = self._decode(emb, pts, labels, attn, geo, scale, cascade, st)
         with phase('masks + run lengths'):
-            masks = ops.mask_post_logits(low, (S, S), nhw, hw)
-            score = ops.mask_score_box(low, (S, S), nhw, hw)
+            masks = ops.mask_post_logits(low, *geo)
+            score = ops.mask_score_box(low, *geo)
             if output == 'rle':
                 counts = torch.empty((B, self.RLE_CAP), dtype=torch.int32, device=dev)
                 ws = torch.empty((B, self.RLE_CAP), dtype=torch.int32, device=dev)
@@ -469,21 +490,123 @@ class PerSam:
             _stages.setdefault('batches', []).append(st)
         # ---- the transfer of the batch's results: the first host reads since the upload ----
         with phase('transfer'):
-            ints = torch.cat([xy[:, :4], score[:, 3:7]] + ([n.view(B, 1)] if output == 'rle' else []), 1).cpu()
-            flts = torch.cat([stats[:, :2], iou.reshape(B, 1)], 1).cpu()
+            ints = torch.cat([xy[:, :2 * P], score[:, 3:7]] + ([n.view(B, 1)] if output == 'rle' else []), 1).cpu()
+            flts = torch.cat([stats[:, :P], iou.reshape(B, 1)], 1).cpu()
+            extra = self._extra_results()
             if output == 'rle':
-                nn = ints[:, 8].tolist()
+                nn = ints[:, 2 * P + 4].tolist()
                 if min(nn) < 0:                                # a mask with more runs than RLE_CAP: again with room (rare)
                     counts, n = ops.mask_rle_counts(masks, cap=1 << (-min(nn) - 1).bit_length())
                     nn = n.cpu().tolist()
                 counts = counts[:, :max(nn)].cpu().numpy()
         res = []
         for b in range(B):
-            r = dict(score=float(flts[b, 2]), bbox=ints[b, 4:8].tolist(), points=ints[b, :4].reshape(2, 2).tolist(),
-                     point_sims=flts[b, :2].tolist())
+            r = dict(score=float(flts[b, P]), bbox=ints[b, 2 * P:2 * P + 4].tolist(), points=ints[b, :2 * P].reshape(P, 2).tolist(),
+                     point_sims=flts[b, :P].tolist(), **extra)
             r['mask'] = dict(size=[H, W], counts=counts[b, :nn[b]].tolist()) if output == 'rle' else masks[b]
             res.append(r)
         return res
+
+    def _extra_results(self):
+        """further entries of every result dict (read inside the transfer phase)"""
+        return {}
+
+
+# --------------------------------------------------------------------------------------------------- PerSAM-F (DESIGN §15)
+class PerSamF(PerSam):
+    """PerSAM-F, the variant of the same paper that LEARNS which of SAM's three mask scales the object lives at (persam_f.py
+    of the paper's code): two numbers, fitted on the one labelled reference, weigh the three masks of the first decoder
+    pass.  Nothing is back-propagated through SAM.
+
+    `PerSamF(sam, ref_image, ref_mask, epochs=1000, lr=1e-3)`, arguments as for `PerSam`.  The constructor (1) embeds the
+    reference and selects cells as `PerSam` does (no selected cell: the same ValueError, after the constructor's only host
+    read); (2) `.target_feature` = unit vector of mean(rows) / 2 + max(rows) / 2 over the selected embedding rows (the mean
+    is `rsp_persam_target`'s, the masked maximum and the normalisation torch, once per reference); (3) the similarity of the
+    reference with itself, `rsp_persam_locate`: its peak is the one positive point -- no negative point, no
+    `attention_similarity`, no `target_embedding` anywhere here; (4) ONE decoder pass on the reference, three masks; (5)
+    `rsp_persam_f_fit`: from w1 = w2 = 1 / 3 (w0 = 1 - w1 - w2), `epochs` steps of AdamW(lr, eps=1e-4, weight_decay=0.01)
+    under a cosine schedule on the dice + focal loss of sigmoid(sum_k w_k field_k) against `ref_mask` at original resolution;
+    a step is one traversal of the three fields and a one-wave update, the whole fit is enqueued without a host read.
+    `.weights` fp32 [3] = (w0, w1, w2) and `.loss_history` fp64 [epochs, 3] = (loss, d / d w1, d / d w2) each step was taken
+    from stay on the device; `.cell_mask`, `.cells` as in `PerSam`; `.ref_point` (int32 [x, y]), `.ref_point_sim` and
+    `.ref_low_res` [1, 3, 4g, 4g] keep what the fit saw.
+
+    `segment(images, batch_size=8, output='rle')`: grouping, batching and results as `PerSam.segment`.  Per batch: similarity
+    and locate with the new target, the peak alone as prompt; pass 1: three masks, no hooks, `low_w = sum_k w_k low_k` in fp32
+    (resampling is linear and the weights sum to 1: the field of low_w is the paper's weighted sum of the up-sampled logits
+    up to rounding); pass 2: the point + the box of `field(low_w) > 0` + low_w as `input_masks`, three masks, best by
+    predicted IoU (first index on a tie); pass 3: the point + the box of that mask + its logits, best by IoU; mask, score,
+    box and run lengths as `PerSam` makes them.  Nothing is read on the host between a batch's upload and the transfer of
+    its results.  Results as `PerSam`'s with points [[x+, y+]], point_sims [s+] and `weights` [w0, w1, w2] added.
+    Not implemented: topk > 1, several references."""
+
+    N_POINTS = 1
+
+    def __init__(self, sam, ref_image, ref_mask, epochs=1000, lr=1e-3):
+        self.sam = _sam_of(sam)
+        if _is_hq(self.sam):
+            raise NotImplementedError('PerSamF with a SamHQModelHIP: PerSamF feeds the decoder image embeddings it has built '
+                                      'itself (batched, without the ViT\'s early feature the HQ branch needs); use a SamModelHIP')
+        if int(epochs) < 1:
+            raise ValueError('PerSamF: epochs must be >= 1')
+        dev = next(self.sam.parameters()).device
+        ops.require_device(dev)
+        self.device = dev
+        self._phase = lambda name: contextlib.nullcontext()
+        S, g = self.sam.image_size, self.sam.vision_encoder.grid
+        ref_image = self._as_image(ref_image)
+        if isinstance(ref_mask, np.ndarray):
+            ref_mask = torch.from_numpy(np.ascontiguousarray(ref_mask))
+        if ref_mask.dim() != 2 or tuple(ref_mask.shape) != tuple(ref_image.shape[:2]):
+            raise ValueError('ref_mask: expected [H, W], the size of ref_image')
+        hw = (int(ref_image.shape[0]), int(ref_image.shape[1]))
+        nhw = preprocess_shape(hw, S)
+        geo = ((S, S), nhw, hw)
+        with torch.no_grad():
+            pv = ops.resize_pad(ref_image.to(dev), nhw, (S, S), PIXEL_MEAN, normalise=(PIXEL_MEAN, PIXEL_STD, False)).unsqueeze(0)
+            emb = self.sam.get_image_embeddings(pv)
+            gt = (ref_mask.to(dev) != 0)
+            self.cell_mask = self.cells_of(gt, S, g)
+            rows = self._rows(emb)
+            mean, _, cnt = ops.persam_target(rows, self.cell_mask.reshape(-1))
+            self.cells = int(cnt.item())
+            if self.cells == 0:
+                raise ValueError('PerSamF: the reference mask selects no cell of the embedding grid')
+            top = torch.where(self.cell_mask.reshape(-1, 1), rows, torch.full_like(rows, float('-inf'))).amax(0)
+            target = mean / 2 + top / 2
+            self.target_feature = (target / target.norm()).contiguous()
+            sim, low0 = ops.persam_similarity(rows, self.target_feature, 1, g, g)
+            stats, xy, _ = ops.persam_locate(low0, *geo, g)
+            scale = torch.tensor([nhw[1] / hw[1], nhw[0] / hw[0]], dtype=torch.float64).to(dev)
+            pts, labels = self._prompts(xy, scale, 1)
+            out = self.sam(image_embeddings=emb, input_points=pts, input_labels=labels, multimask_output=True)
+            self.ref_low_res = out.pred_masks[:, 0].contiguous()                       # [1, 3, 4g, 4g]
+            w, hist = ops.persam_f_fit(self.ref_low_res, gt.unsqueeze(0), *geo, epochs=int(epochs), lr=float(lr), want_history=True)
+        self.ref_point, self.ref_point_sim = xy[0, :2], stats[0, 0]
+        self.weights, self.loss_history = w[0], hist[0]
+
+    @torch.no_grad()
+    def segment(self, images, batch_size=8, output='rle', _stages=None):
+        return super().segment(images, batch_size=batch_size, output=output, cascade=True, _stages=_stages)
+
+    def _decode(self, emb, pts, labels, attn, geo, scale, cascade, st):
+        sam, phase = self.sam, self._phase
+        with phase('decoder pass 1'):
+            out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, multimask_output=True)
+            low = (out.pred_masks[:, 0] * self.weights.view(1, 3, 1, 1)).sum(1).contiguous()
+            st.update(low1=out.pred_masks[:, 0], iou1=out.iou_scores[:, 0], low_w=low)
+        for n in (2, 3):
+            with phase(f'decoder pass {n}'):
+                box, boxes = self._box_prompt(low, geo, scale)
+                out = sam(image_embeddings=emb, input_points=pts, input_labels=labels, input_boxes=boxes,
+                          input_masks=low.unsqueeze(1), multimask_output=True)
+                low, iou, best = self._best(out)
+                st.update({f'box{n - 1}': box, f'boxes{n - 1}': boxes, f'low{n}': out.pred_masks[:, 0], f'iou{n}': out.iou_scores[:, 0],
+                           f'best{n}': best})
+        return low, iou
+
+    def _extra_results(self):
+        return dict(weights=self.weights.cpu().tolist())
 
 
 # --------------------------------------------------------------------------------------------------- crop layers (DESIGN §15)

@@ -36,7 +36,15 @@ The scoring kernel's achieved input bytes/s and pixel evaluations/s are derived 
   (f) `min_mask_region_area`: ops.remove_small_regions on 64 masks of 1024 x 1024 (thresholded smooth noise plus speckle) per
       mode, after the encoder has run (warm clocks); the bytes the design moves per pixel against norm.hip's streaming rate;
       the same cleaning the host way (device -> host, scipy.ndimage.label per mask, host -> device); SamMaskGenerator.generate
-      (one crop layer) with min_mask_region_area 0 and 100, alternating.  --regions-once: one call per mode (kernel trace)."""
+      (one crop layer) with min_mask_region_area 0 and 100, alternating.  --regions-once: one call per mode (kernel trace).
+
+  python tools/bench_sam_prompts.py --persam-f [--arch base] [--reps 5] [--out profiles/persam_f/persam_f.json]
+
+  (g) PerSAM-F's fit (`ops.persam_f_fit`, 1000 epochs) at 1024 x 1024 (identity crop: the strip form) and at 600 x 900 (the
+      generic form) on smooth logits of amplitude ~10, against -- alternating, same process -- the same fit as torch autograd
+      + AdamW + CosineAnnealingLR in fp32 over the materialised fields on the same device (what the paper's code does); the
+      distance of the two results; the fit's pixel evaluations/s; one encoder pass of ViT-`arch`, for scale.
+      --persam-f-once: one fit per geometry (kernel trace)."""
 import argparse
 import json
 import os
@@ -266,6 +274,66 @@ REGION_BYTES_PER_PIXEL_PASS = 23
 NORM_STREAM_TB_S = 4.8            # what norm.hip's plane-producing LayerNorm reaches here
 
 
+def persam_f(model, a):
+    import torch.nn.functional as F
+    from rsprompter_amd import ops
+    dev = torch.device('cuda:0')
+    epochs, S = 1000, (1024, 1024)
+    res = dict(epochs=epochs, cases={})
+
+    def autograd_fit(fields, t):
+        w = torch.full((2,), 1 / 3, dtype=torch.float32, device=dev, requires_grad=True)
+        opt = torch.optim.AdamW([w], lr=1e-3, betas=(0.9, 0.999), eps=1e-4, weight_decay=0.01)
+        sch = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=epochs)
+        for _ in range(epochs):
+            opt.zero_grad()
+            z = (1 - w[0] - w[1]) * fields[0] + w[0] * fields[1] + w[1] * fields[2]
+            p = z.sigmoid()
+            dice = 1 - (2 * (p * t).sum() + 1) / (p.sum() + t.sum() + 1)
+            ce = F.binary_cross_entropy_with_logits(z, t, reduction='none')
+            p_t = p * t + (1 - p) * (1 - t)
+            loss = dice + ((0.25 * t + 0.75 * (1 - t)) * ce * (1 - p_t) ** 2).mean()
+            loss.backward()
+            opt.step()
+            sch.step()
+        wd = w.detach()
+        return torch.stack([1 - wd[0] - wd[1], wd[0], wd[1]])
+    for name, crop, out_hw in (('1024x1024 identity (strip form)', (1024, 1024), (1024, 1024)), ('600x900 (generic form)', (683, 1024), (600, 900))):
+        g = torch.Generator().manual_seed(11)
+        low = (F.avg_pool2d(torch.randn(1, 3, 256, 256, generator=g), 5, 1, 2) * 20).contiguous().to(dev)
+        fields = ops.mask_post_logits(low[0], S, crop, out_hw, 0.0, want_val=True)[1]
+        gt = (0.05 * fields[0] + 0.8 * fields[1] + 0.15 * fields[2]) > 2.0
+        fused = lambda: ops.persam_f_fit(low, gt[None], S, crop, out_hw, epochs=epochs)       # noqa: E731
+        if a.persam_f_once:
+            fused()
+            torch.cuda.synchronize()
+            continue
+        t = gt.float()
+        fused(); autograd_fit(fields, t)                                                       # noqa: E702  (warm-up of both)
+        ms = dict(fused=[], autograd=[])
+        for _ in range(a.reps):
+            for key, fn in (('fused', fused), ('autograd', lambda: autograd_fit(fields, t))):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ms[key].append(e0.elapsed_time(e1))
+        wf, wa = fused()[0].cpu(), autograd_fit(fields, t).cpu()
+        c = dict(fused_fit=_spread(ms['fused']), torch_autograd_fp32_fit=_spread(ms['autograd']))
+        c['speedup_of_medians'] = round(c['torch_autograd_fp32_fit']['median_ms'] / c['fused_fit']['median_ms'], 2)
+        c['fused_us_per_epoch'] = round(c['fused_fit']['median_ms'] * 1e3 / epochs, 2)
+        c['fused_pixel_evaluations_per_s'] = round(3.0 * out_hw[0] * out_hw[1] * epochs / (c['fused_fit']['median_ms'] * 1e-3), 0)
+        c['weights_fused'], c['weights_autograd_fp32'] = wf.tolist(), wa.tolist()
+        c['weights_distance'] = float((wf - wa).abs().max())
+        res['cases'][name] = c
+    if not a.persam_f_once:
+        pv = torch.randn(1, 3, 1024, 1024, device=dev)
+        with torch.no_grad():
+            res['encoder_pass'] = timed(lambda: model.get_image_embeddings(pv), max(5, a.reps))
+    return res
+
+
 def regions_fixture(k, hw, dev, seed=0):
     """thresholded smooth noise plus speckle: bool [k, H, W] on the device"""
     g = torch.Generator().manual_seed(seed)
@@ -376,6 +444,8 @@ def main():
     ap.add_argument('--persam-once', action='store_true', help='one segment() per batch size (for a kernel trace)')
     ap.add_argument('--regions', action='store_true', help='the min_mask_region_area phase (f) only')
     ap.add_argument('--regions-once', action='store_true', help='one remove_small_regions call per mode (for a kernel trace)')
+    ap.add_argument('--persam-f', action='store_true', help="the PerSAM-F phase (g) only")
+    ap.add_argument('--persam-f-once', action='store_true', help='one fit per geometry (for a kernel trace)')
     ap.add_argument('--crop-batch', type=int, default=None)
     ap.add_argument('--crop-batches', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8])
     a = ap.parse_args()
@@ -391,8 +461,10 @@ def main():
     model = model.to(dev).eval()
     img = synth_images(1)[0].permute(1, 2, 0).contiguous().to(dev)                 # [1024, 1024, 3] uint8
     out = dict(arch=a.arch, device=torch.cuda.get_device_name(0), image=[1024, 1024])
-    if a.multicrop or a.multicrop_once or a.persam or a.persam_once or a.regions or a.regions_once:
-        if a.regions or a.regions_once:
+    if a.multicrop or a.multicrop_once or a.persam or a.persam_once or a.regions or a.regions_once or a.persam_f or a.persam_f_once:
+        if a.persam_f or a.persam_f_once:
+            out['persam_f'] = persam_f(model, a)
+        elif a.regions or a.regions_once:
             out['regions'] = regions(model, img, a)
         elif a.persam or a.persam_once:
             out['persam'] = persam(model, a)
