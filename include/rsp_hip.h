@@ -658,6 +658,37 @@ int rsp_rle_shift(const uint32_t* counts_in, const int32_t* n_in, int32_t k, int
 /* k <= 65535.                                                                                                           */
 int rsp_paste_tiles(const uint8_t* masks, const int32_t* offsets, int32_t k, int32_t h, int32_t w, int32_t H, int32_t W,
                     uint8_t* out, rsp_stream_t stream);
+/* Seam merge (csrc/seam_merge.hip): arithmetic between scene-sized masks in the run domain.  Input of all  */
+/* four: counts [k, cap] / n [k] as rsp_rle_shift writes them -- COCO run counts of k masks on ONE (H, W) canvas, only    */
+/* count 0 may be zero, n <= 0 = an empty row.  H * W >= 2^31 is refused (RSP_EINVAL).  Integer arithmetic, exact.        */
+/* Tight box and area: replaces pycocotools maskUtils.toBbox / area on the scene-sized RLE.  boxes int32 [k, 4] =         */
+/* (x0, y0, x1, y1) end-exclusive, zeros for an empty mask; area int32 [k].                                               */
+int rsp_rle_bbox(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W, int32_t* boxes,
+                 int32_t* area, rsp_stream_t stream);
+/* Pair overlap: replaces the dense `(M_i & M_j).sum()`, `M_i[y0:y1, x0:x1].sum()`, `M_j[y0:y1, x0:x1].sum()` on masks     */
+/* padded to the scene (sahi shift_masks).  pairs: DEVICE int32 [P, 2] = row indices (a row outside [0, k) counts as      */
+/* empty); rects: DEVICE int32 [P, 4] = (x0, y0, x1, y1) end-exclusive, clamped into the canvas; out int32 [P, 3] =        */
+/* (inter, a_i, a_j): inter is the FULL intersection, not clipped to the rectangle.  workspace: the rows' run starts and   */
+/* ones prefixes, computed once per call however many pairs a row is in: rsp_rle_pair_overlap_workspace_bytes(k, cap).     */
+int64_t rsp_rle_pair_overlap_workspace_bytes(int32_t k, int32_t cap);
+int rsp_rle_pair_overlap(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                         const int32_t* pairs, const int32_t* rects, int32_t P, void* workspace, int32_t* out,
+                         rsp_stream_t stream);
+/* Union, first half: the ones-runs of M member rows as sortable intervals.  members: DEVICE int32 [M] row indices (a row  */
+/* outside [0, k) has no runs), member_group int32 [M] = the group of each, member_offs int64 [M] = the first slot of       */
+/* each (exclusive sum of max(min(n, cap), 0) / 2 over the members), total = all slots.  keys int64 [total] = group << 31   */
+/* | pixel start, ends int32 [total] = pixel end.  The caller sorts by key (ends along) and hands them to rsp_rle_union.   */
+int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                      const int32_t* members, const int32_t* member_group, const int64_t* member_offs, int32_t M,
+                      int64_t total, int64_t* keys, int32_t* ends, rsp_stream_t stream);
+/* Union, second half: replaces the dense OR of the members' scene-sized masks + encode_mask_results.  keys / ends sorted  */
+/* by key; interval_offs: DEVICE int64 [G + 1] = the intervals of group g (clamped into [0, total]).  counts_out           */
+/* [G, cap_out] / n_out [G]: the canonical COCO run counts of each group's union (adjacent runs of one value merged, first  */
+/* count zero iff pixel 0 is set; a group without intervals is the empty mask, one count H * W), conventions of            */
+/* rsp_rle_shift: n_out = -(needed) when cap_out is too small (the row is then undefined).  A group of one valid row       */
+/* reproduces that row bit for bit.                                                                                       */
+int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const int64_t* interval_offs, int32_t G, int32_t H,
+                  int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */

@@ -1,0 +1,397 @@
+// Merging instances cut by tile seams: arithmetic BETWEEN scene-sized masks in the run domain.  The dense
+// form -- pad every tile mask to the scene (sahi shift_masks), then `(a & b).sum()`, `a[:, y0:y1, x0:x1].sum()`,
+// `a | b` and pycocotools' toBbox / area / encode on scene-sized arrays -- never exists: one 10 000 x 10 000 mask is
+// 100 MB.  Input everywhere: scene-frame COCO run counts as rsp_rle_shift writes them (counts [k, cap], n [k], column-major
+// stream of an (H, W) canvas, only count 0 may be zero, n <= 0 = an empty row).
+//   rsp_rle_bbox         : tight box + area per row (maskUtils.toBbox / area)
+//   rsp_rle_pair_overlap : per pair of rows (i, j) and rectangle R: |M_i & M_j|, |M_i & R|, |M_j & R|
+//   rsp_rle_intervals    : the ones-runs of the member rows of G groups as (group, start) keys + ends, to be sorted by key
+//   rsp_rle_union        : sorted intervals of G groups -> canonical COCO run counts of each group's union
+// Integer arithmetic only; every result is exact and independent of the launch.
+#include "rsp_common.h"
+
+namespace {
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_WAVES = SM_THREADS / 64;
+
+// block-wide exclusive sum scan of one int per thread: wave scan by shuffles, the wave sums through LDS.
+// Callers keep the code in front of a scan free of branches on a lane's validity (clamped index + masked value, bitwise
+// flags): the host compiler of the emulated build (tests/wave_emu) does not know that a shuffle is convergent and clones
+// it into the path of the lanes it knows to hold zero; two call sites are two rendezvous there, and the idle lanes of a
+// partly filled wave would scan among themselves.
+__device__ __forceinline__ int sm_excl_scan(int v, int* tmp, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) tmp[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < SM_WAVES; ++w) {
+    const int t = tmp[w];
+    if (w < wave) base += t;
+    tot += t;
+  }
+  *total = tot;
+  __syncthreads();
+  return base + incl - v;
+}
+
+// block-wide EXCLUSIVE max scan of non-negative ints (identity 0); *total = the block's max
+__device__ __forceinline__ int sm_excl_max_scan(int v, int* tmp, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl = max(incl, t);
+  }
+  int excl = __shfl_up(incl, 1, 64);
+  if (lane == 0) excl = 0;
+  if (lane == 63) tmp[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < SM_WAVES; ++w) {
+    const int t = tmp[w];
+    if (w < wave) base = max(base, t);
+    tot = max(tot, t);
+  }
+  *total = tot;
+  __syncthreads();
+  return max(base, excl);
+}
+
+enum { SM_SUM = 0, SM_MIN = 1, SM_MAX = 2 };
+template <int OP>
+__device__ __forceinline__ int sm_op(int a, int b) {
+  return OP == SM_SUM ? a + b : (OP == SM_MIN ? min(a, b) : max(a, b));
+}
+// block-wide reduction, the result in every thread
+template <int OP>
+__device__ __forceinline__ int sm_reduce(int v, int* tmp) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = sm_op<OP>(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) tmp[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = tmp[0];
+#pragma unroll
+  for (int w = 1; w < SM_WAVES; ++w) r = sm_op<OP>(r, tmp[w]);
+  __syncthreads();
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------------- tight box, area
+// One block per row.  A ones-run [s, e) of the column-major stream touches columns xa = s / H .. xb = (e - 1) / H; when it
+// spans columns it reaches the last row of xa and the first row of xb, so its rows are [0, H).
+__global__ __launch_bounds__(SM_THREADS) void rle_bbox_kernel(const uint32_t* __restrict__ counts,
+                                                              const int32_t* __restrict__ n_in, int cap, int H,
+                                                              int32_t* __restrict__ boxes, int32_t* __restrict__ area) {
+  __shared__ int tmp[SM_WAVES];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int n = min(n_in[m], cap);
+  const uint32_t* c_row = counts + (int64_t)m * cap;
+  int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0, a = 0, carry = 0;
+  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
+    const int i = i0 + tid;
+    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
+    int chunk_px;
+    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
+    if (i < n && (i & 1) && c > 0) {
+      const int e1 = s + c - 1, xa = s / H, xb = e1 / H;
+      x0 = min(x0, xa);
+      x1 = max(x1, xb + 1);
+      y0 = min(y0, xa == xb ? s - xa * H : 0);
+      y1 = max(y1, xa == xb ? e1 - xb * H + 1 : H);
+      a += c;
+    }
+    carry += chunk_px;
+  }
+  x0 = sm_reduce<SM_MIN>(x0, tmp);
+  y0 = sm_reduce<SM_MIN>(y0, tmp);
+  x1 = sm_reduce<SM_MAX>(x1, tmp);
+  y1 = sm_reduce<SM_MAX>(y1, tmp);
+  a = sm_reduce<SM_SUM>(a, tmp);
+  if (tid == 0) {
+    const bool empty = a == 0;
+    boxes[4 * m] = empty ? 0 : x0;
+    boxes[4 * m + 1] = empty ? 0 : y0;
+    boxes[4 * m + 2] = empty ? 0 : x1;
+    boxes[4 * m + 3] = empty ? 0 : y1;
+    area[m] = a;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- pair overlap
+// Workspace row m (int32 [cap], next to the counts row): for ones-run t (count index 2 t + 1 < n)
+//   ws[2 t]     = ones pixels in front of the run          ws[2 t + 1] = pixel start of the run
+// One block per row, computed once however many pairs the row appears in.
+__global__ __launch_bounds__(SM_THREADS) void rle_prefix_kernel(const uint32_t* __restrict__ counts,
+                                                                const int32_t* __restrict__ n_in, int cap,
+                                                                int32_t* __restrict__ ws) {
+  __shared__ int tmp[SM_WAVES];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int n = min(n_in[m], cap);
+  const uint32_t* c_row = counts + (int64_t)m * cap;
+  int32_t* w_row = ws + (int64_t)m * cap;
+  int carry = 0, carry_ones = 0;
+  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
+    const int i = i0 + tid;
+    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
+    int chunk_px, chunk_ones;
+    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
+    const int ob = carry_ones + sm_excl_scan((i & 1) ? c : 0, tmp, &chunk_ones);
+    if (i < n && (i & 1)) {
+      w_row[i - 1] = ob;
+      w_row[i] = s;
+    }
+    carry += chunk_px;
+    carry_ones += chunk_ones;
+  }
+}
+
+struct SmRow {
+  const uint32_t* c;
+  const int32_t* ws;
+  int nr;                   // ones-runs
+};
+
+// last ones-run whose start is <= p; -1: none
+__device__ __forceinline__ int sm_find(const SmRow& r, int p) {
+  int lo = -1, hi = r.nr - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (r.ws[2 * mid + 1] <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ones pixels of the row in [0, p)
+__device__ __forceinline__ int sm_ones_before(const SmRow& r, int p) {
+  const int t = sm_find(r, p);
+  if (t < 0) return 0;
+  return r.ws[2 * t] + min(p - r.ws[2 * t + 1], (int)r.c[2 * t + 1]);
+}
+
+// pixels of the ones-run [s, s + c) inside columns [x0, x1), rows [y0, y1): first / middle / last column in closed form
+__device__ __forceinline__ int sm_run_in_rect(int s, int c, int H, int x0, int y0, int x1, int y1) {
+  const int e1 = s + c - 1, xa = s / H, xb = e1 / H;
+  const int ra = s - xa * H, rb = e1 - xb * H;              // first row in xa, last row in xb (inclusive)
+  if (xa == xb) return (xa >= x0 && xa < x1) ? max(0, min(rb + 1, y1) - max(ra, y0)) : 0;
+  int a = 0;
+  if (xa >= x0 && xa < x1) a += max(0, y1 - max(ra, y0));
+  if (xb >= x0 && xb < x1) a += max(0, min(rb + 1, y1) - y0);
+  a += max(0, min(xb, x1) - max(xa + 1, x0)) * (y1 - y0);
+  return a;
+}
+
+__device__ __forceinline__ int sm_area_in_rect(const SmRow& r, int H, int x0, int y0, int x1, int y1) {
+  if (r.nr == 0 || x1 <= x0 || y1 <= y0) return 0;
+  // only the runs that can touch columns [x0, x1): from the last run starting at or before the first pixel of x0 to the
+  // last run starting at or before the last pixel of x1 - 1
+  const int lo = max(sm_find(r, x0 * H), 0), hi = sm_find(r, x1 * H - 1);
+  int a = 0;
+  for (int t = lo + (int)threadIdx.x; t <= hi; t += SM_THREADS) {
+    const int c = (int)r.c[2 * t + 1];
+    if (c > 0) a += sm_run_in_rect(r.ws[2 * t + 1], c, H, x0, y0, x1, y1);
+  }
+  return a;
+}
+
+// One block per pair.  inter: the lanes walk the ones-runs of the row that has FEWER of them and look each run's two ends
+// up in the other row's prefix (two binary searches): one run against 50 000 costs one lane two searches.
+__global__ __launch_bounds__(SM_THREADS) void rle_pair_overlap_kernel(const uint32_t* __restrict__ counts,
+                                                                      const int32_t* __restrict__ n_in, int k, int cap,
+                                                                      int H, int W, const int32_t* __restrict__ ws,
+                                                                      const int32_t* __restrict__ pairs,
+                                                                      const int32_t* __restrict__ rects,
+                                                                      int32_t* __restrict__ out) {
+  __shared__ int tmp[SM_WAVES];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  SmRow r[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int m = pairs[2 * p + q];
+    const bool ok = m >= 0 && m < k;
+    const int mm = ok ? m : 0;
+    r[q].c = counts + (int64_t)mm * cap;
+    r[q].ws = ws + (int64_t)mm * cap;
+    r[q].nr = ok ? max(min(n_in[mm], cap), 0) >> 1 : 0;
+  }
+  const int x0 = min(max(rects[4 * p], 0), W), y0 = min(max(rects[4 * p + 1], 0), H);
+  const int x1 = min(max(rects[4 * p + 2], 0), W), y1 = min(max(rects[4 * p + 3], 0), H);
+  const SmRow& A = r[0].nr <= r[1].nr ? r[0] : r[1];
+  const SmRow& B = r[0].nr <= r[1].nr ? r[1] : r[0];
+  int inter = 0;
+  if (B.nr > 0) {
+    for (int t = tid; t < A.nr; t += SM_THREADS) {
+      const int s = A.ws[2 * t + 1], e = s + (int)A.c[2 * t + 1];
+      inter += sm_ones_before(B, e) - sm_ones_before(B, s);
+    }
+  }
+  const int ai = sm_area_in_rect(r[0], H, x0, y0, x1, y1), aj = sm_area_in_rect(r[1], H, x0, y0, x1, y1);
+  inter = sm_reduce<SM_SUM>(inter, tmp);
+  const int si = sm_reduce<SM_SUM>(ai, tmp), sj = sm_reduce<SM_SUM>(aj, tmp);
+  if (tid == 0) {
+    out[3 * p] = inter;
+    out[3 * p + 1] = si;
+    out[3 * p + 2] = sj;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- union
+// One block per member: ones-run t of member mi goes to slot moff[mi] + t as key = group << 31 | start, end = start + count
+// (start < 2^31).  Slots at or beyond `total` are not written.
+__global__ __launch_bounds__(SM_THREADS) void rle_intervals_kernel(const uint32_t* __restrict__ counts,
+                                                                   const int32_t* __restrict__ n_in, int k, int cap,
+                                                                   const int32_t* __restrict__ members,
+                                                                   const int32_t* __restrict__ member_group,
+                                                                   const int64_t* __restrict__ moff, int64_t total,
+                                                                   int64_t* __restrict__ keys, int32_t* __restrict__ ends) {
+  __shared__ int tmp[SM_WAVES];
+  const int mi = blockIdx.x, tid = threadIdx.x;
+  const int m = members[mi];
+  if (m < 0 || m >= k) return;
+  const int n = min(n_in[m], cap);
+  const uint32_t* c_row = counts + (int64_t)m * cap;
+  const int64_t g = (int64_t)member_group[mi] << 31, base = moff[mi];
+  int carry = 0;
+  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
+    const int i = i0 + tid;
+    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
+    int chunk_px;
+    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
+    const int64_t q = base + (i >> 1);
+    if (i < n && (i & 1) && q >= 0 && q < total) {
+      keys[q] = g | (int64_t)s;
+      ends[q] = s + c;
+    }
+    carry += chunk_px;
+  }
+}
+
+// One block per group over its intervals sorted by start.  With pm(q) = the largest end among the intervals in front of q,
+// interval q OPENS an output ones-run iff it is the group's first or start(q) > pm(q) (touching intervals merge: adjacent
+// runs of one value are one run).  Pass 1 writes the stream POSITIONS of the run boundaries -- S_0, E_0, S_1, E_1, ...,
+// and N when the last run ends before it: the opener of run r knows S_r = its start and E_{r-1} = pm.  Pass 2 turns
+// positions into counts, out[i] -= out[i - 1], chunk by chunk from the top so that no chunk reads what another rewrote.
+__global__ __launch_bounds__(SM_THREADS) void rle_union_kernel(const int64_t* __restrict__ keys,
+                                                               const int32_t* __restrict__ ends, int64_t total,
+                                                               const int64_t* __restrict__ iv_offs, uint32_t N,
+                                                               uint32_t* __restrict__ counts_out,
+                                                               int32_t* __restrict__ n_out, int cap_out) {
+  __shared__ int tmp[SM_WAVES];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int64_t o0 = iv_offs[g], o1 = iv_offs[g + 1];                  // clamped into [0, total], whatever the array holds
+  const int64_t q0 = o0 < 0 ? 0 : (o0 > total ? total : o0), q1 = o1 < q0 ? q0 : (o1 > total ? total : o1);
+  uint32_t* out = counts_out + (int64_t)g * cap_out;
+  int carry_max = 0;
+  int64_t carry_slot = 0;
+  for (int64_t qb = q0; qb < q1; qb += SM_THREADS) {
+    const int64_t q = qb + tid;
+    const bool valid = q < q1;
+    const int64_t over = q - (q1 - 1), qc = q - (over & ~(over >> 63));     // min(q, q1 - 1) and the masks below: no branch
+    const int s = (int)(keys[qc] & 0x7fffffffLL) & -(int)valid, e = ends[qc] & -(int)valid;   // in front of the shuffles
+    int chunk_max, chunk_open;
+    const int pm = max(carry_max, sm_excl_max_scan(e, tmp, &chunk_max));
+    const bool opens = (int)valid & ((int)(q == q0) | (int)(s > pm));      // bitwise: no branch between the two scans
+    const int64_t slot = carry_slot + sm_excl_scan(opens ? 1 : 0, tmp, &chunk_open);
+    if (opens) {
+      if (2 * slot < cap_out) out[2 * slot] = (uint32_t)s;
+      if (slot > 0 && 2 * slot - 1 < cap_out) out[2 * slot - 1] = (uint32_t)pm;
+    }
+    carry_max = max(carry_max, chunk_max);
+    carry_slot += chunk_open;
+  }
+  const uint32_t last_e = (uint32_t)carry_max;
+  const int64_t needed = carry_slot == 0 ? 1 : 2 * carry_slot + (last_e < N ? 1 : 0);
+  if (needed > cap_out) {                              // caller retries with a larger capacity
+    if (tid == 0) n_out[g] = (int32_t)-needed;
+    return;
+  }
+  if (tid == 0) {
+    if (carry_slot == 0) {
+      out[0] = N;
+    } else {
+      out[2 * carry_slot - 1] = last_e;
+      if (last_e < N) out[2 * carry_slot] = N;
+    }
+    n_out[g] = (int32_t)needed;
+  }
+  __syncthreads();
+  for (int i1 = (int)needed; i1 > 0; i1 -= SM_THREADS) {
+    const int i = i1 - SM_THREADS + tid;
+    uint32_t cur = 0u, prev = 0u;
+    if (i >= 0) {
+      cur = out[i];
+      prev = i > 0 ? out[i - 1] : 0u;
+    }
+    __syncthreads();
+    if (i >= 0) out[i] = cur - prev;
+  }
+}
+
+inline bool sm_scene_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffffLL; }
+
+}  // namespace
+
+extern "C" int rsp_rle_bbox(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                            int32_t* boxes, int32_t* area, rsp_stream_t stream) {
+  if (!counts || !n || !boxes || !area || k < 0 || cap < 1 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (k == 0) return RSP_OK;
+  hipLaunchKernelGGL(rle_bbox_kernel, dim3(k), dim3(SM_THREADS), 0, (hipStream_t)stream, counts, n, cap, H, boxes, area);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+extern "C" int64_t rsp_rle_pair_overlap_workspace_bytes(int32_t k, int32_t cap) {
+  if (k < 0 || cap < 1) return 0;
+  return (int64_t)(k > 0 ? k : 1) * cap * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int rsp_rle_pair_overlap(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                                    const int32_t* pairs, const int32_t* rects, int32_t P, void* workspace, int32_t* out,
+                                    rsp_stream_t stream) {
+  if (!counts || !n || !workspace || k < 0 || cap < 1 || P < 0 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (P > 0 && (!pairs || !rects || !out)) return RSP_EINVAL;
+  if (P == 0 || k == 0) return RSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* ws = static_cast<int32_t*>(workspace);
+  hipLaunchKernelGGL(rle_prefix_kernel, dim3(k), dim3(SM_THREADS), 0, s, counts, n, cap, ws);
+  RSP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rle_pair_overlap_kernel, dim3(P), dim3(SM_THREADS), 0, s, counts, n, k, cap, H, W, ws, pairs, rects,
+                     out);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+extern "C" int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                                 const int32_t* members, const int32_t* member_group, const int64_t* member_offs, int32_t M,
+                                 int64_t total, int64_t* keys, int32_t* ends, rsp_stream_t stream) {
+  if (!counts || !n || k < 0 || cap < 1 || M < 0 || total < 0 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (M > 0 && (!members || !member_group || !member_offs)) return RSP_EINVAL;
+  if (total > 0 && (!keys || !ends)) return RSP_EINVAL;
+  if (M == 0 || k == 0 || total == 0) return RSP_OK;
+  hipLaunchKernelGGL(rle_intervals_kernel, dim3(M), dim3(SM_THREADS), 0, (hipStream_t)stream, counts, n, k, cap, members,
+                     member_group, member_offs, total, keys, ends);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}
+
+extern "C" int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const int64_t* interval_offs, int32_t G,
+                             int32_t H, int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out,
+                             rsp_stream_t stream) {
+  if (G < 0 || total < 0 || cap_out < 2 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (total > 0 && (!keys || !ends)) return RSP_EINVAL;
+  if (G > 0 && (!interval_offs || !counts_out || !n_out)) return RSP_EINVAL;
+  if (G == 0) return RSP_OK;
+  hipLaunchKernelGGL(rle_union_kernel, dim3(G), dim3(SM_THREADS), 0, (hipStream_t)stream, keys, ends, total, interval_offs,
+                     (uint32_t)((int64_t)H * W), counts_out, n_out, cap_out);
+  RSP_CHECK_LAUNCH();
+  return RSP_OK;
+}

@@ -7,7 +7,9 @@ mask to the full scene as a dense array and merges with a class-aware NMS.  Here
 tiles are cut by a kernel straight into the model's input batch (`rsp_slice_resize_pad`); a batch's tile masks are
 reduced to run counts as soon as it is done (`rsp_mask_rle`); the merge is `rsp_batched_nms`; and the scene-sized COCO
 RLE of the kept instances is produced in the run domain from the tile-sized runs (`rsp_rle_shift` ->
-`rsp_rle_to_string`), so a scene-sized dense mask exists only when the caller asks for one.
+`rsp_rle_to_string`), so a scene-sized dense mask exists only when the caller asks for one.  merge_nms_type='seam_mask'
+first joins the fragments of objects cut by tile seams by their mask IoU inside the tiles' common rectangle, also in the run
+domain (`rsp_rle_bbox`, `rsp_rle_pair_overlap`, `rsp_rle_union`: DESIGN §14.6).
 
 CLI: `python -m rsprompter_amd.large_image IMG_OR_DIR CONFIG CHECKPOINT --out-dir DIR` writes one `<name>.json` per scene.
 """
@@ -94,19 +96,26 @@ def shift_predictions(det_data_samples, offsets, src_image_shape):
 
 
 def _check_nms_cfg(nms_cfg):
+    """-> (type, box IoU threshold, seam IoU threshold)"""
     cfg = dict(nms_cfg)
     typ = cfg.pop('type', 'nms')
-    if typ != 'nms':
-        raise NotImplementedError(f"merge nms type {typ!r}: only 'nms' (mmcv.ops.nms through batched_nms) is implemented")
+    if typ not in ('nms', 'seam_mask'):
+        raise NotImplementedError(f"merge nms type {typ!r}: only 'nms' (mmcv.ops.nms through batched_nms) and 'seam_mask' "
+                                  'are implemented')
     if cfg.get('class_agnostic', False):
         raise NotImplementedError('class_agnostic merging is not implemented')
-    return float(cfg.get('iou_threshold', cfg.get('iou_thr', 0.5)))
+    return typ, float(cfg.get('iou_threshold', cfg.get('iou_thr', 0.5))), float(cfg.get('seam_iou_threshold', 0.5))
 
 
 def merge_results_by_nms(results, offsets, src_image_shape, nms_cfg):
     """mmdet/utils/large_image.py:75-104: shift, then mmcv.ops.batched_nms over all instances of the scene; returns a
-    DetDataSample with the metainfo of results[0] and the kept instances in batched_nms' order (descending score)."""
-    thr = _check_nms_cfg(nms_cfg)
+    DetDataSample with the metainfo of results[0] and the kept instances in batched_nms' order (descending score).
+    nms_cfg = dict(type='seam_mask', iou_threshold=..., seam_iou_threshold=...): fragments of one object are first joined
+    by their mask IoU at the tile seams (the tile size is the masks' shape, as in shift_predictions); the
+    sample then also carries `keep` and `members` like inference_large_image's."""
+    typ, thr, seam_thr = _check_nms_cfg(nms_cfg)
+    if typ == 'seam_mask':
+        return _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr)
     inst = shift_predictions(results, offsets, src_image_shape)
     keep = ops.nms_flat(inst.bboxes, inst.scores, inst.labels, thr)
     merged = DetDataSample(metainfo=results[0].metainfo)
@@ -142,20 +151,23 @@ def _encode_tile_masks(masks, cap):
         return counts[:, :int(nh.max())].clone(), n, cap
 
 
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
-    """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
-    k = int(n.shape[0])
-    H, W = scene_hw
-    if k == 0:
-        return []
+def _shift_runs(counts, n, offsets, tile_hw, scene_hw):
+    """rsp_rle_shift with its capacity retry -> (scene counts, scene n)"""
     # a column end inside a run adds at most one ones-run and one zero run: n_in + 2 w bounds the scene's runs
     cap_out = int(counts.shape[1]) + 2 * int(tile_hw[1]) + 2
     while True:
         sc, sn = ops.rle_shift(counts, n, offsets, tile_hw, scene_hw, cap_out)
-        need = int((-sn).max().item())
+        need = int((-sn).max().item()) if sn.shape[0] else 0
         if need <= 0:
-            break
+            return sc, sn
         cap_out = 1 << (need - 1).bit_length()
+
+
+def _strings(sc, sn, scene_hw):
+    """scene run counts -> list of dict(size=[H, W], counts=bytes) (rsp_rle_to_string)"""
+    k = int(sn.shape[0])
+    if k == 0:
+        return []
     flat_cap = 2 * int(sn.sum().item()) + 16
     while True:
         _, offs, flat = ops.rle_to_string(sc, sn, k, flat_cap)
@@ -164,21 +176,225 @@ def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
             break
         flat_cap = int(offs_h[-1])
     buf, o = flat[:int(offs_h[-1])].cpu().numpy().tobytes(), offs_h.tolist()
-    return [dict(size=[int(H), int(W)], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+    return [dict(size=[int(scene_hw[0]), int(scene_hw[1])], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+
+
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
+    """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
+    if int(n.shape[0]) == 0:
+        return []
+    sc, sn = _shift_runs(counts, n, offsets, tile_hw, scene_hw)
+    return _strings(sc, sn, scene_hw)
+
+
+# ------------------------------------------------------------------------------------------------------- seam merge
+SEAM_PAIR_CHUNK_ELEMS = 1 << 24     # box tests materialised at once while pairing the instances of overlapping tiles
+
+
+def _seam_pairs(tile_rects, cand_tile, tight, labels, dev):
+    """candidate pairs of the seam merge.  tile_rects: host [T, 4]; cand_tile: host int [nc] (ascending) = the tile of each
+    candidate; tight int32 [nc, 4] / labels [nc] on the device.  Per pair of tiles whose rectangles overlap, the pairs of
+    their candidates with one label and intersecting TIGHT boxes (exact: disjoint tight boxes imply an empty intersection)
+    -> (pairs int32 [P, 2] candidate rows, first < second; rects int32 [P, 4] = the tiles' common rectangle)."""
+    empty = (torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((0, 4), dtype=torch.int32, device=dev))
+    T, nc = len(tile_rects), len(cand_tile)
+    if nc == 0 or T < 2:
+        return empty
+    r = np.asarray(tile_rects, np.int64).reshape(T, 4)
+    first = np.searchsorted(cand_tile, np.arange(T), 'left')
+    cnt = np.searchsorted(cand_tile, np.arange(T), 'right') - first
+    live = np.flatnonzero(cnt > 0)
+    ix0, iy0 = np.maximum(r[live, None, 0], r[None, live, 0]), np.maximum(r[live, None, 1], r[None, live, 1])
+    ix1, iy1 = np.minimum(r[live, None, 2], r[None, live, 2]), np.minimum(r[live, None, 3], r[None, live, 3])
+    a, b = np.nonzero(np.triu((ix1 > ix0) & (iy1 > iy0), 1))
+    if a.size == 0:
+        return empty
+    tp_rect = torch.from_numpy(np.stack([ix0[a, b], iy0[a, b], ix1[a, b], iy1[a, b]], 1).astype(np.int32)).to(dev)
+    kmax = int(cnt.max())
+    table = np.full((T, kmax), -1, np.int64)
+    for t in live.tolist():
+        table[t, :cnt[t]] = np.arange(first[t], first[t] + cnt[t])
+    table = torch.from_numpy(table).to(dev)
+    ta, tb = torch.from_numpy(live[a]).to(dev), torch.from_numpy(live[b]).to(dev)
+    lab = labels.to(torch.int64)
+    pairs, rects = [], []
+    step = max(1, SEAM_PAIR_CHUNK_ELEMS // (kmax * kmax))
+    for c0 in range(0, int(ta.shape[0]), step):
+        ia, ib = table[ta[c0:c0 + step]], table[tb[c0:c0 + step]]                       # [C, kmax]
+        A, B = tight[ia.clamp(min=0)][:, :, None, :], tight[ib.clamp(min=0)][:, None, :, :]
+        hit = (ia >= 0)[:, :, None] & (ib >= 0)[:, None, :] & (lab[ia.clamp(min=0)][:, :, None] == lab[ib.clamp(min=0)][:, None, :])
+        hit &= (A[..., 0] < B[..., 2]) & (B[..., 0] < A[..., 2]) & (A[..., 1] < B[..., 3]) & (B[..., 1] < A[..., 3])
+        c, p, q = hit.nonzero(as_tuple=True)
+        pairs.append(torch.stack([ia[c, p], ib[c, q]], 1).to(torch.int32))
+        rects.append(tp_rect[c0:c0 + step][c])
+    return torch.cat(pairs, 0).contiguous(), torch.cat(rects, 0).contiguous()
+
+
+def _seam_components(n, edges, scores):
+    """connected components of the edge graph on the host (union-find; the edge list is small) -> list of (representative,
+    members ascending), ascending by representative: the member with the highest score, the lowest index among equals"""
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    for i, j in edges:
+        a, b = find(i), find(j)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    groups = {}
+    for i in range(n):
+        groups.setdefault(find(i), []).append(i)
+    out = []
+    for mem in groups.values():
+        rep = mem[0]
+        for i in mem[1:]:
+            if scores[i] > scores[rep]:
+                rep = i
+        out.append((rep, mem))
+    out.sort(key=lambda g: g[0])
+    return out
+
+
+def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, scene_hw, seam_iou_thr, merge_iou_thr):
+    """The 'seam_mask' merge over the tile-ordered concatenation: boxes fp32 [N, 4] in the scene, scores,
+    labels, tile_of int64 [N] (ascending), tile_rects host [T, 4], counts / n = the TILE run counts of all N instances.
+    Returns (InstanceData(bboxes, scores, labels) of the merged instances in nms_flat's keep order, keep = their
+    representatives, members = list of index lists, (member rows int64 [M], group offsets int32 [K + 1]) on the device)."""
+    dev = boxes.device
+    N = int(scores.shape[0])
+    H, W = scene_hw
+    th, tw = tile_hw
+    rect_d = torch.tensor(np.asarray(tile_rects, np.int64).reshape(-1, 4), dtype=torch.int32, device=dev)
+    origin = rect_d[tile_of][:, :2] if N else torch.zeros((0, 2), dtype=torch.int32, device=dev)
+    edges = []
+    if N:
+        # tight boxes of the tile runs, moved into the scene: an instance whose mask stays outside every other tile's
+        # rectangle cannot share a pixel with another tile's instance and stays a singleton without being shifted
+        tb, area = ops.rle_bbox(counts, n, th, tw)
+        tb = tb + torch.cat([origin, origin], 1)
+        reach = (tb[:, None, 0] < rect_d[None, :, 2]) & (rect_d[None, :, 0] < tb[:, None, 2]) \
+            & (tb[:, None, 1] < rect_d[None, :, 3]) & (rect_d[None, :, 1] < tb[:, None, 3])
+        reach[torch.arange(N, device=dev), tile_of] = False
+        cand = ((area > 0) & reach.any(1)).nonzero().view(-1)
+        cand_h = cand.cpu().numpy()
+        if cand_h.size:
+            sc, sn = _shift_runs(counts[cand], n[cand].contiguous(), origin[cand].contiguous(), tile_hw, scene_hw)
+            tight, _ = ops.rle_bbox(sc, sn, H, W)
+            pairs, rects = _seam_pairs(tile_rects, tile_of.cpu().numpy()[cand_h], tight, labels[cand], dev)
+            if pairs.shape[0]:
+                ov = ops.rle_pair_overlap(sc, sn, H, W, pairs, rects).to(torch.int64)
+                inter, union = ov[:, 0], ov[:, 1] + ov[:, 2] - ov[:, 0]
+                is_edge = (inter > 0) & (inter.double() >= float(seam_iou_thr) * union.double())
+                e = pairs[is_edge].cpu().numpy()
+                edges = np.stack([cand_h[e[:, 0]], cand_h[e[:, 1]]], 1).tolist() if e.size else []
+            del sc, sn
+    comps = _seam_components(N, edges, scores.cpu().tolist())
+    K = len(comps)
+    reps = torch.tensor([c[0] for c in comps], dtype=torch.int64, device=dev)
+    gid_h = np.zeros((N,), np.int64)
+    for g, (_, mem) in enumerate(comps):
+        gid_h[mem] = g
+    gid = torch.from_numpy(gid_h).to(dev)
+    g2 = gid[:, None].expand(-1, 2)
+    mb = torch.empty((K, 4), dtype=boxes.dtype, device=dev)
+    if K:
+        mb[:, :2] = torch.zeros((K, 2), dtype=boxes.dtype, device=dev).scatter_reduce(0, g2, boxes[:, :2], 'amin', include_self=False)
+        mb[:, 2:] = torch.zeros((K, 2), dtype=boxes.dtype, device=dev).scatter_reduce(0, g2, boxes[:, 2:], 'amax', include_self=False)
+    ms, ml = scores[reps], labels[reps]
+    keep_m = ops.nms_flat(mb, ms, ml, merge_iou_thr)
+    out = InstanceData(bboxes=mb[keep_m], scores=ms[keep_m], labels=ml[keep_m])
+    members = [comps[g][1] for g in keep_m.tolist()]
+    flat = torch.tensor([i for mem in members for i in mem], dtype=torch.int64, device=dev)
+    offs = torch.tensor(np.concatenate([[0], np.cumsum([len(mem) for mem in members])]).astype(np.int32), device=dev)
+    return out, reps[keep_m], members, (flat, offs)
+
+
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw):
+    """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
+    (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
+    flat, offs = groups
+    K = int(offs.shape[0]) - 1
+    if K == 0:
+        return []
+    sc, sn = _shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
+    # the union of a group has at most as many runs as its members together
+    csum = torch.cat([sn.new_zeros((1,), dtype=torch.int64), torch.cumsum(sn.clamp(min=1).to(torch.int64), 0)])
+    o64 = offs.to(torch.int64)
+    cap_out = max(int((csum[o64[1:]] - csum[o64[:-1]]).max().item()) + 1, 2)
+    while True:
+        uc, un = ops.rle_union(sc, sn, scene_hw[0], scene_hw[1], offs, torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device), cap_out)
+        need = int((-un).max().item())
+        if need <= 0:
+            break
+        cap_out = 1 << (need - 1).bit_length()
+    return _strings(uc, un, scene_hw)
+
+
+def _seam_dense(tile_masks, origin, groups, scene_hw):
+    """the merged instances' dense masks: the members pasted (rsp_paste_tiles) and OR-reduced per group"""
+    flat, offs = groups
+    K, M = int(offs.shape[0]) - 1, int(flat.shape[0])
+    H, W = scene_hw
+    _check_dense(M, H, W)
+    out = torch.zeros((K, H, W), dtype=torch.uint8, device=flat.device)
+    if M:
+        o64 = offs.to(torch.int64)
+        gid = torch.repeat_interleave(torch.arange(K, device=flat.device), o64[1:] - o64[:-1], output_size=M)
+        pasted = ops.paste_tiles(tile_masks[flat].to(torch.bool), origin[flat].contiguous(), (H, W))
+        out.index_add_(0, gid, pasted.to(torch.uint8))                 # a group is a handful of fragments: no overflow
+    return out > 0
+
+
+def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr):
+    insts = [s.pred_instances for s in results]
+    assert len(results) == len(offsets), 'The `results` should has the same length with `offsets`.'
+    if not insts or not all('masks' in p and p.masks is not None for p in insts):
+        raise ValueError("merge type 'seam_mask' compares masks: every patch result needs pred_instances.masks")
+    for p in insts:
+        if p.bboxes.shape[-1] != 4:
+            raise NotImplementedError(f'boxes with {p.bboxes.shape[-1]} columns (rotated boxes) are not supported')
+    shapes = {tuple(p.masks.shape[1:]) for p in insts}
+    if len(shapes) != 1:
+        raise ValueError(f'the patches must have one size, got masks of {sorted(shapes)}')
+    th, tw = shapes.pop()
+    H, W = int(src_image_shape[0]), int(src_image_shape[1])
+    if H * W >= 2 ** 31:
+        raise ValueError(f'a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
+    masks = torch.cat([p.masks for p in insts], 0).to(torch.bool)
+    dev = masks.device
+    boxes = torch.cat([shift_bboxes(p.bboxes, o) for p, o in zip(insts, offsets)], 0)
+    scores, labels = torch.cat([p.scores for p in insts], 0), torch.cat([p.labels for p in insts], 0)
+    tile_of = torch.repeat_interleave(torch.arange(len(insts)), torch.tensor([len(p.scores) for p in insts])).to(dev)
+    rects = [[int(o[0]), int(o[1]), int(o[0]) + tw, int(o[1]) + th] for o in offsets]
+    counts, n, _ = _encode_tile_masks(masks, 4096)
+    out, keep, members, groups = _seam_merge(boxes, scores, labels, tile_of, rects, counts, n, (th, tw), (H, W), seam_thr, thr)
+    origin = torch.tensor(rects, dtype=torch.int32, device=dev).reshape(-1, 4)[tile_of][:, :2]
+    out.masks = _seam_dense(masks, origin, groups, (H, W))
+    merged = DetDataSample(metainfo=results[0].metainfo)
+    merged.pred_instances = out
+    merged.keep, merged.members = keep, members
+    return merged
 
 
 @torch.no_grad()
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
-                          batch_size=1, masks='rle', return_patches=False):
+                          batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
     (masks='rle') or a bool [K, H, W] device tensor (masks='dense').  return_patches=True: (sample, per-tile samples,
-    starting_pixels)."""
+    starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
+    agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
+    instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
+    `sample.keep` then holds the representatives (the best-scored member) and `sample.members` the index lists."""
     from .apis import TestPipeline, get_test_pipeline_cfg
-    if merge_nms_type != 'nms':
-        raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms' is implemented (soft_nms and the other "
-                                  'mmcv variants are not)')
+    if merge_nms_type not in ('nms', 'seam_mask'):
+        raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms' and 'seam_mask' are implemented (soft_nms "
+                                  'and the other mmcv variants are not)')
+    seam = merge_nms_type == 'seam_mask'
     if masks not in ('rle', 'dense'):
         raise ValueError("masks must be 'rle' or 'dense'")
     ph_, pw_ = (int(patch_size), int(patch_size)) if isinstance(patch_size, (int, float)) else (int(patch_size[0]), int(patch_size[1]))
@@ -225,11 +441,13 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             bm = torch.cat([p.masks for p in insts], 0).to(torch.bool)
             if masks == 'dense':
                 dense_tiles.append(bm)
-            else:
+            if masks != 'dense' or seam:                                # the seam merge compares runs in either form
                 c, n, cap = _encode_tile_masks(bm, cap)                 # the batch's dense masks go once the runs fit
                 runs.append(c)
                 run_n.append(n)
             del bm
+        elif seam:
+            raise ValueError("merge_nms_type='seam_mask' compares masks: the detector returned none")
         if return_patches:
             patch_samples.extend(res)
         del res, insts
@@ -240,25 +458,45 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     all_boxes = (torch.cat(boxes, 0) if boxes else torch.zeros((0, 4), device=dev))
     all_boxes = all_boxes + torch.cat([off_all, off_all], 1).to(all_boxes.dtype)       # sahi shift_bboxes, fp32
     all_scores, all_labels = cat(scores, torch.float32), cat(labels, torch.int64)
-    keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
-    out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
-    koff = off_all[keep].to(torch.int32).contiguous()
-    if masks == 'dense' and dense_tiles:
-        _check_dense(keep.shape[0], H, W)
-        out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
-    elif runs:
-        # only the kept instances' runs are gathered, batch by batch, into one [K, widest] array
-        width = max(int(c.shape[1]) for c in runs)
-        kc = torch.zeros((int(keep.shape[0]), width), dtype=torch.int32, device=dev)
+    members = None
+    if seam:
+        width = max([int(c.shape[1]) for c in runs] + [1])
+        ac = torch.zeros((int(all_scores.shape[0]), width), dtype=torch.int32, device=dev)
         r0 = 0
         for c in runs:
-            sel = ((keep >= r0) & (keep < r0 + c.shape[0])).nonzero().view(-1)
-            kc[sel, :c.shape[1]] = c[keep[sel] - r0]
+            ac[r0:r0 + c.shape[0], :c.shape[1]] = c
             r0 += c.shape[0]
-        out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W))
+        an = torch.cat(run_n, 0) if run_n else torch.zeros((0,), dtype=torch.int32, device=dev)
+        out, keep, members, groups = _seam_merge(all_boxes, all_scores, all_labels, tile_of, tiles, ac, an, (th, tw), (H, W),
+                                                 seam_iou_thr, merge_iou_thr)
+        origin = off_all.to(torch.int32)
+        if masks == 'dense':
+            tm = torch.cat(dense_tiles, 0) if dense_tiles else torch.zeros((0, th, tw), dtype=torch.bool, device=dev)
+            out.masks = _seam_dense(tm, origin, groups, (H, W))
+        else:
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W))
+    else:
+        keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
+        out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
+        koff = off_all[keep].to(torch.int32).contiguous()
+        if masks == 'dense' and dense_tiles:
+            _check_dense(keep.shape[0], H, W)
+            out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
+        elif runs:
+            # only the kept instances' runs are gathered, batch by batch, into one [K, widest] array
+            width = max(int(c.shape[1]) for c in runs)
+            kc = torch.zeros((int(keep.shape[0]), width), dtype=torch.int32, device=dev)
+            r0 = 0
+            for c in runs:
+                sel = ((keep >= r0) & (keep < r0 + c.shape[0])).nonzero().view(-1)
+                kc[sel, :c.shape[1]] = c[keep[sel] - r0]
+                r0 += c.shape[0]
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W))
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
+    if members is not None:
+        sample.members = members                                        # per output instance, its fragments
     if return_patches:
         return sample, patch_samples, starting_pixels
     return sample
@@ -292,14 +530,17 @@ def main(argv=None):
     ap.add_argument('--patch-size', type=int, default=640, help='The size of patches')
     ap.add_argument('--patch-overlap-ratio', type=float, default=0.25, help='Ratio of overlap between two patches')
     ap.add_argument('--merge-iou-thr', type=float, default=0.25, help='IoU threshould for merging results')
-    ap.add_argument('--merge-nms-type', default='nms', help='NMS type for merging results')
+    ap.add_argument('--merge-nms-type', default='nms', help="NMS type for merging results: 'nms', or 'seam_mask' to join "
+                    'the fragments of objects cut by tile seams first')
+    ap.add_argument('--seam-iou-thr', type=float, default=0.5, help="mask IoU inside the tiles' overlap above which two "
+                    "fragments are one object (--merge-nms-type seam_mask)")
     ap.add_argument('--batch-size', type=int, default=1, help='Batch size of patches')
     a = ap.parse_args(argv)
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
     os.makedirs(a.out_dir, exist_ok=True)
     for path in DetInferencer._inputs_to_list(a.img):
         s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
-                                  a.batch_size)
+                                  a.batch_size, seam_iou_thr=a.seam_iou_thr)
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + '.json')
         with open(dst, 'w') as f:
             json.dump(pred2dict(s, a.score_thr), f)

@@ -1654,6 +1654,102 @@ def paste_tiles(masks, offsets, scene_hw):
     return out
 
 
+# ----------------------------------------------------------------------------- seam merge (csrc/seam_merge.hip)
+def _rle_rows(what, counts, n, H, W):
+    """the common checks of the run-domain entry points: counts int32 [k, cap] / n int32 [k] on one (H, W) canvas"""
+    H, W = int(H), int(W)
+    if H * W >= 2 ** 31:
+        raise ValueError(f'{what}: a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
+    if H < 1 or W < 1:
+        raise ValueError(f'{what}: an empty {H} x {W} canvas')
+    if counts.dtype != torch.int32 or counts.dim() != 2 or n.dtype != torch.int32 or n.dim() != 1 \
+            or n.shape[0] != counts.shape[0] or counts.shape[1] < 1 or n.device != counts.device:
+        raise ValueError(f'{what}: expected counts int32 [k, cap >= 1] and n int32 [k] on one device')
+    return counts.contiguous(), n.contiguous(), int(n.shape[0]), int(counts.shape[1]), H, W
+
+
+def _rle_index(what, name, t, cols, dev):
+    if t.dtype != torch.int32 or t.device != dev or (t.dim() != 2 or t.shape[1] != cols if cols else t.dim() != 1):
+        raise ValueError(f'{what}: {name} must be int32 {"[P, %d]" % cols if cols else "[n]"} on the device of the counts')
+    return t.contiguous()
+
+
+def rle_bbox(counts, n, H, W):
+    """scene-frame run counts (as rle_shift returns them) -> (boxes int32 [k, 4] = tight (x0, y0, x1, y1), end-exclusive,
+    zeros for an empty mask; area int32 [k]): maskUtils.toBbox / area in the run domain (rsp_rle_bbox).  No host read."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('rle_bbox', counts, n, H, W)
+    boxes = torch.zeros((k, 4), dtype=torch.int32, device=n.device)
+    area = torch.zeros((k,), dtype=torch.int32, device=n.device)
+    if k:
+        _lib.check(lib.rsp_rle_bbox(counts.data_ptr(), n.data_ptr(), k, cap, H, W, boxes.data_ptr(), area.data_ptr(),
+                                    _stream()), "rsp_rle_bbox")
+    return boxes, area
+
+
+def rle_pair_overlap(counts, n, H, W, pairs, rects):
+    """for P pairs of rows (pairs int32 [P, 2], device) and rectangles (rects int32 [P, 4] = (x0, y0, x1, y1),
+    end-exclusive, device): int32 [P, 3] = (|M_i & M_j|, |M_i & R|, |M_j & R|) (rsp_rle_pair_overlap); the intersection is
+    NOT clipped to the rectangle.  No host read."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('rle_pair_overlap', counts, n, H, W)
+    pairs = _rle_index('rle_pair_overlap', 'pairs', pairs, 2, n.device)
+    rects = _rle_index('rle_pair_overlap', 'rects', rects, 4, n.device)
+    P = int(pairs.shape[0])
+    if rects.shape[0] != P:
+        raise ValueError('rle_pair_overlap: one rectangle per pair')
+    out = torch.zeros((P, 3), dtype=torch.int32, device=n.device)
+    if P and k:
+        ws = torch.empty((int(lib.rsp_rle_pair_overlap_workspace_bytes(k, cap)) // 4,), dtype=torch.int32, device=n.device)
+        _lib.check(lib.rsp_rle_pair_overlap(counts.data_ptr(), n.data_ptr(), k, cap, H, W, pairs.data_ptr(), rects.data_ptr(),
+                                            P, ws.data_ptr(), out.data_ptr(), _stream()), "rsp_rle_pair_overlap")
+    return out
+
+
+def rle_union(counts, n, H, W, group_offs, members, cap_out):
+    """the union of the member rows of G groups (group_offs int32 [G + 1], members int32 [M] row indices, groups
+    contiguous, group_offs[0] = 0, group_offs[G] = M; both on the device) as canonical COCO run counts: (counts_out int32 [G, cap_out], n_out int32 [G]), n_out =
+    -(needed) when cap_out is too small.  rsp_rle_intervals -> a device key sort of (group, start) -> rsp_rle_union.  One
+    host read (the number of intervals, which sizes the sort)."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('rle_union', counts, n, H, W)
+    dev = n.device
+    group_offs = _rle_index('rle_union', 'group_offs', group_offs, 0, dev)
+    members = _rle_index('rle_union', 'members', members, 0, dev)
+    G, M = int(group_offs.shape[0]) - 1, int(members.shape[0])
+    if G < 0 or int(cap_out) < 2:
+        raise ValueError('rle_union: group_offs holds G + 1 entries and cap_out is at least 2')
+    out = torch.empty((max(G, 1), int(cap_out)), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((max(G, 1),), dtype=torch.int32, device=dev)
+    if G == 0:
+        return out[:0], n_out[:0]
+    go = group_offs.to(torch.int64).clamp(0, M)
+    if M and k:
+        inside = (members >= 0) & (members < k)
+        runs = torch.where(inside, n[members.to(torch.int64).clamp(0, k - 1)].clamp(0, cap) // 2, 0).to(torch.int64)
+        ends_incl = torch.cumsum(runs, 0)
+        moff = (ends_incl - runs).contiguous()
+        total = int(ends_incl[-1].item())
+        # the group of member mi: the last g with group_offs[g] <= mi (group_offs[0] = 0, group_offs[G] = M)
+        group_of = torch.searchsorted(go[1:].contiguous(), torch.arange(M, dtype=torch.int64, device=dev), right=True)
+        group_of = group_of.clamp(max=G - 1).to(torch.int32).contiguous()
+        iv_offs = torch.cat([moff, ends_incl[-1:]])[go].contiguous()
+    else:
+        total = 0
+        iv_offs = torch.zeros((G + 1,), dtype=torch.int64, device=dev)
+    keys = torch.empty((max(total, 1),), dtype=torch.int64, device=dev)
+    ends = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
+    if total:
+        _lib.check(lib.rsp_rle_intervals(counts.data_ptr(), n.data_ptr(), k, cap, H, W, members.data_ptr(), group_of.data_ptr(),
+                                         moff.data_ptr(), M, total, keys.data_ptr(), ends.data_ptr(), _stream()),
+                   "rsp_rle_intervals")
+        keys, order = torch.sort(keys[:total])
+        ends = ends[:total][order].contiguous()
+    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), total, iv_offs.data_ptr(), G, H, W, out.data_ptr(),
+                                 n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_union")
+    return out, n_out
+
+
 MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
 # the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call
