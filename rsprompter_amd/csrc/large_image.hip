@@ -152,29 +152,6 @@ __global__ __launch_bounds__(256) void crops_resize_pad_kernel(const CropsP P) {
 // ------------------------------------------------------------------------------------------------- run-domain shift
 constexpr int SHIFT_THREADS = 256;
 
-// block-wide exclusive scan of one int per thread (256 threads): wave scan by shuffles, the four wave sums through LDS
-__device__ __forceinline__ int shift_excl_scan(int v, int* tmp, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) tmp[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SHIFT_THREADS / 64; ++w) {
-    const int t = tmp[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  __syncthreads();
-  return base + incl - v;
-}
-
 // One block per instance.  The tile's column-major stream has pixel p at column p / h, row p % h; in the scene that pixel
 // sits at stream position P(p) = (ox + p / h) * H + oy + p % h.  Runs of ONES are what survives the placement: a ones-run
 // [s, e) that touches columns xa .. xb becomes xb - xa + 1 ones-runs when H > h (H - h zeros separate the columns) and
@@ -209,10 +186,10 @@ __global__ __launch_bounds__(SHIFT_THREADS) void rle_shift_kernel(const uint32_t
     const int i = i0 + tid;
     const int c = i < n ? (int)cin[i] : 0;
     int chunk_px, chunk_pieces;
-    const int s = carry_pos + shift_excl_scan(c, tmp, &chunk_px), e = s + c;
+    const int s = carry_pos + rsp_block_excl_scan<SHIFT_THREADS>(c, tmp, &chunk_px), e = s + c;
     const bool ones = i < n && (i & 1) && c > 0;
     const int pieces = ones ? (whole ? 1 : (e - 1) / h - s / h + 1) : 0;
-    l_slot[tid] = shift_excl_scan(pieces, tmp, &chunk_pieces);
+    l_slot[tid] = rsp_block_excl_scan<SHIFT_THREADS>(pieces, tmp, &chunk_pieces);
     l_s[tid] = s;
     l_e[tid] = e;
     l_pe[tid] = (ones && i >= 3) ? s - (int)cin[i - 1] : 0;    // pixel end of the previous ones-run (0: there is none)

@@ -221,6 +221,35 @@ __device__ __forceinline__ float rsp_wave_max(float v) {
   return v;
 }
 
+// block-wide exclusive sum scan of one int per thread (NTHREADS threads, tmp = NTHREADS / 64 ints of LDS): wave scan by
+// shuffles, the wave sums through LDS; *total = the block's sum.
+// Callers keep the code in front of a scan free of branches on a lane's validity (clamped index + masked value, bitwise
+// flags): the host compiler of the emulated build (tests/wave_emu) does not know that a shuffle is convergent and clones
+// it into the path of the lanes it knows to hold zero; two call sites are two rendezvous there, and the idle lanes of a
+// partly filled wave would scan among themselves.
+template <int NTHREADS>
+__device__ __forceinline__ int rsp_block_excl_scan(int v, int* tmp, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) tmp[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NTHREADS / 64; ++w) {
+    const int t = tmp[w];
+    if (w < wave) base += t;
+    tot += t;
+  }
+  *total = tot;
+  __syncthreads();
+  return base + incl - v;
+}
+
 // unsigned division by a run-time constant prepared on the host (Granlund-Montgomery, branch-free form):
 // q = (t + ((x - t) >> sh1)) >> sh2 with t = mulhi(m, x); exact for all 32-bit x.
 struct FastDiv {

@@ -15,33 +15,6 @@ namespace {
 constexpr int SM_THREADS = 256;
 constexpr int SM_WAVES = SM_THREADS / 64;
 
-// block-wide exclusive sum scan of one int per thread: wave scan by shuffles, the wave sums through LDS.
-// Callers keep the code in front of a scan free of branches on a lane's validity (clamped index + masked value, bitwise
-// flags): the host compiler of the emulated build (tests/wave_emu) does not know that a shuffle is convergent and clones
-// it into the path of the lanes it knows to hold zero; two call sites are two rendezvous there, and the idle lanes of a
-// partly filled wave would scan among themselves.
-__device__ __forceinline__ int sm_excl_scan(int v, int* tmp, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) tmp[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SM_WAVES; ++w) {
-    const int t = tmp[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  __syncthreads();
-  return base + incl - v;
-}
-
 // block-wide EXCLUSIVE max scan of non-negative ints (identity 0); *total = the block's max
 __device__ __forceinline__ int sm_excl_max_scan(int v, int* tmp, int* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -101,7 +74,7 @@ __global__ __launch_bounds__(SM_THREADS) void rle_bbox_kernel(const uint32_t* __
     const int i = i0 + tid;
     const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
     int chunk_px;
-    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
+    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
     if (i < n && (i & 1) && c > 0) {
       const int e1 = s + c - 1, xa = s / H, xb = e1 / H;
       x0 = min(x0, xa);
@@ -144,8 +117,8 @@ __global__ __launch_bounds__(SM_THREADS) void rle_prefix_kernel(const uint32_t* 
     const int i = i0 + tid;
     const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
     int chunk_px, chunk_ones;
-    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
-    const int ob = carry_ones + sm_excl_scan((i & 1) ? c : 0, tmp, &chunk_ones);
+    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
+    const int ob = carry_ones + rsp_block_excl_scan<SM_THREADS>((i & 1) ? c : 0, tmp, &chunk_ones);
     if (i < n && (i & 1)) {
       w_row[i - 1] = ob;
       w_row[i] = s;
@@ -265,7 +238,7 @@ __global__ __launch_bounds__(SM_THREADS) void rle_intervals_kernel(const uint32_
     const int i = i0 + tid;
     const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
     int chunk_px;
-    const int s = carry + sm_excl_scan(c, tmp, &chunk_px);
+    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
     const int64_t q = base + (i >> 1);
     if (i < n && (i & 1) && q >= 0 && q < total) {
       keys[q] = g | (int64_t)s;
@@ -300,7 +273,7 @@ __global__ __launch_bounds__(SM_THREADS) void rle_union_kernel(const int64_t* __
     int chunk_max, chunk_open;
     const int pm = max(carry_max, sm_excl_max_scan(e, tmp, &chunk_max));
     const bool opens = (int)valid & ((int)(q == q0) | (int)(s > pm));      // bitwise: no branch between the two scans
-    const int64_t slot = carry_slot + sm_excl_scan(opens ? 1 : 0, tmp, &chunk_open);
+    const int64_t slot = carry_slot + rsp_block_excl_scan<SM_THREADS>(opens ? 1 : 0, tmp, &chunk_open);
     if (opens) {
       if (2 * slot < cap_out) out[2 * slot] = (uint32_t)s;
       if (slot > 0 && 2 * slot - 1 < cap_out) out[2 * slot - 1] = (uint32_t)pm;

@@ -128,12 +128,13 @@ class ExchangeState:
         return need[0] <= self.img_cap and need[1] <= self.inst_cap and need[2] <= self.byte_cap and need[3] <= 0
 
     def grow(self, need):
+        from . import ops
         p2 = lambda v, lo: max(lo, 1 << (max(int(v), 1) * 5 // 4).bit_length())
         self.img_cap = max(self.img_cap, p2(need[0], 1))
         self.inst_cap = max(self.inst_cap, p2(need[1], 16))
         self.byte_cap = max(self.byte_cap, p2(need[2], 1 << 16))
         if need[3] > 0:
-            self.run_cap = max(self.run_cap, 1 << (int(need[3]) - 1).bit_length())
+            self.run_cap = max(self.run_cap, ops.grown_cap(need[3]))
 
 
 _STATES = {}

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, rle
 from .structures import DetDataSample, InstanceData
 
 # masks='dense' materialises bool [K, H, W]; a request beyond this many bytes is refused with the figure in the message
@@ -131,60 +131,12 @@ def _check_dense(k, H, W):
 
 
 # ------------------------------------------------------------------------------------------------------------- pipeline
-def _encode_tile_masks(masks, cap):
-    """bool [k, h, w] -> (counts int32 [k, max runs], n int32 [k], cap): rsp_mask_rle with one small device-to-host read
-    (the run numbers) that tells whether every mask fit; grows `cap` and re-encodes like rle.encode_rle_strings."""
-    k = int(masks.shape[0])
-    dev = masks.device
-    if k == 0:
-        return torch.zeros((0, 1), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), cap
-    while True:
-        counts = torch.empty((k, cap), dtype=torch.int32, device=dev)
-        ws = torch.empty((k, cap), dtype=torch.int32, device=dev)
-        n = torch.empty((k,), dtype=torch.int32, device=dev)
-        ops.mask_rle_into(masks, counts, ws, n)
-        nh = n.cpu()
-        need = int((-nh).max())
-        if need > 0:
-            cap = 1 << (need - 1).bit_length()
-            continue
-        return counts[:, :int(nh.max())].clone(), n, cap
-
-
-def _shift_runs(counts, n, offsets, tile_hw, scene_hw):
-    """rsp_rle_shift with its capacity retry -> (scene counts, scene n)"""
-    # a column end inside a run adds at most one ones-run and one zero run: n_in + 2 w bounds the scene's runs
-    cap_out = int(counts.shape[1]) + 2 * int(tile_hw[1]) + 2
-    while True:
-        sc, sn = ops.rle_shift(counts, n, offsets, tile_hw, scene_hw, cap_out)
-        need = int((-sn).max().item()) if sn.shape[0] else 0
-        if need <= 0:
-            return sc, sn
-        cap_out = 1 << (need - 1).bit_length()
-
-
-def _strings(sc, sn, scene_hw):
-    """scene run counts -> list of dict(size=[H, W], counts=bytes) (rsp_rle_to_string)"""
-    k = int(sn.shape[0])
-    if k == 0:
-        return []
-    flat_cap = 2 * int(sn.sum().item()) + 16
-    while True:
-        _, offs, flat = ops.rle_to_string(sc, sn, k, flat_cap)
-        offs_h = offs.cpu()
-        if int(offs_h[-1]) <= flat_cap:
-            break
-        flat_cap = int(offs_h[-1])
-    buf, o = flat[:int(offs_h[-1])].cpu().numpy().tobytes(), offs_h.tolist()
-    return [dict(size=[int(scene_hw[0]), int(scene_hw[1])], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
-
-
 def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
         return []
-    sc, sn = _shift_runs(counts, n, offsets, tile_hw, scene_hw)
-    return _strings(sc, sn, scene_hw)
+    sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
+    return rle.runs_to_strings(sc, sn, scene_hw)
 
 
 # ------------------------------------------------------------------------------------------------------- seam merge
@@ -281,7 +233,7 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
         cand = ((area > 0) & reach.any(1)).nonzero().view(-1)
         cand_h = cand.cpu().numpy()
         if cand_h.size:
-            sc, sn = _shift_runs(counts[cand], n[cand].contiguous(), origin[cand].contiguous(), tile_hw, scene_hw)
+            sc, sn, _, _ = rle.shift_runs(counts[cand], n[cand].contiguous(), origin[cand].contiguous(), tile_hw, scene_hw)
             tight, _ = ops.rle_bbox(sc, sn, H, W)
             pairs, rects = _seam_pairs(tile_rects, tile_of.cpu().numpy()[cand_h], tight, labels[cand], dev)
             if pairs.shape[0]:
@@ -319,18 +271,10 @@ def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw):
     K = int(offs.shape[0]) - 1
     if K == 0:
         return []
-    sc, sn = _shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
-    # the union of a group has at most as many runs as its members together
-    csum = torch.cat([sn.new_zeros((1,), dtype=torch.int64), torch.cumsum(sn.clamp(min=1).to(torch.int64), 0)])
-    o64 = offs.to(torch.int64)
-    cap_out = max(int((csum[o64[1:]] - csum[o64[:-1]]).max().item()) + 1, 2)
-    while True:
-        uc, un = ops.rle_union(sc, sn, scene_hw[0], scene_hw[1], offs, torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device), cap_out)
-        need = int((-un).max().item())
-        if need <= 0:
-            break
-        cap_out = 1 << (need - 1).bit_length()
-    return _strings(uc, un, scene_hw)
+    sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
+    members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
+    uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
+    return rle.runs_to_strings(uc, un, scene_hw)
 
 
 def _seam_dense(tile_masks, origin, groups, scene_hw):
@@ -369,7 +313,7 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
     scores, labels = torch.cat([p.scores for p in insts], 0), torch.cat([p.labels for p in insts], 0)
     tile_of = torch.repeat_interleave(torch.arange(len(insts)), torch.tensor([len(p.scores) for p in insts])).to(dev)
     rects = [[int(o[0]), int(o[1]), int(o[0]) + tw, int(o[1]) + th] for o in offsets]
-    counts, n, _ = _encode_tile_masks(masks, 4096)
+    counts, n, _, _ = rle.encode_runs(masks)
     out, keep, members, groups = _seam_merge(boxes, scores, labels, tile_of, rects, counts, n, (th, tw), (H, W), seam_thr, thr)
     origin = torch.tensor(rects, dtype=torch.int32, device=dev).reshape(-1, 4)[tile_of][:, :2]
     out.masks = _seam_dense(masks, origin, groups, (H, W))
@@ -442,7 +386,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             if masks == 'dense':
                 dense_tiles.append(bm)
             if masks != 'dense' or seam:                                # the seam merge compares runs in either form
-                c, n, cap = _encode_tile_masks(bm, cap)                 # the batch's dense masks go once the runs fit
+                c, n, _, cap = rle.encode_runs(bm, cap)                 # the batch's dense masks go once the runs fit
                 runs.append(c)
                 run_n.append(n)
             del bm
@@ -460,12 +404,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     all_scores, all_labels = cat(scores, torch.float32), cat(labels, torch.int64)
     members = None
     if seam:
-        width = max([int(c.shape[1]) for c in runs] + [1])
-        ac = torch.zeros((int(all_scores.shape[0]), width), dtype=torch.int32, device=dev)
-        r0 = 0
-        for c in runs:
-            ac[r0:r0 + c.shape[0], :c.shape[1]] = c
-            r0 += c.shape[0]
+        ac = rle.concat_runs(runs, device=dev)
         an = torch.cat(run_n, 0) if run_n else torch.zeros((0,), dtype=torch.int32, device=dev)
         out, keep, members, groups = _seam_merge(all_boxes, all_scores, all_labels, tile_of, tiles, ac, an, (th, tw), (H, W),
                                                  seam_iou_thr, merge_iou_thr)
@@ -483,14 +422,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             _check_dense(keep.shape[0], H, W)
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
-            # only the kept instances' runs are gathered, batch by batch, into one [K, widest] array
-            width = max(int(c.shape[1]) for c in runs)
-            kc = torch.zeros((int(keep.shape[0]), width), dtype=torch.int32, device=dev)
-            r0 = 0
-            for c in runs:
-                sel = ((keep >= r0) & (keep < r0 + c.shape[0])).nonzero().view(-1)
-                kc[sel, :c.shape[1]] = c[keep[sel] - r0]
-                r0 += c.shape[0]
+            kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
             out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W))
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
@@ -511,8 +443,7 @@ def pred2dict(sample, score_thr=0.0):
     if 'masks' in p and p.masks is not None:
         rles = p.masks
         if isinstance(rles, torch.Tensor):
-            from .rle import encode_mask_results
-            rles = encode_mask_results(rles) if rles.shape[0] else []
+            rles = rle.encode_mask_results(rles) if rles.shape[0] else []
         out['masks'] = [dict(size=rles[i]['size'], counts=rles[i]['counts'].decode()) for i in sel]
     return out
 

@@ -1505,25 +1505,42 @@ def pack_masks(masks):
     return out
 
 
-def mask_rle_counts(masks, cap=4096):
-    """bool [k, H, W] -> (counts int32 [k, cap'], n int32 [k]): COCO RLE run lengths (column-major stream, first run
-    counts zeros).  Retries with a larger capacity when a mask has more runs than `cap`."""
-    lib = _lib.load()
-    k, H, W = masks.shape
-    m = masks.contiguous()
-    dev = masks.device
+def grown_cap(need):
+    """the run capacity to retry with when a producer reported n[i] = -need: the next power of two"""
+    return 1 << (int(need) - 1).bit_length()
+
+
+def fit_runs(launch, cap):
+    """The capacity protocol of the run-table producers (rsp_mask_rle, rsp_rle_from_string, rsp_rle_shift, rsp_rle_union:
+    counts int32 [k, cap] + n int32 [k], n[i] = -(slots needed) for a row that did not fit).  `launch(cap)` enqueues one
+    producer and returns (counts, n); one device-to-host read of n per attempt, again at grown_cap(the largest need)
+    until every row fits (an empty n fits) -> (counts, n, n on the host, cap)."""
     while True:
+        counts, n = launch(cap)
+        n_host = n.cpu()
+        need = int(-n_host.min()) if n_host.numel() else 0
+        if need <= 0:
+            return counts, n, n_host, cap
+        cap = grown_cap(need)
+
+
+def mask_rle_launcher(masks):
+    """the `launch(cap)` of fit_runs for rsp_mask_rle on bool [k, H, W]: fresh [k, cap] buffers, no host read"""
+    k, dev = masks.shape[0], masks.device
+
+    def launch(cap):
         counts = torch.empty((k, cap), dtype=torch.int32, device=dev)
         ws = torch.empty((k, cap), dtype=torch.int32, device=dev)
         n = torch.empty((k,), dtype=torch.int32, device=dev)
-        if k:
-            _lib.check(lib.rsp_mask_rle(m.data_ptr(), k, H, W, ws.data_ptr(), counts.data_ptr(), n.data_ptr(), cap,
-                                        _stream()), "rsp_mask_rle")
-            need = int((-n).max().item())
-            if need > 0:
-                cap = 1 << (need - 1).bit_length()
-                continue
+        mask_rle_into(masks, counts, ws, n)
         return counts, n
+    return launch
+
+
+def mask_rle_counts(masks, cap=4096):
+    """bool [k, H, W] -> (counts int32 [k, cap'], n int32 [k]): COCO RLE run lengths (column-major stream, first run
+    counts zeros).  Retries with a larger capacity when a mask has more runs than `cap`."""
+    return fit_runs(mask_rle_launcher(masks), cap)[:2]
 
 
 def mask_rle_into(masks, counts, ws, n):
@@ -1828,19 +1845,17 @@ def rle_from_string(flat, offs, cap=1024):
     """COCO compressed strings flat[offs[i]:offs[i + 1]] (uint8 / int64 device tensors) -> (counts int32 [k, cap'],
     n int32 [k]) on the device (rsp_rle_from_string); grows `cap` and retries when a string holds more counts."""
     lib = _lib.load()
-    k = offs.shape[0] - 1
+    k = max(offs.shape[0] - 1, 0)
     dev = offs.device
-    while True:
+
+    def launch(cap):
         counts = torch.empty((max(k, 1), cap), dtype=torch.int32, device=dev)
         n = torch.zeros((max(k, 1),), dtype=torch.int32, device=dev)
-        if k <= 0:
-            return counts[:0], n[:0]
-        _lib.check(lib.rsp_rle_from_string(_ptr(flat), offs.data_ptr(), k, cap, counts.data_ptr(), n.data_ptr(),
-                                           _stream()), "rsp_rle_from_string")
-        need = int((-n).max().item())
-        if need <= 0:
-            return counts, n
-        cap = 1 << (need - 1).bit_length()
+        if k:
+            _lib.check(lib.rsp_rle_from_string(_ptr(flat), offs.data_ptr(), k, cap, counts.data_ptr(), n.data_ptr(),
+                                               _stream()), "rsp_rle_from_string")
+        return counts[:k], n[:k]
+    return fit_runs(launch, cap)[:2]
 
 
 def rle_to_bits(counts, n, word_offs):

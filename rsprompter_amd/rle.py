@@ -2,7 +2,13 @@
 (mmdet/structures/mask/utils.py:38-53 -> pycocotools.mask.encode): run-length counting (`rsp_mask_rle`) and the
 compression of the counts to COCO's ASCII string (cocoapi maskApi.c rleToString -> `rsp_rle_to_string`) both run on the
 GPU; the host receives finished strings.  The result is what CocoMetric.process stores per instance
-(coco_metric.py:346-391): dict(size=[h, w], counts=bytes)."""
+(coco_metric.py:346-391): dict(size=[h, w], counts=bytes).
+
+This module is also the one home of the RUN TABLE that every mask leaves the device as: counts int32
+[k, cap] + n int32 [k], the column-major COCO stream with zeros as the first run, written by producers that never read the
+host and report a row that did not fit as n[i] = -(slots needed).  The retry on run capacity is `ops.fit_runs`, the retry on
+string bytes (offs[k] > flat_cap: again with flat_cap = offs[k]) is `_string_bytes`; the features call the pipelines below
+and hold no capacity loop of their own."""
 import torch
 
 from . import ops
@@ -28,37 +34,104 @@ def counts_to_string(cnts):
 _counts_to_string = counts_to_string      # round-2 name
 
 
+def encode_runs(masks, cap=4096):
+    """bool [k, H, W] on the device -> (counts int32 [k, widest row] (a copy: the [k, cap] buffer goes; two columns at least,
+    which rsp_rle_to_string asks for), n int32 [k], n on the host, the capacity that fit): rsp_mask_rle, one device-to-host
+    read (n) per attempt."""
+    ops.require_device(masks.device)
+    counts, n, n_host, cap = ops.fit_runs(ops.mask_rle_launcher(masks), cap)
+    width = max(int(n_host.max()) if n_host.numel() else 0, 2)
+    return counts[:, :width].clone(), n, n_host, cap
+
+
+def shift_runs(counts, n, offsets, tile_hw, scene_hw, cap=None):
+    """tile run tables placed at offsets (int32 [k, 2] = (ox, oy), device) in the scene (rsp_rle_shift) -> (scene counts,
+    scene n, n on the host, cap); one device-to-host read per attempt."""
+    if cap is None:     # a column end inside a run adds at most one ones-run and one zero run: n_in + 2 w bounds the scene's runs
+        cap = int(counts.shape[1]) + 2 * int(tile_hw[1]) + 2
+    return ops.fit_runs(lambda cap: ops.rle_shift(counts, n, offsets, tile_hw, scene_hw, cap), cap)
+
+
+def union_runs(counts, n, scene_hw, group_offs, members, cap=None):
+    """the union of the member rows of every group as one run table (ops.rle_union's arguments) -> (counts, n, n on the
+    host, cap); per attempt one device-to-host read and the one inside ops.rle_union.  cap=None reads the bound once."""
+    if cap is None:     # the union of a group has at most as many runs as its members together
+        runs = n[members.to(torch.int64)].clamp(min=1).to(torch.int64)
+        csum = torch.cat([runs.new_zeros((1,)), torch.cumsum(runs, 0)])
+        o64 = group_offs.to(torch.int64)
+        cap = max(int((csum[o64[1:]] - csum[o64[:-1]]).max().item()) + 1, 2) if o64.shape[0] > 1 else 2
+    return ops.fit_runs(lambda cap: ops.rle_union(counts, n, scene_hw[0], scene_hw[1], group_offs, members, cap), cap)
+
+
+def concat_runs(tables, rows=None, device=None):
+    """run tables int32 [k_i, w_i] -> one zero-padded table [sum k_i, widest] (at least one column), or with `rows` (int64,
+    device: row numbers of the concatenation, any order) only those rows, gathered table by table.  `device` places the
+    result of an empty list."""
+    dev = tables[0].device if tables else device
+    width = max([int(t.shape[1]) for t in tables] + [1])
+    total = sum(int(t.shape[0]) for t in tables)
+    out = torch.zeros((total if rows is None else int(rows.shape[0]), width), dtype=torch.int32, device=dev)
+    r0 = 0
+    for t in tables:
+        if rows is None:
+            out[r0:r0 + t.shape[0], :t.shape[1]] = t
+        else:
+            sel = ((rows >= r0) & (rows < r0 + t.shape[0])).nonzero().view(-1)
+            out[sel, :t.shape[1]] = t[rows[sel] - r0]
+        r0 += t.shape[0]
+    return out
+
+
+def _string_bytes(counts, n, flat_cap):
+    """run table -> (flat uint8, offs int64 [k + 1]) on the HOST: string i is flat[offs[i]:offs[i + 1]]
+    (rsp_rle_to_string).  One device-to-host read (offs) per attempt, then the bytes."""
+    k = int(n.shape[0])
+    while True:
+        _, offs, flat = ops.rle_to_string(counts, n, k, flat_cap)
+        offs_h = offs.cpu()
+        total = int(offs_h[-1])
+        if total <= flat_cap:
+            return flat[:total].cpu(), offs_h
+        flat_cap = total
+
+
+def runs_to_strings(counts, n, size, flat_cap=None):
+    """run table -> list of dict(size=[H, W], counts=bytes), COCO's compressed form.  `flat_cap`: the first guess of the
+    strings' bytes (two per table entry when None)."""
+    k = int(n.shape[0])
+    if k == 0:
+        return []
+    flat, offs = _string_bytes(counts, n, flat_cap or 2 * k * int(counts.shape[1]) + 16)
+    buf, o = flat.numpy().tobytes(), offs.tolist()
+    return [dict(size=[int(size[0]), int(size[1])], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+
+
+def runs_to_dicts(counts, n_host, size):
+    """run table -> list of dict(size=[H, W], counts=list), the uncompressed form (HF `_mask_to_rle`).  n_host: the row
+    lengths on the host (what fit_runs returned); one transfer, the table."""
+    counts, n_host = counts.cpu().numpy(), n_host.tolist()
+    return [dict(size=[int(size[0]), int(size[1])], counts=counts[i, :n_host[i]].tolist()) for i in range(len(n_host))]
+
+
 def encode_rle_strings(masks, cap=4096, flat_cap=None):
     """bool [k, H, W] on the device -> (flat uint8 tensor, offsets int64 [k + 1]) on the HOST: string i is
-    flat[offs[i]:offs[i + 1]].  Two device kernels, one host synchronisation for the sizes; grows its capacities and
-    retries when a mask has more runs / the strings more bytes than assumed."""
-    ops.require_device(masks.device)
-    k, h, w = masks.shape
-    dev = masks.device
+    flat[offs[i]:offs[i + 1]].  Two device kernels and three transfers (n, offs, flat); grows its capacities and retries
+    when a mask has more runs / the strings more bytes than assumed."""
+    k = int(masks.shape[0])
+    counts, n, _, cap = encode_runs(masks, cap)
     if k == 0:
         return torch.zeros((0,), dtype=torch.uint8), torch.zeros((1,), dtype=torch.int64)
-    flat_cap = flat_cap or 2 * cap * k
-    while True:
-        counts = torch.empty((k, cap), dtype=torch.int32, device=dev)
-        ws = torch.empty((k, cap), dtype=torch.int32, device=dev)
-        n = torch.empty((k,), dtype=torch.int32, device=dev)
-        ops.mask_rle_into(masks, counts, ws, n)
-        lens, offs, flat = ops.rle_to_string(counts, n, k, flat_cap)
-        need_runs = int((-n).max().item())
-        offs_h = offs.cpu()
-        if need_runs > 0:
-            cap = 1 << (need_runs - 1).bit_length()
-            flat_cap = max(flat_cap, 2 * cap * k)
-            continue
-        if int(offs_h[-1]) > flat_cap:
-            flat_cap = int(offs_h[-1])
-            continue
-        return flat[:int(offs_h[-1])].cpu(), offs_h
+    return _string_bytes(counts, n, flat_cap or 2 * cap * k)
 
 
 def encode_mask_results(masks):
     """masks: bool tensor [k, H, W] on the HIP device -> list of k RLE dicts (same as the reference's function)."""
     k, h, w = masks.shape
-    flat, offs = encode_rle_strings(masks)
-    buf, o = flat.numpy().tobytes(), offs.tolist()
-    return [dict(size=[int(h), int(w)], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+    counts, n, _, cap = encode_runs(masks)
+    return runs_to_strings(counts, n, (h, w), 2 * cap * k)
+
+
+def encode_mask_dicts(masks):
+    """encode_mask_results in the uncompressed form: bool [k, H, W] on the device -> list of k dict(size, counts=list)."""
+    counts, _, n_host, _ = encode_runs(masks)
+    return runs_to_dicts(counts, n_host, masks.shape[1:])

@@ -16,7 +16,7 @@ from itertools import product
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, rle
 from .structures import InstanceData
 
 # SamImageProcessor defaults (IMAGENET_DEFAULT_MEAN / STD on a 0..1 image, i.e. these on 0..255)
@@ -197,14 +197,6 @@ def filter_candidates(iou, score, pred_iou_thresh, stability_score_thresh):
     return keep
 
 
-def _rle_dicts(masks):
-    """bool [k, H, W] on the device -> HF `_mask_to_rle` dicts: uncompressed column-major run lengths, first run zeros."""
-    k, H, W = masks.shape
-    counts, n = ops.mask_rle_counts(masks)
-    counts, n = counts.cpu().numpy(), n.cpu().tolist()
-    return [dict(size=[H, W], counts=counts[i, :n[i]].tolist()) for i in range(k)]
-
-
 def _check_region_area(min_mask_region_area):
     if int(min_mask_region_area) != min_mask_region_area or int(min_mask_region_area) < 0:
         raise ValueError(f'min_mask_region_area must be a non-negative integer, got {min_mask_region_area!r}')
@@ -298,7 +290,7 @@ def generate_masks(model, image, points_per_side=32, pred_iou_thresh=0.88, stabi
         if output == 'dense':
             dense.append(m)
         else:
-            rles.extend(_rle_dicts(m))
+            rles.extend(rle.encode_mask_dicts(m))
     if output == 'dense':
         res.masks = torch.cat(dense, 0) if dense else torch.zeros((0, H, W), dtype=torch.bool, device=low.device)
     else:
@@ -494,16 +486,16 @@ class PerSam:
             flts = torch.cat([stats[:, :P], iou.reshape(B, 1)], 1).cpu()
             extra = self._extra_results()
             if output == 'rle':
-                nn = ints[:, 2 * P + 4].tolist()
-                if min(nn) < 0:                                # a mask with more runs than RLE_CAP: again with room (rare)
-                    counts, n = ops.mask_rle_counts(masks, cap=1 << (-min(nn) - 1).bit_length())
-                    nn = n.cpu().tolist()
-                counts = counts[:, :max(nn)].cpu().numpy()
+                nn = ints[:, 2 * P + 4]
+                if int(nn.min()) < 0:                          # a mask with more runs than RLE_CAP: again with room (rare)
+                    counts, _, nn, _ = rle.encode_runs(masks, cap=ops.grown_cap(-int(nn.min())))
+                counts = counts[:, :int(nn.max())].cpu()
+        rles = rle.runs_to_dicts(counts, nn, hw) if output == 'rle' else None       # host lists: after the transfer phase
         res = []
         for b in range(B):
             r = dict(score=float(flts[b, P]), bbox=ints[b, 2 * P:2 * P + 4].tolist(), points=ints[b, :2 * P].reshape(P, 2).tolist(),
                      point_sims=flts[b, :P].tolist(), **extra)
-            r['mask'] = dict(size=[H, W], counts=counts[b, :nn[b]].tolist()) if output == 'rle' else masks[b]
+            r['mask'] = rles[b] if output == 'rle' else masks[b]
             res.append(r)
         return res
 
@@ -854,7 +846,7 @@ class SamMaskGenerator:
                         off = torch.tensor([[x0, y0]] * len(pos), dtype=torch.int32).to(dev)
                         dense[pos_t] = ops.paste_tiles(mk, off, (H, W))
                 elif whole:
-                    for i, d in zip(pos, _rle_dicts(mk)):
+                    for i, d in zip(pos, rle.encode_mask_dicts(mk)):
                         rles[i] = d
                 else:
                     pending.append((pos, mk, (x0, y0), (ch, cw)))
@@ -864,15 +856,8 @@ class SamMaskGenerator:
             return dense
         for pos, mk, (x0, y0), chw in pending:
             off = torch.tensor([[x0, y0]] * len(pos), dtype=torch.int32).to(dev)
-            counts, n = ops.mask_rle_counts(mk)
-            cap_out = int(counts.shape[1]) + 2 * chw[1] + 2            # a column end inside a run adds at most two runs
-            while True:
-                sc, sn = ops.rle_shift(counts, n, off, chw, (H, W), cap_out)
-                sn_h = sn.cpu().tolist()
-                if min(sn_h) >= 0:
-                    break
-                cap_out = 1 << (-min(sn_h) - 1).bit_length()
-            sc = sc.cpu().numpy()
-            for j, i in enumerate(pos):
-                rles[i] = dict(size=[H, W], counts=sc[j, :sn_h[j]].tolist())
+            counts, n, _, _ = rle.encode_runs(mk)
+            sc, _, sn_h, _ = rle.shift_runs(counts, n, off, chw, (H, W))
+            for i, d in zip(pos, rle.runs_to_dicts(sc, sn_h, (H, W))):
+                rles[i] = d
         return rles

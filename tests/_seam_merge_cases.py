@@ -416,6 +416,7 @@ def check_at_scale(ops, li, dev, H, W, patch, n_obj, noise, seed=0, seam_thr=0.5
     """the three kernels and the merge on synthetic_instances against the interval-domain restatement"""
     from oracle import glue
     from oracle import rle as orle
+    from rsprompter_amd import rle
     tiles, per_tile = synthetic_instances(H, W, patch, n_obj, noise, seed)
     inst = [f for frs in per_tile for f in frs]
     tile = [t for t, frs in enumerate(per_tile) for _ in frs]
@@ -430,7 +431,7 @@ def check_at_scale(ops, li, dev, H, W, patch, n_obj, noise, seed=0, seam_thr=0.5
     counts, n = rows_from_counts([f['counts'] for f in inst], dev)
     origin = torch.tensor([[tiles[t][0], tiles[t][1]] for t in tile], dtype=torch.int32, device=dev)
     # kernels: shift + bbox, pair overlap over every pair the restatement evaluated, union of every component
-    sc, sn = li._shift_runs(counts, n, origin, (th, tw), (H, W))
+    sc, sn = rle.shift_runs(counts, n, origin, (th, tw), (H, W))[:2]
     tb, area = ops.rle_bbox(sc, sn, H, W)
     tb, area = tb.cpu().tolist(), area.cpu().tolist()
     for i in range(N):

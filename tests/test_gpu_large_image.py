@@ -136,6 +136,14 @@ def test_rle_shift_and_paste_against_dense_paste_on_a_small_scene(dev):
     assert [r['counts'] for r in encode_mask_results(dense)] == got
 
 
+def test_run_table_pipelines_retry_from_a_capacity_that_is_too_small(dev):
+    """the host loops around rsp_mask_rle, rsp_rle_shift, rsp_rle_union and rsp_rle_to_string (rsprompter_amd/rle.py) on the
+    device: from cap = 2 / flat_cap = 1 each retries and ends with the tables and strings of the default capacities"""
+    import _run_table_cases as cases
+    from rsprompter_amd import ops
+    cases.check_capacity_retries(ops, dev)
+
+
 # --------------------------------------------------------------------------------------------------------- end to end
 def _cfg():
     from rsprompter_amd.config import Config

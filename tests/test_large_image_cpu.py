@@ -155,6 +155,13 @@ def test_rle_shift_refuses_scene_beyond_32_bit_counts(emu):
     assert lib.rsp_rle_shift(z.data_ptr(), z.data_ptr(), 1, 4, z.data_ptr(), 2, 2, 65536, 32768, z.data_ptr(), z.data_ptr(), 4, 0) != 0
 
 
+def test_run_table_pipelines_retry_from_a_capacity_that_is_too_small(emu):
+    """rle.encode_runs / shift_runs / union_runs / runs_to_strings from cap = 2 and flat_cap = 1: each retries, and the tables
+    and strings are those of the default capacities and of the restatement on the dense paste"""
+    import _run_table_cases as cases
+    cases.check_capacity_retries(emu, torch.device('cpu'))
+
+
 # ---------------------------------------------------------------------------------------------------- tile front end
 @pytest.mark.parametrize('dtype', [np.uint8, np.float32])
 @pytest.mark.parametrize('norm', [False, True])

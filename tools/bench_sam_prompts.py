@@ -191,7 +191,8 @@ def multicrop(model, img, a):
 def persam(model, a):
     import torch.nn.functional as F
     from rsprompter_amd import ops
-    from rsprompter_amd.sam_prompts import PerSam, SamSession, _rle_dicts
+    from rsprompter_amd.rle import encode_mask_dicts
+    from rsprompter_amd.sam_prompts import PerSam, SamSession
     from rsprompter_amd.synth import synth_images
     dev = next(model.parameters()).device
     S, g = model.image_size, model.vision_encoder.grid
@@ -225,7 +226,7 @@ def persam(model, a):
             m, iou, low = s.predict(points=pts, labels=lab, boxes=np.array([box], dtype=np.float64), mask_input=low[0, b],
                                     multimask_output=True)
             b = int(iou[0].argmax())
-            res.append(dict(mask=_rle_dicts(m[0, b][None])[0], score=float(iou[0, b]), points=pts[0].astype(int).tolist()))
+            res.append(dict(mask=encode_mask_dicts(m[0, b][None])[0], score=float(iou[0, b]), points=pts[0].astype(int).tolist()))
         return res
 
     for B in (1, 8):
@@ -451,7 +452,8 @@ def main():
     a = ap.parse_args()
     from rsprompter_amd import ops
     from rsprompter_amd.samdet import SamModelHIP
-    from rsprompter_amd.sam_prompts import SamSession, filter_candidates, generate_masks, point_grid, _rle_dicts
+    from rsprompter_amd.rle import encode_mask_dicts
+    from rsprompter_amd.sam_prompts import SamSession, filter_candidates, generate_masks, point_grid
     from rsprompter_amd.synth import synth_images, synth_state_dict
     dev = torch.device('cuda:0')
     model = SamModelHIP(a.arch)
@@ -533,7 +535,7 @@ def main():
 
     def masks_rle():
         for i in range(0, int(sel.shape[0]), 64):
-            _rle_dicts(s.full_res(low[sel[i:i + 64]], 0.0))
+            encode_mask_dicts(s.full_res(low[sel[i:i + 64]], 0.0))
     out['generate']['masks_and_rle_of_kept'] = timed(masks_rle, max(3, a.reps // 4))
     out['generate']['whole_call'] = timed(lambda: generate_masks(model, None, points_per_side=n, pred_iou_thresh=t_iou,
                                                                  stability_score_thresh=t_stab, stability_score_offset=off,

@@ -34,7 +34,7 @@ def _event_ms(f):
 def pairs(dev, n_dense=48, rounds=5):
     import _seam_merge_cases as cases
     from rsprompter_amd import large_image as li
-    from rsprompter_amd import ops
+    from rsprompter_amd import ops, rle
     H, W, patch = 4096, 5000, 640
     tiles, per_tile = cases.synthetic_instances(H, W, patch, 580, 256, 0)
     inst = [f for frs in per_tile for f in frs]
@@ -42,7 +42,7 @@ def pairs(dev, n_dense=48, rounds=5):
     counts, n = cases.rows_from_counts([f['counts'] for f in inst], dev)
     origin = torch.tensor([[tiles[t][0], tiles[t][1]] for t in tile], dtype=torch.int32, device=dev)
     labels = torch.tensor([f['label'] for f in inst], device=dev)
-    sc, sn = li._shift_runs(counts, n, origin, (patch, patch), (H, W))
+    sc, sn = rle.shift_runs(counts, n, origin, (patch, patch), (H, W))[:2]
     tight, _ = ops.rle_bbox(sc, sn, H, W)
     pr, rc = li._seam_pairs(tiles, tile, tight, labels, dev)
     P = int(pr.shape[0])

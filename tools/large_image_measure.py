@@ -110,7 +110,7 @@ def throughput(dev):
 
 def phases(dev):
     from rsprompter_amd import large_image as li
-    from rsprompter_amd import ops
+    from rsprompter_amd import ops, rle
     m = build('huge', dev)
     scene = mosaic(4096, 6400)
     T = {}
@@ -136,7 +136,7 @@ def phases(dev):
     torch.cuda.synchronize()
     free = time.perf_counter() - t0
     peak = torch.cuda.max_memory_allocated() / 2 ** 20
-    saved = [wrap(ops, 'slice_resize_pad', 'front_end'), wrap(m, 'test_step', 'model'), wrap(li, '_encode_tile_masks', 'tile_rle'),
+    saved = [wrap(ops, 'slice_resize_pad', 'front_end'), wrap(m, 'test_step', 'model'), wrap(rle, 'encode_runs', 'tile_rle'),
              wrap(ops, 'nms_flat', 'merge_nms'), wrap(li, '_scene_rle', 'scene_rle'), wrap(ops, 'rle_shift', 'scene_rle.shift'),
              wrap(ops, 'rle_to_string', 'scene_rle.strings')]
     torch.cuda.synchronize()
