@@ -689,6 +689,40 @@ int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32_t k, int32
 /* reproduces that row bit for bit.                                                                                       */
 int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const int64_t* interval_offs, int32_t G, int32_t H,
                   int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out, rsp_stream_t stream);
+/* Polygon export (csrc/mask_polygons.hip): run tables -> exact rings on the pixel-corner lattice, replaces */
+/* decoding every instance to a dense H x W array on the host + cv2.findContours.  Input of the first two: counts [k, cap] */
+/* / n [k] of k masks on ONE (H, W) canvas as above (a row with n <= 0 has no pieces; n beyond cap is read up to cap).     */
+/* H * W >= 2^31 is refused (RSP_EINVAL).  The four calls are one pipeline; the caller reads two sizes in between and      */
+/* sorts the rings (rsprompter_amd/ops.py mask_polygons).  No call reads the host, none uses atomics.                      */
+/* 1. piece_cnt int32 [k]: the column pieces of each row (a ones-run crossing column ends is one piece per column).        */
+int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                            int32_t* piece_cnt, rsp_stream_t stream);
+/* 2. piece_offs int64 [k + 1] = exclusive sum of piece_cnt, P = piece_offs[k] <= (2^31 - 1) / 6.  pieces int32 [4, P] =    */
+/* (x, y0, y1, instance) per piece, sorted by (instance, x, y0).  Six edge slots per piece, E = 6 P: ekey int64 [E] = start */
+/* x * (H + 1) + start y of the directed boundary edge in the slot, INT64_MAX for an empty slot; eoth int32 [E] = the end   */
+/* vertex's other coordinate; succ int32 [E] = the slot of the next edge of the ring (saddles: foreground 8-connected).    */
+int rsp_mask_polygon_edges(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                           const int64_t* piece_offs, int64_t P, int32_t* pieces, int64_t* ekey, int32_t* eoth, int32_t* succ,
+                           rsp_stream_t stream);
+/* 3. list ranking by pointer jumping, `rounds` launches per pass with 2^rounds >= the edges of the longest ring (6 x the   */
+/* largest piece_cnt bounds it).  ring_key int64 [E]: the smallest ekey of the edge's ring = its first vertex; flags uint8  */
+/* [E]: bit 0 the edge is its ring's first, bit 1 its start vertex is a corner; lastof int32 [E]: for a first edge the      */
+/* ring's last edge; corners int32 [E] / area2 int64 [E]: the corners and the doubled signed area (positive = clockwise on   */
+/* screen = outer ring) from the ring's first edge up to and including this one.  workspace:                              */
+/* rsp_mask_polygon_rank_workspace_bytes(P).                                                                            */
+int64_t rsp_mask_polygon_rank_workspace_bytes(int64_t P);
+int rsp_mask_polygon_rank(int64_t P, int32_t H, int32_t rounds, const int64_t* ekey, const int32_t* eoth, const int32_t* succ,
+                          void* workspace, int64_t* ring_key, uint8_t* flags, int32_t* lastof, int32_t* corners, int64_t* area2,
+                          rsp_stream_t stream);
+/* 4. ring_keys int64 [R] = instance << 33 | ring_key of the R rings, ascending; ring_offs int64 [R + 1] their vertex       */
+/* offsets, V = ring_offs[R]; ring_area2 int64 [R]; inst_ring_offs int64 [k + 1].  Writes verts int32 [V, 2] = (x, y), the   */
+/* corners of every ring from its smallest vertex on, and ring_parent int32 [R]: -1 for an outer ring, for a hole the index  */
+/* within its instance of the outer ring of the component around it (`rounds`: 2^rounds >= R; near_ws int32 [2 R]).         */
+int rsp_mask_polygon_write(int64_t P, int32_t k, int32_t H, int64_t R, int64_t V, int32_t rounds, const int32_t* pieces,
+                           const int64_t* piece_offs, const int64_t* ekey, const int32_t* eoth, const int64_t* ring_key,
+                           const uint8_t* flags, const int32_t* corners, const int64_t* ring_keys, const int64_t* ring_offs,
+                           const int64_t* ring_area2, const int64_t* inst_ring_offs, int32_t* near_ws, int32_t* verts,
+                           int32_t* ring_parent, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */

@@ -219,3 +219,125 @@ def remove_small_regions(masks, min_area, mode='both'):
     ops.check_region_status(info[:, 7].cpu().tolist())
     changed = (info[:, 0] | info[:, 1]) != 0
     return (out[0], bool(changed[0])) if single else (out, changed)
+
+
+# ------------------------------------------------------------------------------------------ polygon export
+POLYGON_FORMS = ('rings', 'coco', 'geojson')
+
+
+def _masks_to_runs(masks, device):
+    """the three mask forms of masks_to_polygons -> (counts, n, (H, W)) on the device"""
+    from . import rle
+    if isinstance(masks, torch.Tensor):
+        if masks.dim() != 3:
+            raise ValueError('masks_to_polygons: a mask tensor is bool [k, H, W]')
+        counts, n, _, _ = rle.encode_runs(masks.to(torch.bool))
+        return counts, n, (int(masks.shape[1]), int(masks.shape[2]))
+    masks = list(masks)
+    if not masks:
+        raise ValueError('masks_to_polygons: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
+    sizes = {(int(m['size'][0]), int(m['size'][1])) for m in masks}
+    if len(sizes) != 1:
+        raise ValueError(f'masks_to_polygons: the RLE dicts of one call share one size, got {sorted(sizes)}')
+    size = sizes.pop()
+    dev = torch.device(device)
+    ops.require_device(dev)
+    kinds = {isinstance(m['counts'], (bytes, str)) for m in masks}
+    if len(kinds) != 1:
+        raise ValueError('masks_to_polygons: compressed (bytes / str) and uncompressed (list) counts in one call')
+    if kinds.pop():
+        strings = [m['counts'].encode() if isinstance(m['counts'], str) else bytes(m['counts']) for m in masks]
+        offs = np.cumsum([0] + [len(s) for s in strings]).astype(np.int64)
+        flat = torch.from_numpy(np.frombuffer(b''.join(strings) or b'\0', dtype=np.uint8).copy()).to(dev)
+        counts, n = ops.rle_from_string(flat, torch.from_numpy(offs).to(dev))
+        return counts, n, size
+    width = max(max(len(m['counts']) for m in masks), 1)
+    table = np.zeros((len(masks), width), np.int64)
+    for i, m in enumerate(masks):
+        table[i, :len(m['counts'])] = m['counts']
+    if table.size and (int(table.max()) >= 2 ** 31 or int(table.min()) < 0):
+        raise ValueError('masks_to_polygons: not canonical COCO run counts: a count is negative or does not fit 32 bits')
+    n = torch.tensor([len(m['counts']) for m in masks], dtype=torch.int32)
+    return torch.from_numpy(table.astype(np.int32)).to(dev), n.to(dev), size
+
+
+def _check_canonical(counts, n, size):
+    """RLE dicts come from outside: the tracer reads canonical COCO counts only (a zero count anywhere but in front would
+    make two runs of one value touch, counts that do not sum to H * W describe another canvas).  One device-to-host read."""
+    k, cap = int(counts.shape[0]), int(counts.shape[1])
+    if k == 0:
+        return
+    live = torch.arange(cap, device=counts.device)[None] < n[:, None]
+    c = torch.where(live, counts, 0).to(torch.int64)
+    bad = ((c[:, 1:] <= 0) & live[:, 1:]).any(1) | (c[:, :1] < 0).any(1) | ((c.sum(1) != size[0] * size[1]) & (n > 0))
+    rows = bad.nonzero().view(-1).tolist()
+    if rows:
+        raise ValueError(f'masks_to_polygons: the counts of mask {rows[0]} are not canonical COCO run counts of a '
+                         f'{size[0]} x {size[1]} canvas (a zero or negative count after the first, or a sum other than H * W)'
+                         + (f'; {len(rows)} masks in all' if len(rows) > 1 else ''))
+
+
+def rings_to_coco(rings):
+    """the rings of ONE instance -> (list of flat float lists [x0, y0, x1, y1, ...] of its OUTER rings, holes_dropped): COCO
+    polygons cannot express holes, so the polygons describe the hole-filled mask and the flag says that holes were there"""
+    polys = [[float(c) for c in ring.reshape(-1).tolist()] for ring, parent, area2 in rings if area2 > 0]
+    return polys, any(area2 < 0 for _, _, area2 in rings)
+
+
+def rings_to_geojson(rings, transform=None):
+    """the rings of ONE instance -> a GeoJSON geometry dict: a Polygon for one outer ring, a MultiPolygon for several (or
+    none); every polygon = [outer, hole, ...] with the holes attached by `parent`, every ring closed by repeating its first
+    vertex.  transform = (a, b, c, d, e, f): pixel corner (x, y) -> (a + b x + c y, d + e x + f y), float64 on the host."""
+    def coords(ring):
+        xy = np.asarray(ring, np.float64).reshape(-1, 2)
+        if transform is not None:
+            a, b, c, d, e, f = (float(t) for t in transform)
+            xy = np.stack([a + b * xy[:, 0] + c * xy[:, 1], d + e * xy[:, 0] + f * xy[:, 1]], 1)
+        xy = np.concatenate([xy, xy[:1]], 0)
+        return [[float(x), float(y)] for x, y in xy.tolist()]
+    polys = {}
+    for r, (ring, parent, area2) in enumerate(rings):
+        if area2 > 0:
+            polys[r] = [coords(ring)]
+    for ring, parent, area2 in rings:
+        if area2 < 0:
+            polys[parent].append(coords(ring))
+    polys = [polys[r] for r in sorted(polys)]
+    if len(polys) == 1:
+        return dict(type='Polygon', coordinates=polys[0])
+    return dict(type='MultiPolygon', coordinates=polys)
+
+
+def format_polygons(per_instance, form='rings', transform=None):
+    """per-instance ring lists (rle.polygons_to_lists) in one of POLYGON_FORMS"""
+    if form == 'rings':
+        return per_instance
+    if form == 'coco':
+        out = [rings_to_coco(r) for r in per_instance]
+        return [dict(polygons=p, holes_dropped=h) for p, h in out]
+    if form == 'geojson':
+        return [rings_to_geojson(r, transform) for r in per_instance]
+    raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
+
+
+def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0'):
+    """Masks -> exact vector rings on the pixel-corner lattice, traced on the device in the run domain.
+    masks: a bool [k, H, W] device tensor, or a list of RLE dicts dict(size=[H, W], counts=...) of one size with compressed
+    counts (bytes / str, what `encode_mask_results` returns) or uncompressed ones (list, what `generate_masks` returns);
+    `device` places the run table of the dict forms.
+    form='rings': per instance a list of (ring int32 ndarray [m, 2] = (x, y), parent, area2): corners only, clockwise on
+      screen (area2 > 0) for outer rings and counter-clockwise (area2 < 0) for holes, from the ring's smallest vertex on,
+      first vertex not repeated, ordered by first vertex; parent = the outer ring around a hole, -1 for outer rings.
+      Foreground is 8-connected, background 4-connected (cv2.findContours' connectivity).
+    form='coco': per instance dict(polygons=[[x0, y0, x1, y1, ...], ...] of the OUTER rings only, holes_dropped=bool).
+    form='geojson': per instance a Polygon / MultiPolygon geometry dict with the holes attached; `transform` = (a, b, c, d, e,
+      f) maps pixel corners to X = a + b x + c y, Y = d + e x + f y."""
+    from . import rle
+    if form not in POLYGON_FORMS:
+        raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
+    if transform is not None and form != 'geojson':
+        raise ValueError("transform applies to form='geojson' only")
+    counts, n, size = _masks_to_runs(masks, device)
+    if not isinstance(masks, torch.Tensor):
+        _check_canonical(counts, n, size)
+    return format_polygons(rle.polygons_to_lists(*rle.runs_to_polygons(counts, n, size)), form, transform)

@@ -131,12 +131,20 @@ def _check_dense(k, H, W):
 
 
 # ------------------------------------------------------------------------------------------------------------- pipeline
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw):
+def _runs_out(counts, n, scene_hw, polygons):
+    """the scene run table in the form the caller asked for: COCO strings (rsp_rle_to_string), or with polygons=True the
+    per-instance ring lists of DESIGN §14.7 (csrc/mask_polygons.hip), traced on the table before any string is made"""
+    if polygons:
+        return rle.polygons_to_lists(*rle.runs_to_polygons(counts, n, scene_hw))
+    return rle.runs_to_strings(counts, n, scene_hw)
+
+
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
         return []
     sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
-    return rle.runs_to_strings(sc, sn, scene_hw)
+    return _runs_out(sc, sn, scene_hw, polygons)
 
 
 # ------------------------------------------------------------------------------------------------------- seam merge
@@ -264,7 +272,7 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
     return out, reps[keep_m], members, (flat, offs)
 
 
-def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw):
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False):
     """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
     (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
     flat, offs = groups
@@ -274,7 +282,7 @@ def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw):
     sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
     members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
     uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
-    return rle.runs_to_strings(uc, un, scene_hw)
+    return _runs_out(uc, un, scene_hw, polygons)
 
 
 def _seam_dense(tile_masks, origin, groups, scene_hw):
@@ -329,7 +337,8 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
-    (masks='rle') or a bool [K, H, W] device tensor (masks='dense').  return_patches=True: (sample, per-tile samples,
+    (masks='rle'), a bool [K, H, W] device tensor (masks='dense'), or per instance the list of (ring int32 [m, 2], parent,
+    area2) of DESIGN §14.7 (masks='polygons': traced on the device from the scene run table).  return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -339,8 +348,9 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
         raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms' and 'seam_mask' are implemented (soft_nms "
                                   'and the other mmcv variants are not)')
     seam = merge_nms_type == 'seam_mask'
-    if masks not in ('rle', 'dense'):
-        raise ValueError("masks must be 'rle' or 'dense'")
+    if masks not in ('rle', 'dense', 'polygons'):
+        raise ValueError("masks must be 'rle', 'dense' or 'polygons'")
+    poly = masks == 'polygons'
     ph_, pw_ = (int(patch_size), int(patch_size)) if isinstance(patch_size, (int, float)) else (int(patch_size[0]), int(patch_size[1]))
     if pw_ > MAX_PATCH_WIDTH:
         raise ValueError(f'a patch {pw_} pixels wide: the tile RLE kernel is specified for widths up to {MAX_PATCH_WIDTH}')
@@ -413,7 +423,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             tm = torch.cat(dense_tiles, 0) if dense_tiles else torch.zeros((0, th, tw), dtype=torch.bool, device=dev)
             out.masks = _seam_dense(tm, origin, groups, (H, W))
         else:
-            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W))
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly)
     else:
         keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
@@ -423,7 +433,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
             kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
-            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W))
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly)
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
@@ -434,18 +444,44 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     return sample
 
 
+def _is_rings(masks):
+    return isinstance(masks, list) and all(isinstance(m, list) for m in masks)
+
+
 def pred2dict(sample, score_thr=0.0):
-    """DetInferencer.pred2dict form (det_inferencer.py:573-627): labels, scores, bboxes, masks as RLE with `counts` as str"""
+    """DetInferencer.pred2dict form (det_inferencer.py:573-627): labels, scores, bboxes, masks as RLE with `counts` as str;
+    the rings of masks='polygons' as dict(ring=[[x, y], ...], parent, area2) per ring"""
     p = sample.pred_instances
     sel = (p.scores >= score_thr).nonzero().view(-1).tolist()
     lab, sc, bb = p.labels.tolist(), p.scores.tolist(), p.bboxes.tolist()
     out = dict(labels=[lab[i] for i in sel], scores=[sc[i] for i in sel], bboxes=[bb[i] for i in sel])
     if 'masks' in p and p.masks is not None:
         rles = p.masks
+        if _is_rings(rles) and rles:                                   # a tensor (masks='dense') is no list: falls through
+            out['masks'] = [[dict(ring=r.tolist(), parent=int(par), area2=int(a2)) for r, par, a2 in rles[i]] for i in sel]
+            return out
         if isinstance(rles, torch.Tensor):
             rles = rle.encode_mask_results(rles) if rles.shape[0] else []
         out['masks'] = [dict(size=rles[i]['size'], counts=rles[i]['counts'].decode()) for i in sel]
     return out
+
+
+def pred2geojson(sample, score_thr=0.0, transform=None):
+    """a masks='polygons' result as a GeoJSON FeatureCollection: one feature per instance at or above score_thr, geometry
+    from apis.rings_to_geojson (holes attached, rings closed, `transform` applied), properties label, score, bbox"""
+    from .apis import rings_to_geojson
+    p = sample.pred_instances
+    if 'masks' not in p or p.masks is None:
+        if len(p.scores):
+            raise ValueError('pred2geojson: the detector returned no masks, so there are no geometries to write')
+        return dict(type='FeatureCollection', features=[])
+    if not _is_rings(p.masks):
+        raise ValueError("pred2geojson needs the rings of inference_large_image(..., masks='polygons')")
+    sel = (p.scores >= score_thr).nonzero().view(-1).tolist()
+    lab, sc, bb = p.labels.tolist(), p.scores.tolist(), p.bboxes.tolist()
+    feats = [dict(type='Feature', geometry=rings_to_geojson(p.masks[i], transform),
+                  properties=dict(label=lab[i], score=sc[i], bbox=bb[i])) for i in sel]
+    return dict(type='FeatureCollection', features=feats)
 
 
 def main(argv=None):
@@ -466,15 +502,24 @@ def main(argv=None):
     ap.add_argument('--seam-iou-thr', type=float, default=0.5, help="mask IoU inside the tiles' overlap above which two "
                     "fragments are one object (--merge-nms-type seam_mask)")
     ap.add_argument('--batch-size', type=int, default=1, help='Batch size of patches')
+    ap.add_argument('--mask-format', default='rle', choices=('rle', 'polygons', 'geojson'),
+                    help="masks in <name>.json as COCO RLE (default) or as exact rings ('polygons'), or <name>.geojson: a "
+                    "FeatureCollection with label, score and bbox properties ('geojson')")
+    ap.add_argument('--geo-transform', type=float, nargs=6, default=None, metavar=('A', 'B', 'C', 'D', 'E', 'F'),
+                    help='--mask-format geojson: pixel corner (x, y) -> (A + B x + C y, D + E x + F y)')
     a = ap.parse_args(argv)
+    if a.geo_transform is not None and a.mask_format != 'geojson':
+        ap.error('--geo-transform applies to --mask-format geojson')
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
     os.makedirs(a.out_dir, exist_ok=True)
     for path in DetInferencer._inputs_to_list(a.img):
         s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
-                                  a.batch_size, seam_iou_thr=a.seam_iou_thr)
-        dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + '.json')
+                                  a.batch_size, masks='rle' if a.mask_format == 'rle' else 'polygons',
+                                  seam_iou_thr=a.seam_iou_thr)
+        geo = a.mask_format == 'geojson'
+        dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:
-            json.dump(pred2dict(s, a.score_thr), f)
+            json.dump(pred2geojson(s, a.score_thr, a.geo_transform) if geo else pred2dict(s, a.score_thr), f)
         print(f'{path}: {len(s.pred_instances.scores)} instances -> {dst}')
 
 

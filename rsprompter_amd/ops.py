@@ -1767,6 +1767,79 @@ def rle_union(counts, n, H, W, group_offs, members, cap_out):
     return out, n_out
 
 
+# ----------------------------------------------------------------------------- polygon export (csrc/mask_polygons.hip)
+MASK_POLYGON_MAX_PIECES = (2 ** 31 - 1) // 6     # six edge slots per column piece, 32-bit slot numbers
+
+
+def _log2_ceil(v):
+    return max(int(v) - 1, 0).bit_length()
+
+
+def mask_polygons(counts, n, H, W):
+    """run table (counts int32 [k, cap], n int32 [k]: k masks on one (H, W) canvas) -> the rings of every mask on the
+    pixel-corner lattice, all on the device:
+      verts int32 [V, 2] = (x, y), ring_offs int64 [R + 1], ring_inst int32 [R], ring_parent int32 [R] (-1: outer ring, else the
+      index within the instance of the outer ring around the hole), ring_area2 int64 [R] (> 0 outer, < 0 hole),
+      inst_ring_offs int64 [k + 1].
+    Rings are ordered by (instance, first vertex); a ring starts at its smallest vertex by (x, y), holds corners only and does
+    not repeat its first vertex.  A row with n <= 0 has no rings.  Three device-to-host reads, whatever k is: the pieces
+    (total and largest row), the number of rings (inside torch.nonzero), the number of vertices."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('mask_polygons', counts, n, H, W)
+    dev = n.device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+
+    def empty():
+        return (torch.zeros((0, 2), **i32), torch.zeros((1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+                torch.zeros((0,), **i64), torch.zeros((k + 1,), **i64))
+    if k == 0:
+        return empty()
+    piece_cnt = torch.zeros((k,), **i32)
+    _lib.check(lib.rsp_mask_polygon_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_cnt.data_ptr(), _stream()),
+               "rsp_mask_polygon_pieces")
+    piece_offs = torch.cat([piece_cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(piece_cnt, 0, dtype=torch.int64)])
+    P, widest = torch.stack([piece_offs[-1], piece_cnt.max().to(torch.int64)]).tolist()          # read 1
+    if P == 0:
+        return empty()
+    if P > MASK_POLYGON_MAX_PIECES:
+        raise ValueError(f'mask_polygons: {P} column pieces in one call; at most {MASK_POLYGON_MAX_PIECES} (split the rows)')
+    E = 6 * P
+    pieces = torch.empty((4, P), **i32)
+    ekey, eoth, succ = torch.empty((E,), **i64), torch.empty((E,), **i32), torch.empty((E,), **i32)
+    _lib.check(lib.rsp_mask_polygon_edges(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_offs.data_ptr(), P,
+                                          pieces.data_ptr(), ekey.data_ptr(), eoth.data_ptr(), succ.data_ptr(), _stream()),
+               "rsp_mask_polygon_edges")
+    ws = torch.empty((int(lib.rsp_mask_polygon_rank_workspace_bytes(P)) // 8 + 1,), **i64)
+    ring_key, area2 = torch.empty((E,), **i64), torch.empty((E,), **i64)
+    flags = torch.empty((E,), dtype=torch.uint8, device=dev)
+    lastof, corners = torch.empty((E,), **i32), torch.empty((E,), **i32)
+    _lib.check(lib.rsp_mask_polygon_rank(P, H, _log2_ceil(6 * widest), ekey.data_ptr(), eoth.data_ptr(), succ.data_ptr(),
+                                         ws.data_ptr(), ring_key.data_ptr(), flags.data_ptr(), lastof.data_ptr(),
+                                         corners.data_ptr(), area2.data_ptr(), _stream()), "rsp_mask_polygon_rank")
+    # the rings = the edges that start one, sorted by (instance, first vertex); their sizes sit at each ring's last edge
+    first = torch.nonzero(flags & 1).view(-1)                                                     # read 2 (R)
+    R = int(first.shape[0])
+    if R == 0:
+        return empty()
+    ring_inst = pieces[3][first // 6]
+    ring_keys, order = torch.sort((ring_inst.to(torch.int64) << 33) | ring_key[first])
+    ring_inst = ring_inst[order].contiguous()
+    last = lastof[first[order]].to(torch.int64).clamp(min=0)
+    ring_area2 = area2[last].contiguous()
+    ring_offs = torch.cat([last.new_zeros((1,)), torch.cumsum(corners[last].to(torch.int64), 0)]).contiguous()
+    inst_ring_offs = torch.searchsorted(ring_inst, torch.arange(k + 1, **i32)).to(torch.int64).contiguous()
+    V = int(ring_offs[-1])                                                                        # read 3
+    verts = torch.zeros((V, 2), **i32)
+    ring_parent = torch.empty((R,), **i32)
+    near_ws = torch.empty((2 * R,), **i32)
+    _lib.check(lib.rsp_mask_polygon_write(P, k, H, R, V, _log2_ceil(R), pieces.data_ptr(), piece_offs.data_ptr(),
+                                          ekey.data_ptr(), eoth.data_ptr(), ring_key.data_ptr(), flags.data_ptr(),
+                                          corners.data_ptr(), ring_keys.data_ptr(), ring_offs.data_ptr(), ring_area2.data_ptr(),
+                                          inst_ring_offs.data_ptr(), near_ws.data_ptr(), verts.data_ptr(),
+                                          ring_parent.data_ptr(), _stream()), "rsp_mask_polygon_write")
+    return verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs
+
+
 MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
 # the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call

@@ -8,7 +8,9 @@ This module is also the one home of the RUN TABLE that every mask leaves the dev
 [k, cap] + n int32 [k], the column-major COCO stream with zeros as the first run, written by producers that never read the
 host and report a row that did not fit as n[i] = -(slots needed).  The retry on run capacity is `ops.fit_runs`, the retry on
 string bytes (offs[k] > flat_cap: again with flat_cap = offs[k]) is `_string_bytes`; the features call the pipelines below
-and hold no capacity loop of their own."""
+and hold no capacity loop of their own.  The run table is also where the VECTOR form starts: runs_to_polygons
+turns it into exact rings on the device, polygons_to_lists brings them to the host in one transfer."""
+import numpy as np
 import torch
 
 from . import ops
@@ -104,6 +106,26 @@ def runs_to_strings(counts, n, size, flat_cap=None):
     flat, offs = _string_bytes(counts, n, flat_cap or 2 * k * int(counts.shape[1]) + 16)
     buf, o = flat.numpy().tobytes(), offs.tolist()
     return [dict(size=[int(size[0]), int(size[1])], counts=buf[o[i]:o[i + 1]]) for i in range(k)]
+
+
+def runs_to_polygons(counts, n, size):
+    """run table of k masks on one size = (H, W) canvas -> (verts int32 [V, 2], ring_offs int64 [R + 1], ring_inst int32 [R],
+    ring_parent int32 [R], ring_area2 int64 [R], inst_ring_offs int64 [k + 1]) on the device: the rings of DESIGN §14.7
+    (ops.mask_polygons).  Three device-to-host reads, whatever k is."""
+    return ops.mask_polygons(counts, n, size[0], size[1])
+
+
+def polygons_to_lists(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs):
+    """what runs_to_polygons returns -> per instance a list of (ring int32 ndarray [m, 2] = (x, y), parent, area2) on the
+    host, after ONE transfer (the five arrays that are read, packed into one int64 buffer)."""
+    sizes = [int(verts.numel()), int(ring_offs.numel()), int(ring_parent.numel()), int(ring_area2.numel()),
+             int(inst_ring_offs.numel())]
+    buf = torch.cat([verts.reshape(-1).to(torch.int64), ring_offs, ring_parent.to(torch.int64), ring_area2,
+                     inst_ring_offs]).cpu().numpy()
+    v, ro, par, a2, io = np.split(buf, np.cumsum(sizes)[:-1])
+    v = v.astype(np.int32).reshape(-1, 2)
+    ro, par, a2, io = ro.tolist(), par.tolist(), a2.tolist(), io.tolist()
+    return [[(v[ro[r]:ro[r + 1]], par[r], a2[r]) for r in range(io[i], io[i + 1])] for i in range(len(io) - 1)]
 
 
 def runs_to_dicts(counts, n_host, size):
