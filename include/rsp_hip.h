@@ -724,6 +724,36 @@ int rsp_mask_polygon_write(int64_t P, int32_t k, int32_t H, int64_t R, int64_t V
                            const int64_t* ring_area2, const int64_t* inst_ring_offs, int32_t* near_ws, int32_t* verts,
                            int32_t* ring_parent, rsp_stream_t stream);
 
+/* Polygon simplification (csrc/ring_simplify.hip): exact Douglas-Peucker on the rings rsp_mask_polygon_write   */
+/* leaves (or any rings in that layout: verts int32 [V, 2] with coordinates in [0, 2^20], ring_offs int64 [R + 1]).  A ring   */
+/* is closed (v_m = v_0); v_0 and the vertex farthest from it are kept, then every chain between two kept vertices splits at  */
+/* its vertex farthest from the SEGMENT between them (lowest index among equals) while 256 * distance^2 > tol2_q8, tol2_q8 =  */
+/* round(256 tolerance^2) in [0, 2^40]; all comparisons are exact 128-bit integer ones.  max(H, W) <= 2^20 (the coordinate    */
+/* bound) is checked.  Writes keep uint8 [V] (1: kept), pos int32 [V] (kept vertices of the ring in front of the vertex),     */
+/* kept_cnt int32 [R], area2 int64 [R] (doubled area of the kept ring) and rounds int32 [R] (rounds that kept a vertex: the   */
+/* depth of the ring's split tree).  Rings of up to 64 vertices take one wave each, longer ones a block each; variant 0 is    */
+/* the product's choice (256 threads a block), 1 / 2 = 128 / 512 threads, 3 = every ring through the block path (the          */
+/* alternatives tools/bench_ring_simplify.py measures; all give the same result).  No host read, no atomics.                  */
+int rsp_ring_simplify_mark(const int32_t* verts, const int64_t* ring_offs, int64_t R, int64_t V, int64_t tol2_q8, int32_t H,
+                           int32_t W, int32_t variant, uint8_t* keep, int32_t* pos, int32_t* kept_cnt, int64_t* area2,
+                           int32_t* rounds, rsp_stream_t stream);
+/* Which rings stay (one lane per ring): |ring_area2| >= 2 min_ring_area (the area BEFORE simplification), at least 3 kept   */
+/* vertices, a new doubled area that is not 0 and has the old one's sign, and for a hole a parent that stays.  Writes sums    */
+/* int64 [2, R]: row 0 = 1 / 0, row 1 = the kept vertices of a ring that stays / 0.                                           */
+int rsp_ring_simplify_survive(const int32_t* ring_inst, const int32_t* ring_parent, const int64_t* ring_area2,
+                              const int64_t* inst_ring_offs, int64_t R, int32_t k, int64_t min_ring_area, const int32_t* kept_cnt,
+                              const int64_t* area2_new, int64_t* sums, rsp_stream_t stream);
+/* ... and their compaction: csum int64 [2, R] = the inclusive sums of the rows of `sums` over the rings, R2 / V2 = their     */
+/* totals (the surviving rings and their vertices).  Writes verts_out int32 [V2, 2], ring_offs_out int64 [R2 + 1],            */
+/* ring_inst_out / ring_parent_out (re-indexed among the survivors of the instance) / ring_src_out int32 [R2] (the survivor's */
+/* index among the input rings), ring_area2_out int64 [R2] and inst_ring_offs_out int64 [k + 1].  R2 = 0 writes nothing.      */
+int rsp_ring_simplify_write(const int32_t* verts, const int64_t* ring_offs, const int32_t* ring_inst, const int32_t* ring_parent,
+                            const int64_t* inst_ring_offs, int64_t R, int64_t V, int32_t k, const uint8_t* keep,
+                            const int32_t* pos, const int64_t* area2_new, const int64_t* sums, const int64_t* csum, int64_t R2,
+                            int64_t V2, int32_t* verts_out, int64_t* ring_offs_out, int32_t* ring_inst_out,
+                            int32_t* ring_parent_out, int64_t* ring_area2_out, int64_t* inst_ring_offs_out, int32_t* ring_src_out,
+                            rsp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */
 /* ------------------------------------------------------------------------ */

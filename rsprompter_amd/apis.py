@@ -320,7 +320,7 @@ def format_polygons(per_instance, form='rings', transform=None):
     raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
 
 
-def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0'):
+def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tolerance=None, min_ring_area=0):
     """Masks -> exact vector rings on the pixel-corner lattice, traced on the device in the run domain.
     masks: a bool [k, H, W] device tensor, or a list of RLE dicts dict(size=[H, W], counts=...) of one size with compressed
     counts (bytes / str, what `encode_mask_results` returns) or uncompressed ones (list, what `generate_masks` returns);
@@ -331,13 +331,25 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0'):
       Foreground is 8-connected, background 4-connected (cv2.findContours' connectivity).
     form='coco': per instance dict(polygons=[[x0, y0, x1, y1, ...], ...] of the OUTER rings only, holes_dropped=bool).
     form='geojson': per instance a Polygon / MultiPolygon geometry dict with the holes attached; `transform` = (a, b, c, d, e,
-      f) maps pixel corners to X = a + b x + c y, Y = d + e x + f y."""
+      f) maps pixel corners to X = a + b x + c y, Y = d + e x + f y.
+    tolerance (pixels; None: the exact rings) simplifies every ring on the device by Douglas-Peucker before
+      it reaches the host: a dropped vertex lies within `tolerance` of the kept outline; rings are simplified independently
+      (they may then cross); rings of less than min_ring_area pixels, rings that collapse, and the holes of a dropped outer
+      ring are dropped -- a dropped hole is filled.  Both apply to all three forms; min_ring_area alone (tolerance=None)
+      filters at tolerance 0, which keeps every vertex of the rings that stay."""
     from . import rle
     if form not in POLYGON_FORMS:
         raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
     if transform is not None and form != 'geojson':
         raise ValueError("transform applies to form='geojson' only")
+    simplify = tolerance is not None or min_ring_area != 0
+    if simplify:                                                        # refused before anything runs
+        rle.polygon_tolerance_q8(0 if tolerance is None else tolerance)
+        rle.polygon_min_ring_area(min_ring_area)
     counts, n, size = _masks_to_runs(masks, device)
     if not isinstance(masks, torch.Tensor):
         _check_canonical(counts, n, size)
-    return format_polygons(rle.polygons_to_lists(*rle.runs_to_polygons(counts, n, size)), form, transform)
+    polys = rle.runs_to_polygons(counts, n, size)
+    if simplify:
+        polys, _ = rle.simplify_polygons(polys, size, 0 if tolerance is None else tolerance, min_ring_area)
+    return format_polygons(rle.polygons_to_lists(*polys), form, transform)

@@ -132,10 +132,14 @@ def _check_dense(k, H, W):
 
 # ------------------------------------------------------------------------------------------------------------- pipeline
 def _runs_out(counts, n, scene_hw, polygons):
-    """the scene run table in the form the caller asked for: COCO strings (rsp_rle_to_string), or with polygons=True the
-    per-instance ring lists of DESIGN §14.7 (csrc/mask_polygons.hip), traced on the table before any string is made"""
+    """the scene run table in the form the caller asked for: COCO strings (rsp_rle_to_string), or with polygons (True, or
+    (tolerance, min_ring_area) to simplify them on the device) the per-instance ring lists of DESIGN §14.7
+    (csrc/mask_polygons.hip), traced on the table before any string is made"""
     if polygons:
-        return rle.polygons_to_lists(*rle.runs_to_polygons(counts, n, scene_hw))
+        polys = rle.runs_to_polygons(counts, n, scene_hw)
+        if polygons is not True:
+            polys, _ = rle.simplify_polygons(polys, scene_hw, polygons[0], polygons[1])
+        return rle.polygons_to_lists(*polys)
     return rle.runs_to_strings(counts, n, scene_hw)
 
 
@@ -333,12 +337,15 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 
 @torch.no_grad()
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
-                          batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5):
+                          batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
+                          polygon_min_ring_area=0):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
     (masks='rle'), a bool [K, H, W] device tensor (masks='dense'), or per instance the list of (ring int32 [m, 2], parent,
-    area2) of DESIGN §14.7 (masks='polygons': traced on the device from the scene run table).  return_patches=True: (sample, per-tile samples,
+    area2) of DESIGN §14.7 (masks='polygons': traced on the device from the scene run table; polygon_tolerance in pixels and
+    polygon_min_ring_area in pixels simplify the rings there first, DESIGN §14.8 -- apis.masks_to_polygons says how; they
+    apply to masks='polygons' only).  return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -351,6 +358,12 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     if masks not in ('rle', 'dense', 'polygons'):
         raise ValueError("masks must be 'rle', 'dense' or 'polygons'")
     poly = masks == 'polygons'
+    if polygon_tolerance is not None or polygon_min_ring_area != 0:
+        if not poly:
+            raise ValueError("polygon_tolerance and polygon_min_ring_area apply to masks='polygons'")
+        poly = (0 if polygon_tolerance is None else polygon_tolerance, polygon_min_ring_area)
+        rle.polygon_tolerance_q8(poly[0])                               # refused before the first tile runs
+        rle.polygon_min_ring_area(poly[1])
     ph_, pw_ = (int(patch_size), int(patch_size)) if isinstance(patch_size, (int, float)) else (int(patch_size[0]), int(patch_size[1]))
     if pw_ > MAX_PATCH_WIDTH:
         raise ValueError(f'a patch {pw_} pixels wide: the tile RLE kernel is specified for widths up to {MAX_PATCH_WIDTH}')
@@ -507,15 +520,28 @@ def main(argv=None):
                     "FeatureCollection with label, score and bbox properties ('geojson')")
     ap.add_argument('--geo-transform', type=float, nargs=6, default=None, metavar=('A', 'B', 'C', 'D', 'E', 'F'),
                     help='--mask-format geojson: pixel corner (x, y) -> (A + B x + C y, D + E x + F y)')
+    ap.add_argument('--simplify-tolerance', type=float, default=None, metavar='T',
+                    help='--mask-format polygons|geojson: Douglas-Peucker on the device, dropped vertices lie within T pixels '
+                    'of the kept outline (default: the exact rings)')
+    ap.add_argument('--min-ring-area', type=int, default=0, metavar='A',
+                    help='--mask-format polygons|geojson: drop rings of less than A pixels (a dropped hole is filled)')
     a = ap.parse_args(argv)
     if a.geo_transform is not None and a.mask_format != 'geojson':
         ap.error('--geo-transform applies to --mask-format geojson')
+    if (a.simplify_tolerance is not None or a.min_ring_area != 0) and a.mask_format == 'rle':
+        ap.error('--simplify-tolerance and --min-ring-area apply to --mask-format polygons and geojson')
+    try:
+        rle.polygon_tolerance_q8(0 if a.simplify_tolerance is None else a.simplify_tolerance)
+        rle.polygon_min_ring_area(a.min_ring_area)
+    except ValueError as e:
+        ap.error(str(e))
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
     os.makedirs(a.out_dir, exist_ok=True)
     for path in DetInferencer._inputs_to_list(a.img):
         s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
                                   a.batch_size, masks='rle' if a.mask_format == 'rle' else 'polygons',
-                                  seam_iou_thr=a.seam_iou_thr)
+                                  seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
+                                  polygon_min_ring_area=a.min_ring_area)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

@@ -1840,6 +1840,82 @@ def mask_polygons(counts, n, H, W):
     return verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs
 
 
+# ----------------------------------------------------------------------------- polygon simplification (csrc/ring_simplify.hip)
+RING_SIMPLIFY_MAX_TOL2_Q8 = 2 ** 40      # tolerance^2 in 1 / 256 px^2: tolerances up to 65 536 px
+RING_SIMPLIFY_MAX_SIDE = 2 ** 20         # coordinates in [0, 2^20]: every distance comparison fits 128-bit integers
+_RING_ARRAYS = (('verts', torch.int32, 2), ('ring_offs', torch.int64, 1), ('ring_inst', torch.int32, 1),
+                ('ring_parent', torch.int32, 1), ('ring_area2', torch.int64, 1), ('inst_ring_offs', torch.int64, 1))
+
+
+def ring_simplify(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs, tol2_q8, min_ring_area, H, W,
+                  with_rounds=False, variant=0):
+    """Douglas-Peucker on the rings of mask_polygons (the six arrays it returns, or synthetic rings in that layout with
+    coordinates in [0, 2^20]), exact and on the device: every ring keeps its first vertex and the vertex
+    farthest from it, then the vertices farther than the tolerance from the SEGMENT between the kept vertices around them,
+    chain by chain; tol2_q8 = round(256 tolerance^2), an integer in [0, 2^40].  A ring is dropped when |ring_area2| <
+    2 min_ring_area (the area BEFORE simplification), when fewer than 3 vertices are kept, when its new doubled area is 0 or
+    changed sign, or when it is a hole whose outer ring was dropped.  Returns the six arrays of the surviving rings in their
+    old order (ring_area2 recomputed, ring_parent re-indexed among the survivors of the instance, inst_ring_offs rebuilt) and
+    ring_src int32 [R'], each survivor's index among the input rings; with_rounds=True appends rounds int32 [R], the depth of
+    every INPUT ring's split tree.  One device-to-host read (R' and V', together).  `variant`: the launch alternatives of
+    rsp_ring_simplify_mark (measurement only: the results are the same)."""
+    lib = _lib.load()
+    arrays = (verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs)
+    for (name, dtype, dim), t in zip(_RING_ARRAYS, arrays):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dim or t.device != verts.device:
+            raise ValueError(f'ring_simplify: {name} must be a {dtype} tensor of {dim} dimension(s) on the device of verts')
+    if not _is_device(verts):
+        raise ValueError('ring_simplify: the ring arrays live on the HIP device')
+    R, V, k = int(ring_inst.shape[0]), int(verts.shape[0]), int(inst_ring_offs.shape[0]) - 1
+    if verts.shape[1] != 2 or ring_offs.shape[0] != R + 1 or ring_parent.shape[0] != R or ring_area2.shape[0] != R or k < 0:
+        raise ValueError('ring_simplify: expected verts [V, 2], ring_offs [R + 1], ring_inst / ring_parent / ring_area2 [R] '
+                         'and inst_ring_offs [k + 1]')
+    if isinstance(tol2_q8, bool) or not isinstance(tol2_q8, int) or not 0 <= tol2_q8 <= RING_SIMPLIFY_MAX_TOL2_Q8:
+        raise ValueError(f'ring_simplify: tol2_q8 is an integer in [0, 2^40], got {tol2_q8!r}')
+    if isinstance(min_ring_area, bool) or not isinstance(min_ring_area, int) or min_ring_area < 0:
+        raise ValueError(f'ring_simplify: min_ring_area is a non-negative integer of pixels, got {min_ring_area!r}')
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or max(H, W) > RING_SIMPLIFY_MAX_SIDE:
+        raise ValueError(f'ring_simplify: a {H} x {W} canvas; the sides are in [1, 2^20]')
+    if V >= 2 ** 31 or R >= 2 ** 31:
+        raise ValueError('ring_simplify: at most 2^31 - 1 vertices and rings in one call')
+    dev = verts.device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs = (t.contiguous() for t in arrays)
+    rounds = torch.zeros((0,), **i32)
+
+    def nothing():
+        out = (torch.zeros((0, 2), **i32), torch.zeros((1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+               torch.zeros((0,), **i64), torch.zeros((k + 1,), **i64), torch.zeros((0,), **i32))
+        return out + (rounds,) if with_rounds else out
+    if R == 0:
+        return nothing()
+    keep = torch.zeros((max(V, 1),), dtype=torch.uint8, device=dev)
+    pos = torch.empty((max(V, 1),), **i32)
+    cnt, area2, sums = torch.empty((R,), **i32), torch.empty((R,), **i64), torch.empty((2, R), **i64)
+    rounds = torch.empty((R,), **i32)
+    _lib.check(lib.rsp_ring_simplify_mark(verts.data_ptr(), ring_offs.data_ptr(), R, V, tol2_q8, H, W, int(variant),
+                                          keep.data_ptr(), pos.data_ptr(), cnt.data_ptr(), area2.data_ptr(), rounds.data_ptr(),
+                                          _stream()), "rsp_ring_simplify_mark")
+    _lib.check(lib.rsp_ring_simplify_survive(ring_inst.data_ptr(), ring_parent.data_ptr(), ring_area2.data_ptr(),
+                                             inst_ring_offs.data_ptr(), R, k, min(min_ring_area, 2 ** 62), cnt.data_ptr(),
+                                             area2.data_ptr(), sums.data_ptr(), _stream()), "rsp_ring_simplify_survive")
+    csum = torch.cumsum(sums, 1)                      # survivors and their vertices up to every ring: one sum over both rows
+    R2, V2 = csum[:, -1].tolist()                                                                   # the one read
+    if R2 == 0:
+        return nothing()
+    out_verts = torch.zeros((V2, 2), **i32)
+    out_offs, out_area2, out_inst_offs = torch.empty((R2 + 1,), **i64), torch.empty((R2,), **i64), torch.empty((k + 1,), **i64)
+    out_inst, out_parent, out_src = torch.empty((R2,), **i32), torch.empty((R2,), **i32), torch.empty((R2,), **i32)
+    _lib.check(lib.rsp_ring_simplify_write(verts.data_ptr(), ring_offs.data_ptr(), ring_inst.data_ptr(), ring_parent.data_ptr(),
+                                           inst_ring_offs.data_ptr(), R, V, k, keep.data_ptr(), pos.data_ptr(), area2.data_ptr(),
+                                           sums.data_ptr(), csum.data_ptr(), R2, V2, out_verts.data_ptr(), out_offs.data_ptr(),
+                                           out_inst.data_ptr(), out_parent.data_ptr(), out_area2.data_ptr(),
+                                           out_inst_offs.data_ptr(), out_src.data_ptr(), _stream()), "rsp_ring_simplify_write")
+    out = (out_verts, out_offs, out_inst, out_parent, out_area2, out_inst_offs, out_src)
+    return out + (rounds,) if with_rounds else out
+
+
 MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
 # the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call

@@ -9,7 +9,10 @@ This module is also the one home of the RUN TABLE that every mask leaves the dev
 host and report a row that did not fit as n[i] = -(slots needed).  The retry on run capacity is `ops.fit_runs`, the retry on
 string bytes (offs[k] > flat_cap: again with flat_cap = offs[k]) is `_string_bytes`; the features call the pipelines below
 and hold no capacity loop of their own.  The run table is also where the VECTOR form starts: runs_to_polygons
-turns it into exact rings on the device, polygons_to_lists brings them to the host in one transfer."""
+turns it into exact rings on the device, simplify_polygons thins them there, polygons_to_lists brings them
+to the host in one transfer."""
+import math
+
 import numpy as np
 import torch
 
@@ -113,6 +116,40 @@ def runs_to_polygons(counts, n, size):
     ring_parent int32 [R], ring_area2 int64 [R], inst_ring_offs int64 [k + 1]) on the device: the rings of DESIGN §14.7
     (ops.mask_polygons).  Three device-to-host reads, whatever k is."""
     return ops.mask_polygons(counts, n, size[0], size[1])
+
+
+def polygon_tolerance_q8(tolerance):
+    """a simplification tolerance in pixels -> tol2_q8 = round(256 tolerance^2), the integer every distance is compared with
+    (DESIGN §14.8); refuses what is negative, not finite, or above 2^40 (65 536 px)"""
+    try:
+        t = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError(f'a simplification tolerance is a number of pixels, got {tolerance!r}') from None
+    if isinstance(tolerance, bool) or not math.isfinite(t) or t < 0:
+        raise ValueError(f'a simplification tolerance is a finite number of pixels >= 0, got {tolerance!r}')
+    q8 = int(round(t * t * 256))
+    if q8 > ops.RING_SIMPLIFY_MAX_TOL2_Q8:
+        raise ValueError(f'a simplification tolerance of {tolerance!r} px: 256 tolerance^2 is at most 2^40 (65 536 px)')
+    return q8
+
+
+def polygon_min_ring_area(min_ring_area):
+    """min_ring_area as the non-negative integer of pixels ops.ring_simplify takes (a float with an integer value passes)"""
+    a = min_ring_area
+    if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not math.isfinite(a) or a < 0 \
+            or a != int(a):
+        raise ValueError(f'min_ring_area is a non-negative integer number of pixels, got {min_ring_area!r}')
+    return int(a)
+
+
+def simplify_polygons(polys, size, tolerance, min_ring_area=0):
+    """what runs_to_polygons returns, on a size = (H, W) canvas -> (the six arrays of the simplified rings, ring_src int32
+    [R']) on the device: exact Douglas-Peucker at `tolerance` pixels (distance to the segment between the kept vertices
+    around a vertex; tolerance^2 is quantised to 1 / 256 px^2), rings of less than min_ring_area pixels (before
+    simplification) dropped, with the holes of a dropped outer ring (ops.ring_simplify).  ring_src[r] = the
+    input ring that output ring r was.  One device-to-host read."""
+    out = ops.ring_simplify(*polys, polygon_tolerance_q8(tolerance), polygon_min_ring_area(min_ring_area), size[0], size[1])
+    return out[:6], out[6]
 
 
 def polygons_to_lists(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs):
