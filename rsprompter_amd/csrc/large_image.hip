@@ -8,6 +8,7 @@
 //                          in the run domain (the scene-sized dense mask of sahi's shift_masks never exists)
 //   rsp_paste_tiles      : the dense form of shift_masks, for callers who ask for dense scene masks
 #include "rsp_common.h"
+#include "run_table.h"
 
 namespace {
 
@@ -160,7 +161,9 @@ constexpr int SHIFT_THREADS = 256;
 // runs: scan of the counts (pixel starts), scan of the pieces each ones-run emits (output slots), then the pieces of the
 // chunk are dealt out to the threads round-robin (a full-tile mask is ONE input run with w pieces), each finding its
 // input run by a binary search over the chunk's slot prefix in LDS.
-// Input as rsp_mask_rle writes it: only count 0 may be zero.
+// Input: a tile-frame run table as rsp_mask_rle writes it (run_table.h).  This kernel keeps its own walk over the row and
+// its own column arithmetic: on RspRunWalk the compiler lays the piece loop out differently and the kernel measured
+// 9 % slower (profiles/run_walk/parent_vs_this.txt).
 __global__ __launch_bounds__(SHIFT_THREADS) void rle_shift_kernel(const uint32_t* __restrict__ counts_in,
                                                                   const int32_t* __restrict__ n_in, int cap_in,
                                                                   const int32_t* __restrict__ offsets, int h, int w,
@@ -331,7 +334,7 @@ extern "C" int rsp_rle_shift(const uint32_t* counts_in, const int32_t* n_in, int
   if (!counts_in || !n_in || !offsets || !counts_out || !n_out || k < 0 || cap_in < 1 || cap_out < 2 || h <= 0 || w <= 0 ||
       h > H || w > W)
     return RSP_EINVAL;
-  if ((int64_t)H * W > 0x7fffffffLL) return RSP_EINVAL;          // COCO's counts are 32-bit
+  if (!rsp_run_canvas_ok(H, W)) return RSP_EINVAL;               // h <= H and w <= W above: refuses the pixel count only
   if (k == 0) return RSP_OK;
   hipLaunchKernelGGL(rle_shift_kernel, dim3(k), dim3(SHIFT_THREADS), 0, (hipStream_t)stream, counts_in, n_in, cap_in,
                      offsets, h, w, H, W, counts_out, n_out, cap_out);

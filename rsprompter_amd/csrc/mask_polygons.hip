@@ -1,6 +1,6 @@
 // Polygon export: run tables -> exact vector rings on the pixel-corner lattice, in work proportional to
-// the number of runs.  Input: counts [k, cap] / n [k] as rsp_mask_rle / rsp_rle_shift / rsp_rle_union write them (COCO run
-// counts of k masks on ONE (H, W) canvas, column-major stream, only count 0 may be zero, n <= 0 = no rings).
+// the number of runs.  Input: a run table as rsp_mask_rle / rsp_rle_shift / rsp_rle_union write it, read through
+// run_table.h; a row with n <= 0 has no rings.
 //
 // PIECES.  A ones-run that crosses a column end is split into column pieces (x, y0, y1), y0 < y1; in stream order they
 // are sorted by (x, y0), and the pieces of one column neither overlap nor touch.
@@ -20,6 +20,7 @@
 // of corners and the doubled area in front of every edge.  Both take `rounds` launches, 2^rounds >= the longest ring.
 // No lane walks a ring.  Integer arithmetic; no atomics: a second launch is bit-identical.
 #include "rsp_common.h"
+#include "run_table.h"
 
 namespace {
 
@@ -77,16 +78,12 @@ __global__ __launch_bounds__(MP_THREADS) void mp_count_kernel(const uint32_t* __
                                                               int32_t* __restrict__ piece_cnt) {
   __shared__ int tmp[MP_THREADS / 64];
   const int m = blockIdx.x, tid = threadIdx.x;
-  const int n = min(n_in[m], cap);
-  const uint32_t* c_row = counts + (int64_t)m * cap;
-  int carry = 0, pieces = 0;
-  for (int i0 = 0; i0 < n; i0 += MP_THREADS) {
-    const int i = i0 + tid;
-    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
-    int chunk_px;
-    const int s = carry + rsp_block_excl_scan<MP_THREADS>(c, tmp, &chunk_px);
-    if (i < n && (i & 1) && c > 0) pieces += (s + c - 1) / H - s / H + 1;
-    carry += chunk_px;
+  int pieces = 0;
+  for (RspRunWalk<MP_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
+    if ((r.i & 1) && r.c > 0) {
+      const RspRunCols q = rsp_run_cols(r.s, r.c, H);
+      pieces += q.xb - q.xa + 1;
+    }
   }
   int total;
   rsp_block_excl_scan<MP_THREADS>(pieces, tmp, &total);
@@ -100,31 +97,23 @@ __global__ __launch_bounds__(MP_THREADS) void mp_pieces_kernel(const uint32_t* _
                                                                int32_t* __restrict__ px, int32_t* __restrict__ py0,
                                                                int32_t* __restrict__ py1, int32_t* __restrict__ pinst) {
   __shared__ int tmp[MP_THREADS / 64];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  const int n = min(n_in[m], cap);
-  const uint32_t* c_row = counts + (int64_t)m * cap;
+  const int m = blockIdx.x;
   const int64_t base = piece_offs[m] < 0 ? 0 : piece_offs[m], end = piece_offs[m + 1] < P ? piece_offs[m + 1] : P;
-  int carry = 0;
   int64_t carry_p = 0;
-  for (int i0 = 0; i0 < n; i0 += MP_THREADS) {
-    const int i = i0 + tid;
-    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scans' shuffles
-    int chunk_px, chunk_p;
-    const int s = carry + rsp_block_excl_scan<MP_THREADS>(c, tmp, &chunk_px);
-    const int ones = c & -(int)(i & 1);
-    const int e1 = s + ones - 1;
-    const int xa = s / H, np = ones > 0 ? e1 / H - xa + 1 : 0;
+  for (RspRunWalk<MP_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
+    const int ones = r.c & -(int)(r.i & 1);
+    const RspRunCols c = rsp_run_cols(r.s, ones, H);        // not used where ones == 0
+    const int np = ones > 0 ? c.xb - c.xa + 1 : 0;           // a mask and a select up to the second scan: run_table.h
+    int chunk_p;
     const int64_t q0 = base + carry_p + rsp_block_excl_scan<MP_THREADS>(np, tmp, &chunk_p);
     for (int j = 0; j < np; ++j) {
       const int64_t q = q0 + j;
       if (q < base || q >= end) break;
-      const int x = xa + j;
-      px[q] = x;
-      py0[q] = j == 0 ? s - xa * H : 0;
-      py1[q] = j == np - 1 ? e1 - x * H + 1 : H;
+      px[q] = c.xa + j;
+      py0[q] = j == 0 ? c.ra : 0;
+      py1[q] = j == np - 1 ? c.rb + 1 : H;
       pinst[q] = m;
     }
-    carry += chunk_px;
     carry_p += chunk_p;
   }
 }
@@ -396,7 +385,6 @@ __global__ __launch_bounds__(MP_THREADS) void mp_parent_kernel(int64_t R, int k,
   parent[r] = par;
 }
 
-inline bool mp_scene_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffffLL; }
 inline unsigned mp_blocks(int64_t n) { return (unsigned)((n + MP_THREADS - 1) / MP_THREADS); }
 constexpr int64_t MP_MAX_PIECES = 0x7fffffffLL / 6;
 
@@ -404,7 +392,7 @@ constexpr int64_t MP_MAX_PIECES = 0x7fffffffLL / 6;
 
 extern "C" int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                                        int32_t* piece_cnt, rsp_stream_t stream) {
-  if (!counts || !n || !piece_cnt || k < 0 || cap < 1 || !mp_scene_ok(H, W)) return RSP_EINVAL;
+  if (!counts || !n || !piece_cnt || k < 0 || cap < 1 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipLaunchKernelGGL(mp_count_kernel, dim3(k), dim3(MP_THREADS), 0, (hipStream_t)stream, counts, n, cap, H, piece_cnt);
   RSP_CHECK_LAUNCH();
@@ -414,7 +402,7 @@ extern "C" int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n,
 extern "C" int rsp_mask_polygon_edges(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                                       const int64_t* piece_offs, int64_t P, int32_t* pieces, int64_t* ekey, int32_t* eoth,
                                       int32_t* succ, rsp_stream_t stream) {
-  if (!counts || !n || !piece_offs || k < 0 || cap < 1 || P < 0 || P > MP_MAX_PIECES || !mp_scene_ok(H, W)) return RSP_EINVAL;
+  if (!counts || !n || !piece_offs || k < 0 || cap < 1 || P < 0 || P > MP_MAX_PIECES || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (P > 0 && (!pieces || !ekey || !eoth || !succ)) return RSP_EINVAL;
   if (k == 0 || P == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;

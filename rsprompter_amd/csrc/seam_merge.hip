@@ -1,14 +1,14 @@
 // Merging instances cut by tile seams: arithmetic BETWEEN scene-sized masks in the run domain.  The dense
 // form -- pad every tile mask to the scene (sahi shift_masks), then `(a & b).sum()`, `a[:, y0:y1, x0:x1].sum()`,
 // `a | b` and pycocotools' toBbox / area / encode on scene-sized arrays -- never exists: one 10 000 x 10 000 mask is
-// 100 MB.  Input everywhere: scene-frame COCO run counts as rsp_rle_shift writes them (counts [k, cap], n [k], column-major
-// stream of an (H, W) canvas, only count 0 may be zero, n <= 0 = an empty row).
+// 100 MB.  Input everywhere: a scene-frame run table as rsp_rle_shift writes it, read through run_table.h.
 //   rsp_rle_bbox         : tight box + area per row (maskUtils.toBbox / area)
 //   rsp_rle_pair_overlap : per pair of rows (i, j) and rectangle R: |M_i & M_j|, |M_i & R|, |M_j & R|
 //   rsp_rle_intervals    : the ones-runs of the member rows of G groups as (group, start) keys + ends, to be sorted by key
 //   rsp_rle_union        : sorted intervals of G groups -> canonical COCO run counts of each group's union
 // Integer arithmetic only; every result is exact and independent of the launch.
 #include "rsp_common.h"
+#include "run_table.h"
 
 namespace {
 
@@ -60,30 +60,23 @@ __device__ __forceinline__ int sm_reduce(int v, int* tmp) {
 }
 
 // ------------------------------------------------------------------------------------------------- tight box, area
-// One block per row.  A ones-run [s, e) of the column-major stream touches columns xa = s / H .. xb = (e - 1) / H; when it
-// spans columns it reaches the last row of xa and the first row of xb, so its rows are [0, H).
+// One block per row.  A ones-run that spans columns (rsp_run_cols) reaches the last row of one and the first row of the
+// next, so its rows are [0, H).
 __global__ __launch_bounds__(SM_THREADS) void rle_bbox_kernel(const uint32_t* __restrict__ counts,
                                                               const int32_t* __restrict__ n_in, int cap, int H,
                                                               int32_t* __restrict__ boxes, int32_t* __restrict__ area) {
   __shared__ int tmp[SM_WAVES];
   const int m = blockIdx.x, tid = threadIdx.x;
-  const int n = min(n_in[m], cap);
-  const uint32_t* c_row = counts + (int64_t)m * cap;
-  int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0, a = 0, carry = 0;
-  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
-    const int i = i0 + tid;
-    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
-    int chunk_px;
-    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
-    if (i < n && (i & 1) && c > 0) {
-      const int e1 = s + c - 1, xa = s / H, xb = e1 / H;
-      x0 = min(x0, xa);
-      x1 = max(x1, xb + 1);
-      y0 = min(y0, xa == xb ? s - xa * H : 0);
-      y1 = max(y1, xa == xb ? e1 - xb * H + 1 : H);
-      a += c;
+  int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0, a = 0;
+  for (RspRunWalk<SM_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
+    if ((r.i & 1) && r.c > 0) {
+      const RspRunCols q = rsp_run_cols(r.s, r.c, H);
+      x0 = min(x0, q.xa);
+      x1 = max(x1, q.xb + 1);
+      y0 = min(y0, q.xa == q.xb ? q.ra : 0);
+      y1 = max(y1, q.xa == q.xb ? q.rb + 1 : H);
+      a += r.c;
     }
-    carry += chunk_px;
   }
   x0 = sm_reduce<SM_MIN>(x0, tmp);
   y0 = sm_reduce<SM_MIN>(y0, tmp);
@@ -108,22 +101,17 @@ __global__ __launch_bounds__(SM_THREADS) void rle_prefix_kernel(const uint32_t* 
                                                                 const int32_t* __restrict__ n_in, int cap,
                                                                 int32_t* __restrict__ ws) {
   __shared__ int tmp[SM_WAVES];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  const int n = min(n_in[m], cap);
-  const uint32_t* c_row = counts + (int64_t)m * cap;
+  const int m = blockIdx.x;
+  const RspRunRow row = rsp_run_row(counts, n_in, cap, m);
   int32_t* w_row = ws + (int64_t)m * cap;
-  int carry = 0, carry_ones = 0;
-  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
-    const int i = i0 + tid;
-    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
-    int chunk_px, chunk_ones;
-    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
-    const int ob = carry_ones + rsp_block_excl_scan<SM_THREADS>((i & 1) ? c : 0, tmp, &chunk_ones);
-    if (i < n && (i & 1)) {
-      w_row[i - 1] = ob;
-      w_row[i] = s;
+  int carry_ones = 0;
+  for (RspRunWalk<SM_THREADS> r(row, tmp); r.next();) {
+    int chunk_ones;
+    const int ob = carry_ones + rsp_block_excl_scan<SM_THREADS>((r.i & 1) ? r.c : 0, tmp, &chunk_ones);
+    if (r.i < row.n && (r.i & 1)) {
+      w_row[r.i - 1] = ob;
+      w_row[r.i] = r.s;
     }
-    carry += chunk_px;
     carry_ones += chunk_ones;
   }
 }
@@ -153,13 +141,12 @@ __device__ __forceinline__ int sm_ones_before(const SmRow& r, int p) {
 
 // pixels of the ones-run [s, s + c) inside columns [x0, x1), rows [y0, y1): first / middle / last column in closed form
 __device__ __forceinline__ int sm_run_in_rect(int s, int c, int H, int x0, int y0, int x1, int y1) {
-  const int e1 = s + c - 1, xa = s / H, xb = e1 / H;
-  const int ra = s - xa * H, rb = e1 - xb * H;              // first row in xa, last row in xb (inclusive)
-  if (xa == xb) return (xa >= x0 && xa < x1) ? max(0, min(rb + 1, y1) - max(ra, y0)) : 0;
+  const RspRunCols q = rsp_run_cols(s, c, H);
+  if (q.xa == q.xb) return (q.xa >= x0 && q.xa < x1) ? max(0, min(q.rb + 1, y1) - max(q.ra, y0)) : 0;
   int a = 0;
-  if (xa >= x0 && xa < x1) a += max(0, y1 - max(ra, y0));
-  if (xb >= x0 && xb < x1) a += max(0, min(rb + 1, y1) - y0);
-  a += max(0, min(xb, x1) - max(xa + 1, x0)) * (y1 - y0);
+  if (q.xa >= x0 && q.xa < x1) a += max(0, y1 - max(q.ra, y0));
+  if (q.xb >= x0 && q.xb < x1) a += max(0, min(q.rb + 1, y1) - y0);
+  a += max(0, min(q.xb, x1) - max(q.xa + 1, x0)) * (y1 - y0);
   return a;
 }
 
@@ -227,24 +214,17 @@ __global__ __launch_bounds__(SM_THREADS) void rle_intervals_kernel(const uint32_
                                                                    const int64_t* __restrict__ moff, int64_t total,
                                                                    int64_t* __restrict__ keys, int32_t* __restrict__ ends) {
   __shared__ int tmp[SM_WAVES];
-  const int mi = blockIdx.x, tid = threadIdx.x;
+  const int mi = blockIdx.x;
   const int m = members[mi];
   if (m < 0 || m >= k) return;
-  const int n = min(n_in[m], cap);
-  const uint32_t* c_row = counts + (int64_t)m * cap;
+  const RspRunRow row = rsp_run_row(counts, n_in, cap, m);
   const int64_t g = (int64_t)member_group[mi] << 31, base = moff[mi];
-  int carry = 0;
-  for (int i0 = 0; i0 < n; i0 += SM_THREADS) {
-    const int i = i0 + tid;
-    const int c = (int)c_row[min(i, n - 1)] & -(int)(i < n);          // no branch in front of the scan's shuffles
-    int chunk_px;
-    const int s = carry + rsp_block_excl_scan<SM_THREADS>(c, tmp, &chunk_px);
-    const int64_t q = base + (i >> 1);
-    if (i < n && (i & 1) && q >= 0 && q < total) {
-      keys[q] = g | (int64_t)s;
-      ends[q] = s + c;
+  for (RspRunWalk<SM_THREADS> r(row, tmp); r.next();) {
+    const int64_t q = base + (r.i >> 1);
+    if (r.i < row.n && (r.i & 1) && q >= 0 && q < total) {
+      keys[q] = g | (int64_t)r.s;
+      ends[q] = r.s + r.c;
     }
-    carry += chunk_px;
   }
 }
 
@@ -309,13 +289,11 @@ __global__ __launch_bounds__(SM_THREADS) void rle_union_kernel(const int64_t* __
   }
 }
 
-inline bool sm_scene_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffffLL; }
-
 }  // namespace
 
 extern "C" int rsp_rle_bbox(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                             int32_t* boxes, int32_t* area, rsp_stream_t stream) {
-  if (!counts || !n || !boxes || !area || k < 0 || cap < 1 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (!counts || !n || !boxes || !area || k < 0 || cap < 1 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   hipLaunchKernelGGL(rle_bbox_kernel, dim3(k), dim3(SM_THREADS), 0, (hipStream_t)stream, counts, n, cap, H, boxes, area);
   RSP_CHECK_LAUNCH();
@@ -330,7 +308,7 @@ extern "C" int64_t rsp_rle_pair_overlap_workspace_bytes(int32_t k, int32_t cap) 
 extern "C" int rsp_rle_pair_overlap(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                                     const int32_t* pairs, const int32_t* rects, int32_t P, void* workspace, int32_t* out,
                                     rsp_stream_t stream) {
-  if (!counts || !n || !workspace || k < 0 || cap < 1 || P < 0 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (!counts || !n || !workspace || k < 0 || cap < 1 || P < 0 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (P > 0 && (!pairs || !rects || !out)) return RSP_EINVAL;
   if (P == 0 || k == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -346,7 +324,7 @@ extern "C" int rsp_rle_pair_overlap(const uint32_t* counts, const int32_t* n, in
 extern "C" int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                                  const int32_t* members, const int32_t* member_group, const int64_t* member_offs, int32_t M,
                                  int64_t total, int64_t* keys, int32_t* ends, rsp_stream_t stream) {
-  if (!counts || !n || k < 0 || cap < 1 || M < 0 || total < 0 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (!counts || !n || k < 0 || cap < 1 || M < 0 || total < 0 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (M > 0 && (!members || !member_group || !member_offs)) return RSP_EINVAL;
   if (total > 0 && (!keys || !ends)) return RSP_EINVAL;
   if (M == 0 || k == 0 || total == 0) return RSP_OK;
@@ -359,7 +337,7 @@ extern "C" int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32
 extern "C" int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const int64_t* interval_offs, int32_t G,
                              int32_t H, int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out,
                              rsp_stream_t stream) {
-  if (G < 0 || total < 0 || cap_out < 2 || !sm_scene_ok(H, W)) return RSP_EINVAL;
+  if (G < 0 || total < 0 || cap_out < 2 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (total > 0 && (!keys || !ends)) return RSP_EINVAL;
   if (G > 0 && (!interval_offs || !counts_out || !n_out)) return RSP_EINVAL;
   if (G == 0) return RSP_OK;
