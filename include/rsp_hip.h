@@ -754,6 +754,35 @@ int rsp_ring_simplify_write(const int32_t* verts, const int64_t* ring_offs, cons
                             int32_t* ring_parent_out, int64_t* ring_area2_out, int64_t* inst_ring_offs_out, int32_t* ring_src_out,
                             rsp_stream_t stream);
 
+/* Oriented boxes (csrc/mask_obb.hip): the convex hull and the minimum-area rectangle of every mask of a run    */
+/* table, exact in integers; replaces decoding every instance to a dense H x W array on the host + cv2.convexHull +           */
+/* cv2.minAreaRect.  Pixel (x, y) covers [x, x + 1] x [y, y + 1]; an instance is the union of the squares of ALL its pixels.  */
+/* counts [k, cap] / n [k]: k masks on ONE (H, W) canvas as above (n <= 0: no vertices; n beyond cap is read up to cap).      */
+/* H * W >= 2^31 and max(H, W) > 65 535 are refused (RSP_EINVAL).  No call reads the host, none uses atomics.                 */
+/* 1. bound_offs int64 [k + 1], ascending from 0, bound_offs[m + 1] - bound_offs[m] >= 3 * (min(n[m], cap) / 2) (a row whose   */
+/* slot is smaller has no vertices), B = bound_offs[k] <= 2^30 - 1; workspace: rsp_mask_hull_workspace_bytes(B) (0: B out of   */
+/* range).  One block per (instance, chain): the first / last set pixel of every column from the run stream, then the upper   */
+/* and the lower hull chain by pruning rounds.  Writes chain_cnt int32 [2, k] (the vertices of the upper / lower chain, each   */
+/* with both of its ends) and rounds int32 [2, k] (the pruning rounds that removed a point); the chains stay in the workspace. */
+int64_t rsp_mask_hull_workspace_bytes(int64_t B);
+int rsp_mask_hull_chains(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                         const int64_t* bound_offs, int64_t B, void* workspace, int32_t* chain_cnt, int32_t* rounds,
+                         rsp_stream_t stream);
+/* 2. hull_offs int64 [k + 1] = the exclusive sum of chain_cnt[0] + chain_cnt[1], Vh = hull_offs[k] < 2^31.  Writes hull_verts */
+/* int32 [Vh, 2] = (x, y): per instance the strictly convex hull from its smallest vertex by (x, y) on, clockwise on screen,    */
+/* first vertex not repeated (at least 4 vertices for a non-empty instance), and hull_area2 int64 [k], its doubled area (> 0;  */
+/* 0 for an empty instance).                                                                                                  */
+int rsp_mask_hull_write(const int32_t* n, int32_t k, int32_t cap, const int64_t* bound_offs, int64_t B, const void* workspace,
+                        const int32_t* chain_cnt, const int64_t* hull_offs, int64_t Vh, int32_t* hull_verts,
+                        int64_t* hull_area2, rsp_stream_t stream);
+/* The minimum-area rectangle of k convex polygons in that layout (any strictly convex rings, clockwise on screen, coordinates */
+/* in [0, 65 535]), one block per polygon.  Edge j runs from vertex j to j + 1 (cyclic): e = (ex, ey), nrm = (-ey, ex), L =     */
+/* |e|^2; over the vertices p, a = p . e and b = p . nrm.  The rectangle flush with edge j has area (amax - amin) (bmax - bmin)  */
+/* / L; edge int32 [k] = the edge that minimises it, compared exactly in 128-bit integers, the lowest among equals (-1 for a    */
+/* polygon without vertices); q int64 [k, 6] = (ex, ey, amin, amax, bmin, bmax) of that edge (zeros for -1).                    */
+int rsp_hull_min_rect(const int32_t* hull_verts, const int64_t* hull_offs, int32_t k, int64_t Vh, int32_t* edge, int64_t* q,
+                      rsp_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */
 /* ------------------------------------------------------------------------ */

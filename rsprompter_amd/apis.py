@@ -353,3 +353,59 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tole
     if simplify:
         polys, _ = rle.simplify_polygons(polys, size, 0 if tolerance is None else tolerance, min_ring_area)
     return format_polygons(rle.polygons_to_lists(*polys), form, transform)
+
+
+# ------------------------------------------------------------------------------------------- oriented boxes
+OBB_FORMS = ('corners', 'xywha', 'hull', 'geojson')
+
+
+def _affine(xy, transform):
+    """float64 [..., 2] pixel coordinates through transform = (a, b, c, d, e, f) of rings_to_geojson"""
+    if transform is None:
+        return xy
+    a, b, c, d, e, f = (float(t) for t in transform)
+    return np.stack([a + b * xy[..., 0] + c * xy[..., 1], d + e * xy[..., 0] + f * xy[..., 1]], -1)
+
+
+def obb_to_geojson(corners, transform=None):
+    """float64 [k, 4, 2] corners -> per box a GeoJSON Polygon of the closed rectangle (an empty mask: no coordinates)"""
+    out = []
+    for c in _affine(np.asarray(corners, np.float64), transform):
+        if np.isnan(c).any():
+            out.append(dict(type='Polygon', coordinates=[]))
+        else:
+            out.append(dict(type='Polygon', coordinates=[[[float(x), float(y)] for x, y in c.tolist() + c[:1].tolist()]]))
+    return out
+
+
+def masks_to_obb(masks, form='corners', transform=None, device='cuda:0'):
+    """Masks -> oriented boxes: the minimum-area rectangle around each mask (all its components together), exact on the
+    device in the run domain; what cv2.convexHull + cv2.minAreaRect give on a dense mask.  `masks` as in
+    masks_to_polygons (a bool [k, H, W] device tensor, or RLE dicts of one size with compressed or uncompressed counts).
+    form='corners': float64 [k, 4, 2], the corners in pixel-corner coordinates (pixel (x, y) covers [x, x + 1] x [y, y + 1]),
+      clockwise on screen, the first side on a hull edge; NaN rows for empty masks.
+    form='xywha': float64 [k, 5] = centre x, y, w >= h, angle of the w side in radians from +x towards +y in [-pi / 2, pi / 2).
+    form='hull': per instance the int32 [m, 2] hull vertices, clockwise on screen from the smallest by (x, y).
+    form='geojson': per instance a Polygon geometry of the closed rectangle.
+    transform = (a, b, c, d, e, f) maps X = a + b x + c y, Y = d + e x + f y for 'corners' and 'geojson'; it is refused with
+      'xywha' (an affine map does not keep rectangles) and 'hull' (integer vertices)."""
+    from . import rle
+    if form not in OBB_FORMS:
+        raise ValueError(f'oriented-box form {form!r}: one of {OBB_FORMS}')
+    if transform is not None and form not in ('corners', 'geojson'):
+        raise ValueError("transform applies to form='corners' and form='geojson' only: an affine map does not keep the "
+                         "rectangle of 'xywha'")
+    counts, n, size = _masks_to_runs(masks, device)
+    if not isinstance(masks, torch.Tensor):
+        _check_canonical(counts, n, size)
+    hull_verts, hull_offs, _, edge, q = rle.runs_to_obb(counts, n, size)
+    if form == 'hull':
+        sizes = [int(hull_verts.numel()), int(hull_offs.numel())]
+        buf = torch.cat([hull_verts.reshape(-1).to(torch.int64), hull_offs]).cpu().numpy()          # one transfer
+        v, o = np.split(buf, sizes[:1])
+        v, o = v.astype(np.int32).reshape(-1, 2), o.tolist()
+        return [v[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+    if form == 'xywha':
+        return rle.obb_to_numpy(edge, q, 'xywha')
+    corners = rle.obb_to_numpy(edge, q, 'corners')
+    return obb_to_geojson(corners, transform) if form == 'geojson' else _affine(corners, transform)

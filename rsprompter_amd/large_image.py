@@ -131,10 +131,13 @@ def _check_dense(k, H, W):
 
 
 # ------------------------------------------------------------------------------------------------------------- pipeline
-def _runs_out(counts, n, scene_hw, polygons):
+def _runs_out(counts, n, scene_hw, polygons, obb_out=None):
     """the scene run table in the form the caller asked for: COCO strings (rsp_rle_to_string), or with polygons (True, or
     (tolerance, min_ring_area) to simplify them on the device) the per-instance ring lists of DESIGN §14.7
-    (csrc/mask_polygons.hip), traced on the table before any string is made"""
+    (csrc/mask_polygons.hip), traced on the table before any string is made.  obb_out: a list that receives the oriented
+    boxes of the table, float64 [k, 4, 2] (csrc/mask_obb.hip), made from the same table first"""
+    if obb_out is not None:
+        obb_out.append(rle.obb_to_numpy(*rle.runs_to_obb(counts, n, scene_hw)[3:], form='corners'))
     if polygons:
         polys = rle.runs_to_polygons(counts, n, scene_hw)
         if polygons is not True:
@@ -143,12 +146,14 @@ def _runs_out(counts, n, scene_hw, polygons):
     return rle.runs_to_strings(counts, n, scene_hw)
 
 
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False):
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
+        if obb_out is not None:
+            obb_out.append(np.zeros((0, 4, 2), np.float64))
         return []
     sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
-    return _runs_out(sc, sn, scene_hw, polygons)
+    return _runs_out(sc, sn, scene_hw, polygons, obb_out)
 
 
 # ------------------------------------------------------------------------------------------------------- seam merge
@@ -276,17 +281,19 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
     return out, reps[keep_m], members, (flat, offs)
 
 
-def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False):
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None):
     """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
     (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
     flat, offs = groups
     K = int(offs.shape[0]) - 1
     if K == 0:
+        if obb_out is not None:
+            obb_out.append(np.zeros((0, 4, 2), np.float64))
         return []
     sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
     members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
     uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
-    return _runs_out(uc, un, scene_hw, polygons)
+    return _runs_out(uc, un, scene_hw, polygons, obb_out)
 
 
 def _seam_dense(tile_masks, origin, groups, scene_hw):
@@ -338,14 +345,16 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 @torch.no_grad()
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
                           batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
-                          polygon_min_ring_area=0):
+                          polygon_min_ring_area=0, oriented_boxes=False):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
     (masks='rle'), a bool [K, H, W] device tensor (masks='dense'), or per instance the list of (ring int32 [m, 2], parent,
     area2) of DESIGN §14.7 (masks='polygons': traced on the device from the scene run table; polygon_tolerance in pixels and
     polygon_min_ring_area in pixels simplify the rings there first, DESIGN §14.8 -- apis.masks_to_polygons says how; they
-    apply to masks='polygons' only).  return_patches=True: (sample, per-tile samples,
+    apply to masks='polygons' only).  oriented_boxes=True (masks='rle' or 'polygons'): pred_instances.obb is float64 numpy
+    [K, 4, 2], the corners of the minimum-area rectangle around each instance's scene mask (clockwise on screen,
+    NaN for an empty mask), made on the device from the scene run table before any string is made.  return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -358,6 +367,9 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     if masks not in ('rle', 'dense', 'polygons'):
         raise ValueError("masks must be 'rle', 'dense' or 'polygons'")
     poly = masks == 'polygons'
+    if oriented_boxes and masks == 'dense':                             # refused before the first tile runs
+        raise ValueError("oriented_boxes=True reads the scene run table: use masks='rle' or masks='polygons'")
+    obb = [] if oriented_boxes else None
     if polygon_tolerance is not None or polygon_min_ring_area != 0:
         if not poly:
             raise ValueError("polygon_tolerance and polygon_min_ring_area apply to masks='polygons'")
@@ -436,7 +448,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             tm = torch.cat(dense_tiles, 0) if dense_tiles else torch.zeros((0, th, tw), dtype=torch.bool, device=dev)
             out.masks = _seam_dense(tm, origin, groups, (H, W))
         else:
-            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly)
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb)
     else:
         keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
@@ -446,7 +458,9 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
             kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
-            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly)
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb)
+    if obb:
+        out.obb = obb[0]
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
@@ -463,11 +477,15 @@ def _is_rings(masks):
 
 def pred2dict(sample, score_thr=0.0):
     """DetInferencer.pred2dict form (det_inferencer.py:573-627): labels, scores, bboxes, masks as RLE with `counts` as str;
-    the rings of masks='polygons' as dict(ring=[[x, y], ...], parent, area2) per ring"""
+    the rings of masks='polygons' as dict(ring=[[x, y], ...], parent, area2) per ring; with oriented boxes an "obb" key, the
+    four corners of each (NaN for an empty mask, which json writes as NaN)"""
     p = sample.pred_instances
     sel = (p.scores >= score_thr).nonzero().view(-1).tolist()
     lab, sc, bb = p.labels.tolist(), p.scores.tolist(), p.bboxes.tolist()
     out = dict(labels=[lab[i] for i in sel], scores=[sc[i] for i in sel], bboxes=[bb[i] for i in sel])
+    if 'obb' in p and p.obb is not None:                               # oriented_boxes=True: [[x, y] x 4] per instance
+        corners = np.asarray(p.obb).tolist()
+        out['obb'] = [corners[i] for i in sel]
     if 'masks' in p and p.masks is not None:
         rles = p.masks
         if _is_rings(rles) and rles:                                   # a tensor (masks='dense') is no list: falls through
@@ -494,6 +512,10 @@ def pred2geojson(sample, score_thr=0.0, transform=None):
     lab, sc, bb = p.labels.tolist(), p.scores.tolist(), p.bboxes.tolist()
     feats = [dict(type='Feature', geometry=rings_to_geojson(p.masks[i], transform),
                   properties=dict(label=lab[i], score=sc[i], bbox=bb[i])) for i in sel]
+    if 'obb' in p and p.obb is not None:                               # the corners in pixel coordinates, like bbox
+        corners = np.asarray(p.obb).tolist()
+        for f, i in zip(feats, sel):
+            f['properties']['obb'] = corners[i]
     return dict(type='FeatureCollection', features=feats)
 
 
@@ -525,6 +547,8 @@ def main(argv=None):
                     'of the kept outline (default: the exact rings)')
     ap.add_argument('--min-ring-area', type=int, default=0, metavar='A',
                     help='--mask-format polygons|geojson: drop rings of less than A pixels (a dropped hole is filled)')
+    ap.add_argument('--oriented-boxes', action='store_true',
+                    help='add "obb": the four corners of the minimum-area rectangle around each mask, made on the device')
     a = ap.parse_args(argv)
     if a.geo_transform is not None and a.mask_format != 'geojson':
         ap.error('--geo-transform applies to --mask-format geojson')
@@ -541,7 +565,7 @@ def main(argv=None):
         s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
                                   a.batch_size, masks='rle' if a.mask_format == 'rle' else 'polygons',
                                   seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
-                                  polygon_min_ring_area=a.min_ring_area)
+                                  polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

@@ -1916,6 +1916,82 @@ def ring_simplify(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_rin
     return out + (rounds,) if with_rounds else out
 
 
+# ----------------------------------------------------------------------------- oriented boxes (csrc/mask_obb.hip)
+MASK_OBB_MAX_SIDE = 65535                # coordinates in [0, 65 535]: 16 bits each, and every product of the calipers fits 128
+MASK_OBB_MAX_BOUND = 2 ** 30 - 1         # three records per ones-run over all rows of one call (32-bit hull offsets)
+
+
+def mask_hull(counts, n, H, W, with_rounds=False):
+    """run table (counts int32 [k, cap], n int32 [k]: k masks on one (H, W) canvas) -> the convex hull of every mask (the
+    union of the closed unit squares of ALL its pixels), exact and on the device:
+      hull_verts int32 [Vh, 2] = (x, y), hull_offs int64 [k + 1], hull_area2 int64 [k] (doubled area, > 0).
+    A hull is strictly convex, starts at its smallest vertex by (x, y), runs clockwise on screen and does not repeat its
+    first vertex; a non-empty mask has at least 4 vertices, a row with n <= 0 none.  with_rounds=True appends rounds int32
+    [2, k], the pruning rounds of the upper and the lower chain.  Two device-to-host reads, whatever k is: the size of the
+    workspace (three records per ones-run) and the number of hull vertices."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('mask_hull', counts, n, H, W)
+    if max(H, W) > MASK_OBB_MAX_SIDE:
+        raise ValueError(f'mask_hull: a {H} x {W} canvas; the sides are at most {MASK_OBB_MAX_SIDE}')
+    dev = n.device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    rounds = torch.zeros((2, k), **i32)
+
+    def empty():
+        out = (torch.zeros((0, 2), **i32), torch.zeros((k + 1,), **i64), torch.zeros((k,), **i64))
+        return out + (rounds,) if with_rounds else out
+    if k == 0:
+        return empty()
+    bound = 3 * (n.clamp(0, cap) // 2).to(torch.int64)
+    bound_offs = torch.cat([bound.new_zeros((1,)), torch.cumsum(bound, 0)]).contiguous()
+    B = int(bound_offs[-1])                                                                         # read 1
+    if B == 0:
+        return empty()
+    if B > MASK_OBB_MAX_BOUND:
+        raise ValueError(f'mask_hull: {B // 3} ones-runs in one call; at most {MASK_OBB_MAX_BOUND // 3} (split the rows), so '
+                         'that the hull vertices of one call stay below 2^31')
+    ws = torch.empty((int(lib.rsp_mask_hull_workspace_bytes(B)) // 4,), **i32)
+    chain_cnt = torch.zeros((2, k), **i32)
+    _lib.check(lib.rsp_mask_hull_chains(counts.data_ptr(), n.data_ptr(), k, cap, H, W, bound_offs.data_ptr(), B, ws.data_ptr(),
+                                        chain_cnt.data_ptr(), rounds.data_ptr(), _stream()), "rsp_mask_hull_chains")
+    hull_offs = torch.cat([bound.new_zeros((1,)), torch.cumsum(chain_cnt.sum(0, dtype=torch.int64), 0)]).contiguous()
+    Vh = int(hull_offs[-1])                                                                         # read 2
+    verts, area2 = torch.zeros((Vh, 2), **i32), torch.zeros((k,), **i64)
+    _lib.check(lib.rsp_mask_hull_write(n.data_ptr(), k, cap, bound_offs.data_ptr(), B, ws.data_ptr(), chain_cnt.data_ptr(),
+                                       hull_offs.data_ptr(), Vh, verts.data_ptr(), area2.data_ptr(), _stream()),
+               "rsp_mask_hull_write")
+    out = (verts, hull_offs, area2)
+    return out + (rounds,) if with_rounds else out
+
+
+def hull_min_rect(hull_verts, hull_offs):
+    """convex polygons (hull_verts int32 [Vh, 2], hull_offs int64 [k + 1]: what mask_hull returns, or any canonical strictly
+    convex rings, clockwise on screen, with coordinates in [0, 65 535]) -> (edge int32 [k], q int64 [k, 6]): the
+    minimum-area rectangle of each, flush with hull edge `edge` (the lowest among equals, -1 for a polygon without vertices);
+    q = (ex, ey, amin, amax, bmin, bmax) in the frame of that edge (rle.obb_to_numpy turns it into corners).
+    Exact 128-bit integer comparisons on the device; the coordinate range of the vertices is the caller's to keep (they are
+    not read here).  No device-to-host read."""
+    lib = _lib.load()
+    for name, t, dtype, dim in (('hull_verts', hull_verts, torch.int32, 2), ('hull_offs', hull_offs, torch.int64, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dim or t.device != hull_verts.device:
+            raise ValueError(f'hull_min_rect: {name} must be a {dtype} tensor of {dim} dimension(s) on the device of hull_verts')
+    if not _is_device(hull_verts):
+        raise ValueError('hull_min_rect: the hull arrays live on the HIP device')
+    Vh, k = int(hull_verts.shape[0]), int(hull_offs.shape[0]) - 1
+    if hull_verts.shape[1] != 2 or k < 0:
+        raise ValueError('hull_min_rect: expected hull_verts [Vh, 2] and hull_offs [k + 1]')
+    if Vh >= 2 ** 31 or k >= 2 ** 31:
+        raise ValueError('hull_min_rect: at most 2^31 - 1 vertices and polygons in one call')
+    dev = hull_verts.device
+    edge = torch.full((k,), -1, dtype=torch.int32, device=dev)
+    q = torch.zeros((k, 6), dtype=torch.int64, device=dev)
+    if k:
+        hull_verts, hull_offs = hull_verts.contiguous(), hull_offs.contiguous()
+        _lib.check(lib.rsp_hull_min_rect(hull_verts.data_ptr(), hull_offs.data_ptr(), k, Vh, edge.data_ptr(), q.data_ptr(),
+                                         _stream()), "rsp_hull_min_rect")
+    return edge, q
+
+
 MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
 # the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call

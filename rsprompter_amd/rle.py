@@ -165,6 +165,56 @@ def polygons_to_lists(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst
     return [[(v[ro[r]:ro[r + 1]], par[r], a2[r]) for r in range(io[i], io[i + 1])] for i in range(len(io) - 1)]
 
 
+def runs_to_hulls(counts, n, size):
+    """run table of k masks on one size = (H, W) canvas -> (hull_verts int32 [Vh, 2], hull_offs int64 [k + 1], hull_area2
+    int64 [k]) on the device: the convex hull of every mask, all its components together (ops.mask_hull).
+    Two device-to-host reads, whatever k is."""
+    return ops.mask_hull(counts, n, size[0], size[1])
+
+
+def runs_to_obb(counts, n, size):
+    """run table -> (hull_verts, hull_offs, hull_area2, edge int32 [k], q int64 [k, 6]) on the device: the hulls and the
+    minimum-area rectangle of each (ops.hull_min_rect: flush with hull edge `edge`, -1 for an empty mask; q = (ex, ey, amin,
+    amax, bmin, bmax) in that edge's frame).  Exact integers; the two device-to-host reads of runs_to_hulls."""
+    hull_verts, hull_offs, hull_area2 = runs_to_hulls(counts, n, size)
+    edge, q = ops.hull_min_rect(hull_verts, hull_offs)
+    return hull_verts, hull_offs, hull_area2, edge, q
+
+
+OBB_FORMS = ('corners', 'xywha')
+
+
+def obb_to_numpy(edge, q, form='corners'):
+    """what runs_to_obb returns -> float64 numpy on the host after ONE transfer (edge and q in one int64 buffer).
+    form='corners': [k, 4, 2] = C0..C3 in pixel coordinates, clockwise on screen, C0 -> C1 on the hull edge: (amin, bmin),
+      (amax, bmin), (amax, bmax), (amin, bmax) in the frame e = (ex, ey), nrm = (-ey, ex), divided by L = |e|^2.
+    form='xywha': [k, 5] = centre x, y (the mean of the corners), w >= h (the sides U / sqrt L along e and V / sqrt L along
+      nrm; w is e's on U == V) and the angle of the w side from +x towards +y in [-pi / 2, pi / 2), radians.
+    Empty masks (edge = -1) give NaN rows."""
+    if form not in OBB_FORMS:
+        raise ValueError(f'oriented-box form {form!r}: one of {OBB_FORMS}')
+    k = int(edge.shape[0])
+    buf = torch.cat([edge.to(torch.int64).view(-1, 1), q.view(k, 6)], 1).cpu().numpy()
+    live = buf[:, 0] >= 0
+    ex, ey, amin, amax, bmin, bmax = (buf[:, i].astype(np.float64) for i in range(1, 7))
+    L = np.where(live, ex * ex + ey * ey, 1.0)
+    a = np.stack([amin, amax, amax, amin], 1)
+    b = np.stack([bmin, bmin, bmax, bmax], 1)
+    c = np.stack([a * ex[:, None] - b * ey[:, None], a * ey[:, None] + b * ex[:, None]], 2) / L[:, None, None]
+    c[~live] = np.nan
+    if form == 'corners':
+        return c
+    U, V = amax - amin, bmax - bmin
+    along_e = U >= V
+    root = np.sqrt(L)
+    w, h = np.where(along_e, U, V) / root, np.where(along_e, V, U) / root
+    ang = np.where(along_e, np.arctan2(ey, ex), np.arctan2(ex, -ey))
+    ang = np.where(ang >= np.pi / 2, ang - np.pi, np.where(ang < -np.pi / 2, ang + np.pi, ang))
+    out = np.stack([c[:, :, 0].mean(1), c[:, :, 1].mean(1), w, h, ang], 1)
+    out[~live] = np.nan
+    return out
+
+
 def runs_to_dicts(counts, n_host, size):
     """run table -> list of dict(size=[H, W], counts=list), the uncompressed form (HF `_mask_to_rle`).  n_host: the row
     lengths on the host (what fit_runs returned); one transfer, the table."""
