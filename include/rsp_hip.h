@@ -36,8 +36,14 @@ extern "C" {
 
 typedef void* rsp_stream_t;
 
-/* Library / build identification (also used by the "symbols load" CPU test). */
-int rsp_abi_version(void);
+/* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
+/* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
+/* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
+/* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
+/* 3: RspBoxCoder in RspRpnDesc / rsp_bbox_post; 2: RspGemmDesc gained c_ncols / pl_col0, plane format words decode       */
+/* strictly.                                                                                                             */
+#define RSP_ABI_VERSION 5
+int rsp_abi_version(void);   /* = RSP_ABI_VERSION of the header the library was built from */
 const char* rsp_build_info(void);
 
 /* ------------------------------------------------------------------------ */
@@ -275,6 +281,7 @@ int rsp_attention(const RspAttnDesc* desc, rsp_stream_t stream);
 /* HF:396-404), exact fp32:                                                                                          */
 /*  token -> image: q [R,T,128] (T <= 12), kv [Rkv*N, 256] = image rows with K | V side by side, kv_map[r] = image    */
 /*  row block of RoI r (NULL: r); out [R,T,128].                                                                      */
+#define RSP_SAM_T2I_MAX_TOKENS 12        /* more tokens go through the generic rsp_attention */
 int rsp_sam_t2i_attention(const float* q, const float* kv, const int32_t* kv_map, float* out, int32_t R, int32_t T,
                           int32_t N, float scale, rsp_stream_t stream);
 /*  token -> image with a key bias (HF:260 `attn = attn + attention_similarity` in front of the softmax, as HF:328-330  */
@@ -284,6 +291,7 @@ int rsp_sam_t2i_attention_bias(const float* q, const float* kv, const int32_t* k
                                float* out, int32_t R, int32_t T, int32_t N, float scale, rsp_stream_t stream);
 /*  image -> token: q [Rq*N,128] image-side queries (q_map[r] = row block, NULL: r), k, v [R,T,128] (T <= 16);        */
 /*  result [R*N,128] as fp32 `out` and/or fp16 planes (KB32, value * 2^out_scale_log2).                               */
+#define RSP_SAM_I2T_MAX_TOKENS 16
 int rsp_sam_i2t_attention(const float* q, const int32_t* q_map, const float* k, const float* v, float* out,
                           uint16_t* out_hi, uint16_t* out_lo, int32_t out_scale_log2, int32_t R, int32_t T, int32_t N,
                           float scale, rsp_stream_t stream);
@@ -293,6 +301,8 @@ int rsp_sam_i2t_attention(const float* q, const int32_t* q_map, const float* k, 
 /*  it and the separate LayerNorm pass are never materialised.  wo [256,128], bo [256] = out_proj; the residual is      */
 /*  either fp32 rows `res` [Rres*N, 256] with res_map[r] = row block of RoI r (NULL: r) -- layer 0, one copy per image   */
 /*  -- or fp16 planes res_hi / res_lo of the [R*N, 256] tensor (layer 1); result as fp32 `out` and/or fp16 planes.      */
+/*  T <= RSP_SAM_I2T_FUSED_MAX_TOKENS (the LDS budget); more tokens: rsp_sam_i2t_attention + GEMM + layernorm.          */
+#define RSP_SAM_I2T_FUSED_MAX_TOKENS 10
 typedef struct RspI2tFusedDesc {
   const float* q; const int32_t* q_map; const float* k; const float* v;
   const float* wo; const float* bo;
@@ -361,6 +371,10 @@ int rsp_bbox_post(const float* head, int32_t ld, const float* rois, const int32_
                   const RspBoxCoder* coder /*host*/, int32_t cap, float* cand_boxes,
                   float* cand_scores, int32_t* cand_ids, int32_t* cand_src, int32_t* cand_cnt,
                   rsp_stream_t stream);
+/* cap <= RSP_NMS_MAX_CANDIDATES per image; up to RSP_NMS_LDS_CANDIDATES they are sorted in LDS (128 KB), above that in */
+/* memory (same block, same network), which the workspace then has to hold.                                             */
+#define RSP_NMS_LDS_CANDIDATES 16384
+#define RSP_NMS_MAX_CANDIDATES 131072
 int64_t rsp_nms_workspace_bytes(int32_t B, int32_t cap);
 /* greedy NMS per image with per-id coordinate offsets; outputs [B, max_out(,4)] */
 int rsp_batched_nms(const float* boxes, const float* scores, const int32_t* ids, const int32_t* src,
@@ -372,7 +386,9 @@ int rsp_batched_nms(const float* boxes, const float* scores, const int32_t* ids,
 /* (q_proj output, head h at columns 16 h ..; HF:243-262 "_separate_heads") -> fp16 planes of the block-diagonal matrix      */
 /* [R*96, 128]: row r*96 + h*T + t = scale * tq[r, t, head h] in columns 16 h .. 16 h + 15, zeros elsewhere; rows of the    */
 /* columns >= 8 T zero.  gather: full [R*96, 128] -> ao [R*T, 128], ao[r*T + t, 16 h + d] = full[r*96 + h*T + t, 16 h + d]    */
-/* (HF:264-268 "_recombine_heads" of the columns' own heads).  8 T <= 96.                                                   */
+/* (HF:264-268 "_recombine_heads" of the columns' own heads).  T <= RSP_SAM_T2I_FOLD_MAX_TOKENS: 8 heads x T query columns   */
+/* fit the 96 of a RoI.                                                                                                     */
+#define RSP_SAM_T2I_FOLD_MAX_TOKENS 12
 int rsp_sam_fold_expand(const float* tq, uint16_t* out_hi, uint16_t* out_lo, int32_t out_scale_log2, int32_t R, int32_t T,
                         float scale, rsp_stream_t stream);
 int rsp_sam_fold_gather(const float* full, float* ao, int32_t R, int32_t T, rsp_stream_t stream);
@@ -381,7 +397,8 @@ int rsp_sam_fold_gather(const float* full, float* ao, int32_t R, int32_t T, rsp_
 /* (HF:326-331, 397-400; csrc/t2i_fold.hip): keys = fp16 planes of [k_rows >= R*N, 256]; pek = planes of k_proj(pe) +    */
 /* bias [N, 128]; qp = planes of q' [q_rows >= R*96, 256] with q'[r*96 + h*T + t] = Wk_h^T tq[r, t, h] (softmax scale     */
 /* inside); tqx = planes of the block-diagonal tq [q_rows, 128]; *_e = plane scale exponents.  u [R*96, 256] fp32 receives */
-/* sum_n softmax(score)[n] * keys[n] per column (rows of columns >= ncols = 8 T <= 96 stay untouched); the caller applies  */
+/* sum_n softmax(score)[n] * keys[n] per column (rows of columns >= ncols = 8 T <= 8 RSP_SAM_T2I_FOLD_MAX_TOKENS stay       */
+/* untouched); the caller applies                                                                                          */
 /* v_proj to it.  N % 32 == 0.                                                                                           */
 int rsp_sam_t2i_fold(const uint16_t* keys_hi, const uint16_t* keys_lo, int64_t k_rows, int32_t keys_e,
                      const uint16_t* pek_hi, const uint16_t* pek_lo, int32_t pek_e, const uint16_t* qp_hi,
@@ -427,7 +444,9 @@ int rsp_sam_hq_mask(const uint16_t* up_hi, const uint16_t* up_lo, int64_t up_row
 /* Evaluation hand-off: COCO RLE counts of k bool masks [k,H,W] (row-major bytes), i.e. the run      */
 /* lengths of the column-major pixel stream, first run = zeros (pycocotools.mask.encode as used by                   */
 /* encode_mask_results, mmdet/structures/mask/utils.py:38-53).  counts [k, cap] uint32, n_counts[k] = number of runs */
-/* or -(needed) when cap is too small; workspace: k*cap uint32.  W <= 8192.                                          */
+/* or -(needed) when cap is too small; workspace: k*cap uint32.  W <= RSP_RLE_MAX_WIDTH (a column counter per x in   */
+/* LDS).                                                                                                             */
+#define RSP_RLE_MAX_WIDTH 8192
 int rsp_mask_rle(const uint8_t* masks, int32_t k, int32_t H, int32_t W, void* workspace, uint32_t* counts,
                  int32_t* n_counts, int32_t cap, rsp_stream_t stream);
 /* ... and their compression to COCO's ASCII strings (cocoapi maskApi.c rleToString: what encode_mask_results returns   */
@@ -697,10 +716,12 @@ int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const
 /* 1. piece_cnt int32 [k]: the column pieces of each row (a ones-run crossing column ends is one piece per column).        */
 int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                             int32_t* piece_cnt, rsp_stream_t stream);
-/* 2. piece_offs int64 [k + 1] = exclusive sum of piece_cnt, P = piece_offs[k] <= (2^31 - 1) / 6.  pieces int32 [4, P] =    */
+/* 2. piece_offs int64 [k + 1] = exclusive sum of piece_cnt, P = piece_offs[k] <= RSP_MASK_POLYGON_MAX_PIECES (six edge     */
+/* slots per column piece, 32-bit slot numbers).  pieces int32 [4, P] =                                                     */
 /* (x, y0, y1, instance) per piece, sorted by (instance, x, y0).  Six edge slots per piece, E = 6 P: ekey int64 [E] = start */
 /* x * (H + 1) + start y of the directed boundary edge in the slot, INT64_MAX for an empty slot; eoth int32 [E] = the end   */
 /* vertex's other coordinate; succ int32 [E] = the slot of the next edge of the ring (saddles: foreground 8-connected).    */
+#define RSP_MASK_POLYGON_MAX_PIECES (0x7fffffffLL / 6)
 int rsp_mask_polygon_edges(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                            const int64_t* piece_offs, int64_t P, int32_t* pieces, int64_t* ekey, int32_t* eoth, int32_t* succ,
                            rsp_stream_t stream);
@@ -734,6 +755,8 @@ int rsp_mask_polygon_write(int64_t P, int32_t k, int32_t H, int64_t R, int64_t V
 /* depth of the ring's split tree).  Rings of up to 64 vertices take one wave each, longer ones a block each; variant 0 is    */
 /* the product's choice (256 threads a block), 1 / 2 = 128 / 512 threads, 3 = every ring through the block path (the          */
 /* alternatives tools/bench_ring_simplify.py measures; all give the same result).  No host read, no atomics.                  */
+#define RSP_RING_SIMPLIFY_MAX_SIDE (1 << 20)         /* coordinates in [0, 2^20]: every distance comparison fits 128-bit integers */
+#define RSP_RING_SIMPLIFY_MAX_TOL2_Q8 (1LL << 40)   /* tolerance^2 in 1 / 256 px^2: tolerances up to 65 536 px                   */
 int rsp_ring_simplify_mark(const int32_t* verts, const int64_t* ring_offs, int64_t R, int64_t V, int64_t tol2_q8, int32_t H,
                            int32_t W, int32_t variant, uint8_t* keep, int32_t* pos, int32_t* kept_cnt, int64_t* area2,
                            int32_t* rounds, rsp_stream_t stream);
@@ -764,6 +787,8 @@ int rsp_ring_simplify_write(const int32_t* verts, const int64_t* ring_offs, cons
 /* range).  One block per (instance, chain): the first / last set pixel of every column from the run stream, then the upper   */
 /* and the lower hull chain by pruning rounds.  Writes chain_cnt int32 [2, k] (the vertices of the upper / lower chain, each   */
 /* with both of its ends) and rounds int32 [2, k] (the pruning rounds that removed a point); the chains stay in the workspace. */
+#define RSP_MASK_OBB_MAX_SIDE 65535            /* x and y fit 16 bits each: every product of the calipers fits 128 bits        */
+#define RSP_MASK_OBB_MAX_BOUND 0x3fffffffLL    /* three records per ones-run over all rows of one call (32-bit hull offsets)   */
 int64_t rsp_mask_hull_workspace_bytes(int64_t B);
 int rsp_mask_hull_chains(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                          const int64_t* bound_offs, int64_t B, void* workspace, int32_t* chain_cnt, int32_t* rounds,
@@ -817,6 +842,7 @@ int rsp_mask_score_box(const float* low_res, int32_t k, int32_t h, int32_t w, in
 /* x0, y0) (the empty-mask box [0, 0, 0, 0] is crop-local and shifted too), 7 = 1 when a coordinate of the shifted box is  */
 /* within 20 of the same coordinate of [x0, y0, x1, y1] and not within 20 of that of [0, 0, W, H].  Integer reductions     */
 /* only.  A table row with a non-positive size scores as an empty mask.                                                  */
+#define RSP_CROP_TABLE_COLS 12
 int rsp_mask_score_box_crops(const float* low_res, int32_t k, int32_t h, int32_t w, const int32_t* crop_idx,
                              const int32_t* table, int32_t n_crops, int32_t max_out_h, int32_t max_out_w, float t_hi,
                              float t_lo, float t_mid, int32_t* out, rsp_stream_t stream);
@@ -893,6 +919,9 @@ int rsp_persam_f_fit(const float* low_res, const uint8_t* gt, int32_t k, int32_t
 /* every size, box and count an integer reduction: the result does not depend on scheduling.  workspace:                  */
 /* rsp_mask_regions_workspace_bytes(k, H, W) bytes, 16-byte aligned (-1 for arguments the call would refuse).  RSP_EINVAL: */
 /* mode outside 1..3, min_area < 0, H * W >= 2^31, a non-positive size; k = 0 does nothing.                                */
+/* Components are labelled inside tiles of RSP_MASK_REGION_TILE_H x _W pixels first, then merged across the tile borders.   */
+#define RSP_MASK_REGION_TILE_H 64
+#define RSP_MASK_REGION_TILE_W 64
 int64_t rsp_mask_regions_workspace_bytes(int32_t k, int32_t H, int32_t W);
 int rsp_mask_remove_small_regions(const uint8_t* masks, int32_t k, int32_t H, int32_t W, int32_t min_area, int32_t mode,
                                   void* workspace, uint8_t* out, int32_t* info, rsp_stream_t stream);

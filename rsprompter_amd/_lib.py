@@ -1,10 +1,19 @@
-"""ctypes binding of librsp_hip.so (the C ABI declared in include/rsp_hip.h).
+"""ctypes binding of librsp_hip.so, derived from include/rsp_hip.h at import.
 
-The product path has NO fallback: if the library is missing, or a call returns
-a non-zero status, a RuntimeError is raised.  Nothing here imports `oracle/`.
+The header is the only declaration of the C ABI.  `parse_header` reads it once and yields
+  PROTOTYPES   name -> (restype, argtypes) of every entry point,
+  the `Rsp*` ctypes.Structure classes (module attributes, e.g. `_lib.RspGemmDesc`),
+  CONST        name -> value of every object-like integer `#define` (status codes, flags, limits);
+a new entry point, descriptor field or limit needs no line here.
+
+The product path has NO fallback: if the header or the library is missing, or a call returns a non-zero status, a
+RuntimeError is raised.  Nothing here imports `oracle/`.
 """
 import ctypes
 import os
+import re
+
+from .build import HEADER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librsp_hip.so")
@@ -15,254 +24,97 @@ c_int64 = ctypes.c_int64
 c_float = ctypes.c_float
 c_double = ctypes.c_double
 
-
-class RspGemmDesc(ctypes.Structure):
-    _fields_ = [
-        ("A", c_void_p), ("Bhi", c_void_p), ("Blo", c_void_p), ("C", c_void_p),
-        ("bias", c_void_p), ("res", c_void_p), ("a_rowmap", c_void_p), ("c_rowmap", c_void_p),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("lda", c_int), ("ldc", c_int), ("ldr", c_int),
-        ("res_mod", c_int), ("act", c_int),
-        ("alpha", c_float), ("a_scale_log2", c_int),
-        ("conv_k", c_int), ("conv_stride", c_int), ("conv_pad", c_int),
-        ("conv_H", c_int), ("conv_W", c_int), ("conv_C", c_int),
-        ("conv_Ho", c_int), ("conv_Wo", c_int),
-        ("ct_W", c_int), ("ct_dy", c_int),
-        ("res_bmap", c_void_p), ("res_brows", c_int),
-        ("Ahi", c_void_p), ("Alo", c_void_p), ("Chi", c_void_p), ("Clo", c_void_p), ("c_scale_log2", c_int),
-        ("a_rows", c_int), ("c_rows", c_int), ("b_rows", c_int),
-        ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
-        ("res_hi", c_void_p), ("res_lo", c_void_p), ("res_scale_log2", c_int), ("res_rows", c_int),
-        ("hd_hyper", c_void_p), ("hd_out", c_void_p), ("hd_rows", c_int),
-        ("c_ncols", c_int), ("pl_col0", c_int),
-        ("tile_hint", c_int),
-    ]
+# by-value C types; a pointer is POINTER(struct) to a struct declared above it, c_char_p as a `const char*` result and
+# c_void_p otherwise (from_param takes device addresses, ctypes arrays of host values, byref() results and None)
+SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "float": c_float, "double": c_double,
+           "rsp_stream_t": c_void_p}
+_INT = r"(0[xX][0-9a-fA-F]+|\d+)[uUlL]*"
+_DECL = r"(?:const\s)?(\w+)\s*(\**)\s*(\w*)\s*(\[\s*\d*\s*\])?"      # one parameter or result: base, stars, name, array
 
 
-class RspAttnDesc(ctypes.Structure):
-    _fields_ = [
-        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("out", c_void_p), ("kv_batch_map", c_void_p),
-        ("q_batch_map", c_void_p),
-        ("q_bs", c_int64), ("q_ts", c_int64), ("q_hs", c_int64),
-        ("k_bs", c_int64), ("k_ts", c_int64), ("k_hs", c_int64),
-        ("v_bs", c_int64), ("v_ts", c_int64), ("v_hs", c_int64),
-        ("o_bs", c_int64), ("o_ts", c_int64), ("o_hs", c_int64),
-        ("B", c_int), ("nh", c_int), ("dh", c_int), ("Tq", c_int), ("Tk", c_int),
-        ("scale", c_float),
-        ("out_hi", c_void_p), ("out_lo", c_void_p), ("out_scale_log2", c_int),
-        ("mask", c_void_p),
-    ]
+def parse_header(text):
+    """(structs, prototypes, constants) of a header in the C subset that include/rsp_hip.h keeps to:
+      /* */ comments (a `//` outside a string is an error);
+      `#define NAME <integers, unary minus, ( ) << * / - +, suffixes u / L / LL>` (/ of non-negative values); function-like
+        macros, the include guard and every other directive are passed over;
+      `typedef struct [Name] { ... } Name;` of scalars, pointers, arrays `T x[4]` and earlier structs by value, several
+        declarators (`int32_t M, N, K;`) or declarations on a line;
+      prototypes of `rsp_*` functions over any number of lines, `(void)`, array parameters;
+      `typedef void* rsp_stream_t;` and the `extern "C" { }` pair.
+    Anything else raises RuntimeError with the text in question: nothing is skipped."""
+    def fail(what, at):
+        raise RuntimeError(f"rsp_hip.h: {what}: {' '.join(at.split())[:200]!r}")
+
+    code = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    m = re.search(r"//.*", re.sub(r'"[^"\n]*"', '""', code))
+    if m:
+        fail("`//` comment (only /* */ is read)", m.group(0))
+    code = code.replace("\\\n", " ")
+
+    const = {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(?!\()[ \t]+(\S.*)$", code, re.M):
+        if not re.fullmatch(rf"(?:{_INT}|<<|[-+*/()\s])+", m.group(2)):
+            fail("macro value is not an integer expression", m.group(0))
+        try:
+            const[m.group(1)] = eval(re.sub(_INT, lambda k: str(int(k.group(1), 0)), m.group(2)).replace("/", "//"),
+                                     {"__builtins__": {}})
+        except (SyntaxError, ValueError, ZeroDivisionError):
+            fail("macro value does not evaluate", m.group(0))
+    code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
+    calls = re.findall(r"(rsp_[a-z0-9_]+)\s*\(", code)
+
+    structs = {}
+
+    def ctype(base, pointer, at):
+        if pointer:
+            return ctypes.POINTER(structs[base]) if base in structs else c_void_p
+        if base in SCALARS or base in structs:
+            return SCALARS.get(base) or structs[base]
+        fail(f"type `{base}` by value", at)
+
+    def take_struct(m):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(2).split(";"))):
+            d = re.fullmatch(r"(?:const\s)?(\w+)\b\s*(.+)", decl) or fail("struct field", decl)
+            for item in d.group(2).split(","):
+                f = re.fullmatch(r"(\**)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?", item.strip()) or fail("struct field", decl)
+                t = ctype(d.group(1), f.group(1), decl)
+                fields.append((f.group(2), t * int(f.group(3)) if f.group(3) else t))
+        structs[m.group(3)] = type(m.group(3), (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    code = re.sub(r"typedef\s+struct\s*(\w*)\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, code, flags=re.S)
+
+    protos = {}
+
+    def take_proto(m):
+        r = re.fullmatch(_DECL, m.group(1).strip())
+        if not r or r.group(3) or r.group(4):
+            fail("result type", m.group(0))
+        res = (ctypes.c_char_p if r.group(1) == "char" else c_void_p) if r.group(2) else ctype(r.group(1), "", m.group(0))
+        args = []
+        for par in (p.strip() for p in m.group(3).split(",")) if m.group(3).strip() != "void" else ():
+            a = re.fullmatch(_DECL, par) or fail("parameter", f"{par} in {m.group(2)}")
+            args.append(ctype(a.group(1), a.group(2) or a.group(4), f"{par} in {m.group(2)}"))
+        protos[m.group(2)] = (res, args)
+        return ""
+
+    code = re.sub(r"((?:const\s+)?\w+[\s*]+)\b(rsp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", take_proto, code)
+    if len(calls) != len(protos):
+        fail(f"{len(calls)} `rsp_*(` but {len(protos)} prototypes parsed; missed or declared twice",
+             " ".join(sorted(n for n in set(calls) if n not in protos or calls.count(n) > 1)))
+    rest = re.sub(r'typedef\s+void\s*\*\s*rsp_stream_t\s*;|extern\s+"C"\s*\{|\}', "", code)
+    if rest.strip():
+        fail("not parsed", rest)
+    return structs, protos, const
 
 
-class RspMaskEmbedDesc(ctypes.Structure):
-    _fields_ = [(n, c_void_p) for n in (
-        "mask_pred_plus", "image_embeddings", "roi_img", "conv1_w", "conv1_b", "ln1_w", "ln1_b", "conv2_w",
-        "conv2_b", "ln2_w", "ln2_b", "conv3_w", "conv3_b", "out")] + [
-        ("R", c_int), ("he", c_int), ("we", c_int), ("C", c_int), ("eps", c_float)]
-
-
-class RspI2tFusedDesc(ctypes.Structure):
-    _fields_ = [("q", c_void_p), ("q_map", c_void_p), ("k", c_void_p), ("v", c_void_p), ("wo", c_void_p), ("bo", c_void_p),
-                ("res", c_void_p), ("res_map", c_void_p), ("res_hi", c_void_p), ("res_lo", c_void_p),
-                ("res_scale_log2", c_int), ("gamma", c_void_p), ("beta", c_void_p), ("eps", c_float),
-                ("out", c_void_p), ("out_hi", c_void_p), ("out_lo", c_void_p), ("out_scale_log2", c_int),
-                ("R", c_int), ("T", c_int), ("N", c_int), ("scale", c_float)]
-
-
-class RspRoiAlignDesc(ctypes.Structure):
-    _fields_ = [
-        ("feat", c_void_p * 4), ("pe", c_void_p * 4), ("H", c_int * 4), ("W", c_int * 4),
-        ("spatial_scale", c_float * 4), ("rois", c_void_p), ("out", c_void_p),
-        ("K", c_int), ("P", c_int), ("C", c_int), ("num_levels", c_int), ("finest_scale", c_int),
-    ]
-
-
-class RspBoxCoder(ctypes.Structure):
-    _fields_ = [("means", c_float * 4), ("stds", c_float * 4), ("max_ratio", c_float), ("ctr_clamp", c_float),
-                ("clip_border", c_int), ("add_ctr_clamp", c_int)]
-
-
-class RspRpnDesc(ctypes.Structure):
-    _fields_ = [
-        ("head", c_void_p * 5), ("H", c_int * 5), ("W", c_int * 5), ("stride", c_float * 5),
-        ("ld", c_int), ("A", c_int), ("nms_pre", c_int), ("num_levels", c_int),
-        ("base_anchors", c_void_p), ("coder", RspBoxCoder), ("min_bbox_size", c_float),
-    ]
-
-
-class RspCocoUnit(ctypes.Structure):
-    _fields_ = [("dt0", c_int64), ("gt0", c_int64), ("out0", c_int64), ("nd", c_int), ("ng", c_int), ("nwords", c_int),
-                ("pad", c_int)]
-
-
-# name -> (restype, argtypes); the CPU test checks every symbol is exported.
-PROTOTYPES = {
-    "rsp_abi_version": (c_int, []),
-    "rsp_build_info": (ctypes.c_char_p, []),
-    "rsp_split_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    "rsp_split_f16_kb32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "rsp_gemm": (c_int, [ctypes.POINTER(RspGemmDesc), c_void_p]),
-    "rsp_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_void_p]),
-    "rsp_layernorm_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
-                                 c_float, c_int, c_void_p]),
-    "rsp_vit_attention_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                     c_int, c_float, c_void_p]),
-    "rsp_vit_relpos": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_vit_attention_global_ws_bytes": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
-    "rsp_vit_attention_global": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                         c_int, c_int, c_float, c_void_p]),
-    "rsp_vit_attention_planes": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "rsp_vit_attention_planes_ex": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
-                                            c_void_p]),
-    "rsp_vit_window_attention": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
-                                         c_void_p]),
-    "rsp_pack_relpos_tables": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "rsp_vit_relpos_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                    c_int64, c_void_p]),
-    "rsp_vit_relpos_q": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_vit_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "rsp_preprocess": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                               ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_float, c_void_p]),
-    "rsp_paste_masks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                c_void_p]),
-    "rsp_resize_pad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                               ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
-                               c_void_p]),
-    "rsp_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_attention": (c_int, [ctypes.POINTER(RspAttnDesc), c_void_p]),
-    "rsp_mask_rle": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "rsp_sam_upscale2": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                 c_void_p, c_int, c_int, c_void_p]),
-    "rsp_sam_t2i_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "rsp_sam_i2t_fused": (c_int, [ctypes.POINTER(RspI2tFusedDesc), c_void_p]),
-    "rsp_sam_i2t_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                      c_int, c_int, c_int, c_float, c_void_p]),
-    "rsp_roi_align": (c_int, [ctypes.POINTER(RspRoiAlignDesc), c_void_p]),
-    "rsp_rpn_topk": (c_int, [ctypes.POINTER(RspRpnDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_rpn_decode": (c_int, [ctypes.POINTER(RspRpnDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_bbox_post": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
-                              ctypes.POINTER(RspBoxCoder), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_void_p]),
-    "rsp_sam_t2i_fold": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "rsp_sam_fold_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "rsp_sam_fold_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "rsp_sam_upscale_fused": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                      c_void_p]),
-    "rsp_sam_hq_mask": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "rsp_nms_workspace_bytes": (c_int64, [c_int, c_int]),
-    "rsp_batched_nms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_hyper_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "rsp_mask_post": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                              c_void_p, c_void_p, c_void_p]),
-    "rsp_pool2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_add_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "rsp_sincos_pairs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "rsp_div_boxes": (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_float), c_void_p]),
-    "rsp_fill_bias_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64,
-                                   c_int, c_int, c_void_p]),
-    "rsp_scale_boxes": (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_float), c_void_p]),
-    "rsp_pack_bits": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "rsp_groupnorm_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                   c_int, c_float, c_int, c_void_p]),
-    "rsp_resize_bilinear_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_msdeform_attn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                  ctypes.POINTER(c_int), c_void_p]),
-    "rsp_msdeform_attn_ex": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                     ctypes.POINTER(c_int), c_int, c_void_p]),
-    "rsp_query_attn_mask": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_sam_mask_embed": (c_int, [ctypes.POINTER(RspMaskEmbedDesc), c_void_p]),
-    "rsp_query_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "rsp_query_mask_post": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    "rsp_gemm_uses_s2": (c_int, [ctypes.POINTER(RspGemmDesc)]),
-    "rsp_gemm_s2_epilogue": (c_int, [ctypes.POINTER(RspGemmDesc)]),
-    "rsp_gemm_uses_pp": (c_int, [ctypes.POINTER(RspGemmDesc)]),
-    "rsp_rle_to_string": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "rsp_mask_post_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                     c_void_p, c_void_p, c_void_p]),
-    "rsp_resnet_stem": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "rsp_maxpool_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_upsample_nearest_add": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "rsp_sam_embed_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                    c_void_p]),
-    "rsp_rle_from_string": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "rsp_rle_to_bits": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_coco_iou": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_coco_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                               c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_slice_resize_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
-                                     c_int, c_int, ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_float),
-                                     ctypes.POINTER(c_float), c_void_p]),
-    "rsp_rle_shift": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                              c_int, c_void_p]),
-    "rsp_paste_tiles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "rsp_rle_bbox": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "rsp_rle_pair_overlap_workspace_bytes": (c_int64, [c_int, c_int]),
-    "rsp_rle_pair_overlap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                     c_void_p, c_void_p]),
-    "rsp_rle_intervals": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_int64, c_void_p, c_void_p, c_void_p]),
-    "rsp_rle_union": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                              c_void_p]),
-    "rsp_mask_polygon_pieces": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "rsp_mask_polygon_edges": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p]),
-    "rsp_mask_polygon_rank_workspace_bytes": (c_int64, [c_int64]),
-    "rsp_mask_polygon_rank": (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_mask_polygon_write": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p]),
-    "rsp_ring_simplify_mark": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_ring_simplify_survive": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
-                                          c_void_p, c_void_p]),
-    "rsp_ring_simplify_write": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_mask_hull_workspace_bytes": (c_int64, [c_int64]),
-    "rsp_mask_hull_chains": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
-                                     c_void_p, c_void_p]),
-    "rsp_mask_hull_write": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                    c_void_p, c_void_p]),
-    "rsp_hull_min_rect": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
-    "rsp_sam_embed_prompts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "rsp_mask_score_box": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                   c_float, c_float, c_void_p, c_void_p]),
-    "rsp_crops_resize_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                     ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_float),
-                                     ctypes.POINTER(c_float), c_void_p]),
-    "rsp_mask_score_box_crops": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                         c_float, c_float, c_void_p, c_void_p]),
-    "rsp_sam_t2i_attention_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                                           c_float, c_void_p]),
-    "rsp_persam_target": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_persam_similarity": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "rsp_persam_locate_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
-    "rsp_persam_locate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "rsp_persam_f_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
-    "rsp_persam_f_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                       c_float, c_void_p, c_int64, c_void_p, c_void_p]),
-    "rsp_persam_f_fit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                 c_double, c_double, c_double, c_double, c_double, c_float, c_void_p, c_int64, c_void_p, c_void_p,
-                                 c_void_p]),
-    "rsp_mask_regions_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
-    "rsp_mask_remove_small_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                              c_void_p]),
-}
+if not os.path.exists(HEADER):
+    raise RuntimeError(f"{os.path.normpath(HEADER)} is missing: it is the declaration of the C ABI that this module binds. "
+                       "There is no fallback path.")
+with open(HEADER) as _f:
+    STRUCTS, PROTOTYPES, CONST = parse_header(_f.read())
+globals().update(STRUCTS)       # RspGemmDesc, RspAttnDesc, ...: one ctypes.Structure per `typedef struct` of the header
 
 _lib = None
 
@@ -278,7 +130,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m rsprompter_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no fallback path.")
     # a library left over from older sources would be loaded silently and its struct layouts (RspGemmDesc, ...) would
-    # no longer match this file: compare the source digest recorded at build time; rebuild when hipcc is here, else fail
+    # no longer match the header: compare the source digest recorded at build time; rebuild when hipcc is here, else fail
     from . import build as _build
     try:
         stale = (not os.path.exists(_build.STAMP)) or open(_build.STAMP).read().strip() != _build._digest()

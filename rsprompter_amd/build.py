@@ -11,6 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+HEADER = os.path.join(HERE, "..", "include", "rsp_hip.h")   # the C ABI: compiled into the library, parsed by _lib.py
 LIB = os.path.join(HERE, "librsp_hip.so")
 STAMP = os.path.join(HERE, ".librsp_hip.stamp")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -46,8 +47,7 @@ def sources():
 
 def _digest():
     h = hashlib.sha256()
-    for p in sources() + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [
-            os.path.join(HERE, "..", "include", "rsp_hip.h")]:
+    for p in sources() + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [HEADER]:
         with open(p, "rb") as f:
             h.update(os.path.basename(p).encode())      # names, not absolute paths: the tree moves (gpurun snapshot)
             h.update(f.read())

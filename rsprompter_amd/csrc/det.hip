@@ -400,7 +400,7 @@ struct NmsP {
   int32_t* keep_cnt;  // [B]
 };
 
-constexpr int NMS_LDS_KEYS = 16384;  // 128 KB of LDS; larger candidate sets sort in memory (same block, same network)
+constexpr int NMS_LDS_KEYS = RSP_NMS_LDS_CANDIDATES;  // 128 KB of LDS; larger candidate sets sort in memory (same block, same network)
 __global__ __launch_bounds__(1024) void nms_prepare_kernel(const NmsP p) {
   extern __shared__ unsigned long long skeys_lds[];
   unsigned long long* skeys_dyn = p.gkeys ? p.gkeys + (int64_t)blockIdx.x * p.nsort : skeys_lds;
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const NmsP p) {
 }
 
 // NMS_MAXW removal words per lane: 64 lanes * NMS_MAXW words * 64 bits candidates (4: 16384, the RSPrompter sizes; 32: 131072)
-constexpr int NMS_MAXW_LARGE = 32;
+constexpr int NMS_MAXW_LARGE = RSP_NMS_MAX_CANDIDATES / (64 * 64);
 template <int NMS_MAXW>
 __global__ __launch_bounds__(64) void nms_reduce_kernel(const NmsP p) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -651,7 +651,7 @@ extern "C" int64_t rsp_nms_workspace_bytes(int32_t B, int32_t cap) {
   const int64_t words = (cap + 63) / 64;
   int64_t nsort = 1;
   while (nsort < cap) nsort <<= 1;
-  const int64_t keys = nsort > 16384 ? (int64_t)B * nsort * sizeof(unsigned long long) : 0;  // NMS_LDS_KEYS
+  const int64_t keys = nsort > NMS_LDS_KEYS ? (int64_t)B * nsort * sizeof(unsigned long long) : 0;
   return (int64_t)B * cap * (4 * sizeof(float) + sizeof(int32_t) + words * sizeof(unsigned long long)) + keys + 256;
 }
 
@@ -661,7 +661,7 @@ extern "C" int rsp_batched_nms(const float* boxes, const float* scores, const in
                                int32_t* keep_cnt, float* out_boxes, float* out_scores, int32_t* out_ids,
                                int32_t* out_src, rsp_stream_t stream) {
   if (!boxes || !scores || !ids || !cnt || !workspace || !keep || !keep_cnt || !out_boxes || !out_scores ||
-      !out_ids || B <= 0 || cap <= 0 || cap > 64 * 64 * NMS_MAXW_LARGE || max_out <= 0)
+      !out_ids || B <= 0 || cap <= 0 || cap > RSP_NMS_MAX_CANDIDATES || max_out <= 0)
     return RSP_EINVAL;
   int nsort = 1;
   while (nsort < cap) nsort <<= 1;

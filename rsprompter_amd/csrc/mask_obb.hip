@@ -40,7 +40,7 @@ typedef unsigned __int128 mo_u128;
 constexpr int MO_THREADS = 256;
 constexpr int MO_LDS_PTS = 4096;             // candidate points of a chain that stay in LDS (two buffers of packed points)
 constexpr int MO_RECT_LDS = 1024;            // hull vertices of mo_rect_kernel that are staged in LDS (mask hulls: a few hundred)
-constexpr int32_t MO_MAX_SIDE = 65535;       // x and y of a point fit 16 bits each; every product of the calipers fits 128
+constexpr int32_t MO_MAX_SIDE = RSP_MASK_OBB_MAX_SIDE;       // x and y of a point fit 16 bits each; every product of the calipers fits 128
 constexpr int MO_NONE = 0x7fffffff;
 
 // a point / a record: x << 16 | y
@@ -321,14 +321,14 @@ __global__ __launch_bounds__(MO_THREADS) void mo_rect_kernel(const int32_t* __re
 }  // namespace
 
 extern "C" int64_t rsp_mask_hull_workspace_bytes(int64_t B) {
-  if (B < 0 || B > 0x3fffffffLL) return 0;
+  if (B < 0 || B > RSP_MASK_OBB_MAX_BOUND) return 0;
   return 8 * B * (int64_t)sizeof(uint32_t);
 }
 
 extern "C" int rsp_mask_hull_chains(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
                                     const int64_t* bound_offs, int64_t B, void* workspace, int32_t* chain_cnt, int32_t* rounds,
                                     rsp_stream_t stream) {
-  if (k < 0 || cap < 1 || !rsp_run_canvas_ok(H, W) || H > MO_MAX_SIDE || W > MO_MAX_SIDE || B < 0 || B > 0x3fffffffLL)
+  if (k < 0 || cap < 1 || !rsp_run_canvas_ok(H, W) || H > MO_MAX_SIDE || W > MO_MAX_SIDE || B < 0 || B > RSP_MASK_OBB_MAX_BOUND)
     return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   if (!counts || !n || !bound_offs || !chain_cnt || !rounds || (B > 0 && !workspace)) return RSP_EINVAL;
@@ -341,7 +341,7 @@ extern "C" int rsp_mask_hull_chains(const uint32_t* counts, const int32_t* n, in
 extern "C" int rsp_mask_hull_write(const int32_t* n, int32_t k, int32_t cap, const int64_t* bound_offs, int64_t B,
                                    const void* workspace, const int32_t* chain_cnt, const int64_t* hull_offs, int64_t Vh,
                                    int32_t* hull_verts, int64_t* hull_area2, rsp_stream_t stream) {
-  if (k < 0 || cap < 1 || B < 0 || B > 0x3fffffffLL || Vh < 0 || Vh > 0x7fffffffLL) return RSP_EINVAL;
+  if (k < 0 || cap < 1 || B < 0 || B > RSP_MASK_OBB_MAX_BOUND || Vh < 0 || Vh > 0x7fffffffLL) return RSP_EINVAL;
   if (k == 0) return RSP_OK;
   if (!n || !bound_offs || !chain_cnt || !hull_offs || !hull_area2 || (B > 0 && !workspace) || (Vh > 0 && !hull_verts))
     return RSP_EINVAL;

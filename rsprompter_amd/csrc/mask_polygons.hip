@@ -386,7 +386,7 @@ __global__ __launch_bounds__(MP_THREADS) void mp_parent_kernel(int64_t R, int k,
 }
 
 inline unsigned mp_blocks(int64_t n) { return (unsigned)((n + MP_THREADS - 1) / MP_THREADS); }
-constexpr int64_t MP_MAX_PIECES = 0x7fffffffLL / 6;
+constexpr int64_t MP_MAX_PIECES = RSP_MASK_POLYGON_MAX_PIECES;
 
 }  // namespace
 

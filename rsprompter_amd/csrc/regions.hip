@@ -25,7 +25,7 @@
 
 namespace {
 
-constexpr int TH = 64, TW = 64, TPX = TH * TW;      // the tile (ops.MASK_REGION_TILE restates it)
+constexpr int TH = RSP_MASK_REGION_TILE_H, TW = RSP_MASK_REGION_TILE_W, TPX = TH * TW;      // the tile
 constexpr int ACC_INTS = 16;                        // per mask: see Acc
 constexpr int MAX_MASKS_PER_LAUNCH = 32768;
 

@@ -34,8 +34,8 @@ constexpr int RS_WAVE_MAX = 64;               // the longest ring of the wave pa
 constexpr int RS_LDS_VERTS = 2048;            // rs_mark_block_kernel: coordinates of rings up to here are staged in LDS
 constexpr int RS_MAX_BLOCKS = 4096;           // rs_mark_block_kernel strides over the rings
 constexpr int RS_NONE = 0x7fffffff;
-constexpr int64_t RS_MAX_TOL2_Q8 = 1LL << 40;
-constexpr int32_t RS_MAX_SIDE = 1 << 20;
+constexpr int64_t RS_MAX_TOL2_Q8 = RSP_RING_SIMPLIFY_MAX_TOL2_Q8;
+constexpr int32_t RS_MAX_SIDE = RSP_RING_SIMPLIFY_MAX_SIDE;
 
 // the numerator of the squared distance from p to the segment a b; *den = its denominator
 __device__ __forceinline__ rs_u128 rs_num(int ax, int ay, int bx, int by, int px, int py, uint64_t* den) {

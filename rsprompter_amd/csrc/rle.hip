@@ -10,7 +10,7 @@
 namespace {
 
 constexpr int RLE_THREADS = 1024;
-constexpr int RLE_MAX_W = 8192;
+constexpr int RLE_MAX_W = RSP_RLE_MAX_WIDTH;
 
 // one block per mask; thread t owns columns t, t + 1024, ... so that at every step the block reads one row segment
 // of the row-major mask contiguously.  Pass 1 counts the value changes per column, a block scan turns them into

@@ -754,12 +754,12 @@ __global__ __launch_bounds__(F2_THREADS) void sam_i2t_fused_mfma_kernel(const I2
 
 extern "C" int rsp_sam_t2i_attention(const float* q, const float* kv, const int32_t* kv_map, float* out, int32_t R,
                                      int32_t T, int32_t N, float scale, rsp_stream_t stream) {
-  if (!q || !kv || !out || R < 0 || T <= 0 || T > 12 || N <= 0) return RSP_EINVAL;   // T > 12: rsp_attention
+  if (!q || !kv || !out || R < 0 || T <= 0 || T > RSP_SAM_T2I_MAX_TOKENS || N <= 0) return RSP_EINVAL;   // more tokens: rsp_attention
   if (R == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;
   if (T <= 8) hipLaunchKernelGGL((sam_t2i_kernel<8>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
   else if (T <= 10) hipLaunchKernelGGL((sam_t2i_kernel<10>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
-  else hipLaunchKernelGGL((sam_t2i_kernel<12>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
+  else hipLaunchKernelGGL((sam_t2i_kernel<RSP_SAM_T2I_MAX_TOKENS>), dim3(R), dim3(512), 0, s, q, kv, kv_map, out, T, N, scale);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }
@@ -767,14 +767,14 @@ extern "C" int rsp_sam_t2i_attention(const float* q, const float* kv, const int3
 extern "C" int rsp_sam_t2i_attention_bias(const float* q, const float* kv, const int32_t* kv_map, const float* bias,
                                           int32_t Rb, float* out, int32_t R, int32_t T, int32_t N, float scale,
                                           rsp_stream_t stream) {
-  if (!q || !kv || !out || !bias || R < 0 || T <= 0 || T > 12 || N <= 0) return RSP_EINVAL;
+  if (!q || !kv || !out || !bias || R < 0 || T <= 0 || T > RSP_SAM_T2I_MAX_TOKENS || N <= 0) return RSP_EINVAL;
   if (R == 0) return RSP_OK;
   if (Rb != 1 && Rb != R) return RSP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int bs = Rb == 1 ? 0 : N;
   if (T <= 8) hipLaunchKernelGGL((sam_t2i_bias_kernel<8>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
   else if (T <= 10) hipLaunchKernelGGL((sam_t2i_bias_kernel<10>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
-  else hipLaunchKernelGGL((sam_t2i_bias_kernel<12>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
+  else hipLaunchKernelGGL((sam_t2i_bias_kernel<RSP_SAM_T2I_MAX_TOKENS>), dim3(R), dim3(512), 0, s, q, kv, kv_map, bias, bs, out, T, N, scale);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }
@@ -782,7 +782,7 @@ extern "C" int rsp_sam_t2i_attention_bias(const float* q, const float* kv, const
 extern "C" int rsp_sam_i2t_attention(const float* q, const int32_t* q_map, const float* k, const float* v, float* out,
                                      uint16_t* out_hi, uint16_t* out_lo, int32_t out_scale_log2, int32_t R, int32_t T,
                                      int32_t N, float scale, rsp_stream_t stream) {
-  if (!q || !k || !v || (!out && !(out_hi && out_lo)) || R < 0 || T <= 0 || T > 16 || N <= 0) return RSP_EINVAL;
+  if (!q || !k || !v || (!out && !(out_hi && out_lo)) || R < 0 || T <= 0 || T > RSP_SAM_I2T_MAX_TOKENS || N <= 0) return RSP_EINVAL;
   if ((out_hi == nullptr) != (out_lo == nullptr)) return RSP_EINVAL;
   if (R == 0) return RSP_OK;
   if (R > 65535) return RSP_EINVAL;
@@ -794,7 +794,7 @@ extern "C" int rsp_sam_i2t_attention(const float* q, const int32_t* q_map, const
   const int64_t rows = (int64_t)R * N;
   if (T <= 8) hipLaunchKernelGGL((sam_i2t_kernel<8>), grid, dim3(256), 0, s, q, q_map, k, v, out, hi, lo, ps, T, N, rows, scale);
   else if (T <= 12) hipLaunchKernelGGL((sam_i2t_kernel<12>), grid, dim3(256), 0, s, q, q_map, k, v, out, hi, lo, ps, T, N, rows, scale);
-  else hipLaunchKernelGGL((sam_i2t_kernel<16>), grid, dim3(256), 0, s, q, q_map, k, v, out, hi, lo, ps, T, N, rows, scale);
+  else hipLaunchKernelGGL((sam_i2t_kernel<RSP_SAM_I2T_MAX_TOKENS>), grid, dim3(256), 0, s, q, q_map, k, v, out, hi, lo, ps, T, N, rows, scale);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }
@@ -804,7 +804,7 @@ extern "C" int rsp_sam_i2t_fused(const RspI2tFusedDesc* d, rsp_stream_t stream) 
   if (!d->out && !(d->out_hi && d->out_lo)) return RSP_EINVAL;
   if ((d->out_hi == nullptr) != (d->out_lo == nullptr)) return RSP_EINVAL;
   if ((d->res != nullptr) == (d->res_hi != nullptr) || (d->res_hi && !d->res_lo)) return RSP_EINVAL;   // exactly one residual form
-  if (d->R < 0 || d->T <= 0 || d->T > 10 || d->N <= 0 || d->R > 65535) return RSP_EINVAL;   // T <= 10: the LDS budget
+  if (d->R < 0 || d->T <= 0 || d->T > RSP_SAM_I2T_FUSED_MAX_TOKENS || d->N <= 0 || d->R > 65535) return RSP_EINVAL;   // the token limit: the LDS budget
   if (RSP_PLANE_IS_F8(d->out_scale_log2) || RSP_PLANE_IS_F8(d->res_scale_log2)) return RSP_EINVAL;
   if (d->R == 0) return RSP_OK;
   I2tFusedP p;
@@ -836,7 +836,7 @@ extern "C" int rsp_sam_i2t_fused(const RspI2tFusedDesc* d, rsp_stream_t stream) 
   }
   dim3 grid((d->N + FUSED_PIX_PER_BLOCK - 1) / FUSED_PIX_PER_BLOCK, d->R);
   if (d->T <= 8) hipLaunchKernelGGL((sam_i2t_fused_kernel<8>), grid, dim3(1024), 0, s, p);
-  else hipLaunchKernelGGL((sam_i2t_fused_kernel<10>), grid, dim3(1024), 0, s, p);
+  else hipLaunchKernelGGL((sam_i2t_fused_kernel<RSP_SAM_I2T_FUSED_MAX_TOKENS>), grid, dim3(1024), 0, s, p);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void mask_score_final_kernel(int32_t* __restri
 // (scalar loads) and mask_form() is evaluated per crop: counts and crop-local box are those of rsp_mask_score_box on that
 // crop's slice.  acc is [k, 8]: the finalising launch shifts the box into the image frame and writes HF's
 // _is_box_near_crop_edge into column 7.
-constexpr int CROP_ROW = 12;
+constexpr int CROP_ROW = RSP_CROP_TABLE_COLS;
 constexpr int CROP_EDGE_ATOL = 20;      // _is_box_near_crop_edge(atol=20.0); every quantity is an integer
 struct MaskScoreCropsP {
   const float* low;          // [k, h, w]
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256) void sam_fold_gather_kernel(const float* __res
 
 extern "C" int rsp_sam_fold_expand(const float* tq, uint16_t* out_hi, uint16_t* out_lo, int32_t out_scale_log2, int32_t R, int32_t T,
                                    float scale, rsp_stream_t stream) {
-  if (!tq || !out_hi || !out_lo || R < 0 || T <= 0 || 8 * T > 96 || !RSP_PLANE_WORD_VALID(out_scale_log2) ||
+  if (!tq || !out_hi || !out_lo || R < 0 || T <= 0 || T > RSP_SAM_T2I_FOLD_MAX_TOKENS || !RSP_PLANE_WORD_VALID(out_scale_log2) ||
       RSP_PLANE_IS_F8(out_scale_log2))
     return RSP_EINVAL;
   if (R == 0) return RSP_OK;
@@ -666,7 +666,7 @@ extern "C" int rsp_sam_fold_expand(const float* tq, uint16_t* out_hi, uint16_t* 
 }
 
 extern "C" int rsp_sam_fold_gather(const float* full, float* ao, int32_t R, int32_t T, rsp_stream_t stream) {
-  if (!full || !ao || R < 0 || T <= 0 || 8 * T > 96) return RSP_EINVAL;
+  if (!full || !ao || R < 0 || T <= 0 || T > RSP_SAM_T2I_FOLD_MAX_TOKENS) return RSP_EINVAL;
   if (R == 0) return RSP_OK;
   const int64_t n4 = (int64_t)R * T * 32;
   hipLaunchKernelGGL(sam_fold_gather_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, full, ao, n4, T);

@@ -322,7 +322,7 @@ extern "C" int rsp_sam_t2i_fold(const uint16_t* keys_hi, const uint16_t* keys_lo
                                 int32_t tqx_e, int64_t q_rows, float* u, int32_t R, int32_t N, int32_t ncols,
                                 rsp_stream_t stream) {
   if (!keys_hi || !keys_lo || !pek_hi || !pek_lo || !qp_hi || !qp_lo || !tqx_hi || !tqx_lo || !u || R < 0 || N <= 0 ||
-      (N % FKT) || ncols <= 0 || ncols > 96 || (ncols & 7) || k_rows < (int64_t)R * N || q_rows < (int64_t)R * 96 ||
+      (N % FKT) || ncols <= 0 || ncols > 8 * RSP_SAM_T2I_FOLD_MAX_TOKENS || (ncols & 7) || k_rows < (int64_t)R * N || q_rows < (int64_t)R * 96 ||
       k_rows * 512 > 0x7fffffffLL || (int64_t)N * 256 > 0x7fffffffLL)
     return RSP_EINVAL;
   if (R == 0) return RSP_OK;

@@ -19,13 +19,13 @@ import os
 import numpy as np
 import torch
 
-from . import ops, rle
+from . import _lib, ops, rle
 from .structures import DetDataSample, InstanceData
 
 # masks='dense' materialises bool [K, H, W]; a request beyond this many bytes is refused with the figure in the message
 # (settable, like ops.NMS_WORKSPACE_LIMIT_BYTES)
 DENSE_MASK_LIMIT_BYTES = 8 << 30
-MAX_PATCH_WIDTH = 8192          # rsp_mask_rle is specified for W <= 8192
+MAX_PATCH_WIDTH = _lib.CONST['RSP_RLE_MAX_WIDTH']          # rsp_mask_rle is specified for widths up to here
 
 
 # ----------------------------------------------------------------------------------------------------------------- host

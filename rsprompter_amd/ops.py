@@ -1,6 +1,7 @@
 """Thin Python wrappers: torch tensors (device memory + stream plumbing only)
 -> C-ABI calls into librsp_hip.so.  No arithmetic happens in torch here.
 """
+import ctypes
 import math
 import os
 
@@ -8,7 +9,9 @@ import torch
 
 from . import _lib as _lib_real
 
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_SIGMOID, ACT_RELU_POST = 0, 1, 2, 3, 4
+CONST = _lib_real.CONST     # the integer macros of include/rsp_hip.h: flags and limits of the C ABI are stated there only
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_SIGMOID, ACT_RELU_POST = (
+    CONST['RSP_ACT_' + a] for a in ('NONE', 'RELU', 'GELU', 'SIGMOID', 'RELU_POST'))
 # Power-of-two pre-scale of activation planes (x * 2^e is what gets split into fp16 hi + lo).  e = 2 keeps |x| < 16376
 # exactly representable (the split saturates beyond, rsp_common.h) -- headroom for the outlier activations of real SAM
 # checkpoints (MLP hidden layer, residual stream) and for the RSFeatureAggregator's running sum over 16 layers, which
@@ -157,7 +160,7 @@ class PackedWeight:
         self.bias = None if bias is None else bias.detach().to(torch.float32).contiguous().to(device)
 
 
-PLANE_F8 = 0x100        # include/rsp_hip.h "Plane format word"
+PLANE_F8 = CONST['RSP_PLANE_F8']        # include/rsp_hip.h "Plane format word"
 # Opt-in fast mode (RSP_F8CORR=1, or set ops.F8_CORR before the model is built / first run): the four big GEMMs of every
 # encoder block run fp16 hi.hi + ONE fp8 MFMA carrying both correction terms (2 units of matrix time instead of 3).
 # Measured: GEMMs 1.15-1.25x faster, image embeddings 1.0-1.4e-4 instead of 1.2-1.6e-5 off the fp32
@@ -501,7 +504,7 @@ def vit_window_attention(q, kv, rel_tab, Bp, nh, dh, scale, planes=False, f8=Fal
     return pl if planes else out
 
 
-SAM_I2T_FUSED_MAX_TOKENS = 10   # rsp_sam_i2t_fused (LDS budget); more tokens: sam_i2t_attention + GEMM + layernorm
+SAM_I2T_FUSED_MAX_TOKENS = CONST['RSP_SAM_I2T_FUSED_MAX_TOKENS']   # rsp_sam_i2t_fused (LDS budget); more tokens: sam_i2t_attention + GEMM + layernorm
 
 
 def sam_i2t_fused(q, k, v, wo, bo, gamma, beta, *, R, T, N, scale, eps=1e-6, q_map=None, res=None, res_map=None,
@@ -767,8 +770,8 @@ def attention(q, k, v, out, *, B, nh, dh, Tq, Tk, scale, q_strides, k_strides, v
     return out if out_planes is None else out_planes
 
 
-SAM_T2I_MAX_TOKENS = 12     # rsp_sam_t2i_attention; more tokens go through the generic rsp_attention
-SAM_I2T_MAX_TOKENS = 16
+SAM_T2I_MAX_TOKENS = CONST['RSP_SAM_T2I_MAX_TOKENS']     # rsp_sam_t2i_attention; more tokens go through the generic rsp_attention
+SAM_I2T_MAX_TOKENS = CONST['RSP_SAM_I2T_MAX_TOKENS']
 
 
 def sam_t2i_attention(q, kv, out, *, R, T, N, scale, kv_map=None):
@@ -880,7 +883,7 @@ def sam_hq_mask(up, w2, bias2, w1, bias1, gamma, beta, eps, wf, biasf, hyper, fe
     return out if not n_sam else (out, out_sam)
 
 
-SAM_T2I_FOLD_MAX_TOKENS = 12    # 8 heads x T query columns fit the kernel's 96
+SAM_T2I_FOLD_MAX_TOKENS = CONST['RSP_SAM_T2I_FOLD_MAX_TOKENS']    # 8 heads x T query columns fit the kernel's 96
 
 
 def sam_t2i_fold(keys, pek, qp, tqx, *, R, N, ncols):
@@ -1296,7 +1299,7 @@ def persam_f_fit(low_res, gt, img_shape, crop_hw, out_hw, epochs=1000, lr=1e-3, 
     return (weights, hist) if want_history else weights
 
 
-CROP_TABLE_COLS = 12    # rsp_mask_score_box_crops: Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H
+CROP_TABLE_COLS = CONST['RSP_CROP_TABLE_COLS']    # rsp_mask_score_box_crops: Hb, Wb, crop_h, crop_w, out_h, out_w, x0, y0, x1, y1, W, H
 
 
 def mask_score_box_crops(low_res, crop_idx, table, max_out_hw, mask_threshold=0.0, stability_score_offset=1.0,
@@ -1380,8 +1383,8 @@ class RpnSelector:
         return batched_nms(cand, B, cap, self.iou_thr, self.max_per_img)
 
 
-NMS_LDS_CANDIDATES = 16384     # rsp_batched_nms sorts up to here in LDS (det.hip NMS_LDS_KEYS), in memory above
-NMS_MAX_CANDIDATES = 131072    # ... and holds this many candidates per image at most
+NMS_LDS_CANDIDATES = CONST['RSP_NMS_LDS_CANDIDATES']     # rsp_batched_nms sorts up to here in LDS, in memory above
+NMS_MAX_CANDIDATES = CONST['RSP_NMS_MAX_CANDIDATES']    # ... and holds this many candidates per image at most
 # the pair mask of the in-memory path is quadratic: B * cap * cap / 8 bytes (200 MB per image at 40 k candidates, 2 GiB at
 # the kernel's limit).  A call that would need more than this many bytes of workspace is refused with the figures in the
 # message instead of failing inside the allocator (settable: a box with spare HBM may raise it).
@@ -1768,7 +1771,7 @@ def rle_union(counts, n, H, W, group_offs, members, cap_out):
 
 
 # ----------------------------------------------------------------------------- polygon export (csrc/mask_polygons.hip)
-MASK_POLYGON_MAX_PIECES = (2 ** 31 - 1) // 6     # six edge slots per column piece, 32-bit slot numbers
+MASK_POLYGON_MAX_PIECES = CONST['RSP_MASK_POLYGON_MAX_PIECES']     # six edge slots per column piece, 32-bit slot numbers
 
 
 def _log2_ceil(v):
@@ -1841,8 +1844,8 @@ def mask_polygons(counts, n, H, W):
 
 
 # ----------------------------------------------------------------------------- polygon simplification (csrc/ring_simplify.hip)
-RING_SIMPLIFY_MAX_TOL2_Q8 = 2 ** 40      # tolerance^2 in 1 / 256 px^2: tolerances up to 65 536 px
-RING_SIMPLIFY_MAX_SIDE = 2 ** 20         # coordinates in [0, 2^20]: every distance comparison fits 128-bit integers
+RING_SIMPLIFY_MAX_TOL2_Q8 = CONST['RSP_RING_SIMPLIFY_MAX_TOL2_Q8']      # tolerance^2 in 1 / 256 px^2: tolerances up to 65 536 px
+RING_SIMPLIFY_MAX_SIDE = CONST['RSP_RING_SIMPLIFY_MAX_SIDE']         # coordinates in [0, 2^20]: every distance comparison fits 128-bit integers
 _RING_ARRAYS = (('verts', torch.int32, 2), ('ring_offs', torch.int64, 1), ('ring_inst', torch.int32, 1),
                 ('ring_parent', torch.int32, 1), ('ring_area2', torch.int64, 1), ('inst_ring_offs', torch.int64, 1))
 
@@ -1917,8 +1920,8 @@ def ring_simplify(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_rin
 
 
 # ----------------------------------------------------------------------------- oriented boxes (csrc/mask_obb.hip)
-MASK_OBB_MAX_SIDE = 65535                # coordinates in [0, 65 535]: 16 bits each, and every product of the calipers fits 128
-MASK_OBB_MAX_BOUND = 2 ** 30 - 1         # three records per ones-run over all rows of one call (32-bit hull offsets)
+MASK_OBB_MAX_SIDE = CONST['RSP_MASK_OBB_MAX_SIDE']                # coordinates in [0, 65 535]: 16 bits each, and every product of the calipers fits 128
+MASK_OBB_MAX_BOUND = CONST['RSP_MASK_OBB_MAX_BOUND']         # three records per ones-run over all rows of one call (32-bit hull offsets)
 
 
 def mask_hull(counts, n, H, W, with_rounds=False):
@@ -1992,7 +1995,8 @@ def hull_min_rect(hull_verts, hull_offs):
     return edge, q
 
 
-MASK_REGION_TILE = (64, 64)    # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling (regions.hip TH, TW)
+# (th, tw) of rsp_mask_remove_small_regions' tile-local labelling
+MASK_REGION_TILE = (CONST['RSP_MASK_REGION_TILE_H'], CONST['RSP_MASK_REGION_TILE_W'])
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}
 # the labelling keeps two int32 per pixel: 8 bytes x k x H x W of workspace.  remove_small_regions splits k so that one call
 # stays under this (64 masks of 1024 x 1024 are 512 MiB); a single mask larger than that gets its workspace all the same.
@@ -2099,15 +2103,19 @@ def rle_to_bits(counts, n, word_offs):
     return bits, area[:k], wrange[:k]
 
 
-COCO_IOU_BBOX, COCO_IOU_SEGM = 0, 1
-COCO_UNIT_BYTES = 40
+COCO_IOU_BBOX, COCO_IOU_SEGM = CONST['RSP_COCO_IOU_BBOX'], CONST['RSP_COCO_IOU_SEGM']
+COCO_UNIT_BYTES = ctypes.sizeof(_lib.RspCocoUnit)
+
+
+def _units_ptr(units):
+    """the device address of a `coco_units` tensor as the `const RspCocoUnit*` the entry points declare"""
+    return ctypes.cast(units.data_ptr(), ctypes.POINTER(_lib.RspCocoUnit))
 
 
 def coco_units(dt0, gt0, out0, nd, ng, nwords, device):
     """RspCocoUnit records (include/rsp_hip.h) from per-unit numpy columns -> uint8 device tensor."""
     import numpy as np
-    rec = np.zeros(len(nd), dtype=np.dtype([('dt0', '<i8'), ('gt0', '<i8'), ('out0', '<i8'), ('nd', '<i4'),
-                                             ('ng', '<i4'), ('nwords', '<i4'), ('pad', '<i4')]))
+    rec = np.zeros(len(nd), dtype=np.dtype(_lib.RspCocoUnit))
     rec['dt0'], rec['gt0'], rec['out0'], rec['nd'], rec['ng'], rec['nwords'] = dt0, gt0, out0, nd, ng, nwords
     return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
 
@@ -2120,7 +2128,7 @@ def coco_iou(units, n_iou, mode, *, gt_crowd, dt_box=None, gt_box=None, dt_bits=
     iou = torch.zeros((max(n_iou, 1),), dtype=torch.float64, device=dev)
     nu = units.numel() // COCO_UNIT_BYTES
     if nu:
-        _lib.check(lib.rsp_coco_iou(units.data_ptr(), nu, mode, _ptr(dt_bits), _ptr(gt_bits), _ptr(dt_woff),
+        _lib.check(lib.rsp_coco_iou(_units_ptr(units), nu, mode, _ptr(dt_bits), _ptr(gt_bits), _ptr(dt_woff),
                                     _ptr(gt_woff), _ptr(dt_wrange), _ptr(gt_wrange), _ptr(dt_area), _ptr(gt_area),
                                     _ptr(dt_box), _ptr(gt_box), gt_crowd.data_ptr(), iou.data_ptr(), _stream()),
                    "rsp_coco_iou")
@@ -2140,7 +2148,7 @@ def coco_match(units, iou, gt_area, gt_crowd, gt_id, dt_area, area_rng, thrs, n_
     dtig = torch.zeros((A, T, max(n_dt, 1)), dtype=torch.uint8, device=dev)
     npig = torch.zeros((max(nu, 1), A), dtype=torch.int32, device=dev)
     if nu:
-        _lib.check(lib.rsp_coco_match(units.data_ptr(), nu, iou.data_ptr(), gt_area.data_ptr(), gt_crowd.data_ptr(),
+        _lib.check(lib.rsp_coco_match(_units_ptr(units), nu, iou.data_ptr(), gt_area.data_ptr(), gt_crowd.data_ptr(),
                                       gt_id.data_ptr(), dt_area.data_ptr(), area_rng.data_ptr(), A, thrs.data_ptr(), T,
                                       n_dt, ws.data_ptr(), dtm.data_ptr(), dtig.data_ptr(), npig.data_ptr(), _stream()),
                    "rsp_coco_match")
