@@ -39,6 +39,8 @@ typedef void* rsp_stream_t;
 /* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
 /* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
 /* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
+/* Still 5 with rsp_run_components_* (as with the polygon, simplification and oriented-box entry points before them): an  */
+/* addition that leaves every earlier entry point, structure and macro as it was does not change the number.              */
 /* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
 /* 3: RspBoxCoder in RspRpnDesc / rsp_bbox_post; 2: RspGemmDesc gained c_ncols / pl_col0, plane format words decode       */
 /* strictly.                                                                                                             */
@@ -807,6 +809,37 @@ int rsp_mask_hull_write(const int32_t* n, int32_t k, int32_t cap, const int64_t*
 /* polygon without vertices); q int64 [k, 6] = (ex, ey, amin, amax, bmin, bmax) of that edge (zeros for -1).                    */
 int rsp_hull_min_rect(const int32_t* hull_verts, const int64_t* hull_offs, int32_t k, int64_t Vh, int32_t* edge, int64_t* q,
                       rsp_stream_t stream);
+
+/* Run-domain connected components (csrc/run_components.hip): the 8-connected components of every mask of a     */
+/* run table; replaces decoding every instance to a dense H x W array + cv2.connectedComponentsWithStats (segment-anything     */
+/* utils/amg.py remove_small_regions) and the dense labelling of rsp_mask_remove_small_regions where the masks live as runs.   */
+/* counts [k, cap] / n [k]: k masks on ONE (H, W) canvas as above (n <= 0: no pieces; n beyond cap is read up to cap).         */
+/* H * W >= 2^31 and P > RSP_RUN_COMPONENTS_MAX_PIECES (32-bit piece indices) are refused (RSP_EINVAL);                        */
+/* rsp_run_components_workspace_bytes(H, W, P) is -1 for what the calls refuse.  No call reads the host.  Atomics: integer     */
+/* min / max / add only, so a second launch gives the same bits.                                                              */
+/* 1. piece_offs int64 [k + 1] = exclusive sum of rsp_mask_polygon_pieces' piece_cnt, P = piece_offs[k].  Writes pieces int32   */
+/* [4, P] = (x, y0, y1, instance) sorted by (instance, x, y0) (-1 as the instance of a slot no row filled), label int32 [P] =  */
+/* the lowest piece index of the piece's component (pieces of columns x and x + 1 are joined iff their closed row ranges,       */
+/* widened by one row, overlap), root int32 [P] = 1 where label[p] == p.  status int32 [1], zeroed by the caller: set to 1      */
+/* when a find / union loop reached its step cap (the result is then invalid; a correct run never does).                       */
+#define RSP_RUN_COMPONENTS_MAX_PIECES 0x7fffff00LL
+int64_t rsp_run_components_workspace_bytes(int32_t H, int32_t W, int64_t P);
+int rsp_run_components_label(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                             const int64_t* piece_offs, int64_t P, int32_t* pieces, void* workspace, int32_t* label,
+                             int32_t* root, int32_t* status, rsp_stream_t stream);
+/* 2. root_cum int64 [P] = the inclusive sum of root, C = root_cum[P - 1]: component c is the c-th root, which orders the       */
+/* components by (instance, label).  Writes piece_comp int32 [P] (-1 for an unfilled slot), comp_area int32 [C], comp_box       */
+/* int32 [C, 4] = (x0, y0, x1, y1) end-exclusive as rsp_rle_bbox, comp_first int32 [C] = the lowest row-major index y W + x of  */
+/* the component's pixels (the tie rule of rsp_mask_remove_small_regions), comp_inst int32 [C].                                 */
+int rsp_run_components_stats(const int32_t* pieces, int64_t P, int32_t H, int32_t W, const int32_t* label, const int32_t* root,
+                             const int64_t* root_cum, int64_t C, int32_t* piece_comp, int32_t* comp_area, int32_t* comp_box,
+                             int32_t* comp_first, int32_t* comp_inst, rsp_stream_t stream);
+/* 3. Which components stay, one block per instance over comp_offs int64 [k + 1]: keep int32 [C] = 1 for a component of at      */
+/* least min_area pixels; keep_largest != 0 (islands): when an instance has none, its largest stays, the one with the lowest    */
+/* comp_first among equals.  changed int32 [k, 2]: column `slot` = 1 when the instance has a smaller component.                 */
+int rsp_run_components_select(const int64_t* comp_offs, int32_t k, int64_t C, const int32_t* comp_area, const int32_t* comp_first,
+                              int32_t min_area, int32_t keep_largest, int32_t slot, int32_t* keep, int32_t* changed,
+                              rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */

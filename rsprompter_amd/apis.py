@@ -208,12 +208,26 @@ from .sam_prompts import PerSam, PerSamF, SamMaskGenerator, SamSession, generate
 from .samdet import SamHQModelHIP  # noqa: E402,F401  (HF SamHQModel on HIP kernels, DESIGN §15 "SAM-HQ")
 
 
-def remove_small_regions(masks, min_area, mode='both'):
+def remove_small_regions(masks, min_area, mode='both', device='cuda:0'):
     """segment-anything's `remove_small_regions` for masks that come from elsewhere (`SamSession.predict`,
     `PerSam(output='dense')`, a detector's results): masks bool / uint8 [k, H, W] or [H, W] on the device; mode 'holes'
     (8-connected components of the background with fewer than min_area pixels are filled), 'islands' (components of the mask
     that small are removed; if all are, the largest stays) or 'both' (holes first).  Returns (masks bool of the input's
-    shape, changed bool [k] or a bool).  One host read (the labelling's status)."""
+    shape, changed bool [k] or a bool).  One host read (the labelling's status).
+    masks may also be a list of RLE dicts dict(size=[H, W], counts=...) of one size, compressed (bytes / str) or uncompressed
+    (list) counts as in masks_to_polygons: they are cleaned in the run domain (rle.clean_runs; `device` places
+    the run table) and come back as (RLE dicts of the input's counts form, changed bool [k] on the host)."""
+    if not isinstance(masks, torch.Tensor):
+        from . import rle
+        masks = list(masks)
+        counts, n, size = _masks_to_runs(masks, device)
+        _check_canonical(counts, n, size)
+        counts, n, n_host, _, changed = rle.clean_runs(counts, n, size, min_area, mode)
+        if isinstance(masks[0]['counts'], (bytes, str)):
+            out = rle.runs_to_strings(counts, n, size)
+        else:
+            out = rle.runs_to_dicts(counts, n_host, size)
+        return out, (changed != 0).any(1).cpu()
     single = masks.dim() == 2
     out, info = ops.remove_small_regions(masks[None] if single else masks, min_area, mode)
     ops.check_region_status(info[:, 7].cpu().tolist())
@@ -378,7 +392,7 @@ def obb_to_geojson(corners, transform=None):
     return out
 
 
-def masks_to_obb(masks, form='corners', transform=None, device='cuda:0'):
+def masks_to_obb(masks, form='corners', transform=None, device='cuda:0', per_component=False):
     """Masks -> oriented boxes: the minimum-area rectangle around each mask (all its components together), exact on the
     device in the run domain; what cv2.convexHull + cv2.minAreaRect give on a dense mask.  `masks` as in
     masks_to_polygons (a bool [k, H, W] device tensor, or RLE dicts of one size with compressed or uncompressed counts).
@@ -388,7 +402,9 @@ def masks_to_obb(masks, form='corners', transform=None, device='cuda:0'):
     form='hull': per instance the int32 [m, 2] hull vertices, clockwise on screen from the smallest by (x, y).
     form='geojson': per instance a Polygon geometry of the closed rectangle.
     transform = (a, b, c, d, e, f) maps X = a + b x + c y, Y = d + e x + f y for 'corners' and 'geojson'; it is refused with
-      'xywha' (an affine map does not keep rectangles) and 'hull' (integer vertices)."""
+      'xywha' (an affine map does not keep rectangles) and 'hull' (integer vertices).
+    per_component=True: a list with one entry per instance, holding in the same form the boxes or hulls of its 8-connected
+      components in component order (rle.split_runs); an empty mask has an empty entry."""
     from . import rle
     if form not in OBB_FORMS:
         raise ValueError(f'oriented-box form {form!r}: one of {OBB_FORMS}')
@@ -398,14 +414,34 @@ def masks_to_obb(masks, form='corners', transform=None, device='cuda:0'):
     counts, n, size = _masks_to_runs(masks, device)
     if not isinstance(masks, torch.Tensor):
         _check_canonical(counts, n, size)
+    if per_component:                                                   # one row per component, regrouped below
+        counts, n, _, _, comp_offs = rle.split_runs(counts, n, size)
+        co = comp_offs.tolist()
     hull_verts, hull_offs, _, edge, q = rle.runs_to_obb(counts, n, size)
     if form == 'hull':
         sizes = [int(hull_verts.numel()), int(hull_offs.numel())]
         buf = torch.cat([hull_verts.reshape(-1).to(torch.int64), hull_offs]).cpu().numpy()          # one transfer
         v, o = np.split(buf, sizes[:1])
         v, o = v.astype(np.int32).reshape(-1, 2), o.tolist()
-        return [v[o[i]:o[i + 1]] for i in range(len(o) - 1)]
-    if form == 'xywha':
-        return rle.obb_to_numpy(edge, q, 'xywha')
-    corners = rle.obb_to_numpy(edge, q, 'corners')
-    return obb_to_geojson(corners, transform) if form == 'geojson' else _affine(corners, transform)
+        out = [v[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+    elif form == 'xywha':
+        out = rle.obb_to_numpy(edge, q, 'xywha')
+    else:
+        corners = rle.obb_to_numpy(edge, q, 'corners')
+        out = obb_to_geojson(corners, transform) if form == 'geojson' else _affine(corners, transform)
+    return [out[co[i]:co[i + 1]] for i in range(len(co) - 1)] if per_component else out
+
+
+def mask_components(masks, device='cuda:0'):
+    """Masks -> per instance dict(count, areas int32 [c], bboxes int32 [c, 4] = (x0, y0, x1, y1) end-exclusive) of its
+    8-connected components, ordered by their first pixel in column-major order; labelled on the device in the run domain
+    (rle.runs_components).  `masks` as in masks_to_polygons.  One transfer after the labelling's two reads."""
+    from . import rle
+    counts, n, size = _masks_to_runs(masks, device)
+    if not isinstance(masks, torch.Tensor):
+        _check_canonical(counts, n, size)
+    comps = rle.runs_components(counts, n, size)
+    k, C = int(n.shape[0]), int(comps.comp_area.shape[0])
+    buf = torch.cat([comps.comp_offs, comps.comp_area.to(torch.int64), comps.comp_box.reshape(-1).to(torch.int64)]).cpu().numpy()
+    o, area, box = buf[:k + 1].tolist(), buf[k + 1:k + 1 + C].astype(np.int32), buf[k + 1 + C:].astype(np.int32).reshape(-1, 4)
+    return [dict(count=o[i + 1] - o[i], areas=area[o[i]:o[i + 1]], bboxes=box[o[i]:o[i + 1]]) for i in range(k)]

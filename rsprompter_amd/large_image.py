@@ -146,13 +146,24 @@ def _runs_out(counts, n, scene_hw, polygons, obb_out=None):
     return rle.runs_to_strings(counts, n, scene_hw)
 
 
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None):
+def _clean_scene(counts, n, scene_hw, region):
+    """region = (min_mask_region_area, a list that receives changed bool [K]) or None: the scene run table with holes and
+    islands of fewer pixels than that removed (rle.clean_runs, mode 'both': DESIGN §14.10), before it takes any output form"""
+    if region is None:
+        return counts, n
+    counts, n, _, _, changed = rle.clean_runs(counts, n, scene_hw, region[0], 'both')
+    region[1].append((changed != 0).any(1))
+    return counts, n
+
+
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None, region=None):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
         if obb_out is not None:
             obb_out.append(np.zeros((0, 4, 2), np.float64))
         return []
     sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
+    sc, sn = _clean_scene(sc, sn, scene_hw, region)
     return _runs_out(sc, sn, scene_hw, polygons, obb_out)
 
 
@@ -281,7 +292,7 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
     return out, reps[keep_m], members, (flat, offs)
 
 
-def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None):
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None, region=None):
     """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
     (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
     flat, offs = groups
@@ -293,6 +304,7 @@ def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_
     sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
     members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
     uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
+    uc, un = _clean_scene(uc, un, scene_hw, region)
     return _runs_out(uc, un, scene_hw, polygons, obb_out)
 
 
@@ -345,7 +357,7 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 @torch.no_grad()
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
                           batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
-                          polygon_min_ring_area=0, oriented_boxes=False):
+                          polygon_min_ring_area=0, oriented_boxes=False, min_mask_region_area=0):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
@@ -354,7 +366,11 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     polygon_min_ring_area in pixels simplify the rings there first, DESIGN §14.8 -- apis.masks_to_polygons says how; they
     apply to masks='polygons' only).  oriented_boxes=True (masks='rle' or 'polygons'): pred_instances.obb is float64 numpy
     [K, 4, 2], the corners of the minimum-area rectangle around each instance's scene mask (clockwise on screen,
-    NaN for an empty mask), made on the device from the scene run table before any string is made.  return_patches=True: (sample, per-tile samples,
+    NaN for an empty mask), made on the device from the scene run table before any string is made.  min_mask_region_area > 0
+    (masks='rle' or 'polygons'): holes and islands of fewer pixels than that are removed from every scene mask
+    (segment-anything's remove_small_regions, 'both', in the run domain; with 'seam_mask' after the union), before strings,
+    rings and oriented boxes are made; bboxes, scores and labels stay the detector's, no mask is emptied, and
+    pred_instances.region_changed is bool [K].  return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -370,6 +386,12 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     if oriented_boxes and masks == 'dense':                             # refused before the first tile runs
         raise ValueError("oriented_boxes=True reads the scene run table: use masks='rle' or masks='polygons'")
     obb = [] if oriented_boxes else None
+    from .sam_prompts import _check_region_area
+    region_area = _check_region_area(min_mask_region_area)              # refused before the first tile runs
+    region = (region_area, []) if region_area else None
+    if region is not None and masks == 'dense':                         # refused before the first tile runs
+        raise ValueError("min_mask_region_area cleans the scene run table: use masks='rle' or masks='polygons' (dense masks "
+                         'are cleaned by apis.remove_small_regions)')
     if polygon_tolerance is not None or polygon_min_ring_area != 0:
         if not poly:
             raise ValueError("polygon_tolerance and polygon_min_ring_area apply to masks='polygons'")
@@ -448,7 +470,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             tm = torch.cat(dense_tiles, 0) if dense_tiles else torch.zeros((0, th, tw), dtype=torch.bool, device=dev)
             out.masks = _seam_dense(tm, origin, groups, (H, W))
         else:
-            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb)
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region)
     else:
         keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
@@ -458,9 +480,11 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
             kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
-            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb)
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region)
     if obb:
         out.obb = obb[0]
+    if region is not None:
+        out.region_changed = region[1][0] if region[1] else torch.zeros((len(out.scores),), dtype=torch.bool, device=dev)
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
@@ -549,6 +573,8 @@ def main(argv=None):
                     help='--mask-format polygons|geojson: drop rings of less than A pixels (a dropped hole is filled)')
     ap.add_argument('--oriented-boxes', action='store_true',
                     help='add "obb": the four corners of the minimum-area rectangle around each mask, made on the device')
+    ap.add_argument('--min-mask-region-area', type=int, default=0, metavar='A',
+                    help='remove holes and islands of less than A pixels from every scene mask, on the device')
     a = ap.parse_args(argv)
     if a.geo_transform is not None and a.mask_format != 'geojson':
         ap.error('--geo-transform applies to --mask-format geojson')
@@ -557,6 +583,8 @@ def main(argv=None):
     try:
         rle.polygon_tolerance_q8(0 if a.simplify_tolerance is None else a.simplify_tolerance)
         rle.polygon_min_ring_area(a.min_ring_area)
+        if a.min_mask_region_area < 0:
+            raise ValueError(f'--min-mask-region-area must be a non-negative integer, got {a.min_mask_region_area}')
     except ValueError as e:
         ap.error(str(e))
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
@@ -565,7 +593,8 @@ def main(argv=None):
         s = inference_large_image(model, path, a.patch_size, a.patch_overlap_ratio, a.merge_iou_thr, a.merge_nms_type,
                                   a.batch_size, masks='rle' if a.mask_format == 'rle' else 'polygons',
                                   seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
-                                  polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes)
+                                  polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes,
+                                  min_mask_region_area=a.min_mask_region_area)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

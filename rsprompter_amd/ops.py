@@ -1,6 +1,7 @@
 """Thin Python wrappers: torch tensors (device memory + stream plumbing only)
 -> C-ABI calls into librsp_hip.so.  No arithmetic happens in torch here.
 """
+import collections
 import ctypes
 import math
 import os
@@ -1993,6 +1994,141 @@ def hull_min_rect(hull_verts, hull_offs):
         _lib.check(lib.rsp_hull_min_rect(hull_verts.data_ptr(), hull_offs.data_ptr(), k, Vh, edge.data_ptr(), q.data_ptr(),
                                          _stream()), "rsp_hull_min_rect")
     return edge, q
+
+
+# ----------------------------------------------------------------------------- run-domain components (csrc/run_components.hip)
+RUN_COMPONENTS_MAX_PIECES = CONST['RSP_RUN_COMPONENTS_MAX_PIECES']      # column pieces of one call: 32-bit piece indices
+RunComponents = collections.namedtuple('RunComponents', 'comp_offs piece_comp comp_area comp_box comp_first comp_inst pieces '
+                                       'piece_offs status')
+
+
+def check_components_status(status):
+    """`status` of rle_components ON THE HOST: non-zero means that a find / union loop of the labelling reached its step cap
+    and the result is invalid"""
+    if any(int(s) != 0 for s in list(status)):
+        raise RuntimeError("rsp_run_components_label: the labelling reached its iteration cap (status != 0); the result is "
+                           "invalid")
+
+
+def rle_components(counts, n, H, W):
+    """run table (counts int32 [k, cap], n int32 [k]: k masks on one (H, W) canvas) -> the 8-connected components of every
+    mask, all on the device, as RunComponents:
+      comp_offs int64 [k + 1] (the components of each instance), piece_comp int32 [P], comp_area int32 [C], comp_box int32
+      [C, 4] = (x0, y0, x1, y1) end-exclusive, comp_first int32 [C] (the lowest row-major index y W + x of the component's
+      pixels), comp_inst int32 [C], pieces int32 [4, P] = (x, y0, y1, instance) of the column pieces sorted by (instance, x,
+      y0), piece_offs int64 [k + 1], status int32 [1].
+    Components are numbered by (instance, first pixel in stream order).  A row with n <= 0 has none.  Two device-to-host
+    reads, whatever k is: the pieces P, and the components C together with status (non-zero raises RuntimeError)."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('rle_components', counts, n, H, W)
+    dev = n.device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    status = torch.zeros((1,), **i32)
+
+    def empty(piece_offs):
+        return RunComponents(torch.zeros((k + 1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+                             torch.zeros((0, 4), **i32), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+                             torch.zeros((4, 0), **i32), piece_offs, status)
+    if k == 0:
+        return empty(torch.zeros((1,), **i64))
+    piece_cnt = torch.zeros((k,), **i32)
+    _lib.check(lib.rsp_mask_polygon_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_cnt.data_ptr(), _stream()),
+               "rsp_mask_polygon_pieces")
+    piece_offs = torch.cat([piece_cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(piece_cnt, 0, dtype=torch.int64)])
+    P = int(piece_offs[-1])                                                                         # read 1
+    if P == 0:
+        return empty(piece_offs)
+    if P > RUN_COMPONENTS_MAX_PIECES:
+        raise ValueError(f'rle_components: {P} column pieces in one call; at most {RUN_COMPONENTS_MAX_PIECES} (split the rows)')
+    pieces = torch.empty((4, P), **i32)
+    ws = torch.empty((int(lib.rsp_run_components_workspace_bytes(H, W, P)) // 4,), **i32)
+    label, root = torch.empty((P,), **i32), torch.empty((P,), **i32)
+    _lib.check(lib.rsp_run_components_label(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_offs.data_ptr(), P,
+                                            pieces.data_ptr(), ws.data_ptr(), label.data_ptr(), root.data_ptr(),
+                                            status.data_ptr(), _stream()), "rsp_run_components_label")
+    root_cum = torch.cumsum(root, 0, dtype=torch.int64)
+    C, bad = torch.stack([root_cum[-1], status[0].to(torch.int64)]).tolist()                         # read 2
+    check_components_status([bad])
+    piece_comp = torch.empty((P,), **i32)
+    comp_area, comp_box = torch.empty((C,), **i32), torch.empty((C, 4), **i32)
+    comp_first, comp_inst = torch.empty((C,), **i32), torch.empty((C,), **i32)
+    _lib.check(lib.rsp_run_components_stats(pieces.data_ptr(), P, H, W, label.data_ptr(), root.data_ptr(), root_cum.data_ptr(),
+                                            C, piece_comp.data_ptr(), comp_area.data_ptr(), comp_box.data_ptr(),
+                                            comp_first.data_ptr(), comp_inst.data_ptr(), _stream()), "rsp_run_components_stats")
+    comp_offs = torch.searchsorted(comp_inst, torch.arange(k + 1, **i32)).to(torch.int64).contiguous()
+    return RunComponents(comp_offs, piece_comp, comp_area, comp_box, comp_first, comp_inst, pieces, piece_offs, status)
+
+
+def components_select(comps, min_area, keep_largest, slot, changed):
+    """which components of rle_components stay (rsp_run_components_select): keep int32 [C] = 1 for a component of at least
+    min_area pixels; keep_largest: when an instance has none, its largest stays, among equals the one with the lowest
+    comp_first.  changed int32 [k, 2] (device): column `slot` receives 1 where an instance has a smaller component.  No host
+    read."""
+    lib = _lib.load()
+    k, C = int(comps.comp_offs.shape[0]) - 1, int(comps.comp_area.shape[0])
+    if int(min_area) != min_area or not 0 <= int(min_area) < 2 ** 31:
+        raise ValueError(f'components_select: min_area must be an integer in [0, 2^31), got {min_area!r}')
+    if changed.dtype != torch.int32 or tuple(changed.shape) != (k, 2) or not changed.is_contiguous():
+        raise ValueError('components_select: changed is a contiguous int32 [k, 2] tensor')
+    keep = torch.zeros((C,), dtype=torch.int32, device=changed.device)
+    if k:
+        _lib.check(lib.rsp_run_components_select(comps.comp_offs.data_ptr(), k, C, comps.comp_area.data_ptr(),
+                                                 comps.comp_first.data_ptr(), int(min_area), 1 if keep_largest else 0, int(slot),
+                                                 keep.data_ptr(), changed.data_ptr(), _stream()), "rsp_run_components_select")
+    return keep
+
+
+def components_union(comps, H, W, cap_out, keep=None):
+    """the pieces of rle_components as run tables through rsp_rle_union (its (group << 31 | pixel start, end) intervals are
+    index arithmetic on the pieces and one device key sort).  keep=None: one row per COMPONENT, C rows in component order (a
+    split); keep int32 [C]: one row per INSTANCE holding its components with keep != 0 (a filter; an instance without any is
+    the empty mask, one count H * W).  -> (counts int32 [G, cap_out], n int32 [G]), n = -(needed) for a row that does not fit
+    (the protocol of fit_runs).  No host read."""
+    lib = _lib.load()
+    H, W = int(H), int(W)
+    dev = comps.piece_comp.device
+    k, C, P = int(comps.comp_offs.shape[0]) - 1, int(comps.comp_area.shape[0]), int(comps.piece_comp.shape[0])
+    G = C if keep is None else k
+    if int(cap_out) < 2:
+        raise ValueError('components_union: cap_out is at least 2')
+    out = torch.empty((max(G, 1), int(cap_out)), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((max(G, 1),), dtype=torch.int32, device=dev)
+    if G == 0:
+        return out[:0], n_out[:0]
+    if P and C:
+        pc = comps.piece_comp.to(torch.int64)
+        x, y0, y1, inst = (comps.pieces[i].to(torch.int64) for i in range(4))
+        live = pc >= 0
+        if keep is None:
+            group = torch.where(live, pc, G)                           # a slot no row filled sorts behind every group
+        else:
+            group = torch.where(live & (keep.to(torch.int64)[pc.clamp(min=0)] != 0), inst, G)
+        keys, order = torch.sort((group << 31) | ((x * H + y0) & 0x7fffffff))
+        ends = (x * H + y1).to(torch.int32)[order].contiguous()
+        iv_offs = torch.searchsorted(keys, torch.arange(G + 1, dtype=torch.int64, device=dev) << 31).contiguous()
+        total = P
+    else:
+        keys, ends = torch.zeros((1,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+        iv_offs, total = torch.zeros((G + 1,), dtype=torch.int64, device=dev), 0
+    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), total, iv_offs.data_ptr(), G, H, W, out.data_ptr(),
+                                 n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_union")
+    return out, n_out
+
+
+def rle_complement(counts, n):
+    """the complement of every row of a canonical run table: the same counts with a leading zero count added, or removed
+    where the row has one, so n changes by one -> (counts int32 [k, cap + 1], n int32 [k]).  A row with n <= 0 stays empty
+    (n = 0); n beyond cap is cut at cap.  Index arithmetic on the device, no host read."""
+    k, cap = int(counts.shape[0]), int(counts.shape[1])
+    nn = n.clamp(0, cap)
+    lead0 = counts[:, 0] == 0
+    added = torch.zeros((k, cap + 1), dtype=torch.int32, device=counts.device)
+    added[:, 1:] = counts
+    removed = torch.zeros((k, cap + 1), dtype=torch.int32, device=counts.device)
+    removed[:, :cap - 1] = counts[:, 1:]
+    out = torch.where(lead0[:, None], removed, added)
+    n2 = torch.where(nn <= 0, torch.zeros_like(nn), torch.where(lead0, nn - 1, nn + 1))
+    return out.contiguous(), n2.to(torch.int32).contiguous()
 
 
 # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling

@@ -215,6 +215,62 @@ def obb_to_numpy(edge, q, form='corners'):
     return out
 
 
+def runs_components(counts, n, size):
+    """run table of k masks on one size = (H, W) canvas -> ops.RunComponents on the device: the 8-connected components of
+    every mask (comp_offs, piece_comp, comp_area, comp_box, comp_first, comp_inst, pieces, piece_offs, status; DESIGN §14.10,
+    ops.rle_components).  Two device-to-host reads, whatever k is."""
+    return ops.rle_components(counts, n, size[0], size[1])
+
+
+def split_runs(counts, n, size, comps=None, cap=None):
+    """run table -> (counts, n, n on the host, cap, comp_offs int64 [k + 1]): a run table with ONE ROW PER COMPONENT, C rows
+    in component order (instance, then first pixel in stream order); rows comp_offs[i] .. comp_offs[i + 1] are the components
+    of instance i.  A row holding one component comes back bit for bit.  comps: what runs_components returned for the table;
+    cap: the first capacity (the input's plus two when None); the retry is ops.fit_runs'."""
+    if comps is None:
+        comps = runs_components(counts, n, size)
+    if cap is None:
+        cap = int(counts.shape[1]) + 2
+    out = ops.fit_runs(lambda cap: ops.components_union(comps, size[0], size[1], cap), max(int(cap), 2))
+    return out + (comps.comp_offs,)
+
+
+def clean_runs(counts, n, size, min_area, mode='both', cap=None):
+    """segment-anything's `remove_small_regions` in the run domain, with the semantics of ops.remove_small_regions (DESIGN §15
+    "Small regions"): mode 'holes' (the 8-connected components of the complement with fewer than min_area pixels are set;
+    the outer background is a component like any other), 'islands' (components of the mask that small are cleared; if all
+    are, the largest stays, among equals the one with the lowest row-major first pixel) or 'both' (holes, then islands of the
+    filled mask) -> (counts, n, n on the host, cap, changed int32 [k, 2] = a small hole / a small island existed).  A row
+    with n <= 0 comes back as n = 0.  min_area = 0 returns the input table itself, without a launch.  Every pass labels the
+    pieces (runs_components), selects components (ops.components_select) and writes the rows again through rsp_rle_union
+    under ops.fit_runs; the complement of a row is the same counts with a leading zero added or removed."""
+    if mode not in ops.MASK_REGION_MODES:
+        raise ValueError(f'clean_runs: mode must be one of {sorted(ops.MASK_REGION_MODES)}, got {mode!r}')
+    if isinstance(min_area, bool) or int(min_area) != min_area or not 0 <= int(min_area) < 2 ** 31:
+        raise ValueError(f'clean_runs: min_area must be an integer in [0, 2^31), got {min_area!r}')
+    k = int(n.shape[0])
+    changed = torch.zeros((k, 2), dtype=torch.int32, device=n.device)
+    if int(min_area) == 0 or k == 0:
+        return counts, n, n.cpu(), int(counts.shape[1]), changed
+    H, W = int(size[0]), int(size[1])
+    live = n > 0
+    cap = max(int(cap), 2) if cap is not None else int(counts.shape[1]) + 2
+    bits = ops.MASK_REGION_MODES[mode]
+
+    def filtered(c, m, keep_largest, slot, cap):
+        comps = runs_components(c, m, (H, W))
+        keep = ops.components_select(comps, int(min_area), keep_largest, slot, changed)
+        return ops.fit_runs(lambda cap: ops.components_union(comps, H, W, cap, keep), cap)
+    if bits & 1:                                   # the complement's small components go: what is left is the new background
+        c, m, _, cap = filtered(*ops.rle_complement(counts, n), False, 0, cap)
+        counts, n = ops.rle_complement(c, m)
+    if bits & 2:
+        counts, n, _, cap = filtered(counts, n, True, 1, cap)
+    n = torch.where(live, n, torch.zeros_like(n))
+    changed *= live[:, None].to(torch.int32)
+    return counts, n, n.cpu(), int(counts.shape[1]), changed
+
+
 def runs_to_dicts(counts, n_host, size):
     """run table -> list of dict(size=[H, W], counts=list), the uncompressed form (HF `_mask_to_rle`).  n_host: the row
     lengths on the host (what fit_runs returned); one transfer, the table."""
