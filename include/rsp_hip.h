@@ -39,7 +39,7 @@ typedef void* rsp_stream_t;
 /* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
 /* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
 /* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
-/* Still 5 with rsp_run_components_* (as with the polygon, simplification and oriented-box entry points before them): an  */
+/* Still 5 with rsp_poly_raster_* (as with the polygon, simplification, oriented-box and component entry points): an      */
 /* addition that leaves every earlier entry point, structure and macro as it was does not change the number.              */
 /* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
 /* 3: RspBoxCoder in RspRpnDesc / rsp_bbox_post; 2: RspGemmDesc gained c_ncols / pl_col0, plane format words decode       */
@@ -840,6 +840,40 @@ int rsp_run_components_stats(const int32_t* pieces, int64_t P, int32_t H, int32_
 int rsp_run_components_select(const int64_t* comp_offs, int32_t k, int64_t C, const int32_t* comp_area, const int32_t* comp_first,
                               int32_t min_area, int32_t keep_largest, int32_t slot, int32_t* keep, int32_t* changed,
                               rsp_stream_t stream);
+
+/* Polygon rasterisation (csrc/poly_raster.hip): rings of float64 vertices -> run tables; replaces cocoapi's    */
+/* maskApi.c rleFrPoly (one polygon at 5x resolution, its sort and its sequential run loop) per part, and with the caller's     */
+/* grouping rleMerge / COCO.annToRLE (rsprompter_amd/rle.py polygons_to_runs).  The result is rleFrPoly's, count for count.     */
+/* verts double [V, 2] = (x, y), any finite values; ring_offs int64 [R + 1] ascending from 0 to V (a ring without vertices      */
+/* contributes nothing; rings of one and two vertices follow rleFrPoly); ring_group int32 [R], non-decreasing, in [0, G);        */
+/* group_hw int32 [G, 2] = (h, w) of EACH group's canvas.  All rings of a group are rasterised onto one canvas with the         */
+/* even-odd rule (a group of one ring is rleFrPoly of it).  The three calls are one pipeline; the caller reads three numbers     */
+/* after the first and sorts the keys after the second.  No call reads the host, none uses atomics.                              */
+/* Limits, refused with RSP_EINVAL: a group canvas with h < 1, w < 1 or h * w >= 2^31; a scaled coordinate (int)(5 x + .5)      */
+/* beyond +-RSP_POLY_RASTER_MAX_COORD; more than RSP_POLY_RASTER_MAX_POINTS walk points; more than                               */
+/* RSP_POLY_RASTER_MAX_GROUPS groups.                                                                                            */
+/* 1. Writes scaled int32 [V, 2] (a value out of range is pinned to +-(RSP_POLY_RASTER_MAX_COORD + 2)), edge_pts int64 [V] =     */
+/* max(|dx|, |dy|) + 1 walk points of the edge from vertex j to the next vertex of its ring (the last one to the first), and     */
+/* group_px int64 [G] = h * w, 2^31 for a canvas that is refused.                                                                */
+#define RSP_POLY_RASTER_MAX_COORD (1 << 24)
+#define RSP_POLY_RASTER_MAX_POINTS 0x7fffffffLL
+#define RSP_POLY_RASTER_MAX_GROUPS 0xffffff
+#define RSP_POLY_RASTER_NO_KEY 0x7fffffffffffffffLL
+int rsp_poly_raster_edges(const double* verts, const int64_t* ring_offs, const int32_t* group_hw, int64_t R, int64_t V,
+                          int32_t G, int32_t* scaled, int64_t* edge_pts, int64_t* group_px, rsp_stream_t stream);
+/* 2. edge_offs int64 [V + 1] = exclusive sum of edge_pts, T = edge_offs[V]; coord_max = the largest |scaled| and pixels_max =   */
+/* the largest group_px, as the caller read them (they are what this call and the next refuse on).  One lane per walk point:     */
+/* keys int64 [T] = group << 32 | xd * h + yd for a point that crosses a pixel column inside the canvas by rleFrPoly's rule,     */
+/* RSP_POLY_RASTER_NO_KEY otherwise.                                                                                            */
+int rsp_poly_raster_crossings(const int32_t* scaled, const int64_t* ring_offs, const int32_t* ring_group, const int32_t* group_hw,
+                              const int64_t* edge_offs, int64_t R, int64_t V, int32_t G, int64_t T, int64_t coord_max,
+                              int64_t pixels_max, int64_t* keys, rsp_stream_t stream);
+/* 3. keys int64 [K] sorted ascending; key_offs int64 [G + 1] = the keys of group g (clamped into [0, K]).  counts_out            */
+/* [G, cap_out] / n_out [G]: rleFrPoly's counts, conventions of rsp_rle_shift: canonical (only count 0 may be zero, the counts    */
+/* sum to h * w), n_out = -(needed) when cap_out is too small (the row is then undefined); a group without keys is one count     */
+/* h * w.  A position below h * w is a run boundary iff it occurs an odd number of times; h * w always is one.                    */
+int rsp_poly_raster_runs(const int64_t* keys, int64_t K, const int64_t* key_offs, const int32_t* group_hw, int32_t G,
+                         int64_t pixels_max, uint32_t* counts_out, int32_t* n_out, int32_t cap_out, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Promptable SAM (HF SamModel with point / box / mask prompts, mask generation) */

@@ -369,8 +369,114 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tole
     return format_polygons(rle.polygons_to_lists(*polys), form, transform)
 
 
+# --------------------------------------------------------------------------------------- polygon rasterisation
+MASK_FORMS = ('rle', 'runs', 'dense')
+
+
+def invert_transform(transform):
+    """the inverse of rings_to_geojson's forward transform (a, b, c, d, e, f): a function float64 [m, 2] world -> pixel corners,
+    x = (f (X - a) - c (Y - d)) / det, y = (b (Y - d) - e (X - a)) / det with det = b f - c e, in float64 on the host (exact
+    for power-of-two scales without rotation); a singular transform raises"""
+    a, b, c, d, e, f = (float(t) for t in transform)
+    det = b * f - c * e
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError(f'transform {tuple(transform)!r} is singular (b f - c e = {det}): it cannot be inverted')
+
+    def back(xy):
+        X, Y = xy[:, 0] - a, xy[:, 1] - d
+        return np.stack([(f * X - c * Y) / det, (b * Y - e * X) / det], 1)
+    return back
+
+
+def _instance_rings(inst):
+    """one instance of polygons_to_masks -> (list of float64 [m, 2] rings, the default fill of its form)"""
+    def ring(p):
+        return np.asarray(p, np.float64).reshape(-1, 2)
+    if isinstance(inst, dict):
+        if 'polygons' in inst:                                          # masks_to_polygons(form='coco')
+            return _instance_rings(list(inst['polygons']))
+        kind = inst.get('type')
+        if kind not in ('Polygon', 'MultiPolygon'):
+            raise ValueError(f"polygons_to_masks: a dict is the dict(polygons=...) of form='coco' or a GeoJSON Polygon / "
+                             f'MultiPolygon geometry, got type {kind!r}')
+        polys = [inst['coordinates']] if kind == 'Polygon' else list(inst['coordinates'])
+        rings = []
+        for poly in polys:
+            for r in poly:                                              # outer ring and holes alike: the fill rule tells them apart
+                r = ring(r)
+                if len(r) > 1 and (r[0] == r[-1]).all():                # GeoJSON closes a ring by repeating its first vertex
+                    r = r[:-1]
+                rings.append(r)
+        return rings, 'evenodd'
+    inst = list(inst)
+    if inst and isinstance(inst[0], (tuple, list)) and len(inst[0]) == 3 and np.ndim(inst[0][0]) == 2:
+        return [ring(r[0]) for r in inst], 'evenodd'                    # masks_to_polygons(form='rings')
+    if inst and not isinstance(inst[0], (list, tuple, np.ndarray)):
+        inst = [inst]                                                   # one flat COCO polygon
+    from .datasets import bbox_polygon
+    return [ring(bbox_polygon(p) if len(p) == 4 else list(p)[:2 * (len(p) // 2)]) for p in inst], 'union'
+
+
+def polygons_to_masks(polygons, size, form='rle', fill=None, transform=None, device='cuda:0'):
+    """Vector instances -> masks on one size = (H, W) canvas, rasterised on the device exactly as cocoapi's rleFrPoly does it
+    (DESIGN §14.11); the reverse of masks_to_polygons.  polygons: one entry per instance, each
+      a COCO polygon list [[x0, y0, x1, y1, ...], ...] or one flat list; a 4-number entry is an xywh box, as in ann_to_rle;
+      the dict(polygons=...) of masks_to_polygons(form='coco');
+      the [(ring [m, 2], parent, area2), ...] list of form='rings';
+      a GeoJSON Polygon / MultiPolygon geometry dict (the closing vertex of every ring is dropped).
+    fill='union': every ring on its own, then their union (pycocotools' annToRLE; bit-equal to datasets.ann_to_rle);
+      'evenodd': the rings of an instance together, holes subtract (the exact inverse of masks_to_polygons).  None: 'union'
+      for COCO lists, 'evenodd' for rings and GeoJSON; instances of both kinds in one call need an explicit fill.
+    transform = (a, b, c, d, e, f): the FORWARD transform of rings_to_geojson, X = a + b x + c y, Y = d + e x + f y; the
+      coordinates are taken back to pixels with its inverse, in float64 on the host.
+    form='rle': list of dict(size=[H, W], counts=bytes), what every run-domain API here takes; 'runs': (counts int32
+      [k, cap], n int32 [k]) on the device; 'dense': bool [k, H, W] on the device (refused above
+      large_image.DENSE_MASK_LIMIT_BYTES)."""
+    from . import rle
+    if form not in MASK_FORMS:
+        raise ValueError(f'mask form {form!r}: one of {MASK_FORMS}')
+    if fill is not None and fill not in rle.POLYGON_FILLS:
+        raise ValueError(f'polygon fill {fill!r}: one of {rle.POLYGON_FILLS}')
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f'polygons_to_masks: a {H} x {W} canvas: both sides at least 1 and fewer than 2^31 pixels')
+    back = invert_transform(transform) if transform is not None else None
+    per = [_instance_rings(p) for p in polygons]
+    k = len(per)
+    if form == 'dense':
+        from .large_image import _check_dense
+        _check_dense(k, H, W)
+    if fill is None:
+        kinds = {d for rings, d in per if rings}
+        if len(kinds) > 1:
+            raise ValueError("polygons_to_masks: COCO lists (fill 'union') and rings / GeoJSON (fill 'evenodd') in one call: "
+                             'pass fill=')
+        fill = kinds.pop() if kinds else 'union'
+    rings = [r if back is None else back(r) for rs, _ in per for r in rs]
+    dev = torch.device(device)
+    ops.require_device(dev)
+    offs = np.cumsum([0] + [len(r) for r in rings]).astype(np.int64)
+    verts = np.concatenate(rings + [np.zeros((0, 2))]).reshape(-1, 2)
+    if not np.isfinite(verts).all():
+        raise ValueError('polygons_to_masks: a coordinate is NaN or infinite')
+    group = np.repeat(np.arange(k, dtype=np.int32), [len(rs) for rs, _ in per])
+    counts, n = rle.polygons_to_runs(torch.from_numpy(verts).to(dev), torch.from_numpy(offs).to(dev),
+                                     torch.from_numpy(group).to(dev),
+                                     torch.tensor([[H, W]] * k, dtype=torch.int32, device=dev).view(k, 2), fill=fill)
+    if form == 'runs':
+        return counts, n
+    if form == 'rle':
+        return rle.runs_to_strings(counts.contiguous(), n, (H, W))
+    nw = (H * W + 63) // 64
+    bits = ops.rle_to_bits(counts.contiguous(), n, torch.arange(k + 1, dtype=torch.int64, device=dev) * nw)[0]
+    # pixel j of the column-major stream is bit j & 7 of byte j >> 3 (little-endian words): one byte per pixel,
+    # then [W, H] -> [H, W]
+    px = (bits[:k * nw].view(torch.uint8).view(k, nw * 8, 1) >> torch.arange(8, dtype=torch.uint8, device=dev)) & 1
+    return px.view(k, nw * 64)[:, :H * W].reshape(k, W, H).transpose(1, 2).to(torch.bool).contiguous()
+
+
 # ------------------------------------------------------------------------------------------- oriented boxes (DESIGN §14.9)
-OBB_FORMS = ('corners', 'xywha', 'hull', 'geojson')
+OBB_FORMS =('corners', 'xywha', 'hull', 'geojson')
 
 
 def _affine(xy, transform):

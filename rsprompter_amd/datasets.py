@@ -11,7 +11,8 @@ image's ground truth -- it travels NEXT TO the pipeline output, the pipeline its
     masks         n COCO RLE dicts at ori_shape, dict(size=[h, w], counts=bytes) (compressed)
 
 Polygons become RLE the way cocoapi does it (maskApi.c rleFrPoly: upsample x5, walk the edges, keep the y-boundary
-crossings, downsample; then rleMerge of the parts).  This is host code: it runs once per dataset.
+crossings, downsample; then rleMerge of the parts).  This is host code: it runs once per dataset.  `anns_to_rle` is its
+batched twin on the device (csrc/poly_raster.hip): many annotations in one call, the same strings.
 """
 import json
 import math
@@ -163,6 +164,59 @@ def ann_to_rle(segm, h, w):
         return dict(size=list(segm['size']), counts=counts_to_string(segm['counts']))
     c = segm['counts']
     return dict(size=list(segm['size']), counts=c.encode() if isinstance(c, str) else bytes(c))
+
+
+def bbox_polygon(bb):
+    """maskApi.c rleFrBbox's polygon of an xywh box: [xs, ys, xs, ye, xe, ye, xe, ys]"""
+    xs, ys = bb[0], bb[1]
+    xe, ye = xs + bb[2], ys + bb[3]
+    return [xs, ys, xs, ye, xe, ye, xe, ys]
+
+
+def anns_to_rle(segms, sizes, device='cuda:0'):
+    """ann_to_rle of MANY segmentations in one device call: segms[i] is what ann_to_rle takes (a COCO polygon
+    list, nested or flat, a 4-number part being an xywh box; or an RLE dict, which passes through as it does there), sizes[i]
+    = (h, w) of its image (one pair serves all) -> list of dict(size=[h, w], counts=bytes), equal to
+    [ann_to_rle(s, h, w) for ...].  Every polygon part is rasterised by csrc/poly_raster.hip, the parts of an annotation are
+    unioned in the run domain (rle.polygons_to_runs, fill='union') and the strings are written by rsp_rle_to_string."""
+    import torch
+    from . import ops, rle
+    segms = list(segms)
+    if len(sizes) == 2 and not isinstance(sizes[0], (list, tuple, np.ndarray)):
+        sizes = [sizes] * len(segms)
+    if len(sizes) != len(segms):
+        raise ValueError(f'anns_to_rle: {len(segms)} segmentations but {len(sizes)} sizes')
+    out = [None] * len(segms)
+    rows, rings, ring_group, hw = [], [], [], []
+    for i, segm in enumerate(segms):
+        h, w = int(sizes[i][0]), int(sizes[i][1])
+        if not isinstance(segm, list):
+            out[i] = ann_to_rle(segm, h, w)
+            continue
+        if len(segm) and not isinstance(segm[0], (list, tuple, np.ndarray)):
+            segm = [segm]
+        if not segm:                                         # rleMerge of no parts: no counts at all
+            out[i] = dict(size=[h, w], counts=b'')
+            continue
+        for p in segm:
+            p = bbox_polygon(p) if len(p) == 4 else p
+            rings.append(np.asarray(p[:2 * (len(p) // 2)], dtype=np.float64).reshape(-1, 2))
+            ring_group.append(len(rows))
+        rows.append(i)
+        hw.append((h, w))
+    if rows:
+        dev = torch.device(device)
+        ops.require_device(dev)
+        offs = np.cumsum([0] + [len(r) for r in rings]).astype(np.int64)
+        counts, n = rle.polygons_to_runs(torch.from_numpy(np.concatenate(rings).reshape(-1, 2)).to(dev),
+                                         torch.from_numpy(offs).to(dev),
+                                         torch.tensor(ring_group, dtype=torch.int32, device=dev),
+                                         torch.tensor(hw, dtype=torch.int32, device=dev), fill='union')
+        flat, soffs = rle._string_bytes(counts.contiguous(), n, 2 * len(rows) * int(counts.shape[1]) + 16)
+        buf, o = flat.numpy().tobytes(), soffs.tolist()
+        for j, i in enumerate(rows):
+            out[i] = dict(size=[hw[j][0], hw[j][1]], counts=buf[o[j]:o[j + 1]])
+    return out
 
 
 def gt_mask_rle(mask_ann, h, w):

@@ -47,10 +47,11 @@ def _samples_for_metric(ds, order, preds):
 
 @torch.no_grad()
 def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_ann_file=None, device=None,
-             verbose=True):
+             verbose=True, gt_raster=None):
     """Run the test set of `cfg` through `model` on this rank's shard; on rank 0 return the metrics dict (mmdet's keys),
     elsewhere None.  `metric_ann_file` sets CocoMetric's ann_file (the ground-truth JSON path of the reference's metric);
-    by default the metric converts the dataset's ground truth as every RSPrompter config does."""
+    by default the metric converts the dataset's ground truth as every RSPrompter config does.  `gt_raster` ('host' /
+    'device') overrides who rasterises the metric's ground-truth polygons (CocoMetric's gt_raster; None: the config's)."""
     import torch.distributed as dist
     ds = build_test_dataset(cfg, data_root, ann_file)
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -83,6 +84,8 @@ def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_
         ev_cfg['ann_file'] = metric_ann_file
     if out_prefix is not None and ev_cfg.get('outfile_prefix') is None:
         ev_cfg['outfile_prefix'] = out_prefix
+    if gt_raster is not None:
+        ev_cfg['gt_raster'] = gt_raster
     metric = METRICS.build(ev_cfg)
     metric.dataset_meta = ds.dataset_meta
     metric.device = str(dev)
@@ -122,13 +125,15 @@ def main(argv=None):
     ap.add_argument('--ann-file', default=None, help='overrides test_dataloader.dataset.ann_file')
     ap.add_argument('--cfg-options', nargs='+', default=None, help='key=value overrides of the config')
     ap.add_argument('--out-prefix', default=None, help='writes <P>.bbox.json, <P>.segm.json and <P>.metrics.json')
+    ap.add_argument('--gt-raster', choices=('host', 'device'), default=None,
+                    help="who rasterises the metric's ground-truth polygons: the host loop (default) or the device")
     args = ap.parse_args(argv)
     rank, local, world = rdist.init_from_env()
     cfg = Config.fromfile(args.config)
     if args.cfg_options:
         cfg.merge_from_dict(_parse_cfg_options(args.cfg_options))
     model = init_detector(cfg, args.checkpoint, device=f'cuda:{local}')
-    res = evaluate(model, cfg, args.data_root, args.ann_file, args.out_prefix, verbose=rank == 0)
+    res = evaluate(model, cfg, args.data_root, args.ann_file, args.out_prefix, verbose=rank == 0, gt_raster=args.gt_raster)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

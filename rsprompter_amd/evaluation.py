@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .datasets import ann_to_rle
+from .datasets import ann_to_rle, anns_to_rle
 from .registry import Registry
 
 METRICS = Registry('metric')
@@ -258,6 +258,9 @@ def load_res(gt, results, iou_type):
     return out
 
 
+GT_RASTERS = ('host', 'device')
+
+
 @METRICS.register_module()
 class CocoMetric:
     """mmdet CocoMetric (bbox / segm) -- `process`, `compute_metrics`, `evaluate(size)`, `dataset_meta`."""
@@ -265,7 +268,7 @@ class CocoMetric:
 
     def __init__(self, ann_file=None, metric='bbox', classwise=False, proposal_nums=(100, 300, 1000), iou_thrs=None,
                  metric_items=None, format_only=False, outfile_prefix=None, file_client_args=None, backend_args=None,
-                 collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None):
+                 collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None, gt_raster='host'):
         self.metrics = metric if isinstance(metric, list) else [metric]
         for m in self.metrics:
             if m in ('proposal', 'proposal_fast'):
@@ -289,6 +292,9 @@ class CocoMetric:
         self.outfile_prefix = outfile_prefix
         self.prefix = prefix or self.default_prefix
         self.device = device
+        if gt_raster not in GT_RASTERS:
+            raise ValueError(f'CocoMetric: gt_raster {gt_raster!r}: one of {GT_RASTERS}')
+        self.gt_raster = gt_raster                          # who rasterises ground-truth polygons
         self._coco_api = None
         if ann_file is not None:
             with open(ann_file) as f:
@@ -405,10 +411,20 @@ class CocoMetric:
         return dict(bbox=bbox_json, segm=segm_json) if segm_json else dict(bbox=bbox_json), files
 
     # ------------------------------------------------------------------ metrics
-    def _gt_with_rles(self, coco):
-        """annToRLE of every gt segmentation (polygons rasterised + merged, uncompressed RLE compressed)."""
+    def _gt_with_rles(self, coco, device=None):
+        """annToRLE of every gt segmentation (polygons rasterised + merged, uncompressed RLE compressed).  gt_raster='host'
+        walks every polygon in Python (datasets.ann_to_rle); 'device' rasterises all of them in one call on `device`
+        (datasets.anns_to_rle, csrc/poly_raster.hip) and gives the same strings."""
         hw = {im['id']: (im['height'], im['width']) for im in coco['images']}
         anns = []
+        if self.gt_raster == 'device':
+            anns = [dict(a) for a in coco['annotations']]
+            todo = [a for a in anns if a['image_id'] in hw and 'segmentation' in a and a['segmentation'] is not None]
+            rles = anns_to_rle([a['segmentation'] for a in todo], [hw[a['image_id']] for a in todo],
+                               device if device is not None else (self.device or 'cuda:0'))
+            for a, r in zip(todo, rles):
+                a['segmentation'] = r
+            return dict(coco, annotations=anns)
         for a in coco['annotations']:
             a = dict(a)
             if a['image_id'] in hw and 'segmentation' in a and a['segmentation'] is not None:
@@ -444,7 +460,7 @@ class CocoMetric:
             if metric == 'segm':
                 preds_m = [{k: v for k, v in x.items() if k != 'bbox'} for x in preds_m]
                 if gt_rle is None:
-                    gt_rle = self._gt_with_rles(coco)
+                    gt_rle = self._gt_with_rles(coco, device)
                 gt_m = gt_rle
             else:
                 gt_m = coco

@@ -543,8 +543,53 @@ def pred2geojson(sample, score_thr=0.0, transform=None):
     return dict(type='FeatureCollection', features=feats)
 
 
+def geojson2dict(collection, size, transform=None, device='cuda:0'):
+    """the reverse of pred2geojson: a GeoJSON FeatureCollection (or a list of features / geometries) of Polygon / MultiPolygon
+    geometries -> the pred2dict form with the masks as COCO RLE on a size = (H, W) canvas, rasterised on the device with the
+    even-odd rule (apis.polygons_to_masks); `transform` is the forward transform the layer was written with.
+    labels / scores / bboxes come from the features' properties where every feature has them."""
+    from .apis import polygons_to_masks
+    feats = collection['features'] if isinstance(collection, dict) and 'features' in collection else list(collection)
+    geoms = [f['geometry'] if isinstance(f, dict) and f.get('type') == 'Feature' else f for f in feats]
+    rles = polygons_to_masks(geoms, size, form='rle', fill='evenodd', transform=transform, device=device) if geoms else []
+    out = {}
+    props = [f.get('properties') or {} if isinstance(f, dict) and f.get('type') == 'Feature' else {} for f in feats]
+    for key, name in (('labels', 'label'), ('scores', 'score'), ('bboxes', 'bbox')):
+        if all(name in p for p in props):
+            out[key] = [p[name] for p in props]
+    out['masks'] = [dict(size=r['size'], counts=r['counts'].decode()) for r in rles]
+    return out
+
+
+def _main_from_geojson(argv):
+    import argparse
+    ap = argparse.ArgumentParser(description='Rasterise a GeoJSON vector layer to COCO RLE masks on the device '
+                                 '(the reverse of --mask-format geojson)')
+    ap.add_argument('--from-geojson', required=True, metavar='FILE', help='a FeatureCollection of Polygon / MultiPolygon features')
+    ap.add_argument('--size', type=int, nargs=2, required=True, metavar=('H', 'W'), help='the canvas of the masks in pixels')
+    ap.add_argument('--geo-transform', type=float, nargs=6, default=None, metavar=('A', 'B', 'C', 'D', 'E', 'F'),
+                    help='the forward transform the layer was written with: pixel corner (x, y) -> (A + B x + C y, D + E x + F y)')
+    ap.add_argument('--out-dir', default='./output', help='<name>.json is written here')
+    ap.add_argument('--device', default='cuda:0')
+    a = ap.parse_args(argv)
+    with open(a.from_geojson) as f:
+        layer = json.load(f)
+    try:
+        out = geojson2dict(layer, a.size, a.geo_transform, a.device)
+    except ValueError as e:
+        ap.error(str(e))
+    os.makedirs(a.out_dir, exist_ok=True)
+    dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.from_geojson))[0] + '.json')
+    with open(dst, 'w') as f:
+        json.dump(out, f)
+    print(f'{a.from_geojson}: {len(out["masks"])} instances -> {dst}')
+
+
 def main(argv=None):
     import argparse
+    import sys
+    if any(str(t).split('=')[0] == '--from-geojson' for t in (sys.argv[1:] if argv is None else argv)):
+        return _main_from_geojson(argv)                                # no model: --from-geojson FILE --size H W [--geo-transform ...]
     from .apis import DetInferencer, init_detector
     ap = argparse.ArgumentParser(description='Sliced inference on large images (demo/large_image_demo.py without drawing)')
     ap.add_argument('img', help='Image path or a directory of images')

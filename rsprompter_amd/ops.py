@@ -2131,6 +2131,92 @@ def rle_complement(counts, n):
     return out.contiguous(), n2.to(torch.int32).contiguous()
 
 
+# ----------------------------------------------------------------------------- polygon rasterisation (csrc/poly_raster.hip)
+POLY_RASTER_MAX_COORD = CONST['RSP_POLY_RASTER_MAX_COORD']        # |(int)(5 x + .5)| of every coordinate
+POLY_RASTER_MAX_POINTS = CONST['RSP_POLY_RASTER_MAX_POINTS']      # walk points of one call
+POLY_RASTER_MAX_GROUPS = CONST['RSP_POLY_RASTER_MAX_GROUPS']      # rows of one call: one block each
+
+
+def poly_raster_launcher(verts, ring_offs, ring_group, group_hw, compact=True):
+    """The stages of DESIGN §14.11 up to the sorted crossing keys -> the `launch(cap)` of fit_runs for rsp_poly_raster_runs.
+    verts float64 [V, 2] = (x, y), ring_offs int64 [R + 1], ring_group int32 [R] (non-decreasing), group_hw int32 [G, 2] =
+    (h, w) per group, all on one device.  Three device-to-host reads (are the coordinates finite; then walk points, largest
+    scaled coordinate, largest canvas and the layout flags in one; then the number of crossings, inside the compaction that
+    drops the slots of walk points without one in front of the sort -- compact=False sorts them along, as the last keys, and
+    saves the read: tools/bench_poly_raster.py measures both); `launch` itself reads nothing.  Refuses NaN / inf (ValueError,
+    before any launch) and what the C entries refuse (ValueError with the limit named)."""
+    lib = _lib.load()
+    dev = verts.device
+    if verts.dtype != torch.float64 or verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError('poly_raster: verts must be float64 [V, 2] = (x, y)')
+    if ring_offs.dtype != torch.int64 or ring_offs.dim() != 1 or ring_offs.shape[0] < 1 or ring_group.dtype != torch.int32 \
+            or ring_group.dim() != 1 or ring_group.shape[0] != ring_offs.shape[0] - 1:
+        raise ValueError('poly_raster: ring_offs must be int64 [R + 1] and ring_group int32 [R]')
+    if group_hw.dtype != torch.int32 or group_hw.dim() != 2 or group_hw.shape[1] != 2:
+        raise ValueError('poly_raster: group_hw must be int32 [G, 2] = (h, w) per group')
+    if not (ring_offs.device == ring_group.device == group_hw.device == dev):
+        raise ValueError('poly_raster: verts, ring_offs, ring_group and group_hw must be on one device')
+    V, R, G = int(verts.shape[0]), int(ring_group.shape[0]), int(group_hw.shape[0])
+    if G > POLY_RASTER_MAX_GROUPS:
+        raise ValueError(f'poly_raster: {G} groups in one call; at most {POLY_RASTER_MAX_GROUPS} (split the call)')
+    verts, ring_offs, ring_group, group_hw = (t.contiguous() for t in (verts, ring_offs, ring_group, group_hw))
+    i64 = dict(dtype=torch.int64, device=dev)
+    if V and not bool(torch.isfinite(verts).all()):
+        raise ValueError('poly_raster: a polygon coordinate is NaN or infinite')
+    if V and not R:
+        raise ValueError('poly_raster: vertices without a ring')
+    # the layout is checked on the device and read with the sizes below; the kernels clamp whatever the arrays hold
+    bad_offs = (ring_offs[0] != 0) | (ring_offs[-1] != V) | (ring_offs[1:] < ring_offs[:-1]).any()
+    bad_group = ((ring_group[1:] < ring_group[:-1]).any() | (ring_group[0] < 0) | (ring_group[-1] >= G)) if R else bad_offs & False
+    scaled = torch.zeros((max(V, 1), 2), dtype=torch.int32, device=dev)
+    edge_pts = torch.zeros((max(V, 1),), **i64)
+    group_px = torch.zeros((max(G, 1),), **i64)
+    _lib.check(lib.rsp_poly_raster_edges(verts.data_ptr(), ring_offs.data_ptr(), group_hw.data_ptr(), R, V, G, scaled.data_ptr(),
+                                         edge_pts.data_ptr(), group_px.data_ptr(), _stream()), "rsp_poly_raster_edges")
+    edge_offs = torch.cat([edge_pts.new_zeros((1,)), torch.cumsum(edge_pts[:V], 0)]).contiguous()
+    T, coord_max, pixels_max, bad_offs, bad_group = torch.stack(
+        [edge_offs[-1], scaled.abs().max().to(torch.int64), group_px.max(), bad_offs.to(torch.int64),
+         bad_group.to(torch.int64)]).tolist()
+    if bad_offs:
+        raise ValueError('poly_raster: ring_offs must ascend from 0 to the number of vertices')
+    if bad_group:
+        raise ValueError('poly_raster: ring_group must be non-decreasing and inside [0, G)')
+    if pixels_max > 2 ** 31 - 1:
+        raise ValueError('poly_raster: a group canvas is empty or has 2^31 pixels or more; COCO run counts are 32-bit')
+    if coord_max > POLY_RASTER_MAX_COORD:
+        raise ValueError(f'poly_raster: a coordinate scales beyond +-{POLY_RASTER_MAX_COORD} (5 x: |x| up to about 3.3 million px)')
+    if T > POLY_RASTER_MAX_POINTS:
+        raise ValueError(f'poly_raster: {T} walk points in one call; at most {POLY_RASTER_MAX_POINTS} (split the rings)')
+    keys = torch.empty((max(T, 1),), **i64)
+    _lib.check(lib.rsp_poly_raster_crossings(scaled.data_ptr(), ring_offs.data_ptr(), ring_group.data_ptr(), group_hw.data_ptr(),
+                                             edge_offs.data_ptr(), R, V, G, T, coord_max, pixels_max, keys.data_ptr(), _stream()),
+               "rsp_poly_raster_crossings")
+    walk = T
+    keys = keys[:T]
+    if compact and T:                       # most walk points cross no pixel column: drop their slots in front of the sort
+        keys = keys[keys != CONST['RSP_POLY_RASTER_NO_KEY']]
+    keys = torch.sort(keys)[0].contiguous() if T else keys
+    T = int(keys.shape[0])
+    key_offs = torch.searchsorted(keys, torch.arange(G + 1, **i64) << 32).contiguous()
+
+    def launch(cap):
+        cap = max(int(cap), 1)
+        counts = torch.empty((max(G, 1), cap), dtype=torch.int32, device=dev)
+        n = torch.zeros((max(G, 1),), dtype=torch.int32, device=dev)
+        _lib.check(lib.rsp_poly_raster_runs(keys.data_ptr(), T, key_offs.data_ptr(), group_hw.data_ptr(), G, pixels_max,
+                                            counts.data_ptr(), n.data_ptr(), cap, _stream()), "rsp_poly_raster_runs")
+        return counts[:G], n[:G]
+    launch.walk_points, launch.crossings = walk, key_offs[-1]          # the walk points, and how many of them cross (on the device)
+    return launch
+
+
+def poly_raster(verts, ring_offs, ring_group, group_hw, cap=64):
+    """rings -> (counts int32 [G, cap'], n int32 [G], n on the host, cap'): maskApi.c rleFrPoly's run counts of every group of
+    rings on its own (h, w) canvas, even-odd over the rings of a group (poly_raster_launcher under fit_runs: the crossings are
+    found and sorted once, only the last stage runs again when a row did not fit `cap`)."""
+    return fit_runs(poly_raster_launcher(verts, ring_offs, ring_group, group_hw), cap)
+
+
 # (th, tw) of rsp_mask_remove_small_regions' tile-local labelling
 MASK_REGION_TILE = (CONST['RSP_MASK_REGION_TILE_H'], CONST['RSP_MASK_REGION_TILE_W'])
 MASK_REGION_MODES = {'holes': 1, 'islands': 2, 'both': 3}

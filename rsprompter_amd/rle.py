@@ -165,6 +165,57 @@ def polygons_to_lists(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst
     return [[(v[ro[r]:ro[r + 1]], par[r], a2[r]) for r in range(io[i], io[i + 1])] for i in range(len(io) - 1)]
 
 
+POLYGON_FILLS = ('union', 'evenodd')
+
+
+def polygons_to_runs(verts, ring_offs, ring_group, group_hw, fill='union', cap=None):
+    """Rings -> the run table of G masks, every one on its own canvas (ops.poly_raster): verts float64 [V, 2] =
+    (x, y), ring_offs int64 [R + 1], ring_group int32 [R] (the instance of each ring, non-decreasing), group_hw int32 [G, 2] =
+    (h, w) per instance, on one device -> (counts int32 [G, cap'], n int32 [G]).  Every ring is rasterised as maskApi.c
+    rleFrPoly does it; an instance without rings is the empty mask.
+    fill='evenodd': all rings of an instance on one canvas, a pixel is set when an odd number of rings covers it: holes
+      subtract.  The inverse of runs_to_polygons, bit for bit.
+    fill='union': pycocotools' COCO.annToRLE: every ring on its own, then rleMerge: the instances of more than one ring are
+      unioned with union_runs, one call per distinct canvas size among them; the rows of the others pass through untouched.
+    cap: the first run capacity (ops.fit_runs grows it)."""
+    if fill not in POLYGON_FILLS:
+        raise ValueError(f'polygon fill {fill!r}: one of {POLYGON_FILLS}')
+    cap = 64 if cap is None else max(int(cap), 2)
+    if fill == 'evenodd':
+        return ops.poly_raster(verts, ring_offs, ring_group, group_hw, cap)[:2]
+    dev = verts.device
+    R, G = int(ring_group.shape[0]), int(group_hw.shape[0])
+    parts = torch.arange(R, dtype=torch.int32, device=dev)
+    part_hw = group_hw[ring_group.to(torch.int64).clamp(0, max(G - 1, 0))].contiguous() if R else group_hw[:0]
+    counts, n, _, _ = ops.poly_raster(verts, ring_offs, parts, part_hw, cap)
+    hw = group_hw.cpu().numpy().astype(np.int64)
+    inst_offs = np.searchsorted(ring_group.cpu().numpy(), np.arange(G + 1))               # the rings of instance g
+    per = inst_offs[1:] - inst_offs[:-1]
+    multi, single = np.flatnonzero(per > 1), np.flatnonzero(per == 1)
+    tables = []                                                                           # (rows of the result, counts, n)
+    for h, w in sorted({(int(a), int(b)) for a, b in hw[multi]}):
+        rows = multi[(hw[multi, 0] == h) & (hw[multi, 1] == w)]
+        members = np.concatenate([np.arange(inst_offs[g], inst_offs[g + 1]) for g in rows])
+        offs = np.concatenate([[0], np.cumsum(per[rows])])
+        c, m, _, _ = union_runs(counts, n, (h, w), torch.from_numpy(offs.astype(np.int32)).to(dev),
+                                torch.from_numpy(members.astype(np.int32)).to(dev))
+        tables.append((rows, c, m))
+    # two columns at least: rsp_rle_to_string
+    width = max([int(t[1].shape[1]) for t in tables] + [int(counts.shape[1]) if single.size else 2, 2])
+    out = torch.zeros((G, width), dtype=torch.int32, device=dev)
+    out[:, 0] = (group_hw[:, 0].to(torch.int64) * group_hw[:, 1]).to(torch.int32)          # no ring: one count h w
+    n_out = torch.ones((G,), dtype=torch.int32, device=dev)
+    if single.size:
+        rows, src = torch.from_numpy(single).to(dev), torch.from_numpy(inst_offs[single]).to(dev)
+        out[rows, :counts.shape[1]] = counts[src]
+        n_out[rows] = n[src]
+    for rows, c, m in tables:
+        rows = torch.from_numpy(rows).to(dev)
+        out[rows, :c.shape[1]] = c
+        n_out[rows] = m
+    return out, n_out
+
+
 def runs_to_hulls(counts, n, size):
     """run table of k masks on one size = (H, W) canvas -> (hull_verts int32 [Vh, 2], hull_offs int64 [k + 1], hull_area2
     int64 [k]) on the device: the convex hull of every mask, all its components together (ops.mask_hull).
