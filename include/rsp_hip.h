@@ -39,7 +39,8 @@ typedef void* rsp_stream_t;
 /* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
 /* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
 /* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
-/* Still 5 with rsp_poly_raster_* (as with the polygon, simplification, oriented-box and component entry points): an      */
+/* Still 5 with rsp_run_prefix / rsp_coco_iou_runs* (as with the polygon, simplification, oriented-box, component and     */
+/* rasterisation entry points): an                                                                                        */
 /* addition that leaves every earlier entry point, structure and macro as it was does not change the number.              */
 /* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
 /* 3: RspBoxCoder in RspRpnDesc / rsp_bbox_post; 2: RspGemmDesc gained c_ncols / pl_col0, plane format words decode       */
@@ -639,6 +640,31 @@ int rsp_coco_match(const RspCocoUnit* units, int32_t n_units, const double* iou,
                    const uint8_t* gt_crowd, const int64_t* gt_id, const double* dt_area, const double* area_rng, int32_t A,
                    const double* thrs, int32_t T, int64_t n_dt, uint8_t* gtm_ws, int64_t* dtm, uint8_t* dtig,
                    int32_t* npig, rsp_stream_t stream);
+/* The same IoU blocks from RUN TABLES (csrc/coco_iou_runs.hip), for masks too large to exist as bits.    */
+/* A run table is counts [k, cap] / n [k] as rsp_rle_from_string writes it (n <= 0: an empty row, n > cap: read up to     */
+/* cap); no canvas size is taken anywhere, a row is its column-major stream; the counts need not be canonical (zero       */
+/* counts anywhere).  rsp_run_prefix: per row the prefix workspace (int32 [k, cap], rsp_run_prefix_workspace_bytes: ones   */
+/* pixels in front of each ones-run and the run's pixel start), area [k] = sum of the odd counts (maskApi rleArea) and    */
+/* extent [k, 2] = (first set pixel, one past the last set pixel) of the stream, (0, 0) for a row without one.            */
+int64_t rsp_run_prefix_workspace_bytes(int32_t k, int32_t cap);
+int rsp_run_prefix(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, void* workspace, int64_t* area,
+                   int32_t* extent, rsp_stream_t stream);
+/* Filter: for every slot p of iou [0, n_iou) -- units as rsp_coco_iou takes them (DEVICE array, nwords ignored), ascending */
+/* in out0 and tiling [0, n_iou) --: alive[p] = dt row << 32 | gt row when the extents of its pair overlap, else -1 and    */
+/* iou[p] = 0.0 (disjoint or touching extents share no pixel: the exact stand-in of rleIou's bbIou prefilter).  No run is   */
+/* read.  The caller compacts the alive slot numbers (slots int64 [n_slots], any order) and hands them to                  */
+/* rsp_coco_iou_runs: one wave per slot walks the ones-runs of the row that has fewer of them inside the overlap of the     */
+/* extents and looks their ends up in the other row's prefix; iou[p] = rsp_coco_iou's SEGM arithmetic (union in 64 bits).  */
+/* Every slot of iou is written once, by one of the two; dt and gt are two tables with capacities of their own.            */
+int rsp_coco_iou_runs_filter(const RspCocoUnit* units, int32_t n_units, int64_t n_iou, const int32_t* dt_extent,
+                             int64_t n_dt, const int32_t* gt_extent, int64_t n_gt, int64_t* alive, double* iou,
+                             rsp_stream_t stream);
+int rsp_coco_iou_runs(const int64_t* slots, int64_t n_slots, int64_t n_iou, const int64_t* alive,
+                      const uint32_t* dt_counts, const int32_t* dt_n, int64_t n_dt, int32_t dt_cap,
+                      const void* dt_workspace, const int64_t* dt_area, const int32_t* dt_extent,
+                      const uint32_t* gt_counts, const int32_t* gt_n, int64_t n_gt, int32_t gt_cap,
+                      const void* gt_workspace, const int64_t* gt_area, const int32_t* gt_extent,
+                      const uint8_t* gt_crowd, double* iou, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Sliced inference on large scenes (csrc/large_image.hip)        */

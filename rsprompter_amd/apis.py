@@ -275,6 +275,57 @@ def _masks_to_runs(masks, device):
     return torch.from_numpy(table.astype(np.int32)).to(dev), n.to(dev), size
 
 
+def _masks_to_runs_mixed(masks, device):
+    """_masks_to_runs for lists whose dicts carry sizes of their own, compressed and uncompressed counts side by side ->
+    (counts, n, [(H, W)] per mask) on the device: one table, the rows in the order of the list (the run-domain IoU takes no
+    canvas size).  An empty list is an empty table."""
+    from . import rle
+    if isinstance(masks, torch.Tensor):
+        counts, n, size = _masks_to_runs(masks, device)
+        return counts, n, [size] * int(n.shape[0])
+    masks = list(masks)
+    dev = torch.device(device)
+    ops.require_device(dev)
+    if not masks:
+        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), []
+    sizes = [(int(m['size'][0]), int(m['size'][1])) for m in masks]
+    packed = [i for i, m in enumerate(masks) if isinstance(m['counts'], (bytes, str))]
+    plain = [i for i, m in enumerate(masks) if not isinstance(m['counts'], (bytes, str))]
+    tables, ns = [], []
+    for idx in (packed, plain):
+        if idx:                                               # one size for _masks_to_runs' sake: the sizes stay with us
+            c, n, _ = _masks_to_runs([dict(size=[1, 1], counts=masks[i]['counts']) for i in idx], dev)
+            tables.append(c)
+            ns.append(n)
+    back = torch.tensor(np.argsort(np.asarray(packed + plain, np.int64), kind='stable'), dtype=torch.int64, device=dev)
+    return rle.concat_runs(tables, rows=back).contiguous(), torch.cat(ns)[back].contiguous(), sizes
+
+
+def mask_iou(dt, gt, iscrowd=None, device='cuda:0'):
+    """pycocotools' `maskUtils.iou(dt, gt, iscrowd)` on the device, in the run domain: float64 [D, G] (on the device), entry
+    (d, g) = |d & g| / |d | g|, or / |d| for a crowd g, 0.0 without a common pixel (csrc/coco_iou_runs.hip).
+    dt / gt: lists of RLE dicts dict(size=[H, W], counts=...) -- compressed (bytes / str) or uncompressed (list) counts,
+    also side by side, any counts that sum to the canvas (zero counts anywhere) -- or bool [k, H, W] tensors on the device.
+    No mask is expanded: scene-sized RLE costs its runs.  iscrowd: a bool per gt (None: none is).  Masks of different sizes
+    in one call are refused (ValueError; cocoapi writes -1 there).  One device-to-host read (the pairs whose extents
+    overlap), and the run capacity retry of bool tensors / compressed strings."""
+    for t in (dt, gt):
+        if isinstance(t, torch.Tensor):
+            device = t.device
+    dc, dn, d_sizes = _masks_to_runs_mixed(dt, device)
+    gc, gn, g_sizes = _masks_to_runs_mixed(gt, device)
+    D, G = len(d_sizes), len(g_sizes)
+    if D and G and len(set(d_sizes) | set(g_sizes)) != 1:
+        raise ValueError(f'mask_iou: masks of different sizes in one call: {sorted(set(d_sizes) | set(g_sizes))}')
+    crowd = np.zeros(G, np.uint8) if iscrowd is None else np.asarray(list(iscrowd)).astype(bool).astype(np.uint8).reshape(-1)
+    if crowd.shape[0] != G:
+        raise ValueError(f'mask_iou: iscrowd has {crowd.shape[0]} entries for {G} ground truths')
+    dev = dn.device
+    units = ops.coco_units([0], [0], [0], [D], [G], [0], dev)
+    g_crowd = torch.from_numpy(np.concatenate([crowd, [0]]).astype(np.uint8)).to(dev)
+    return ops.coco_iou_runs(units, D * G, (dc, dn), (gc, gn), g_crowd).view(D, G)
+
+
 def _check_canonical(counts, n, size):
     """RLE dicts come from outside: the tracer reads canonical COCO counts only (a zero count anywhere but in front would
     make two runs of one value touch, counts that do not sum to H * W describe another canvas).  One device-to-host read."""

@@ -94,8 +94,7 @@ __global__ __launch_bounds__(SM_THREADS) void rle_bbox_kernel(const uint32_t* __
 }
 
 // ------------------------------------------------------------------------------------------------- pair overlap
-// Workspace row m (int32 [cap], next to the counts row): for ones-run t (count index 2 t + 1 < n)
-//   ws[2 t]     = ones pixels in front of the run          ws[2 t + 1] = pixel start of the run
+// The prefix workspace of every row (run_table.h: RspRunPrefix; searched with sm_find / sm_ones_before from there).
 // One block per row, computed once however many pairs the row appears in.
 __global__ __launch_bounds__(SM_THREADS) void rle_prefix_kernel(const uint32_t* __restrict__ counts,
                                                                 const int32_t* __restrict__ n_in, int cap,
@@ -104,39 +103,8 @@ __global__ __launch_bounds__(SM_THREADS) void rle_prefix_kernel(const uint32_t* 
   const int m = blockIdx.x;
   const RspRunRow row = rsp_run_row(counts, n_in, cap, m);
   int32_t* w_row = ws + (int64_t)m * cap;
-  int carry_ones = 0;
-  for (RspRunWalk<SM_THREADS> r(row, tmp); r.next();) {
-    int chunk_ones;
-    const int ob = carry_ones + rsp_block_excl_scan<SM_THREADS>((r.i & 1) ? r.c : 0, tmp, &chunk_ones);
-    if (r.i < row.n && (r.i & 1)) {
-      w_row[r.i - 1] = ob;
-      w_row[r.i] = r.s;
-    }
-    carry_ones += chunk_ones;
-  }
-}
-
-struct SmRow {
-  const uint32_t* c;
-  const int32_t* ws;
-  int nr;                   // ones-runs
-};
-
-// last ones-run whose start is <= p; -1: none
-__device__ __forceinline__ int sm_find(const SmRow& r, int p) {
-  int lo = -1, hi = r.nr - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (r.ws[2 * mid + 1] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// ones pixels of the row in [0, p)
-__device__ __forceinline__ int sm_ones_before(const SmRow& r, int p) {
-  const int t = sm_find(r, p);
-  if (t < 0) return 0;
-  return r.ws[2 * t] + min(p - r.ws[2 * t + 1], (int)r.c[2 * t + 1]);
+  RspRunPrefix<SM_THREADS> p;
+  for (RspRunWalk<SM_THREADS> r(row, tmp); r.next();) p.step(r, row, w_row, tmp);
 }
 
 // pixels of the ones-run [s, s + c) inside columns [x0, x1), rows [y0, y1): first / middle / last column in closed form

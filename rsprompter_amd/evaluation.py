@@ -3,6 +3,9 @@ without pycocotools.  The per-pair and per-(image, category) work of COCOeval.ev
 (csrc/cocoeval.hip: string decode, bits, IoU, greedy matching); accumulate / summarize stay on the host in float64 numpy
 with pycocotools' arithmetic.
 
+The segm IoU has two routes with the same doubles (`iou_domain`): bit planes (`'bits'`, the default) and run tables
+(`'runs'`, csrc/coco_iou_runs.hip: scenes whose masks never exist as bits); `'auto'` chooses by size.
+
 Both ground-truth paths of the reference work and give the reference's (different) numbers:
   * no `ann_file` (every RSPrompter config): the ground truth of the data samples, converted as `gt_to_coco_json` does
     (annotation ids from 1, category ids 0..C-1, every instance non-crowd, area = float32 box area w * h);
@@ -60,6 +63,24 @@ def _masks_on_device(rles, device):
     return bits, woff_d, area, wrange
 
 
+def _runs_on_device(rles, device):
+    """compressed RLE dicts -> the run table (counts, n) on the device (rsp_rle_from_string): _masks_on_device without the
+    bits, for masks of any size"""
+    strings = [r['counts'] if isinstance(r['counts'], bytes) else str(r['counts']).encode() for r in rles]
+    flat, offs = _flat_strings(strings, device)
+    return ops.rle_from_string(flat, offs)
+
+
+IOU_DOMAINS = ('bits', 'runs', 'auto')
+# iou_domain='auto': the run route when the bit words of one device_evaluate call (every dt and gt mask at one bit per
+# pixel) would pass this; one 8 192 x 9 000 mask is 9.2 MB of them
+BITS_BUDGET_BYTES = 1 << 30
+
+
+def _bits_bytes(rles):
+    return sum(8 * ((int(r['size'][0]) * int(r['size'][1]) + 63) // 64) for r in rles)
+
+
 class CocoEvalResult:
     """What COCOeval leaves behind that the metric reads: eval['precision'] / ['recall'] and stats."""
 
@@ -69,12 +90,19 @@ class CocoEvalResult:
         self.tables = tables            # the device's evaluateImg tables (dtm, dtig [A, T, n_dt], npig [units, A], ...)
 
 
-def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, device, timings=None):
+def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, device, timings=None, iou_domain='bits',
+                    keep_iou=False):
     """COCOeval(gt, dt, iou_type) with params imgIds / catIds / iouThrs / maxDets -> evaluate + accumulate + summarize.
 
     gt: dict(images, annotations) (annotations with id, image_id, category_id, area, iscrowd, bbox, segmentation);
-    dt: list of loadRes'd detections (id from 1, image_id, category_id, score, area, bbox or segmentation RLE)."""
+    dt: list of loadRes'd detections (id from 1, image_id, category_id, score, area, bbox or segmentation RLE).
+    iou_domain (segm only): 'bits' expands every mask to one bit per pixel (rsp_rle_to_bits + rsp_coco_iou), 'runs' keeps
+    the run tables (ops.coco_iou_runs: the same doubles, for scenes), 'auto' takes 'runs' when the bits of this call would
+    pass BITS_BUDGET_BYTES.  timings['iou_domain'] tells which one ran.  keep_iou: tables['iou'] = the IoU blocks, on the
+    device (tools/bench_coco_iou_runs.py compares the routes on them)."""
     import time
+    if iou_domain not in IOU_DOMAINS:
+        raise ValueError(f'device_evaluate: iou_domain {iou_domain!r}: one of {IOU_DOMAINS}')
     t0 = time.perf_counter()
     img_ids = np.unique(np.asarray(img_ids))
     cat_ids = np.unique(np.asarray(cat_ids))
@@ -132,7 +160,19 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     g_area = dev([g['area'] for g in gts], np.float64)
     g_id = dev([g['id'] for g in gts], np.int64)
     t1 = time.perf_counter()
-    if iou_type == 'segm':
+    if iou_type == 'segm' and iou_domain == 'auto':
+        iou_domain = 'runs' if _bits_bytes([d['segmentation'] for d in dts]) + \
+            _bits_bytes([g['segmentation'] for g in gts]) > BITS_BUDGET_BYTES else 'bits'
+    if iou_type == 'segm' and iou_domain == 'runs':
+        d_runs = _runs_on_device([d['segmentation'] for d in dts], device)
+        g_runs = _runs_on_device([g['segmentation'] for g in gts], device)
+        d_pre = ops.run_prefix(*d_runs, check=False)           # rle_from_string's retry left no negative n
+        info = {}
+        iou = ops.coco_iou_runs(units, n_iou, d_runs, g_runs, g_crowd, dt_prefix=d_pre, info=info)
+        d_area = d_pre[1].to(torch.float64) if n_dt else dev([0.0], np.float64)
+        if timings is not None:
+            timings.update(pairs=info['pairs'], survivors=info['survivors'])
+    elif iou_type == 'segm':
         db, dwo, da, dwr = _masks_on_device([d['segmentation'] for d in dts], device)
         gb, gwo, ga, gwr = _masks_on_device([g['segmentation'] for g in gts], device)
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
@@ -156,8 +196,12 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         timings['host_prepare'] = timings.get('host_prepare', 0.0) + (t1 - t0)
         timings['device'] = timings.get('device', 0.0) + (t2 - t1)
         timings['host_accumulate'] = timings.get('host_accumulate', 0.0) + (t3 - t2)
+        if iou_type == 'segm':
+            timings['iou_domain'] = iou_domain
     tables = dict(dtm=dtm, dtig=dtig, npig=npig, dt_ids=np.array([d['id'] for d in dts], dtype=np.int64), dt0=dt0,
                   nd=nd, ng=ng, n_img=I, n_cat=K)
+    if keep_iou:
+        tables['iou'] = iou[:n_iou]
     return CocoEvalResult(precision, recall, stats, tables)
 
 
@@ -268,7 +312,8 @@ class CocoMetric:
 
     def __init__(self, ann_file=None, metric='bbox', classwise=False, proposal_nums=(100, 300, 1000), iou_thrs=None,
                  metric_items=None, format_only=False, outfile_prefix=None, file_client_args=None, backend_args=None,
-                 collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None, gt_raster='host'):
+                 collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None, gt_raster='host',
+                 iou_domain='bits'):
         self.metrics = metric if isinstance(metric, list) else [metric]
         for m in self.metrics:
             if m in ('proposal', 'proposal_fast'):
@@ -295,6 +340,9 @@ class CocoMetric:
         if gt_raster not in GT_RASTERS:
             raise ValueError(f'CocoMetric: gt_raster {gt_raster!r}: one of {GT_RASTERS}')
         self.gt_raster = gt_raster                          # who rasterises ground-truth polygons
+        if iou_domain not in IOU_DOMAINS:
+            raise ValueError(f'CocoMetric: iou_domain {iou_domain!r}: one of {IOU_DOMAINS}')
+        self.iou_domain = iou_domain                        # how the segm IoU reads the masks
         self._coco_api = None
         if ann_file is not None:
             with open(ann_file) as f:
@@ -471,7 +519,7 @@ class CocoMetric:
                     d['segmentation'] = dict(size=d['segmentation']['size'], counts=c.encode() if isinstance(c, str) else c)
             tm = {}
             ev = device_evaluate(gt_m, dts, metric, self.img_ids, self.cat_ids, self.iou_thrs, self.proposal_nums,
-                                 device, timings=tm)
+                                 device, timings=tm, iou_domain=self.iou_domain)
             tm['total'] = time.perf_counter() - t0
             self.timings[metric] = tm
             self.eval_results[metric] = ev

@@ -2377,6 +2377,76 @@ def coco_match(units, iou, gt_area, gt_crowd, gt_id, dt_area, area_rng, thrs, n_
     return dtm[:, :, :n_dt], dtig[:, :, :n_dt], npig[:nu]
 
 
+# ----------------------------------------------------------------------------- run-domain mask IoU (csrc/coco_iou_runs.hip)
+def _run_table(what, counts, n):
+    if counts.dtype != torch.int32 or counts.dim() != 2 or n.dtype != torch.int32 or n.dim() != 1 \
+            or n.shape[0] != counts.shape[0] or counts.shape[1] < 1 or n.device != counts.device:
+        raise ValueError(f'{what}: expected counts int32 [k, cap >= 1] and n int32 [k] on one device')
+    return counts.contiguous(), n.contiguous()
+
+
+def run_prefix(counts, n, check=True):
+    """run table (counts int32 [k, cap], n int32 [k]; any canvas, any counts) -> (workspace int32 [k, cap]: ones pixels in
+    front of each ones-run and the run's pixel start, area int64 [k] = rleArea, extent int32 [k, 2] = (first set pixel, one
+    past the last set pixel) of the column-major stream, (0, 0) for a row without one) (rsp_run_prefix).  A negative n is a
+    row that did not fit its producer: ValueError (check=True: one device-to-host read; check=False leaves the test to the
+    caller and reads nothing)."""
+    lib = _lib.load()
+    counts, n = _run_table('run_prefix', counts, n)
+    k, cap, dev = int(n.shape[0]), int(counts.shape[1]), n.device
+    if check and k and bool((n < 0).any()):
+        raise ValueError('run_prefix: a row with negative n did not fit its producer (ops.fit_runs retries those)')
+    ws = torch.empty((max(int(lib.rsp_run_prefix_workspace_bytes(k, cap)) // 4, 1),), dtype=torch.int32, device=dev)
+    area = torch.zeros((max(k, 1),), dtype=torch.int64, device=dev)
+    extent = torch.zeros((max(k, 1), 2), dtype=torch.int32, device=dev)
+    if k:
+        _lib.check(lib.rsp_run_prefix(counts.data_ptr(), n.data_ptr(), k, cap, ws.data_ptr(), area.data_ptr(),
+                                      extent.data_ptr(), _stream()), "rsp_run_prefix")
+    return ws[:k * cap].view(k, cap), area[:k], extent[:k]
+
+
+def coco_iou_runs(units, n_iou, dt_runs, gt_runs, gt_crowd, dt_prefix=None, gt_prefix=None, info=None):
+    """IoU blocks of the units (`coco_units`, ascending in out0) from two run tables dt_runs / gt_runs = (counts, n) ->
+    float64 [n_iou], the doubles of `coco_iou` in SEGM mode without a bit plane: run_prefix of both tables
+    (or what it returned, as dt_prefix / gt_prefix), the extent filter with one lane per pair, the alive pairs compacted with
+    torch, one wave per survivor for the walk.  One device-to-host read: the number of survivors, with the flags of a
+    negative n (ValueError) next to it.  info (a dict) receives pairs / survivors."""
+    lib = _lib.load()
+    dev = units.device
+    (dc, dn), (gc, gn) = _run_table('coco_iou_runs', *dt_runs), _run_table('coco_iou_runs', *gt_runs)
+    iou = torch.zeros((max(n_iou, 1),), dtype=torch.float64, device=dev)
+    nu = units.numel() // COCO_UNIT_BYTES
+    n_dt, n_gt = int(dn.shape[0]), int(gn.shape[0])
+    bad = ((dn < 0).any() if n_dt else torch.zeros((), dtype=torch.bool, device=dev)) | \
+        ((gn < 0).any() if n_gt else torch.zeros((), dtype=torch.bool, device=dev))
+    if not (nu and n_iou and n_dt and n_gt):
+        if bool(bad):
+            raise ValueError('coco_iou_runs: a row with negative n did not fit its producer (ops.fit_runs retries those)')
+        if info is not None:
+            info.update(pairs=0, survivors=0)
+        return iou[:n_iou]
+    d_ws, d_area, d_ext = dt_prefix if dt_prefix is not None else run_prefix(dc, dn, check=False)
+    g_ws, g_area, g_ext = gt_prefix if gt_prefix is not None else run_prefix(gc, gn, check=False)
+    alive = torch.empty((n_iou,), dtype=torch.int64, device=dev)
+    _lib.check(lib.rsp_coco_iou_runs_filter(_units_ptr(units), nu, n_iou, d_ext.data_ptr(), n_dt, g_ext.data_ptr(), n_gt,
+                                            alive.data_ptr(), iou.data_ptr(), _stream()), "rsp_coco_iou_runs_filter")
+    live = alive >= 0
+    S, bad = torch.stack([live.sum(), bad.to(torch.int64)]).tolist()      # the read of the call: the number of survivors
+    if bad:
+        raise ValueError('coco_iou_runs: a row with negative n did not fit its producer (ops.fit_runs retries those)')
+    slots = torch.nonzero_static(live, size=S).view(-1) if S else None
+    if S:
+        _lib.check(lib.rsp_coco_iou_runs(slots.data_ptr(), S, n_iou, alive.data_ptr(),
+                                         dc.data_ptr(), dn.data_ptr(), n_dt, int(dc.shape[1]), d_ws.data_ptr(),
+                                         d_area.data_ptr(), d_ext.data_ptr(),
+                                         gc.data_ptr(), gn.data_ptr(), n_gt, int(gc.shape[1]), g_ws.data_ptr(),
+                                         g_area.data_ptr(), g_ext.data_ptr(), gt_crowd.data_ptr(), iou.data_ptr(),
+                                         _stream()), "rsp_coco_iou_runs")
+    if info is not None:
+        info.update(pairs=int(n_iou), survivors=S)
+    return iou[:n_iou]
+
+
 # ----------------------------------------------------------------------------- query prompter ops
 def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, add=None):
     """GroupNorm on channels-last [B, ..., C]; `add` (same shape) is added after the norm."""
