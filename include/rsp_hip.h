@@ -230,8 +230,12 @@ int rsp_vit_attention_planes_ex(const float* q, int64_t q_ld, const uint16_t* kv
 /* rel_tab = the layer's two tables packed once by rsp_pack_relpos_tables; q / K | V planes / outputs / window grid as    */
 /* above with S = 14.  The kernel is persistent (a block walks the windows of one head); variant: 0 = product (768        */
 /* blocks), n > 0 = 16 n blocks (tests and measurements).                                                                 */
-/* The K | V plane exponent (kv_scale_log2) must lie in [-8, 4] for S = 14 (both entry points): the padded-key mask and   */
-/* the rel-pos bias share the score scale 2^(6 + exponent); outside that range the call returns RSP_EINVAL.                */
+/* Input domain for S = 14 (both entry points).  The K | V plane exponent (kv_scale_log2) must lie in [-8, 4], else       */
+/* RSP_EINVAL.  Inside the kernel scaled q travels as fp16 hi / lo of q * scale * 2^6 and every rel-pos term of a query as  */
+/* fp16 hi / lo of term * 2^(6 + exponent), both through SATURATING splits: the result is fp32-class for                   */
+/* |q * scale| < 1024 per element and |rel-pos term| * 2^(6 + exponent) <= 65504 (256 logits at the encoder's exponent 2,  */
+/* 64 at 4, 1023 at 0); beyond that the operand is clamped silently (no error, no inf / NaN).  The level of the scores     */
+/* themselves sets no limit: the 28 padded keys of the last tile are masked with -inf, their probability is exactly 0.     */
 int rsp_vit_window_attention(const float* q, int64_t q_ld, const uint16_t* kv_hi, const uint16_t* kv_lo,
                              int64_t kv_rows, int32_t kv_scale_log2, const uint16_t* rel_tab, float* out,
                              uint16_t* out_hi, uint16_t* out_lo, int32_t out_scale_log2, int32_t Bp, int32_t nh,
@@ -397,8 +401,8 @@ int rsp_sam_fold_expand(const float* tq, uint16_t* out_hi, uint16_t* out_lo, int
 int rsp_sam_fold_gather(const float* full, float* ao, int32_t R, int32_t T, rsp_stream_t stream);
 
 /* Token -> image attention of the SAM two-way transformer with the K | V projections of the PER-RoI keys folded in   */
-/* (HF:326-331, 397-400; csrc/t2i_fold.hip): keys = fp16 planes of [k_rows >= R*N, 256]; pek = planes of k_proj(pe) +    */
-/* bias [N, 128]; qp = planes of q' [q_rows >= R*96, 256] with q'[r*96 + h*T + t] = Wk_h^T tq[r, t, h] (softmax scale     */
+/* (HF:326-331, 397-400; csrc/t2i_fold.hip): keys = fp16 planes of [k_rows >= R*N, 256]; pek = planes of k_proj(pe),      */
+/* bias left out, [N, 128] (q . bias is constant over the keys: the softmax cancels it); qp = planes of q' [q_rows >= R*96, 256] with q'[r*96 + h*T + t] = Wk_h^T tq[r, t, h] (softmax scale     */
 /* inside); tqx = planes of the block-diagonal tq [q_rows, 128]; *_e = plane scale exponents.  u [R*96, 256] fp32 receives */
 /* sum_n softmax(score)[n] * keys[n] per column (rows of columns >= ncols = 8 T <= 8 RSP_SAM_T2I_FOLD_MAX_TOKENS stay       */
 /* untouched); the caller applies                                                                                          */

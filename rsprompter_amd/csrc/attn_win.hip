@@ -4,10 +4,11 @@
 // instructions per MFMA, matrix pipe busy 21 %):
 //
 //   * the decomposed rel-pos bias enters through the MATRIX CORES.  bias[k, q] = rel_h[q, kh(k)] + rel_w[q, kw(k)] is the
-//     product of a one-hot matrix E[k, k'] (k' = kh for k' < 14, 14 + kw for 14 <= k' < 28, k' = 28 marks the padded keys
-//     196..223 of the last tile) with the query's 28 rel-pos terms B[k', q] (B[28, q] = a large negative number): two
-//     16-k steps x (B_hi, B_lo) = 4 MFMAs per 32-key tile on the score accumulator instead of, per score, two adds, a
-//     half-wave select and the validity select.  E lives in LDS as ready A fragments (a constant of the kernel, 17.5 KB).
+//     product of a one-hot matrix E[k, k'] (k' = kh for k' < 14, 14 + kw for 14 <= k' < 28; column k' = 28 marks the
+//     padded keys 196..223 of the last tile and meets B[28, q] = 0) with the query's 28 rel-pos terms B[k', q]: two
+//     16-k steps x (B_hi, B_lo) = 4 MFMAs per 32-key tile on the score accumulator instead of, per score, two adds and a
+//     half-wave select.  E lives in LDS as ready A fragments (a constant of the kernel, 17.5 KB).  The padded keys
+//     themselves are masked in the score registers of the last tile (-inf in front of the tile maximum: phase_sp).
 //   * the rel-pos terms themselves are computed IN the kernel (rsp_vit_window_attention): G[idx, q] = R_all[idx, :] . q
 //     for both tables on the matrix cores with the attention's own Q fragments (tables pre-split into fp16 hi / lo planes
 //     once per layer, rsp_pack_relpos_tables, DMA'd into LDS), then the Toeplitz band rel_h[q, kh] = G_h[qy - kh + 13, q]
@@ -28,7 +29,6 @@ constexpr int RT = 6;                         // rel-pos tables * 2^RT before th
 constexpr float P_SCALE_LOG2 = 7.0f;          // probabilities (< 2^8, see LAZY_LOG2) are scaled by 2^7 before the fp16 split
 constexpr float LAZY_LOG2 = 8.0f;             // the running maximum follows a tile maximum only beyond this distance
 constexpr float LOG2E_C = 1.4426950408889634f;
-constexpr float NEG_RAW = -60000.0f;          // bias of a padded key in the raw score domain (exp2 underflows to 0)
 constexpr int WT = 196, WS = 14, KT = 32, NTILE = 7;
 // ring of 4 buffers, tile kt in buffer kt % 4, worked on in pairs (one barrier per two tiles): while tiles 2p, 2p + 1 are
 // multiplied, tiles 2p + 2, 2p + 3 land in the other two buffers; the next window's tiles 0, 1 are queued behind tile 6
@@ -341,7 +341,6 @@ __global__ __launch_bounds__(448) void attn_win_kernel(const AttnWP p, const int
 #pragma unroll
         for (int n = 0; n < 16; ++n) vals[n] = qv ? vals[n] : 0.f;
       }
-      if (hh == 1) vals[12] = NEG_RAW;                  // k' = 28: the padded keys of the last tile
       split8w_fast(vals, bbh[0], bbl[0]);
       split8w_fast(vals + 8, bbh[1], bbl[1]);
     }
@@ -411,6 +410,14 @@ __global__ __launch_bounds__(448) void attn_win_kernel(const AttnWP p, const int
     auto phase_sp = [&](auto tc) {
       constexpr int kt = decltype(tc)::value, buf = kt % NBUF;
       // ---- lazy online softmax (per-lane query column; the two half waves hold the two halves of the tile's keys) ----
+      if constexpr ((kt + 1) * KT > WT) {
+        // the last tile ends in padded keys (196..223): -inf BEFORE the tile maximum, so their probability is exactly 0
+        // whatever the level of the real scores.  Register r of half wave hh is key row (r & 3) + 8 (r >> 2) + 4 hh: the
+        // real rows are known at compile time (registers 0..3 of the lower half wave), only this tile pays.
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if ((r & 3) + 8 * (r >> 2) + 4 * hh >= WT - kt * KT) sc[r] = -INFINITY;
+      }
       float tmax = fmaxf(fmaxf(sc[0], sc[1]), sc[2]);
 #pragma unroll
       for (int r = 3; r < 15; r += 2) tmax = fmaxf(fmaxf(tmax, sc[r]), sc[r + 1]);
@@ -595,9 +602,11 @@ int rsp_attn_win_dispatch(const float* q, int64_t q_ld, const uint16_t* kv_hi, c
   const int D = nh * dh;
   if ((D & 31) || (q_ld & 3) || kv_rows < (int64_t)Bp * WT) return RSP_EINVAL;
   if (RSP_PLANE_IS_F8(kv_scale_log2)) return RSP_EINVAL;   // K | V are consumed as fp16 hi / lo planes
-  // the padded-key mask (NEG_RAW) and the rel-pos bias enter the scores as fp16 values scaled by 2^(EQ + kv_e): with a key
-  // plane exponent above 4 the mask would no longer underflow the softmax (-60000 * 2^-(EQ + kv_e) * log2 e > -85) and a
-  // bias beyond |t| ~ 64 would saturate fp16; below -8 the biases lose their low bits.  The encoder uses 2.
+  // the rel-pos bias enters the scores as fp16 hi / lo values scaled by 2^(EQ + kv_e) and scaled q as fp16 values scaled
+  // by 2^EQ, both through SATURATING splits: a bias beyond |t| 2^(EQ + kv_e) = 65504 (|t| ~ 64 logits at exponent 4, ~ 256
+  // at the encoder's 2) or |q scale| >= 1024 is clamped silently, not refused -- the input domain stated in rsp_hip.h.
+  // Above exponent 4 the bias range would fall below 64 logits, below -8 the biases lose their low bits: both refused.
+  // (The padded keys are masked with -inf in the score registers and set no limit here.)
   if (RSP_PLANE_EXP(kv_scale_log2) > 4 || RSP_PLANE_EXP(kv_scale_log2) < -8) return RSP_EINVAL;
   if (rel_tab && (reinterpret_cast<uintptr_t>(rel_tab) & 15)) return RSP_EINVAL;
   if (variant < 0 || variant > 64) return RSP_EINVAL;

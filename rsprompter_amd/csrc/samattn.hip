@@ -36,7 +36,9 @@ __global__ __launch_bounds__(512) void sam_t2i_kernel(const float* __restrict__ 
   const int h = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane & 1;
   for (int i = tid; i < TMAX * W; i += 512)
-    sQ[i] = (i < T * W) ? q[(int64_t)r * T * W + i] * (scale * LOG2E) : 0.f;   // softmax in base 2
+    // logits stay in NATS up to the maximum subtraction (log2 e joins the difference): folded into q it moved every logit
+    // into the next binade (x 1.44) and doubled the rounding error of a softmax at a high level (100-nat ramps, levels)
+    sQ[i] = (i < T * W) ? q[(int64_t)r * T * W + i] * scale : 0.f;
   __syncthreads();
   const int64_t rb = kv_map ? kv_map[r] : r;
   const float* kbase = kv + rb * (int64_t)N * (2 * W) + h * DH + half * HD;
@@ -74,8 +76,8 @@ __global__ __launch_bounds__(512) void sam_t2i_kernel(const float* __restrict__ 
                 q1[0] * k1[0] + q1[1] * k1[1] + q1[2] * k1[2] + q1[3] * k1[3];
       s += __shfl_xor(s, 1, 64);                               // the other 8 dims of the same key
       const float mn = fmaxf(m[t], s);
-      const float a = __builtin_amdgcn_exp2f(m[t] - mn);      // 0 on the first key (m = -inf)
-      const float p = __builtin_amdgcn_exp2f(s - mn);
+      const float a = __builtin_amdgcn_exp2f((m[t] - mn) * LOG2E);      // 0 on the first key (m = -inf)
+      const float p = __builtin_amdgcn_exp2f((s - mn) * LOG2E);
       m[t] = mn;
       l[t] = l[t] * a + p;
 #pragma unroll
@@ -93,8 +95,8 @@ __global__ __launch_bounds__(512) void sam_t2i_kernel(const float* __restrict__ 
       const float mo = __shfl_xor(m[t], o, 64);
       const float lo = __shfl_xor(l[t], o, 64);
       const float mn = fmaxf(m[t], mo);
-      const float a = (m[t] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m[t] - mn);
-      const float b = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+      const float a = (m[t] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m[t] - mn) * LOG2E);
+      const float b = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mo - mn) * LOG2E);
       l[t] = l[t] * a + lo * b;
 #pragma unroll
       for (int d = 0; d < HD; ++d) {
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(512) void sam_t2i_kernel(const float* __restrict__ 
 // parameter of sam_t2i_kernel -- sharing the body through a device function changed hipcc's unrolling of the UNBIASED kernel
 // (2 766 -> 1 281 lines of assembly), and that kernel is on the measured path.
 //   bias [Rb, N]              one additive logit per key: s = q . k * scale + bias[n]; bias_stride = 0 (one row shared by all
-//                             RoIs) or N.  It joins the base-2 softmax as bias * log2(e), AFTER the cross-lane sum of the two
+//                             RoIs) or N.  It joins the logit (in nats, like the product) AFTER the cross-lane sum of the two
 //                             half dot products, so the product's expression tree is the unbiased kernel's, and the value of the
 //                             NEXT key is requested together with its K | V rows (4 bytes on top of the 1 KiB a key costs)
 template <int TMAX>
@@ -138,7 +140,9 @@ __global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restri
   const int h = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane & 1;
   for (int i = tid; i < TMAX * W; i += 512)
-    sQ[i] = (i < T * W) ? q[(int64_t)r * T * W + i] * (scale * LOG2E) : 0.f;   // softmax in base 2
+    // logits stay in NATS up to the maximum subtraction (log2 e joins the difference): folded into q it moved every logit
+    // into the next binade (x 1.44) and doubled the rounding error of a softmax at a high level (100-nat ramps, levels)
+    sQ[i] = (i < T * W) ? q[(int64_t)r * T * W + i] * scale : 0.f;
   __syncthreads();
   const int64_t rb = kv_map ? kv_map[r] : r;
   const float* kbase = kv + rb * (int64_t)N * (2 * W) + h * DH + half * HD;
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restri
     v0 = *reinterpret_cast<const f32x4*>(kr + W); v1 = *reinterpret_cast<const f32x4*>(kr + W + 4);
   }
   const float* brow = bias + (int64_t)r * bias_stride;
-  float b0 = (key < N) ? brow[key] * LOG2E : 0.f;
+  float b0 = (key < N) ? brow[key] : 0.f;
   for (; key < N; key += 32) {
     // the loop-invariant q values fit in registers next to the accumulators up to 10 tokens; beyond that they are
     // re-read from LDS (wave-uniform addresses) every key instead of being hoisted into spills
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restri
     const float* kn = kbase + (int64_t)min(key + 32, N - 1) * (2 * W);
     const f32x4 nk0 = *reinterpret_cast<const f32x4*>(kn), nk1 = *reinterpret_cast<const f32x4*>(kn + 4);
     const f32x4 nv0 = *reinterpret_cast<const f32x4*>(kn + W), nv1 = *reinterpret_cast<const f32x4*>(kn + W + 4);
-    const float nb0 = brow[min(key + 32, N - 1)] * LOG2E;
+    const float nb0 = brow[min(key + 32, N - 1)];
 #pragma unroll
     for (int t = 0; t < TMAX; ++t) {
       const f32x4 q0 = *reinterpret_cast<const f32x4*>(qbase + t * W);
@@ -180,8 +184,8 @@ __global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restri
       s += __shfl_xor(s, 1, 64);                               // the other 8 dims of the same key
       s += b0;
       const float mn = fmaxf(m[t], s);
-      const float a = __builtin_amdgcn_exp2f(m[t] - mn);      // 0 on the first key (m = -inf)
-      const float p = __builtin_amdgcn_exp2f(s - mn);
+      const float a = __builtin_amdgcn_exp2f((m[t] - mn) * LOG2E);      // 0 on the first key (m = -inf)
+      const float p = __builtin_amdgcn_exp2f((s - mn) * LOG2E);
       m[t] = mn;
       l[t] = l[t] * a + p;
 #pragma unroll
@@ -199,8 +203,8 @@ __global__ __launch_bounds__(512) void sam_t2i_bias_kernel(const float* __restri
       const float mo = __shfl_xor(m[t], o, 64);
       const float lo = __shfl_xor(l[t], o, 64);
       const float mn = fmaxf(m[t], mo);
-      const float a = (m[t] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m[t] - mn);
-      const float b = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+      const float a = (m[t] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m[t] - mn) * LOG2E);
+      const float b = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mo - mn) * LOG2E);
       l[t] = l[t] * a + lo * b;
 #pragma unroll
       for (int d = 0; d < HD; ++d) {

@@ -7,7 +7,8 @@
 // that writes 3.4 GB of fp32 which the attention kernel reads back (2.9 ms per call at R = 800).  The algebra allows the
 // opposite order -- with tq[t, h, :] the projected query of token t and head h (16 values),
 //   score[(h, t), n] = tq[t, h] . (Wk_h (keys[n] + pe[n]) + bk_h)
-//                    = keys[n] . (Wk_h^T tq[t, h])  +  PEK[n, h] . tq[t, h],       PEK = k_proj(pe) + bk  ([N, 128], per model)
+//                    = keys[n] . (Wk_h^T tq[t, h])  +  PEK[n, h] . tq[t, h] + const,  PEK = Wk pe  ([N, 128], per model; the term
+//                      bk_h . tq[t, h] is the same for every key, the softmax cancels it, so the caller leaves bk out of PEK)
 //   out[(h, t), :]   = Wv_h (sum_n p[(h, t), n] keys[n]) + bv_h                    (the softmax weights sum to 1)
 // -- so the kernel is an attention with 8 T <= 96 query columns q' = Wk_h^T tq[t, h] of width 256 over keys that are BOTH
 // its K (plus the small PEK term) and its V: one pass over the key planes, no [R * N, 256] K | V tensor.  The two small

@@ -889,7 +889,7 @@ SAM_T2I_FOLD_MAX_TOKENS = CONST['RSP_SAM_T2I_FOLD_MAX_TOKENS']    # 8 heads x T 
 
 def sam_t2i_fold(keys, pek, qp, tqx, *, R, N, ncols):
     """token -> image attention over the per-RoI key planes with the K | V projections folded in (csrc/t2i_fold.hip):
-    keys Planes [R*N, 256]; pek Planes [N, 128] = k_proj(pe) + bias; qp Planes [R*96, 256] and tqx Planes [R*96, 128] (see
+    keys Planes [R*N, 256]; pek Planes [N, 128] = k_proj(pe) without the bias; qp Planes [R*96, 256] and tqx Planes [R*96, 128] (see
     rsp_sam_t2i_fold).  Returns u fp32 [R*96, 256] = sum_n softmax[n] keys[n] per (RoI, column); the rows of the columns
     >= ncols are zero."""
     lib = _lib.load()

@@ -195,7 +195,10 @@ class SamMaskDecoderHIP(HIPModule):
                 vb = _g(self, p + '.v_proj').bias
                 t[pre + '.kv_proj'] = torch.cat([t[pre + '.k_proj'], vb.unsqueeze(0).expand(pe_rows.shape[0], -1)],
                                                 1).contiguous()
-                t[pre + '.pek_planes'] = ops.to_planes(t[pre + '.k_proj'])       # PEK of the folded token -> image form
+                # PEK of the folded token -> image form: k_proj(pe) WITHOUT the bias.  q . b_k is one constant per (query,
+                # head), which the softmax cancels exactly; inside PEK that common level went through the fp16 split of every
+                # key's row and came back as per-key logit noise of level * 2^-22 (tests/_score_fields.py: a k_proj offset)
+                t[pre + '.pek_planes'] = ops.to_planes(ops.gemm(pe_rows, P[pre + '.k_proj'], bias=None))
             # the entry keeps the table it was computed from: while it is cached its memory cannot be handed to another tensor,
             # so an equal (pointer, shape, version) key means the same values.  The key is the table's NHWC rows: the models'
             # own tables are channels-last and hit on every call; a foreign NCHW-contiguous `image_pe` is copied to NHWC per

@@ -180,3 +180,82 @@ def test_query_prompt_kernels(dev):
     cases += [(d.logint(1, 5000), d.logint(1, 5000), d.pick([4, 32, 100, 256])) for _ in range(20)]
     for (n_src, n_idx, C) in cases:
         kp.check_gather_rows(ops, dev, n_src, n_idx, C, d.seed())
+
+
+# ---------------------------------------------------------------------------------------------- prescribed score fields
+# tests/_score_fields.py: the logits of every attention kernel prescribed (staircases around the lazy maximum, straddles of its
+# threshold, ramps, one-key spikes with their known answer, constant levels below the old padded-key mask, lane-divergent
+# forms), each case against the fp64 restatement within max(F, 2 E32).  One function per kernel family; a function runs all
+# its cases, prints `case err E32 bound` for each and asserts at the end.
+def test_score_fields_window_attention(dev):
+    """rsp_vit_window_attention (attn_win_kernel, packed tables): every field, variants 0 / 1, no grid and grids with padded
+    queries, dh 64 / 80, fp32 and plane outputs; the levels at every accepted kv exponent class (0, 2, 4); the bias path"""
+    import _score_fields as sf
+    rep = sf.Report('gpu')
+    sf.run_window_family(_ops(), dev, rep, 'window', [(None, 64, 0), ((2, 10), 80, 1), ((3, 4), 64, 1), (None, 80, 0),
+                                                      ((2, 10), 64, 0), ((3, 4), 80, 1)], planes=(False, True))
+    rep.finish()
+
+
+def test_score_fields_vit_attention_planes(dev):
+    """rsp_vit_attention_planes: S = 14 (the rel tensor form of attn_win_kernel), S = 32 (attn_stream_kernel, tile 64) with
+    every field, one S = 64 case per field class; dh 64 / 80, fp32 and plane outputs"""
+    import _score_fields as sf
+    ops, rep = _ops(), sf.Report('gpu')
+    sf.run_window_family(ops, dev, rep, 'planes', [(None, 64, 0), ((2, 10), 80, 0)], planes=(False, True))
+    for dh in (64, 80):
+        for n, c in enumerate(sf.chunks(sf.global_cases(1024), 4)):
+            sf.check_vit_fields(ops, dev, rep, 'planes', 32, 2, 2, dh, c, planes=(False, True) if n % 4 == 0 else (False,), seed=n)
+    for kv_e in (0, 4):
+        c = sf.pick(sf.global_cases(1024), ['level(-1000)', 'level(300)', 'cold_but_last_tile_hot', 'ramp'])
+        sf.check_vit_fields(ops, dev, rep, 'planes', 32, 2, 2, 64, c, kv_e)
+    for n, c in enumerate(sf.chunks(sf.pick(sf.global_cases(4096), sf.S64_CASES), 2)):
+        sf.check_vit_fields(ops, dev, rep, 'planes', 64, 1, 2, (64, 80)[n % 2], c, planes=(False, True) if n == 0 else (False,), seed=n)
+    rep.finish()
+
+
+def test_score_fields_vit_attention_f32(dev):
+    """rsp_vit_attention (fp32-fed: attn_window_kernel at S = 14, attn_global_kernel at S = 32)"""
+    import _score_fields as sf
+    ops, rep = _ops(), sf.Report('gpu')
+    for dh in (64, 80):
+        for n, c in enumerate(sf.chunks(sf.window_cases() + sf.window_level_cases()[:-1], 8)):
+            sf.check_vit_fields(ops, dev, rep, 'f32', 14, 4, 2, dh, c, seed=n)
+    for n, c in enumerate(sf.chunks(sf.global_cases(1024, full=False), 4)):
+        sf.check_vit_fields(ops, dev, rep, 'f32', 32, 2, 2, (64, 80)[n % 2], c, seed=n)
+    rep.finish()
+
+
+def test_score_fields_generic_attention(dev):
+    """rsp_attention at ragged last tiles"""
+    import _score_fields as sf
+    ops, rep = _ops(), sf.Report('gpu')
+    for (dh, Tq, Tk, nh) in [(16, 10, 300, 8), (64, 70, 130, 2), (32, 33, 257, 2)]:
+        sf.check_generic_fields(ops, dev, rep, dh, Tq, Tk, nh)
+    rep.finish()
+
+
+def test_score_fields_sam_cross_attention(dev):
+    """rsp_sam_t2i_attention, rsp_sam_t2i_attention_bias (the field in k and in the bias), rsp_sam_i2t_attention (fp32 and
+    plane outputs), rsp_sam_i2t_fused (both forms)"""
+    import _score_fields as sf
+    ops, rep = _ops(), sf.Report('gpu')
+    for where in ('k', 'k+bias', 'bias'):
+        sf.check_t2i_fields(ops, dev, rep, 7, 600, where)
+    for T in (7, 10):
+        sf.check_i2t_fields(ops, dev, rep, T, 96)
+        for form in ('valu', 'mfma'):
+            sf.check_i2t_fused_fields(ops, dev, rep, T, form, 96)
+    rep.finish()
+
+
+def test_score_fields_t2i_fold(dev):
+    """the folded token -> image attention: query amplitude x 1 / 8 / 32, a constant offset along one k_proj output direction;
+    both head-count instantiations (T <= 8, T > 8)"""
+    import _score_fields as sf
+    ops, rep = _ops(), sf.Report('gpu')
+    for (R, N, T) in [(2, 96, 10), (2, 64, 7)]:
+        for amp in (1.0, 8.0, 32.0):
+            for offset in (0.0, 20.0):
+                sf.check_t2i_fold_fields(ops, dev, rep, R, N, T, amp, offset)
+    rep.finish()

@@ -278,8 +278,10 @@ def test_vit_window_attention_fused_relpos(dev, nw, real, nh, dh, B, variant):
 
 
 def test_vit_window_attention_refuses_key_planes_with_a_large_exponent(dev):
-    """the padded-key mask and the rel-pos bias share the score scale 2^(6 + kv exponent): beyond 4 the mask would stop
-    underflowing the softmax, so both window entry points return RSP_EINVAL instead of a silently wrong answer."""
+    """the rel-pos bias travels as fp16 at the score scale 2^(6 + kv exponent): beyond 4 its range would be narrower than 64
+    logits, so both window entry points return RSP_EINVAL instead of a silently wrong answer.  (The padded-key
+    mask once shared that scale as an absolute -60000: at exponent 4 a row of logits at -70 lost the softmax to the padded
+    keys.  The mask is -inf in the score registers now; the last lines hold that level at exponent 4.)"""
     from rsprompter_amd import ops
     S, nh, dh, Bp = 14, 2, 64, 1
     D = nh * dh
@@ -292,6 +294,10 @@ def test_vit_window_attention_refuses_key_planes_with_a_large_exponent(dev):
     assert float((ok - ref).abs().max()) < 2e-5
     with pytest.raises(RuntimeError, match='rsp_vit_window_attention'):
         ops.vit_window_attention(q, ops.to_planes(kvf, 8), tab, Bp, nh, dh, dh ** -0.5)
+    import _score_fields as sf
+    rep = sf.Report('exponent 4')
+    sf.check_vit_fields(ops, dev, rep, 'window', S, Bp, nh, dh, [('level(-70)', sf.field('level', S * S, 32, -70.0), 'same', None)] * nh, kv_e=4)
+    rep.finish()
 
 
 def test_gemm_column_range_outputs(dev):

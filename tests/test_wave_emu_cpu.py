@@ -517,3 +517,49 @@ def test_emu_tiny_sam_encoder_end_to_end(emu, monkeypatch):
     e8 = [float((h - r).abs().max()) / float(r.abs().max()) for h, r in zip(out8[1], hs)] + [float((out8[0] - emb).abs().max()) / float(emb.abs().max())]
     print('... with the fp8-corrected product: relative distance to the fp16x3 run', ['%.1e' % e for e in e8])
     assert 0 < max(e8) < 2e-3
+
+
+# ---------------------------------------------------------------------------------------------- prescribed score fields
+# tests/_score_fields.py (the bodies of test_score_fields_* in tests/test_gpu_kernel_props.py): each case against the fp64
+# restatement within max(F, 2 E32), E32 the error of the same restatement in torch float32
+def test_emu_score_fields_window_attention(emu):
+    """attn_win_kernel with prescribed logits: every field (staircases around the lazy maximum, straddles of LAZY_LOG2 in
+    every tile, ramp, spikes at every tile edge with their known answer, lane-divergent forms, the rel-pos bias path) on a
+    grid with padded queries; constant levels far below 0 at kv exponents 0 / 2 / 4 on both grids -- those returned errors
+    of 0.2 while the padded keys of the last tile were masked with an absolute -60000 in the raw score domain"""
+    import _score_fields as sf
+    rep = sf.Report('emu')
+    sf.run_window_family(emu, DEV, rep, 'window', [((2, 10), 64, 0)])
+    for kv_e in (0, 2, 4):
+        sf.check_vit_fields(emu, DEV, rep, 'window', 14, 9, 2, 80, next(sf.chunks(sf.window_level_cases(), 18)), kv_e, (3, 4), 1)
+        sf.check_vit_fields(emu, DEV, rep, 'planes', 14, 4, 2, 80, next(sf.chunks(sf.window_level_cases(), 8)), kv_e, (2, 10))
+    rep.finish()
+
+
+def test_emu_score_fields_global_attention(emu):
+    """attn_stream_kernel (S = 32, plane-fed) on four fields; the fp32-fed window kernel on the levels"""
+    import _score_fields as sf
+    rep = sf.Report('emu')
+    for n, c in enumerate(sf.chunks(sf.pick(sf.global_cases(1024), sf.EMU_S32_CASES), 2)):
+        sf.check_vit_fields(emu, DEV, rep, 'planes', 32, 1, 2, 64, c, seed=n)
+    sf.check_vit_fields(emu, DEV, rep, 'f32', 14, 4, 2, 64, next(sf.chunks(sf.window_level_cases(), 8)))
+    rep.finish()
+
+
+def test_emu_score_fields_generic_and_decoder_attention(emu):
+    """rsp_attention at ragged last tiles, the SAM decoder's token -> image (plain, with a bias, the field in the bias) and
+    image -> token kernels (plain, fused in both forms), the folded token -> image attention under query amplitude and a
+    k_proj offset"""
+    import _score_fields as sf
+    rep = sf.Report('emu')
+    for (dh, Tq, Tk, nh) in [(16, 10, 300, 8), (64, 70, 130, 2), (32, 33, 257, 2)]:
+        sf.check_generic_fields(emu, DEV, rep, dh, Tq, Tk, nh)
+    for where in ('k', 'k+bias', 'bias'):
+        sf.check_t2i_fields(emu, DEV, rep, 7, 600, where)
+    for T in (7, 10):
+        sf.check_i2t_fields(emu, DEV, rep, T, 96)
+        for form in ('valu', 'mfma'):
+            sf.check_i2t_fused_fields(emu, DEV, rep, T, form, 96)
+    for (R, N, T, amp, offset) in [(2, 64, 7, 32.0, 20.0), (2, 96, 10, 8.0, 20.0), (2, 96, 10, 32.0, 0.0)]:
+        sf.check_t2i_fold_fields(emu, DEV, rep, R, N, T, amp, offset)
+    rep.finish()
