@@ -39,7 +39,7 @@ typedef void* rsp_stream_t;
 /* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
 /* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
 /* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
-/* Still 5 with rsp_run_prefix / rsp_coco_iou_runs* (as with the polygon, simplification, oriented-box, component and     */
+/* Still 5 with rsp_gemm_plan / RspGemmPlan (as with the run-table, polygon, simplification, oriented-box, component and   */
 /* rasterisation entry points): an                                                                                        */
 /* addition that leaves every earlier entry point, structure and macro as it was does not change the number.              */
 /* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
@@ -153,23 +153,36 @@ typedef struct RspGemmDesc {
   /* The SAM ViT qkv projection uses c_ncols = pl_col0 = D: q leaves as fp32 (rel-pos + attention Q operand), K | V      */
   /* as the fp16 planes the attention kernel DMAs (rsp_vit_attention_planes) -- no fp32 K / V tensor is ever written.    */
   int32_t c_ncols, pl_col0;
-  int32_t tile_hint;  /* 0 = auto (cost model in gemm_dma.hip).  Benchmarking only: 1/2/3 = plain 128x128 / 256x128 / */
-                      /* 256x256, 11-14 = register-pipelined loops, 17-20 = + DMA spread between the MFMA groups    */
-                      /* (17 = 256x256, 18 = 256x128, 20 = 128x128); other values are tuning probes.                */
+  int32_t tile_hint;  /* bits 0..7: 0 = auto (rsp_gemm_plan).  Benchmarking only: 1 = auto among the csrc/gemm_dma.hip   */
+                      /* tiles, H<n> of the table in csrc/gemm_plan.h = tile n of that file (taken when N fills more    */
+                      /* than half its width), 40 + v = gemm_s2.hip variant v (104: run-time epilogue), 200 / 201 =     */
+                      /* gemm_pp.hip 256 / 128 x 256; bits 8..15: group_m, bits 16..23: gemm_pp blocks per XCD.         */
 } RspGemmDesc;
 
 int rsp_gemm(const RspGemmDesc* desc, rsp_stream_t stream);
-/* 1 when rsp_gemm serves this descriptor with the two-blocks-per-CU persistent kernel (csrc/gemm_s2.hip), 0 when with   */
-/* one of the csrc/gemm_dma.hip / gemm.hip tiles (profiler labels; no device work)                                       */
+
+/* The kernel rsp_gemm launches for a descriptor: every check of the descriptor and the whole selection rule, host code     */
+/* only (csrc/gemm_plan.hip; no device work, nothing is dereferenced).  rsp_gemm itself is rsp_gemm_plan + the launch.      */
+#define RSP_GEMM_KERNEL_NONE 0   /* M == 0: nothing to launch */
+#define RSP_GEMM_KERNEL_F32A 1   /* csrc/gemm.hip gemm_f16x3_kernel<bm, bn, wgm, wgn>: fp32 A staged through registers */
+#define RSP_GEMM_KERNEL_DMA 2    /* csrc/gemm_dma.hip gemm_f16x3_dma_kernel<bm, bn, wgm, wgn, nbuf, var, 0, pipe, conv, ord, f8> */
+#define RSP_GEMM_KERNEL_S2 3     /* csrc/gemm_s2.hip gemm_f16x3_s2_kernel<var, epi>: persistent, two blocks per CU, 256 x 128 */
+#define RSP_GEMM_KERNEL_PP 4     /* csrc/gemm_pp.hip gemm_f16x3_pp_kernel<epi, var, bm>: ping-pong, one 512-thread block per CU */
+typedef struct RspGemmPlan {
+  int32_t kernel;          /* RSP_GEMM_KERNEL_* */
+  int32_t bm, bn;          /* block tile */
+  int32_t wgm, wgn, nbuf, pipe, conv, ord, f8;   /* the gemm.hip / gemm_dma.hip instantiation; 0 elsewhere */
+  int32_t epi;             /* s2 / pp: epilogue form, bit flags 1 = fp32 residual, 2 = GELU, 4 = fp32 output, 8 = plane    */
+                           /* output, 16 = output row map; 64 = the run-time form that serves every other mode            */
+  int32_t var;             /* experiment variant (VAR of s2 / pp, ABL of dma): 0 in every shipped library                 */
+} RspGemmPlan;
+/* RSP_OK / RSP_EINVAL exactly where rsp_gemm returns them; on RSP_EINVAL and for M == 0 *plan is RSP_GEMM_KERNEL_NONE.     */
+int rsp_gemm_plan(const RspGemmDesc* desc, RspGemmPlan* plan);
+/* The plan under its earlier names: plan.kernel == RSP_GEMM_KERNEL_S2;  plan.epi then, else -1;  plan.bm (256 / 128) when   */
+/* plan.kernel == RSP_GEMM_KERNEL_PP, else 0.  tile_hint 200 / 201 force the two ping-pong tiles for every descriptor that   */
+/* kernel implements (those with one of the compile-time epilogue forms and K >= 128).                                      */
 int rsp_gemm_uses_s2(const RspGemmDesc* desc);
-/* -1 when rsp_gemm_uses_s2(desc) == 0, else the epilogue form that kernel runs for the descriptor: bit flags 1 = fp32     */
-/* residual, 2 = GELU, 4 = fp32 output, 8 = plane output, 16 = output row map; 64 = the run-time form that serves every    */
-/* other mode (tests assert which compile-time specialisation they exercise; no device work)                               */
 int rsp_gemm_s2_epilogue(const RspGemmDesc* desc);
-/* 256 / 128 when rsp_gemm serves this descriptor with the ping-pong kernel (csrc/gemm_pp.hip: one 512-thread block per   */
-/* CU, block tile 256 x 256 or 128 x 256, the two waves of a SIMD alternating matrix and load phases) = the tile's rows;   */
-/* 0 otherwise.  tile_hint 200 / 201 force the two tiles for every descriptor the kernel implements (those with one of the */
-/* compile-time epilogue forms above and K >= 128).                                                                       */
 int rsp_gemm_uses_pp(const RspGemmDesc* desc);
 
 /* ------------------------------------------------------------------------ */

@@ -19,6 +19,7 @@
 // tile's global loads are issued before the MFMA block and written to LDS
 // after it (issue-early / write-late).
 #include "rsp_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -306,39 +307,9 @@ extern "C" int rsp_split_f16_kb32(const float* w, uint16_t* hi, uint16_t* lo, in
   return RSP_OK;
 }
 
-int rsp_gemm_dma_dispatch(const RspGemmDesc& d, hipStream_t s);  // gemm_dma.hip
-
-extern "C" int rsp_gemm(const RspGemmDesc* desc, rsp_stream_t stream) {
-  if (!desc) return RSP_EINVAL;
-  const RspGemmDesc& d = *desc;
-  if (!d.Bhi || !d.Blo) return RSP_EINVAL;
-  if (!d.A && !(d.Ahi && d.Alo)) return RSP_EINVAL;
-  if (!d.C && !(d.Chi && d.Clo) && !d.hd_out) return RSP_EINVAL;
-  if ((d.Chi == nullptr) != (d.Clo == nullptr)) return RSP_EINVAL;
-  if (d.Chi && (d.c_rows <= 0 || (d.N & 31))) return RSP_EINVAL;
-  if ((d.hd_out || d.ln_gamma || d.res_hi || (d.ct_W > 0 && d.ct_dy < 0)) && !(d.Ahi && d.Alo)) return RSP_EINVAL;   // the fused hyper-network epilogue lives in the plane path
-  if (d.M < 0 || d.N <= 0 || d.K <= 0 || (d.K % BK) != 0) return RSP_EINVAL;
-  // the fp8-corrected product lives in the plane path: with an fp32 A the cat8 plane of W would be read as a lo plane
-  if (RSP_PLANE_IS_F8(d.a_scale_log2) && !(d.Ahi && d.Alo)) return RSP_EINVAL;
-  // ... and so do the column-range outputs and the cat8 output planes: the fp32-A kernel writes all N columns of C and
-  // plain (hi, lo) planes from column 0
-  if (!(d.Ahi && d.Alo) && (d.c_ncols != 0 || d.pl_col0 != 0 || (d.Chi && RSP_PLANE_IS_F8(d.c_scale_log2)))) return RSP_EINVAL;
-  if (!RSP_PLANE_WORD_VALID(d.a_scale_log2) || (d.Chi && !RSP_PLANE_WORD_VALID(d.c_scale_log2)) ||
-      (d.res_hi && !RSP_PLANE_WORD_VALID(d.res_scale_log2)))
-    return RSP_EINVAL;
-  if (d.M == 0) return RSP_OK;
-  if (d.conv_k != 0) {
-    if (d.conv_C % BK != 0) return RSP_EINVAL;
-    if (d.K != d.conv_k * d.conv_k * d.conv_C) return RSP_EINVAL;
-    if (d.a_rowmap) return RSP_EINVAL;
-  } else {
-    if ((d.lda & 3) != 0) return RSP_EINVAL;
-  }
-  if (d.M == 0) return RSP_OK;
-  if (d.res && d.ldr <= 0) return RSP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (d.Ahi && d.Alo) return rsp_gemm_dma_dispatch(d, s);
-  if (d.N > 64) return launch_gemm<128, 128, 2, 2>(d, s);
-  if (d.N > 32) return launch_gemm<128, 64, 2, 2>(d, s);
-  return launch_gemm<128, 32, 4, 1>(d, s);
+int rsp_gemm_launch_f32a(const RspGemmPlan& p, const RspGemmDesc& d, hipStream_t s) {
+  if (p.bn == 128) return launch_gemm<128, 128, 2, 2>(d, s);
+  if (p.bn == 64) return launch_gemm<128, 64, 2, 2>(d, s);
+  if (p.bn == 32) return launch_gemm<128, 32, 4, 1>(d, s);
+  return RSP_EINVAL;
 }

@@ -20,6 +20,7 @@
 // accumulators through the (then idle) ring and stores row-wise, 4 consecutive columns per thread.
 #include <type_traits>
 #include "rsp_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -673,150 +674,11 @@ int launch_dma(const RspGemmDesc& d, hipStream_t s) {
 
 }  // namespace
 
-bool rsp_gemm_s2_eligible(const RspGemmDesc& d);                       // gemm_s2.hip
-int rsp_gemm_s2_auto(const RspGemmDesc& d);
-int rsp_gemm_s2_dispatch(const RspGemmDesc& d, int var, hipStream_t s);
-bool rsp_gemm_pp_eligible(const RspGemmDesc& d);                       // gemm_pp.hip
-int rsp_gemm_pp_auto(const RspGemmDesc& d);
-int rsp_gemm_pp_dispatch(const RspGemmDesc& d, int var, hipStream_t s);
-
-// called from rsp_gemm (gemm.hip) when the descriptor carries A planes
-int rsp_gemm_dma_dispatch(const RspGemmDesc& d, hipStream_t s) {
-  if (d.a_rows <= 0) return RSP_EINVAL;
-  // tile hints 40 + v: the two-blocks-per-CU persistent kernel (gemm_s2.hip), experiment variant v
-  if ((d.tile_hint & 0xff) >= 40 && (d.tile_hint & 0xff) < 168) {
-    if (!rsp_gemm_s2_eligible(d)) return RSP_EINVAL;
-    return rsp_gemm_s2_dispatch(d, (d.tile_hint & 0xff) - 40, s);
-  }
-  // tile hint 200: the ping-pong kernel (gemm_pp.hip), forced; product rule (round 5): wherever its 256 x 256 tiles fill
-  // the CUs for several rounds
-  // 200 + v: gemm_pp.hip, variant v: bit 0 = the 128 x 256 tile; development builds: 4 / 8 / 12 ablations, 16 = time stamps
-  if ((d.tile_hint & 0xff) >= 200) {
-    const int v = (d.tile_hint & 0xff) - 200;
-    return rsp_gemm_pp_dispatch(d, (v & 16) ? 32 | (v & 1) : v, s);
-  }
-  if ((d.tile_hint & 0xff) == 0) {
-    const int bm = rsp_gemm_pp_auto(d);
-    if (bm) return rsp_gemm_pp_dispatch(d, bm == 128 ? 1 : 0, s);
-  }
-  // product rule (round 3): the two-blocks-per-CU persistent kernel wherever it has a specialised epilogue -- 7-20 %
-  // faster than the kernels below on the ViT-H encoder shapes (tools/gemm_s2_exp.py).  Tile hint 1 = "the round-2 rule".
-  if ((d.tile_hint & 0xff) == 0 && rsp_gemm_s2_auto(d)) return rsp_gemm_s2_dispatch(d, 0, s);
-  if (d.ct_W > 0 && (d.res || d.res_hi)) return RSP_EINVAL;   // no caller needs a residual on a ConvTranspose
-  if (d.res_hi && (!d.res_lo || d.res || d.res_rows <= 0 || (d.N & 3))) return RSP_EINVAL;
-  if (d.hd_out && (!d.hd_hyper || d.ct_W <= 0 || d.N != (d.ct_dy < 0 ? 128 : 64) || d.hd_rows <= 0)) return RSP_EINVAL;
-  if (d.ct_W > 0 && d.ct_dy < 0 && (d.N & 127)) return RSP_EINVAL;
-  if (d.ct_W > 0 && d.Chi && ((d.N >> (d.ct_dy < 0 ? 2 : 1)) & 31)) return RSP_EINVAL;
-  if (d.conv_k != 0 && (d.conv_C % BK) != 0) return RSP_EINVAL;
-  if (d.conv_k != 0 && (long long)d.conv_H * d.conv_W * ((d.M + (long long)d.conv_Ho * d.conv_Wo - 1) / ((long long)d.conv_Ho * d.conv_Wo)) > 0x7fffffffLL)
-    return RSP_EINVAL;   // the implicit-GEMM loader indexes input pixels with 32 bits
-  if (d.ln_gamma && (!d.ln_beta || !(d.Chi && d.Clo) || d.C || d.ct_W <= 0 || d.ct_dy >= 0 || d.N != 256 || d.res ||
-                     d.c_rowmap || d.hd_out))
-    return RSP_EINVAL;
-  if (d.hd_out && (d.C || d.Chi || d.res || d.c_rowmap)) return RSP_EINVAL;
-  if ((d.pl_col0 || d.c_ncols) && (d.ct_W > 0 || (d.pl_col0 & 31) || (d.c_ncols & 3) || d.pl_col0 < 0 || (d.N & 3)))
-    return RSP_EINVAL;   // column-range outputs: plain GEMMs only, plane range on a 32-column boundary
-  const bool f8 = RSP_PLANE_IS_F8(d.a_scale_log2);   // A and W "lo" planes are cat8 planes (the caller pairs them)
-  if (f8 && (d.conv_k != 0 || d.N <= 64)) return RSP_EINVAL;
-  if (RSP_PLANE_IS_F8(d.c_scale_log2) && d.Chi && ((d.N & 3) || d.ct_W > 0)) return RSP_EINVAL;
-  auto nblk = [&](int bm, int bn) { return (long long)((d.N + bn - 1) / bn) * ((d.M + bm - 1) / bm); };
-  // Tile rule (tools/gemm_sweep.py on MI355X; run-to-run spread is a few %): the register-pipelined loops win
-  // everywhere; 256x256 needs >= 4 rounds of blocks over the 256 CUs, 256x128 >= 2, else 128x128 (2 blocks/CU).
-  if (d.conv_k != 0) {   // implicit-GEMM convolutions: CONV instantiations of the same kernels
-    if (d.N > 128 && ((d.tile_hint & 0xff) == 17 || ((d.tile_hint & 0xff) <= 1 && nblk(256, 256) >= 1024)))
-      return launch_dma<256, 256, 2, 4, 2, 0, 0, 2, true>(d, s);
-    if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 0, 0, 1, true>(d, s);
-    if (d.N > 32) return launch_dma<128, 64, 2, 2, 3, 0, 0, 0, true>(d, s);
-    return launch_dma<128, 32, 4, 1, 3, 0, 0, 0, true>(d, s);
-  }
-  int tile = d.tile_hint & 0xff;
-  if (tile <= 1) {
-    // short K (<= 8 K tiles): the block is mostly prologue + epilogue, two 128x128 blocks per CU overlap them
-    // (round 2, tools/gemm_sweep.py on the SAM-decoder shapes M = 3.3 M rows: with N = 256 the 256x256 tile reads every A
-    // row once instead of twice and is 7-14 % faster even at 4-8 K tiles; N = 128 stays with 128x128)
-    if (d.K <= 256) tile = (d.N > 128 && nblk(256, 256) >= 1024) ? 17 : 14;
-    else {
-      // cost = rounds over the 256 CUs x tile area / relative efficiency (tools/gemm_sweep.py: 256x256 1.0,
-      // 256x128 0.96, 128x128 0.88 with its two blocks per CU sharing the matrix pipe): the partially filled last
-      // round is what separates the candidates (e.g. M = 39200, N = 1280: 7 rounds of 256x128 vs 6 of 128x128)
-      auto cost = [&](int bm, int bn, int bpc, double eff) {
-        const long long nb = nblk(bm, bn), slots = 256LL * bpc;
-        return (double)((nb + slots - 1) / slots) * bm * bn * bpc / eff;
-      };
-      double best = cost(128, 128, 2, 0.88);
-      tile = 14;
-      if (d.N > 64) { const double c = cost(256, 128, 1, 0.96); if (c < best) { best = c; tile = 18; } }
-      if (d.N > 128) { const double c = cost(256, 256, 1, 1.0); if (c <= best) { best = c; tile = 17; } }
-      // round 2 (tools/gemm_exp.py, ViT-H shapes): from two full rounds of 256x256 tiles on, the big tile wins even
-      // with a ragged last round (blocks do not run in lockstep): qkv 350 vs 322 TFLOP/s, lin2 368 vs 352
-      // (K = 1280 with only 3 rounds -- the proj shape -- stays with the small tile: 279 vs 252)
-      if (d.N > 128 && (nblk(256, 256) >= 1024 || (nblk(256, 256) >= 512 && d.K >= 2048))) tile = 17;
-    }
-  }
-  if (f8) {   // fp8-corrected product: the three tiles the rule above picks
-    // with a third less matrix time per tile the big tile already pays from two rounds of blocks on, also at K = 1280
-    // (proj shape, tools/gemm_f8_exp.py: 337 vs 301 TFLOP/s)
-    if ((d.tile_hint & 0xff) <= 1 && d.N > 128 && nblk(256, 256) >= 512) tile = 17;
-    if (tile == 17 && d.N > 128) return launch_dma<256, 256, 2, 4, 2, 0, 0, 2, false, 0, true>(d, s);
-    if ((tile == 18 || tile == 17) && d.N > 64) return launch_dma<256, 128, 4, 2, 2, 0, 0, 2, false, 0, true>(d, s);
-    return launch_dma<128, 128, 2, 2, 2, 0, 0, 1, false, 0, true>(d, s);
-  }
-  switch (tile) {   // hints >= 4 are benchmarking variants of the same arithmetic
-    case 3: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2>(d, s); break;
-    case 2: if (d.N > 64) return launch_dma<256, 128, 4, 2, 3>(d, s); break;
-    case 4: if (d.N > 64) return launch_dma<256, 128, 4, 2, 2>(d, s); break;
-    case 5: if (d.N > 64) return launch_dma<128, 128, 2, 2, 4>(d, s); break;
-    case 6: if (d.N > 64) return launch_dma<128, 128, 2, 2, 3>(d, s); break;
-#ifdef RSP_S2_ABLATIONS   /* development builds only (RSP_DEV_BUILD=1): these compute WRONG results on purpose */
-    case 7: if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 1>(d, s); break;   // ablation: no DMA
-    case 8: if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 2>(d, s); break;   // ablation: no MFMA
-    case 9: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 1>(d, s); break;
-    case 10: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 2>(d, s); break;
-    case 15: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 1, 0, 1>(d, s); break;   // ... without the DMA
-    case 16: if (d.N > 64) return launch_dma<256, 128, 4, 2, 2, 1, 0, 1>(d, s); break;
-#else
-    case 7: case 8: case 9: case 10: case 15: case 16: return RSP_EINVAL;
-#endif
-    case 11: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 0, 0, 1>(d, s); break;   // register-pipelined loops
-    case 12: if (d.N > 64) return launch_dma<256, 128, 4, 2, 2, 0, 0, 1>(d, s); break;
-    case 13: if (d.N > 64) return launch_dma<256, 128, 4, 2, 3, 0, 0, 1>(d, s); break;
-    case 14: if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 0, 0, 1>(d, s); break;
-    case 17: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 0, 0, 2>(d, s); break;   // ... with the DMA spread out
-    case 18: if (d.N > 64) return launch_dma<256, 128, 4, 2, 2, 0, 0, 2>(d, s); break;
-    case 19: if (d.N > 64) return launch_dma<256, 128, 4, 2, 3, 0, 0, 2>(d, s); break;
-    case 20: if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 0, 0, 2>(d, s); break;
-    case 21: return launch_dma<128, 64, 2, 2, 3, 0, 0, 1>(d, s);                         // narrow tile, 3-deep ring
-    case 22: return launch_dma<128, 64, 2, 2, 4, 0, 0, 1>(d, s);
-    case 31: if (d.N > 128) return launch_dma<256, 256, 2, 4, 2, 0, 0, 2, false, 1>(d, s); break;   // pass-major MFMA order
-    case 32: if (d.N > 64) return launch_dma<256, 128, 4, 2, 2, 0, 0, 2, false, 1>(d, s); break;
-    default: break;
-  }
-  if (d.N > 64) return launch_dma<128, 128, 2, 2, 2, 0, 0, 1>(d, s);
-  if (d.N > 32) return launch_dma<128, 64, 2, 2, 3>(d, s);
-  return launch_dma<128, 32, 4, 1, 3>(d, s);
-}
-
-// which kernel rsp_gemm runs for a descriptor of the plane path (profiler labels, tools): 1 = gemm_s2 (two blocks per
-// CU, 256 x 128), 0 = one of this file's tiles
-int rsp_gemm_s2_epilogue_of(const RspGemmDesc& d);                     // gemm_s2.hip
-extern "C" int rsp_gemm_s2_epilogue(const RspGemmDesc* d) {
-  if (!d || !rsp_gemm_uses_s2(d)) return -1;
-  const int h = d->tile_hint & 0xff;
-  if (h >= 40 + 64) return 64;                                         // hint 104: the run-time epilogue, forced
-  return rsp_gemm_s2_epilogue_of(*d);
-}
-
-extern "C" int rsp_gemm_uses_s2(const RspGemmDesc* d) {
-  if (!d || !(d->Ahi && d->Alo)) return 0;
-  const int h = d->tile_hint & 0xff;
-  if (h >= 40 && h < 168) return 1;
-  return h == 0 && !rsp_gemm_pp_auto(*d) && rsp_gemm_s2_auto(*d);
-}
-
-extern "C" int rsp_gemm_uses_pp(const RspGemmDesc* d) {
-  if (!d || !(d->Ahi && d->Alo)) return 0;
-  const int h = d->tile_hint & 0xff;
-  if (h >= 200) return rsp_gemm_pp_eligible(*d) ? (((h - 200) & 1) ? 128 : 256) : 0;
-  if (h != 0) return 0;
-  return rsp_gemm_pp_auto(*d);
+int rsp_gemm_launch_dma(const RspGemmPlan& p, const RspGemmDesc& d, hipStream_t s) {
+#define X(ID, BM, BN, WGM, WGN, NBUF, PIPE, CONV, ORD, F8, ABL)                                                          \
+  if (p.bm == BM && p.bn == BN && p.nbuf == NBUF && p.pipe == PIPE && p.conv == CONV && p.ord == ORD && p.f8 == F8 && p.var == ABL) \
+    return launch_dma<BM, BN, WGM, WGN, NBUF, ABL, 0, PIPE, CONV, ORD, F8>(d, s);
+  RSP_GEMM_DMA_TILES(X)
+#undef X
+  return RSP_EINVAL;
 }

@@ -38,9 +38,10 @@
 // its POWER limit, and a half-empty last round simply clocks higher -- the idle CUs are not the loss they look like.
 // profiles/r5_gemm_pp_split_tail_negative/.)
 // Scope: what gemm_s2.hip's specialised epilogues cover (plain plane-path GEMMs); chosen by rsp_gemm for shapes with
-// enough tiles to fill the 256 CUs several times (rsp_gemm_pp_auto).
+// enough tiles to fill the 256 CUs several times (pp_auto in gemm_plan.hip).
 #include <type_traits>
 #include "rsp_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -60,8 +61,6 @@ struct PPP {
   unsigned long long* trace;     // tools only (VAR bit 5): per block, tile and group {loop start, loop end, epilogue end, hw id}
 };
 unsigned long long* g_pp_trace = nullptr;
-
-constexpr int E_RES = 1, E_GELU = 2, E_C = 4, E_PL = 8, E_RMAP = 16;
 
 template <int I, int N, class F>
 __device__ __forceinline__ void sfor(F&& f) {
@@ -437,54 +436,12 @@ int launch_pp(const RspGemmDesc& d, hipStream_t s) {
 
 }  // namespace
 
-bool rsp_gemm_s2_eligible(const RspGemmDesc& d);                       // gemm_s2.hip
-int rsp_gemm_s2_epilogue_of(const RspGemmDesc& d);
-
-// the descriptors this kernel implements: gemm_s2.hip's, with one of its compile-time epilogues, K >= 128 (the K loop is
-// peeled by up to five steps at its end)
-bool rsp_gemm_pp_eligible(const RspGemmDesc& d) {
-  if (!rsp_gemm_s2_eligible(d) || d.K < 128) return false;
-  const int e = rsp_gemm_s2_epilogue_of(d);
-  return e >= 0 && e != 64;
-}
-
-// product rule: 0 = not this kernel; 256 / 128 = the block tile's rows.  One block per CU and a static walk: a ragged last
-// round idles whole CUs, and the exposed epilogue wants a long K loop.  Measured on the ViT-B / L / H encoder shapes
-// (profiles/r5_gemm_pp/pp_{base,large,huge}.txt, TFLOP/s against gemm_s2): 256 x 256 wins wherever its tiles fill >= 2
-// rounds of the 256 CUs to >= 80 % (+6 ... +16 %; +1 ... 3 % at 2.5 rounds); 128 x 256 (phases of 12 MFMAs: 440 instead of 384
-// cycles each) only pays for residual GEMMs whose 256-row tiles do not fill the chip (ViT-B proj / lin2: +3 ... 9 %).
-int rsp_gemm_pp_auto(const RspGemmDesc& d) {
-  if (!rsp_gemm_pp_eligible(d) || d.K < 512) return 0;
-  const long long nbn = (d.N + BN - 1) / BN;
-  const long long nt256 = (long long)((d.M + 255) / 256) * nbn, r256 = (nt256 + 255) / 256;
-  if (nt256 >= 512 && nt256 * 100 >= r256 * 256 * 80) return 256;
-  const long long nt128 = (long long)((d.M + 127) / 128) * nbn, r128 = (nt128 + 255) / 256;
-  if (d.res && nt128 >= 512 && nt128 * 100 >= r128 * 256 * 90) return 128;
-  return 0;
-}
-
-// var: bit 0 = the 128-row tile; development builds: bit 2 = no DMA in the K loop, bit 3 = no epilogue, bit 5 = time stamps
-int rsp_gemm_pp_dispatch(const RspGemmDesc& d, int var, hipStream_t s) {
-  if (!rsp_gemm_pp_eligible(d)) return RSP_EINVAL;
-  const int epi = rsp_gemm_s2_epilogue_of(d);
-#ifdef RSP_S2_ABLATIONS          /* RSP_DEV_BUILD=1 python -m rsprompter_amd.build; tools/gemm_pp_exp.py */
-#define PP_VCASE(V, E) if (var == V && epi == (E)) return launch_pp<(E), V, 256>(d, s); \
-                       if (var == V + 1 && epi == (E)) return launch_pp<(E), V, 128>(d, s)
-  PP_VCASE(4, E_PL | E_GELU); PP_VCASE(32, E_PL | E_GELU); PP_VCASE(4, E_C | E_RES); PP_VCASE(32, E_C | E_RES);
-  PP_VCASE(32, E_C | E_PL);
-#undef PP_VCASE
-#endif
-  if (var & ~1) return RSP_EINVAL;
-#define PP_CASE(E) if (epi == (E)) return (var & 1) ? launch_pp<(E), 0, 128>(d, s) : launch_pp<(E), 0, 256>(d, s)
-  PP_CASE(E_C);
-  PP_CASE(E_C | E_RES);
-  PP_CASE(E_C | E_RES | E_RMAP);
-  PP_CASE(E_C | E_PL);
-  PP_CASE(E_C | E_PL | E_RMAP);
-  PP_CASE(E_PL);
-  PP_CASE(E_PL | E_GELU);
-  PP_CASE(E_C | E_GELU);
-#undef PP_CASE
+int rsp_gemm_launch_pp(const RspGemmPlan& p, const RspGemmDesc& d, hipStream_t s) {
+#define X(V, E) if (p.var == V && p.epi == (E)) return p.bm == 128 ? launch_pp<(E), V, 128>(d, s) : launch_pp<(E), V, 256>(d, s);
+#define X0(E) X(0, E)
+  RSP_GEMM_EPILOGUES(X0) RSP_GEMM_PP_VARIANTS(X)
+#undef X0
+#undef X
   return RSP_EINVAL;
 }
 

@@ -29,6 +29,7 @@
 #include <atomic>
 #include <type_traits>
 #include "rsp_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -78,10 +79,6 @@ unsigned* s2_ticket_base() {
   }
   return b;
 }
-
-// epilogue specialisations (EPI template argument): bit flags of what the tile's outputs need; E_GENERIC = everything at
-// run time (all modes of the descriptor, slow: branches per 4 outputs)
-constexpr int E_RES = 1, E_GELU = 2, E_C = 4, E_PL = 8, E_RMAP = 16, E_GENERIC = 64;
 
 template <int I, int N, class F>
 __device__ __forceinline__ void sfor(F&& f) {
@@ -575,86 +572,13 @@ int launch_s2(const RspGemmDesc& d, hipStream_t s) {
 
 }  // namespace
 
-// the shapes / modes this kernel implements (everything else stays with gemm_dma.hip)
-bool rsp_gemm_s2_eligible(const RspGemmDesc& d) {
-  if (!(d.Ahi && d.Alo) || d.conv_k != 0 || d.ct_W > 0 || d.ln_gamma || d.hd_out) return false;
-  if (RSP_PLANE_IS_F8(d.a_scale_log2)) return false;
-  if ((d.N & 3) || (d.K & 31) || d.K < 64 || d.M <= 0 || d.a_rows <= 0) return false;
-  if (d.C && ((d.ldc & 3) || (reinterpret_cast<uintptr_t>(d.C) & 15))) return false;
-  if (d.res && ((d.ldr & 3) || (reinterpret_cast<uintptr_t>(d.res) & 15))) return false;
-  if (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15)) return false;
-  if (d.res_hi && (!d.res_lo || d.res || d.res_rows <= 0)) return false;
-  if ((d.pl_col0 & 31) || (d.c_ncols & 3) || d.pl_col0 < 0) return false;
-  const long long brows = d.b_rows > 0 ? d.b_rows : d.N;
-  const long long kb = d.K / 32;
-  if (kb * d.a_rows * 64 >= (1LL << 31) || kb * brows * 64 >= (1LL << 31)) return false;   // 32-bit buffer offsets
-  return true;
-}
-
-// the epilogue specialisation that serves this descriptor (E_GENERIC: only the run-time form does)
-static int s2_epilogue_of(const RspGemmDesc& d) {
-  // the branch-free epilogue addresses every tensor it touches with 32-bit buffer offsets
-  const long long GB2 = 1LL << 31;
-  const long long c_bytes = d.C ? (d.c_rowmap ? (long long)d.c_rows * d.ldc * 4 : 0) : 0;   // no row map: tile-relative
-  const long long pl_bytes = d.Chi ? (((long long)((d.N - d.pl_col0) >> 5) * d.c_rows) << 6) : 0;
-  const long long res_bytes = d.res ? (long long)(d.res_mod > 0 ? d.res_mod : (d.c_rowmap ? d.c_rows : d.M)) * d.ldr * 4 : 0;
-  const bool fast = !(d.N & 63) && !(d.c_ncols & 63) && !(d.pl_col0 & 63) && !d.res_hi &&
-                    (d.act == RSP_ACT_NONE || d.act == RSP_ACT_GELU) && !(d.Chi && RSP_PLANE_IS_F8(d.c_scale_log2)) &&
-                    !(d.c_rowmap && d.c_rows <= 0) && c_bytes < GB2 && pl_bytes < GB2 && res_bytes < GB2 &&
-                    !(d.res && d.res_bmap) &&      /* gathered residual rows: size unknown here, generic path */
-                    (long long)256 * d.ldc * 4 < GB2;
-  if (!fast) return E_GENERIC;
-  return (d.res ? E_RES : 0) | (d.act == RSP_ACT_GELU ? E_GELU : 0) | (d.C ? E_C : 0) | (d.Chi ? E_PL : 0) |
-         (d.c_rowmap ? E_RMAP : 0);
-}
-
-// 1: this kernel is the product choice for the descriptor (eligible, a specialised epilogue exists, enough tiles to fill
-// the 512 block slots once); 0: stay with gemm_dma.hip
-int rsp_gemm_s2_epilogue_of(const RspGemmDesc& d);
-int rsp_gemm_s2_auto(const RspGemmDesc& d) {
-  const int e = rsp_gemm_s2_epilogue_of(d);
-  const bool have = e >= 0 && e != E_GENERIC;
-  const long long nt = (long long)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-  return have && nt >= 256 && d.K >= 128;
-}
-
-// tests / profiler labels: the epilogue form rsp_gemm_s2_dispatch(d, 0) runs (bit flags E_RES = 1, E_GELU = 2, E_C = 4,
-// E_PL = 8, E_RMAP = 16; 64 = the run-time form), -1 for a descriptor this kernel does not implement
-int rsp_gemm_s2_epilogue_of(const RspGemmDesc& d) {
-  if (!rsp_gemm_s2_eligible(d)) return -1;
-  const int e = s2_epilogue_of(d);
-  const bool have = e == E_C || e == (E_C | E_RES) || e == (E_C | E_RES | E_RMAP) || e == (E_C | E_PL) || e == (E_C | E_PL | E_RMAP) || e == E_PL ||
-                    e == (E_PL | E_GELU) || e == (E_C | E_GELU);
-  return have ? e : E_GENERIC;
-}
-
-// var: experiment switches of the kernel (0 = product); the epilogue specialisation follows from the descriptor
-int rsp_gemm_s2_dispatch(const RspGemmDesc& d, int var, hipStream_t s) {
-  const int epi = (var & 64) ? E_GENERIC : s2_epilogue_of(d);
-  var &= 63;
-#define S2_CASE(V, E) if (var == V && epi == (E)) return launch_s2<V, (E)>(d, s)
-  S2_CASE(0, E_C);                 // plain
-  S2_CASE(0, E_C | E_RES);         // proj (global layers), lin2, patch embed
-  S2_CASE(0, E_C | E_RES | E_RMAP); // proj of a windowed layer (row scatter)
-  S2_CASE(0, E_C | E_PL);          // qkv (column ranges), fp32 + planes
-  S2_CASE(0, E_C | E_PL | E_RMAP); // qkv of a windowed layer: token rows scattered to window order
-  S2_CASE(0, E_PL);                // planes only
-  S2_CASE(0, E_PL | E_GELU);       // lin1
-  S2_CASE(0, E_C | E_GELU);
-  S2_CASE(0, E_GENERIC);
-#ifdef RSP_S2_ABLATIONS          /* tools/gemm_s2_exp.py time: RSP_DEV_BUILD=1 python -m rsprompter_amd.build */
-  S2_CASE(1, E_C | E_RES); S2_CASE(1, E_PL | E_GELU);          // raised priority around the DMA slots (round 4)
-  S2_CASE(2, E_C | E_RES); S2_CASE(2, E_PL | E_GELU); S2_CASE(2, E_PL); S2_CASE(8, E_PL);   // no stores
-  S2_CASE(4, E_C | E_RES); S2_CASE(4, E_PL | E_GELU);          // no DMA in the loop
-  S2_CASE(8, E_C | E_RES); S2_CASE(8, E_PL | E_GELU);          // no epilogue
-  S2_CASE(16, E_C | E_RES); S2_CASE(16, E_PL | E_GELU);        // cache-hot DMA sources
-  S2_CASE(32, E_C | E_RES); S2_CASE(32, E_PL | E_GELU);        // time stamps
-  S2_CASE(33, E_C | E_RES); S2_CASE(33, E_PL | E_GELU);        // the six DMA slots of a step as one burst (round 4)
-  S2_CASE(1, E_C); S2_CASE(1, E_C | E_PL);
-#endif
-#undef S2_CASE
-  if (var != 0) return RSP_EINVAL;
-  return launch_s2<0, E_GENERIC>(d, s);       // any other combination of outputs
+int rsp_gemm_launch_s2(const RspGemmPlan& p, const RspGemmDesc& d, hipStream_t s) {
+#define X(V, E) if (p.var == V && p.epi == (E)) return launch_s2<V, (E)>(d, s);
+#define X0(E) X(0, E)
+  RSP_GEMM_EPILOGUES(X0) X0(E_GENERIC) RSP_GEMM_S2_VARIANTS(X)
+#undef X0
+#undef X
+  return RSP_EINVAL;
 }
 
 #ifdef RSP_S2_ABLATIONS

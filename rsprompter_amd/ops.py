@@ -249,35 +249,23 @@ class PlaneWeight:
         self.bias = None
 
 
-def _dma_tile_name(m, n, hint=0, conv=False, k=1 << 30, f8=False):
-    """Mirror of the tile choice in rsp_gemm_dma_dispatch (gemm_dma.hip) - profiler labels only."""
-    nblk = lambda bm, bn: -(-n // bn) * -(-m // bm)
-    small = '128x128' if n > 64 else ('128x64' if n > 32 else '128x32')
-    hint &= 0xff
-    if hint == 1:
-        hint = 0                     # "the round-2 rule"
-    if hint in (3, 9, 10, 11, 15, 17, 31):
-        return '256x256'
-    if hint in (2, 4, 12, 13, 16, 18, 19, 32):
-        return '256x128'
-    if hint != 0:
-        return small
-    if conv:
-        return '256x256' if n > 128 and nblk(256, 256) >= 1024 else small
-    if f8 and n > 128 and nblk(256, 256) >= 512:
-        return '256x256'
-    if k <= 256:
-        return '256x256' if n > 128 and nblk(256, 256) >= 1024 else small
-    if n <= 64:
-        return small
-    cost = lambda bm, bn, bpc, eff: -(-nblk(bm, bn) // (256 * bpc)) * bm * bn * bpc / eff
-    best, name = cost(128, 128, 2, 0.88), '128x128'
-    c = cost(256, 128, 1, 0.96)
-    if c < best:
-        best, name = c, '256x128'
-    if n > 128 and (cost(256, 256, 1, 1.0) <= best or nblk(256, 256) >= 1024 or (nblk(256, 256) >= 512 and k >= 2048)):
-        name = '256x256'
-    return name
+def _gemm_plan(d):
+    """RspGemmPlan of a descriptor (rsp_gemm_plan: the kernel rsp_gemm launches for it; host code, no device work), or None
+    for one that rsp_gemm refuses."""
+    p = _lib_real.RspGemmPlan()
+    return p if _lib_real.load().rsp_gemm_plan(d, p) == 0 else None
+
+
+_GEMM_KERNEL_NAMES = {CONST['RSP_GEMM_KERNEL_F32A']: 'gemm_f16x3_kernel', CONST['RSP_GEMM_KERNEL_DMA']: 'gemm_f16x3_dma_kernel',
+                      CONST['RSP_GEMM_KERNEL_S2']: 'gemm_f16x3_s2_kernel', CONST['RSP_GEMM_KERNEL_PP']: 'gemm_f16x3_pp_kernel'}
+
+
+def _gemm_label(d):
+    """Profiler label of rsp_gemm(d): the kernel and block tile of its plan (bench.py groups its per-kernel table by it)."""
+    p = _gemm_plan(d)
+    if p is None or p.kernel not in _GEMM_KERNEL_NAMES:
+        return 'rsp_gemm'               # refused, or M == 0: nothing is launched
+    return f"{'gemm_f16f8_dma_kernel' if p.f8 else _GEMM_KERNEL_NAMES[p.kernel]}<{p.bm}x{p.bn}>"
 
 
 PP_AUTO = True      # False: rsp_gemm's choice of the ping-pong kernel (csrc/gemm_pp.hip) is overridden by gemm_s2 (A/B runs)
@@ -289,8 +277,9 @@ def gemm(a, w, *, out=None, bias="auto", res=None, act=ACT_NONE, a_rowmap=None, 
          out_f8=False, plan_only=False):
     """C = act(A @ W^T + bias) + res   (see RspGemmDesc in include/rsp_hip.h).
 
-    plan_only=True launches nothing and returns rsp_gemm_s2_epilogue(desc): -1 = a gemm_dma.hip / gemm.hip tile serves
-    the call, otherwise the epilogue form of gemm_f16x3_s2_kernel (tests assert which specialisation they exercise).
+    plan_only launches nothing and answers from rsp_gemm_plan(desc).  True: -1 = a gemm_dma.hip / gemm.hip tile (or the
+    ping-pong kernel) serves the call, otherwise the epilogue form of gemm_f16x3_s2_kernel (tests assert which
+    specialisation they exercise); 'pp': the rows (256 / 128) of the gemm_f16x3_pp_kernel tile that serves it, else 0.
 
     a: [rows, K] fp32 (row stride = a.stride(0)) or, with conv=(k, stride, pad),
        an NHWC tensor [B, H, W, C].
@@ -379,19 +368,15 @@ def gemm(a, w, *, out=None, bias="auto", res=None, act=ACT_NONE, a_rowmap=None, 
     d.act = act
     d.a_scale_log2 = plane_word(a_scale_log2, w_f8)
     d.alpha = math.ldexp(1.0, -(a_scale_log2 + w.scale_log2))
-    if not PP_AUTO and is_planes and tile_hint == 0 and _lib_real.load().rsp_gemm_uses_pp(d):
+    plan = _gemm_plan(d) if plan_only or not PP_AUTO else None
+    if not PP_AUTO and tile_hint == 0 and plan is not None and plan.kernel == CONST['RSP_GEMM_KERNEL_PP']:
         d.tile_hint = 40        # A/B switch (tools/ab_bench.py "ops.PP_AUTO=False"): the round-3 kernel for these shapes
+        plan = _gemm_plan(d)
     if plan_only == 'pp':       # 256 / 128: gemm_f16x3_pp_kernel (csrc/gemm_pp.hip) with that tile serves the call, else 0
-        return int(_lib_real.load().rsp_gemm_uses_pp(d)) if is_planes else 0
+        return plan.bm if plan is not None and plan.kernel == CONST['RSP_GEMM_KERNEL_PP'] else 0
     if plan_only:
-        return int(_lib_real.load().rsp_gemm_s2_epilogue(d)) if is_planes else -1
-    tile = _dma_tile_name(m, n, tile_hint, conv is not None, w.K, w_f8) if is_planes else ('128x128' if n > 64 else ('128x64' if n > 32 else '128x32'))
-    kname = ('gemm_f16f8_dma_kernel' if w_f8 else 'gemm_f16x3_dma_kernel') if is_planes else 'gemm_f16x3_kernel'
-    if is_planes and _prof is not None and _lib_real.load().rsp_gemm_uses_s2(d):
-        kname, tile = 'gemm_f16x3_s2_kernel', '256x128'         # the kernel rsp_gemm really launches (profiler label)
-    elif is_planes and _prof is not None and _lib_real.load().rsp_gemm_uses_pp(d):
-        kname, tile = 'gemm_f16x3_pp_kernel', f'{_lib_real.load().rsp_gemm_uses_pp(d)}x256'
-    _timed(f'{kname}<{tile}>', 2.0 * m * n * w.K, 4.0 * (m * w.K + m * n) + 4.0 * n * w.K,
+        return plan.epi if plan is not None and plan.kernel == CONST['RSP_GEMM_KERNEL_S2'] else -1
+    _timed(_gemm_label(d) if _prof is not None else None, 2.0 * m * n * w.K, 4.0 * (m * w.K + m * n) + 4.0 * n * w.K,
            lambda: _lib.check(lib.rsp_gemm(d, _stream()), "rsp_gemm"),
            detail=f'M={m} N={n} K={w.K}' + (' conv' if conv is not None else ''))
     if DEBUG_FINITE and out is not None and not bool(torch.isfinite(out).all()):

@@ -53,7 +53,7 @@ def test_ctypes_struct_layout_matches_the_c_compiler():
     cc = cc if os.path.exists(cc) else shutil.which('cc')
     if not cc:
         pytest.skip('no host C compiler')
-    assert len(_lib.STRUCTS) == 8
+    assert len(_lib.STRUCTS) == 9
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "rsp_hip.h"', 'int main(void) {']
     for name, cls in _lib.STRUCTS.items():
         lines.append(f'  printf("{name} sizeof %zu\\n", sizeof({name}));')
