@@ -884,6 +884,39 @@ int rsp_run_components_select(const int64_t* comp_offs, int32_t k, int64_t C, co
                               int32_t min_area, int32_t keep_largest, int32_t slot, int32_t* keep, int32_t* changed,
                               rsp_stream_t stream);
 
+/* Run-domain morphology (csrc/run_morphology.hip): erosion of every mask of a run table by the (2 r + 1)^2      */
+/* square in work proportional to the column pieces times log r; replaces cv2.erode / cv2.dilate on dense masks and, with the    */
+/* difference at the end, boundary-iou-api's mask_to_boundary (decode, copyMakeBorder, d iterations of cv2.erode, encode per      */
+/* mask on the host).  Input of the first two: counts [k, cap] / n [k] of k masks on ONE (H, W) canvas, CANONICAL as             */
+/* rsp_rle_union writes them (rsprompter_amd/ops.py canonicalises a table with a group-of-one union first); a row with n <= 0   */
+/* has no pieces, n beyond cap is read up to cap.  H * W >= 2^31 and k * (W + 2 pad) >= 2^31 are refused (RSP_EINVAL).  A TABLE  */
+/* is col / y0 / y1 int32 [P]: the intervals [y0, y1) of column col = instance * Wt + X, sorted by (col, y0), disjoint and not   */
+/* touching within a column.  No call reads the host, none uses atomics; every output slot is stored once.                       */
+/* 1. Level 1: the column pieces of every ones-run shrunk to [y0 + ry, y1 - ry), empty ones dropped.  border = 1: an end on the  */
+/* canvas edge stays and `pad` columns [0, H) stand on either side (Wt = W + 2 pad, canvas column x is X = x + pad); border = 0  */
+/* takes pad = 0.  ry <= H, pad <= W.  _count: piece_cnt int32 [k] (pad columns included); the caller's exclusive sum is          */
+/* piece_offs int64 [k + 1], P = piece_offs[k] < 2^31.  ry = pad = border = 0 gives the pieces themselves.                       */
+int rsp_run_morph_pieces_count(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W, int32_t ry,
+                               int32_t pad, int32_t border, int32_t* piece_cnt, rsp_stream_t stream);
+int rsp_run_morph_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W, int32_t ry,
+                         int32_t pad, int32_t border, const int64_t* piece_offs, int64_t P, int32_t* col, int32_t* y0, int32_t* y1,
+                         rsp_stream_t stream);
+/* 2. Join, one lane per interval of table A (PA intervals on strips of Wa columns) against column X + shift of table B (PB      */
+/* intervals, strips of Wb columns, b_offs int32 [k Wb + 1] = the first interval of every column): op 0 = the intersections,     */
+/* none when X + span > Wa or X + shift is outside B's strip; op 1 = A minus B (all of A where B has no such column).  The       */
+/* output column is X + out_shift on strips of Wout columns; an interval whose output column falls outside writes nothing.       */
+/* _count: cnt int32 [PA]; the caller's exclusive sum is out_offs int64 [PA + 1], total = out_offs[PA] < 2^31.  emit_keys = 0:    */
+/* the result as a table (o_col, o_y0, o_y1 [total]); emit_keys = 1: as rsp_rle_union's intervals on the (H, Wout) canvas,       */
+/* keys int64 [total] = instance << 31 | pixel start, ends int32 [total], in key order as they stand.                            */
+int rsp_run_morph_join_count(int32_t op, const int32_t* a_col, const int32_t* a_y0, const int32_t* a_y1, int64_t PA, int32_t Wa,
+                             const int32_t* b_offs, const int32_t* b_y0, const int32_t* b_y1, int64_t PB, int32_t k, int32_t Wb,
+                             int32_t shift, int32_t span, int32_t out_shift, int32_t Wout, int32_t* cnt, rsp_stream_t stream);
+int rsp_run_morph_join(int32_t op, const int32_t* a_col, const int32_t* a_y0, const int32_t* a_y1, int64_t PA, int32_t Wa,
+                       const int32_t* b_offs, const int32_t* b_y0, const int32_t* b_y1, int64_t PB, int32_t k, int32_t Wb,
+                       int32_t shift, int32_t span, const int64_t* out_offs, int64_t total, int32_t out_shift, int32_t Wout,
+                       int32_t H, int32_t emit_keys, int32_t* o_col, int32_t* o_y0, int32_t* o_y1, int64_t* keys, int32_t* ends,
+                       rsp_stream_t stream);
+
 /* Polygon rasterisation (csrc/poly_raster.hip): rings of float64 vertices -> run tables; replaces cocoapi's    */
 /* maskApi.c rleFrPoly (one polygon at 5x resolution, its sort and its sequential run loop) per part, and with the caller's     */
 /* grouping rleMerge / COCO.annToRLE (rsprompter_amd/rle.py polygons_to_runs).  The result is rleFrPoly's, count for count.     */

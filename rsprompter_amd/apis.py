@@ -326,6 +326,105 @@ def mask_iou(dt, gt, iscrowd=None, device='cuda:0'):
     return ops.coco_iou_runs(units, D * G, (dc, dn), (gc, gn), g_crowd).view(D, G)
 
 
+# --------------------------------------------------------------------------------------- morphology, Boundary IoU
+MORPHOLOGY_OPS = ('erode', 'dilate', 'open', 'close', 'boundary')
+
+
+def _runs_to_dense(counts, n, size):
+    """run table -> bool [k, H, W] on the device, through the bit planes of ops.rle_to_bits"""
+    (H, W), k, dev = size, int(n.shape[0]), n.device
+    nw = (H * W + 63) // 64
+    bits = ops.rle_to_bits(counts.contiguous(), n, torch.arange(k + 1, dtype=torch.int64, device=dev) * nw)[0]
+    px = (bits[:k * nw].view(torch.uint8).view(k, nw * 8, 1) >> torch.arange(8, dtype=torch.uint8, device=dev)) & 1
+    return px.view(k, nw * 64)[:, :H * W].reshape(k, W, H).transpose(1, 2).to(torch.bool).contiguous()
+
+
+def _morph_radius(radius):
+    if isinstance(radius, bool) or int(radius) != radius or int(radius) < 0:
+        raise ValueError(f'radius must be a non-negative integer, got {radius!r}')
+    return int(radius)
+
+
+def _morphology(masks, op, radius, device):
+    from . import rle
+    fn = dict(erode=rle.erode_runs, dilate=rle.dilate_runs, open=rle.open_runs, close=rle.close_runs,
+              boundary=rle.boundary_runs)[op]
+    if isinstance(masks, torch.Tensor):
+        if masks.dim() != 3:
+            raise ValueError('mask_morphology: a mask tensor is bool [k, H, W]')
+        if masks.shape[0] == 0:
+            return masks.to(torch.bool).clone()
+        counts, n, size = _masks_to_runs(masks, masks.device)
+        counts, n, _, _ = fn(counts, n, size, radius)
+        return _runs_to_dense(counts, n, size)
+    masks = list(masks)
+    counts, n, size = _masks_to_runs(masks, device)
+    counts, n, n_host, _ = fn(counts, n, size, radius)
+    if isinstance(masks[0]['counts'], (bytes, str)):
+        return rle.runs_to_strings(counts.contiguous(), n, size)
+    return rle.runs_to_dicts(counts, n_host, size)
+
+
+def mask_morphology(masks, op, radius, device='cuda:0'):
+    """Morphology by the (2 radius + 1)^2 square in the run domain (csrc/run_morphology.hip): op 'erode'
+    (outside the canvas counts as background), 'dilate', 'open' (erode, then dilate), 'close' (dilate, then erode with the
+    outside set) or 'boundary' (the mask minus its erosion) -- cv2.erode / cv2.dilate / cv2.morphologyEx with a square kernel,
+    scipy.ndimage.binary_erosion(M, ones((3, 3)), iterations=radius).  masks: bool [k, H, W] on the device -> bool [k, H, W];
+    or a list of RLE dicts dict(size=[H, W], counts=...) of one size, compressed (bytes / str) or uncompressed (list) ->
+    RLE dicts of the same counts form, never a dense mask (`device` places the run table); the cost is the masks' column
+    pieces times log radius."""
+    if op not in MORPHOLOGY_OPS:
+        raise ValueError(f'mask_morphology: op must be one of {MORPHOLOGY_OPS}, got {op!r}')
+    return _morphology(masks, op, _morph_radius(radius), device)
+
+
+def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0'):
+    """The boundary band of Boundary IoU (Cheng et al., CVPR 2021; boundary-iou-api mask_to_boundary): the pixels of each
+    mask within d of its outline or of the image border, d = rle.boundary_radius(size, dilation_ratio) = max(1, round(ratio *
+    diagonal)) or `radius` when given.  Input and output forms as mask_morphology's."""
+    from . import rle
+    if radius is None:
+        size = tuple(masks.shape[1:]) if isinstance(masks, torch.Tensor) else None
+        if size is None:
+            masks = list(masks)
+            if not masks:
+                raise ValueError('mask_boundary: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
+            size = masks[0]['size']
+        radius = rle.boundary_radius(size, dilation_ratio)
+    return _morphology(masks, 'boundary', _morph_radius(radius), device)
+
+
+def boundary_iou(dt, gt, iscrowd=None, dilation_ratio=0.02, radius=None, min_with_mask=False, device='cuda:0'):
+    """Boundary IoU of every pair: mask_iou of the boundary bands (mask_boundary) -> float64 [D, G] on the device, with the
+    inputs, conventions and refusals of mask_iou (0.0 without a common band pixel, / |dt band| for a crowd gt, masks of
+    different sizes refused).  min_with_mask=True returns min(mask IoU, boundary IoU), what Boundary AP matches with."""
+    from . import rle
+    for t in (dt, gt):
+        if isinstance(t, torch.Tensor):
+            device = t.device
+    dc, dn, d_sizes = _masks_to_runs_mixed(dt, device)
+    gc, gn, g_sizes = _masks_to_runs_mixed(gt, device)
+    D, G = len(d_sizes), len(g_sizes)
+    sizes = set(d_sizes) | set(g_sizes)
+    if D and G and len(sizes) != 1:
+        raise ValueError(f'boundary_iou: masks of different sizes in one call: {sorted(sizes)}')
+    crowd = np.zeros(G, np.uint8) if iscrowd is None else np.asarray(list(iscrowd)).astype(bool).astype(np.uint8).reshape(-1)
+    if crowd.shape[0] != G:
+        raise ValueError(f'boundary_iou: iscrowd has {crowd.shape[0]} entries for {G} ground truths')
+    dev = dn.device
+    units = ops.coco_units([0], [0], [0], [D], [G], [0], dev)
+    g_crowd = torch.from_numpy(np.concatenate([crowd, [0]]).astype(np.uint8)).to(dev)
+    if not (D and G):
+        return torch.zeros((D, G), dtype=torch.float64, device=dev)
+    size = sizes.pop()
+    r = rle.boundary_radius(size, dilation_ratio) if radius is None else _morph_radius(radius)
+    db, gb = rle.boundary_runs(dc, dn, size, r)[:2], rle.boundary_runs(gc, gn, size, r)[:2]
+    out = ops.coco_iou_runs(units, D * G, db, gb, g_crowd)
+    if min_with_mask:
+        out = torch.minimum(out, ops.coco_iou_runs(units, D * G, (dc, dn), (gc, gn), g_crowd))
+    return out.view(D, G)
+
+
 def _check_canonical(counts, n, size):
     """RLE dicts come from outside: the tracer reads canonical COCO counts only (a zero count anywhere but in front would
     make two runs of one value touch, counts that do not sum to H * W describe another canvas).  One device-to-host read."""

@@ -94,15 +94,18 @@ def _scene_predictions(model, ds, mine, large_image):
 
 @torch.no_grad()
 def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_ann_file=None, device=None,
-             verbose=True, gt_raster=None, large_image=None, iou_domain=None):
+             verbose=True, gt_raster=None, large_image=None, iou_domain=None, boundary=False, dilation_ratio=None):
     """Run the test set of `cfg` through `model` on this rank's shard; on rank 0 return the metrics dict (mmdet's keys),
     elsewhere None.  `metric_ann_file` sets CocoMetric's ann_file (the ground-truth JSON path of the reference's metric);
     by default the metric converts the dataset's ground truth as every RSPrompter config does.  `gt_raster` ('host' /
     'device') overrides who rasterises the metric's ground-truth polygons (CocoMetric's gt_raster; None: the config's).
     `large_image`: a dict of inference_large_image keywords (LARGE_IMAGE_KEYS; {} for its defaults) -- every dataset item
     is then a scene, and the metric's iou_domain is 'runs' unless `iou_domain` ('bits' / 'runs' / 'auto') or the config says
-    otherwise.  `iou_domain` alone overrides CocoMetric's on the tile path."""
+    otherwise.  `iou_domain` alone overrides CocoMetric's on the tile path.  `boundary` appends 'boundary' (Boundary AP,
+    DESIGN §14.13) to the metric list; `dilation_ratio` sets its band width and is refused without it."""
     import torch.distributed as dist
+    if dilation_ratio is not None and not boundary:
+        raise ValueError('evaluate: dilation_ratio applies to boundary=True')
     if large_image is not None:
         large_image = dict(large_image)
         unknown = sorted(set(large_image) - set(LARGE_IMAGE_KEYS))
@@ -148,6 +151,12 @@ def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_
         ev_cfg['iou_domain'] = iou_domain
     elif large_image is not None:
         ev_cfg.setdefault('iou_domain', 'runs')
+    if boundary:
+        listed = ev_cfg.get('metric', 'bbox')
+        listed = list(listed) if isinstance(listed, (list, tuple)) else [listed]
+        ev_cfg['metric'] = listed + [m for m in ('boundary',) if m not in listed]
+        if dilation_ratio is not None:
+            ev_cfg['dilation_ratio'] = dilation_ratio
     metric = METRICS.build(ev_cfg)
     metric.dataset_meta = ds.dataset_meta
     metric.device = str(dev)
@@ -192,6 +201,10 @@ def main(argv=None):
     ap.add_argument('--iou-domain', choices=('bits', 'runs', 'auto'), default=None,
                     help="how the segm IoU reads the masks: bit planes, run tables, or by size (default: the config's; 'runs' "
                          'with --large-image)')
+    ap.add_argument('--boundary', action='store_true',
+                    help="adds Boundary AP (metric 'boundary': min(mask IoU, Boundary IoU) per pair) to the metric list")
+    ap.add_argument('--dilation-ratio', type=float, default=None,
+                    help='--boundary: the band width as a fraction of the image diagonal (default 0.02)')
     ap.add_argument('--large-image', action='store_true',
                     help='every image of the dataset is a scene: sliced inference (inference_large_image) instead of test_step')
     ap.add_argument('--patch-size', type=int, default=None, help='--large-image: tile side in pixels')
@@ -205,13 +218,16 @@ def main(argv=None):
     given = {k: getattr(args, k) for k in LARGE_IMAGE_KEYS if getattr(args, k) is not None}
     if given and not args.large_image:
         ap.error('--' + sorted(given)[0].replace('_', '-') + ' applies to --large-image')
+    if args.dilation_ratio is not None and not args.boundary:
+        ap.error('--dilation-ratio applies to --boundary')
     rank, local, world = rdist.init_from_env()
     cfg = Config.fromfile(args.config)
     if args.cfg_options:
         cfg.merge_from_dict(_parse_cfg_options(args.cfg_options))
     model = init_detector(cfg, args.checkpoint, device=f'cuda:{local}')
     res = evaluate(model, cfg, args.data_root, args.ann_file, args.out_prefix, verbose=rank == 0, gt_raster=args.gt_raster,
-                   large_image=given if args.large_image else None, iou_domain=args.iou_domain)
+                   large_image=given if args.large_image else None, iou_domain=args.iou_domain, boundary=args.boundary,
+                   dilation_ratio=args.dilation_ratio)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -90,8 +90,48 @@ class CocoEvalResult:
         self.tables = tables            # the device's evaluateImg tables (dtm, dtig [A, T, n_dt], npig [units, A], ...)
 
 
+def _band_runs(runs, sizes, dilation_ratio):
+    """the boundary bands of a run table whose rows lie on canvases of their own (sizes: (H, W) per row): the rows grouped
+    by size, one rle.boundary_runs call per size with that size's radius, the groups put back in row order"""
+    from . import rle
+    counts, n = runs
+    groups = {}
+    for i, s in enumerate(sizes):
+        groups.setdefault((int(s[0]), int(s[1])), []).append(i)
+    if not groups:
+        return counts, n
+    tables, ns, order = [], [], []
+    for size, idx in groups.items():
+        sel = torch.tensor(idx, dtype=torch.int64, device=n.device)
+        c, m, _, _ = rle.boundary_runs(counts[sel].contiguous(), n[sel].contiguous(), size,
+                                       rle.boundary_radius(size, dilation_ratio))
+        tables.append(c)
+        ns.append(m)
+        order += idx
+    back = torch.tensor(np.argsort(np.asarray(order, np.int64), kind='stable'), dtype=torch.int64, device=n.device)
+    return rle.concat_runs(tables, rows=back).contiguous(), torch.cat(ns)[back].contiguous()
+
+
+def _band_iou(units, n_iou, d_runs, g_runs, d_sizes, g_sizes, g_crowd, dilation_ratio, iou_domain):
+    """the IoU blocks of the boundary bands, through the route the mask IoU took: the bit route gets its words from the band
+    tables"""
+    d_band, g_band = _band_runs(d_runs, d_sizes, dilation_ratio), _band_runs(g_runs, g_sizes, dilation_ratio)
+    if iou_domain == 'runs':
+        return ops.coco_iou_runs(units, n_iou, d_band, g_band, g_crowd)
+    planes = []
+    for (counts, n), sizes in ((d_band, d_sizes), (g_band, g_sizes)):
+        woff = np.zeros(len(sizes) + 1, dtype=np.int64)
+        np.cumsum([(int(s[0]) * int(s[1]) + 63) // 64 for s in sizes], out=woff[1:])
+        woff_d = torch.from_numpy(woff).to(n.device)
+        bits, area, wrange = ops.rle_to_bits(counts, n, woff_d)
+        planes.append((bits, woff_d, area, wrange))
+    (db, dwo, da, dwr), (gb, gwo, ga, gwr) = planes
+    return ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo, gt_woff=gwo,
+                        dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
+
+
 def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, device, timings=None, iou_domain='bits',
-                    keep_iou=False):
+                    keep_iou=False, dilation_ratio=0.02):
     """COCOeval(gt, dt, iou_type) with params imgIds / catIds / iouThrs / maxDets -> evaluate + accumulate + summarize.
 
     gt: dict(images, annotations) (annotations with id, image_id, category_id, area, iscrowd, bbox, segmentation);
@@ -99,8 +139,13 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     iou_domain (segm only): 'bits' expands every mask to one bit per pixel (rsp_rle_to_bits + rsp_coco_iou), 'runs' keeps
     the run tables (ops.coco_iou_runs: the same doubles, for scenes), 'auto' takes 'runs' when the bits of this call would
     pass BITS_BUDGET_BYTES.  timings['iou_domain'] tells which one ran.  keep_iou: tables['iou'] = the IoU blocks, on the
-    device (tools/bench_coco_iou_runs.py compares the routes on them)."""
+    device (tools/bench_coco_iou_runs.py compares the routes on them).
+    iou_type 'boundary'  is 'segm' with the IoU of every pair replaced by min(mask IoU, Boundary IoU): the
+    bands M & ~erode(M, d) of detections and ground truths are made in the run domain (one rle.boundary_runs call per image
+    size, d = rle.boundary_radius(size, dilation_ratio)) and their IoU goes through the same route as the mask IoU; areas,
+    crowds, matching and accumulation are segm's."""
     import time
+    segm = iou_type in ('segm', 'boundary')
     if iou_domain not in IOU_DOMAINS:
         raise ValueError(f'device_evaluate: iou_domain {iou_domain!r}: one of {IOU_DOMAINS}')
     t0 = time.perf_counter()
@@ -144,11 +189,11 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     unit_img = np.tile(img_ids, K)
     nwords = np.array([((img_hw.get(int(i), (0, 0))[0] or 0) * (img_hw.get(int(i), (0, 0))[1] or 0) + 63) // 64
                        for i in unit_img.tolist()], dtype=np.int64)
-    if iou_type == 'segm':
+    if segm:
         for d in dts:
             if tuple(d['segmentation']['size']) != tuple(img_hw[d['image_id']]):
                 raise ValueError('segm: a detection mask does not have the size of its image')
-    units = ops.coco_units(dt0, gt0, out0, nd, ng, nwords if iou_type == 'segm' else np.zeros(U, np.int64), device)
+    units = ops.coco_units(dt0, gt0, out0, nd, ng, nwords if segm else np.zeros(U, np.int64), device)
 
     def dev(a, dtype):
         a = np.asarray(a, dtype=dtype)
@@ -160,10 +205,10 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     g_area = dev([g['area'] for g in gts], np.float64)
     g_id = dev([g['id'] for g in gts], np.int64)
     t1 = time.perf_counter()
-    if iou_type == 'segm' and iou_domain == 'auto':
+    if segm and iou_domain == 'auto':
         iou_domain = 'runs' if _bits_bytes([d['segmentation'] for d in dts]) + \
             _bits_bytes([g['segmentation'] for g in gts]) > BITS_BUDGET_BYTES else 'bits'
-    if iou_type == 'segm' and iou_domain == 'runs':
+    if segm and iou_domain == 'runs':
         d_runs = _runs_on_device([d['segmentation'] for d in dts], device)
         g_runs = _runs_on_device([g['segmentation'] for g in gts], device)
         d_pre = ops.run_prefix(*d_runs, check=False)           # rle_from_string's retry left no negative n
@@ -172,7 +217,7 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         d_area = d_pre[1].to(torch.float64) if n_dt else dev([0.0], np.float64)
         if timings is not None:
             timings.update(pairs=info['pairs'], survivors=info['survivors'])
-    elif iou_type == 'segm':
+    elif segm:
         db, dwo, da, dwr = _masks_on_device([d['segmentation'] for d in dts], device)
         gb, gwo, ga, gwr = _masks_on_device([g['segmentation'] for g in gts], device)
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
@@ -183,6 +228,16 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         g_box = dev(np.asarray([g['bbox'] for g in gts], np.float64).reshape(-1, 4), np.float64)
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_BBOX, gt_crowd=g_crowd, dt_box=d_box, gt_box=g_box)
         d_area = dev([d['area'] for d in dts], np.float64)
+    if iou_type == 'boundary' and n_iou:
+        tb = time.perf_counter()
+        if iou_domain != 'runs':
+            d_runs = _runs_on_device([d['segmentation'] for d in dts], device)
+            g_runs = _runs_on_device([g['segmentation'] for g in gts], device)
+        band = _band_iou(units, n_iou, d_runs, g_runs, [d['segmentation']['size'] for d in dts],
+                         [g['segmentation']['size'] for g in gts], g_crowd, dilation_ratio, iou_domain)
+        iou = torch.minimum(iou[:n_iou], band)
+        if timings is not None:
+            timings['band'] = timings.get('band', 0.0) + (time.perf_counter() - tb)     # inside 'device'
     if n_iou == 0:
         iou = torch.zeros((1,), dtype=torch.float64, device=device)
     dtm, dtig, npig = ops.coco_match(units, iou, g_area, g_crowd, g_id, d_area, dev(AREA_RNG, np.float64),
@@ -196,7 +251,7 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         timings['host_prepare'] = timings.get('host_prepare', 0.0) + (t1 - t0)
         timings['device'] = timings.get('device', 0.0) + (t2 - t1)
         timings['host_accumulate'] = timings.get('host_accumulate', 0.0) + (t3 - t2)
-        if iou_type == 'segm':
+        if segm:
             timings['iou_domain'] = iou_domain
     tables = dict(dtm=dtm, dtig=dtig, npig=npig, dt_ids=np.array([d['id'] for d in dts], dtype=np.int64), dt0=dt0,
                   nd=nd, ng=ng, n_img=I, n_cat=K)
@@ -307,18 +362,20 @@ GT_RASTERS = ('host', 'device')
 
 @METRICS.register_module()
 class CocoMetric:
-    """mmdet CocoMetric (bbox / segm) -- `process`, `compute_metrics`, `evaluate(size)`, `dataset_meta`."""
+    """mmdet CocoMetric (bbox / segm) -- `process`, `compute_metrics`, `evaluate(size)`, `dataset_meta`.  metric 'boundary'
+    adds Boundary AP (LVIS iouType='boundary', boundary-iou-api): segm with min(mask IoU, Boundary IoU) per pair, band width
+    dilation_ratio * the image diagonal; keys boundary_mAP, boundary_mAP_50, ...."""
     default_prefix = 'coco'
 
     def __init__(self, ann_file=None, metric='bbox', classwise=False, proposal_nums=(100, 300, 1000), iou_thrs=None,
                  metric_items=None, format_only=False, outfile_prefix=None, file_client_args=None, backend_args=None,
                  collect_device='cpu', prefix=None, sort_categories=False, use_mp_eval=False, device=None, gt_raster='host',
-                 iou_domain='bits'):
+                 iou_domain='bits', dilation_ratio=0.02):
         self.metrics = metric if isinstance(metric, list) else [metric]
         for m in self.metrics:
             if m in ('proposal', 'proposal_fast'):
                 raise NotImplementedError(f'CocoMetric: metric {m!r} is not implemented (bbox and segm are)')
-            if m not in ('bbox', 'segm'):
+            if m not in ('bbox', 'segm', 'boundary'):
                 raise KeyError(f"metric should be one of 'bbox', 'segm', 'proposal', 'proposal_fast', but got {m}.")
         if file_client_args is not None:
             raise RuntimeError('The `file_client_args` is deprecated, please use `backend_args` instead')
@@ -343,6 +400,10 @@ class CocoMetric:
         if iou_domain not in IOU_DOMAINS:
             raise ValueError(f'CocoMetric: iou_domain {iou_domain!r}: one of {IOU_DOMAINS}')
         self.iou_domain = iou_domain                        # how the segm IoU reads the masks
+        if isinstance(dilation_ratio, bool) or not isinstance(dilation_ratio, (int, float)) \
+                or not (dilation_ratio > 0 and np.isfinite(dilation_ratio)):
+            raise ValueError(f'CocoMetric: dilation_ratio must be a positive finite number, got {dilation_ratio!r}')
+        self.dilation_ratio = float(dilation_ratio)         # the band width of metric 'boundary' 
         self._coco_api = None
         if ann_file is not None:
             with open(ann_file) as f:
@@ -499,13 +560,14 @@ class CocoMetric:
         names = {n: i for i, n in enumerate(STAT_NAMES)}
         gt_rle = None
         for metric in self.metrics:
-            preds_m = result_lists.get(metric)
+            masks = metric in ('segm', 'boundary')          # 'boundary' reads the segm results and ground-truth RLEs
+            preds_m = result_lists.get('segm' if masks else metric)
             if preds_m is None:
                 raise KeyError(f'{metric} is not in results')
             if len(preds_m) == 0:                       # pycocotools loadRes indexes anns[0]: mmdet logs and stops
                 break
             t0 = time.perf_counter()
-            if metric == 'segm':
+            if masks:
                 preds_m = [{k: v for k, v in x.items() if k != 'bbox'} for x in preds_m]
                 if gt_rle is None:
                     gt_rle = self._gt_with_rles(coco, device)
@@ -514,12 +576,12 @@ class CocoMetric:
                 gt_m = coco
             dts = load_res(gt_m, preds_m, metric)
             for d in dts:
-                if metric == 'segm':
+                if masks:
                     c = d['segmentation']['counts']
                     d['segmentation'] = dict(size=d['segmentation']['size'], counts=c.encode() if isinstance(c, str) else c)
             tm = {}
             ev = device_evaluate(gt_m, dts, metric, self.img_ids, self.cat_ids, self.iou_thrs, self.proposal_nums,
-                                 device, timings=tm, iou_domain=self.iou_domain)
+                                 device, timings=tm, iou_domain=self.iou_domain, dilation_ratio=self.dilation_ratio)
             tm['total'] = time.perf_counter() - t0
             self.timings[metric] = tm
             self.eval_results[metric] = ev

@@ -2116,6 +2116,151 @@ def rle_complement(counts, n):
     return out.contiguous(), n2.to(torch.int32).contiguous()
 
 
+# ----------------------------------------------------------------------------- run-domain morphology (csrc/run_morphology.hip)
+def _canonical_rows(lib, counts, n, k, cap, H, W):
+    """every row through a group-of-one rsp_rle_union: zero counts anywhere go, touching ones-runs merge, a row with n <= 0
+    becomes the empty mask (one count H * W) -> (counts int32 [k, cap + 1], n int32 [k]).  The intervals of one row are in
+    key order as rsp_rle_intervals writes them, so nothing is sorted; no host read."""
+    dev = n.device
+    runs = (n.clamp(0, cap) // 2).to(torch.int64)
+    ends_incl = torch.cumsum(runs, 0)
+    moff = (ends_incl - runs).contiguous()
+    iv_offs = torch.cat([ends_incl.new_zeros((1,)), ends_incl]).contiguous()
+    bound = k * (cap // 2)                                      # the slots of all rows, without reading their sum
+    keys = torch.empty((max(bound, 1),), dtype=torch.int64, device=dev)
+    ends = torch.empty((max(bound, 1),), dtype=torch.int32, device=dev)
+    rows = torch.arange(k, dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_rle_intervals(counts.data_ptr(), n.data_ptr(), k, cap, H, W, rows.data_ptr(), rows.data_ptr(),
+                                     moff.data_ptr(), k, bound, keys.data_ptr(), ends.data_ptr(), _stream()), "rsp_rle_intervals")
+    out = torch.empty((k, cap + 1), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((k,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), bound, iv_offs.data_ptr(), k, H, W, out.data_ptr(),
+                                 n_out.data_ptr(), cap + 1, _stream()), "rsp_rle_union")
+    return out, n_out
+
+
+class _RunIntervals:
+    """a table of csrc/run_morphology.hip: P intervals (col, y0, y1) on strips of Wt columns per instance; the arrays hold one
+    slot at least"""
+
+    def __init__(self, P, Wt, dev, keys=False):
+        self.P, self.Wt = int(P), int(Wt)
+        size = (max(self.P, 1),)
+        if keys:
+            self.keys = torch.zeros(size, dtype=torch.int64, device=dev)
+            self.ends = torch.zeros(size, dtype=torch.int32, device=dev)
+        else:
+            self.col, self.y0, self.y1 = (torch.zeros(size, dtype=torch.int32, device=dev) for _ in range(3))
+
+    def offs(self, k):
+        """int32 [k Wt + 1]: the first interval of every column"""
+        cols = torch.arange(k * self.Wt + 1, dtype=torch.int32, device=self.col.device)
+        return torch.searchsorted(self.col[:self.P], cols, out_int32=True).contiguous()
+
+
+def _exclusive_total(cnt):
+    """int32 counts -> (exclusive sum int64 [len + 1], its last entry still on the device)"""
+    offs = torch.cat([cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(cnt, 0, dtype=torch.int64)]).contiguous()
+    return offs, offs[-1]
+
+
+def _run_morph_join(lib, op, A, B, k, shift, span, out_shift, Wout, H, emit):
+    """count pass, exclusive sum, ONE host read (the total), write pass -> _RunIntervals"""
+    dev = A.col.device
+    if A.P == 0:
+        return _RunIntervals(0, Wout, dev, keys=emit)
+    b_offs = B.offs(k)
+    head = (op, A.col.data_ptr(), A.y0.data_ptr(), A.y1.data_ptr(), A.P, A.Wt, b_offs.data_ptr(), B.y0.data_ptr(),
+            B.y1.data_ptr(), B.P, k, B.Wt, shift, span)
+    cnt = torch.zeros((A.P,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_run_morph_join_count(*head, out_shift, Wout, cnt.data_ptr(), _stream()), "rsp_run_morph_join_count")
+    offs, total = _exclusive_total(cnt)
+    out = _RunIntervals(total.item(), Wout, dev, keys=emit)                                        # the read
+    tail = (0, 0, 0, out.keys.data_ptr(), out.ends.data_ptr()) if emit else \
+        (out.col.data_ptr(), out.y0.data_ptr(), out.y1.data_ptr(), 0, 0)
+    _lib.check(lib.rsp_run_morph_join(*head, offs.data_ptr(), out.P, out_shift, Wout, H, 1 if emit else 0, *tail, _stream()),
+               "rsp_run_morph_join")
+    return out
+
+
+def run_morph_levels(radius, W):
+    """the window doublings of an erosion by `radius` on a canvas W columns wide: floor(log2(2 min(radius, W) + 1))"""
+    return (2 * min(int(radius), int(W)) + 1).bit_length() - 1
+
+
+def _run_morph(what, counts, n, H, W, radius, border, band, cap):
+    lib = _lib.load()
+    counts, n, k, cap_in, H, W = _rle_rows(what, counts, n, H, W)
+    if isinstance(radius, bool) or int(radius) != radius or int(radius) < 0:
+        raise ValueError(f'{what}: radius must be a non-negative integer, got {radius!r}')
+    if border not in (0, 1):
+        raise ValueError(f'{what}: border must be 0 or 1, got {border!r}')
+    dev = n.device
+    cap = max(int(cap), 2) if cap is not None else cap_in + 2
+    if k == 0:
+        return torch.zeros((0, cap), dtype=torch.int32, device=dev), n, n.cpu(), cap
+    # beyond the canvas nothing changes with the radius: a window W columns (H rows) to either side covers every column (row)
+    rx, ry = min(int(radius), W), min(int(radius), H)
+    pad = rx if border else 0
+    Wt = W + 2 * pad
+    if k * Wt >= 2 ** 31:
+        raise ValueError(f'{what}: {k} rows x {Wt} columns; column numbers are 32-bit (< 2^31; split the rows)')
+    cc, cn = _canonical_rows(lib, counts, n, k, cap_in, H, W)
+    args = (cc.data_ptr(), cn.data_ptr(), k, cap_in + 1, H, W)
+    shapes = [(ry, pad, int(border))] + ([(0, 0, 0)] if band else [])
+    cnts = torch.zeros((len(shapes), k), dtype=torch.int32, device=dev)
+    for i, s in enumerate(shapes):
+        _lib.check(lib.rsp_run_morph_pieces_count(*args, *s, cnts[i].data_ptr(), _stream()), "rsp_run_morph_pieces_count")
+    offs = torch.cat([cnts.new_zeros((len(shapes), 1), dtype=torch.int64), torch.cumsum(cnts, 1, dtype=torch.int64)], 1).contiguous()
+    totals = offs[:, -1].tolist()                                                                    # read 1
+    if max(totals) >= 2 ** 31:
+        raise ValueError(f'{what}: {max(totals)} column pieces in one call; at most 2^31 - 1 (split the rows)')
+    tables = []
+    for i, s in enumerate(shapes):
+        t = _RunIntervals(totals[i], W + 2 * s[1], dev)
+        _lib.check(lib.rsp_run_morph_pieces(*args, *s, offs[i].data_ptr(), t.P, t.col.data_ptr(), t.y0.data_ptr(),
+                                            t.y1.data_ptr(), _stream()), "rsp_run_morph_pieces")
+        tables.append(t)
+    T, a, L = tables[0], 1, 2 * rx + 1
+    while 2 * a <= L:                                           # T_2a(X) = T_a(X) & T_a(X + a): one read per level
+        T = _run_morph_join(lib, 0, T, T, k, a, 2 * a, 0, Wt, H, False)
+        a *= 2
+    # the window [X, X + L) = two windows of `a` columns that may overlap; canvas column x = X + rx - pad
+    E = _run_morph_join(lib, 0, T, T, k, L - a, L, rx - pad, W, H, not band)
+    if band:
+        E = _run_morph_join(lib, 1, tables[1], E, k, 0, 1, 0, W, H, True)
+    iv_offs = torch.searchsorted(E.keys[:E.P], torch.arange(k + 1, dtype=torch.int64, device=dev) << 31).contiguous()
+
+    def launch(cap):
+        out = torch.empty((k, cap), dtype=torch.int32, device=dev)
+        n_out = torch.zeros((k,), dtype=torch.int32, device=dev)
+        _lib.check(lib.rsp_rle_union(E.keys.data_ptr(), E.ends.data_ptr(), E.P, iv_offs.data_ptr(), k, H, W, out.data_ptr(),
+                                     n_out.data_ptr(), cap, _stream()), "rsp_rle_union")
+        return out, n_out
+    return fit_runs(launch, cap)
+
+
+def rle_erode(counts, n, H, W, radius, border=0, cap=None):
+    """erosion of every row of a run table (counts int32 [k, cap_in], n int32 [k]: k masks on one (H, W) canvas) by the
+    (2 radius + 1)^2 square: a pixel stays iff every pixel within `radius` columns and rows of it is set, the
+    outside of the canvas counting as `border` (0 or 1) -- scipy.ndimage.binary_erosion(M, ones((3, 3)), iterations=radius,
+    border_value=border), cv2.erode on the dense mask.  Zero counts anywhere are legal input (the result is the erosion of the
+    decoded stream); a row with n <= 0 is the empty mask; radius 0 returns the canonical form of the rows; radii beyond the
+    canvas cost what the canvas side costs.  -> (counts int32 [k, cap'], n int32 [k], n on the host, cap') under fit_runs,
+    canonical COCO run counts; cap: the first capacity (the input's plus two when None).
+    Device-to-host reads, whatever k is: 2 + L + one per fit_runs attempt, L = run_morph_levels(radius, W) = floor(log2(2
+    min(radius, W) + 1)): the level-1 pieces, one total per window doubling, the total of the last join."""
+    return _run_morph('rle_erode', counts, n, H, W, radius, border, False, cap)
+
+
+def rle_boundary(counts, n, H, W, radius, cap=None):
+    """the boundary band of every row, M & ~erode(M, radius, border=0): the pixels of the mask within `radius`
+    (Chebyshev) of a pixel outside it or of the canvas edge -- boundary-iou-api's mask_to_boundary with dilation = radius.
+    Input and result as rle_erode's.  Device-to-host reads: 3 + L + one per fit_runs attempt (rle_erode's and the total of the
+    difference)."""
+    return _run_morph('rle_boundary', counts, n, H, W, radius, 0, True, cap)
+
+
 # ----------------------------------------------------------------------------- polygon rasterisation (csrc/poly_raster.hip)
 POLY_RASTER_MAX_COORD = CONST['RSP_POLY_RASTER_MAX_COORD']        # |(int)(5 x + .5)| of every coordinate
 POLY_RASTER_MAX_POINTS = CONST['RSP_POLY_RASTER_MAX_POINTS']      # walk points of one call

@@ -322,6 +322,51 @@ def clean_runs(counts, n, size, min_area, mode='both', cap=None):
     return counts, n, n.cpu(), int(counts.shape[1]), changed
 
 
+def erode_runs(counts, n, size, radius, border=0, cap=None):
+    """run table of k masks on one size = (H, W) canvas -> (counts, n, n on the host, cap): every mask eroded by the
+    (2 radius + 1)^2 square, the outside of the canvas counting as `border` (ops.rle_erode)"""
+    return ops.rle_erode(counts, n, size[0], size[1], radius, border, cap)
+
+
+def dilate_runs(counts, n, size, radius, cap=None):
+    """every mask dilated by the square: the complement of the erosion of the complement with the outside set.  A row with
+    n <= 0 stays the empty mask."""
+    live = n > 0
+    c, m, _, cap = ops.rle_erode(*ops.rle_complement(counts, n), size[0], size[1], radius, 1, cap)
+    c, m = ops.rle_complement(c, m)
+    hw = int(size[0]) * int(size[1])
+    c[:, 0] = torch.where(live, c[:, 0], torch.full_like(c[:, 0], hw))
+    m = torch.where(live, m, torch.ones_like(m))
+    return c, m, m.cpu(), int(c.shape[1])
+
+
+def open_runs(counts, n, size, radius, cap=None):
+    """opening: dilation of the erosion (border 0); removes what the square does not fit into"""
+    c, m, _, cap = erode_runs(counts, n, size, radius, 0, cap)
+    return dilate_runs(c, m, size, radius, cap)
+
+
+def close_runs(counts, n, size, radius, cap=None):
+    """closing: erosion (border 1) of the dilation; fills what the square does not fit into"""
+    c, m, _, cap = dilate_runs(counts, n, size, radius, cap)
+    return erode_runs(c, m, size, radius, 1, cap)
+
+
+def boundary_runs(counts, n, size, radius, cap=None):
+    """the boundary band of every mask, M & ~erode(M, radius) (ops.rle_boundary): Boundary IoU's G_d & G"""
+    return ops.rle_boundary(counts, n, size[0], size[1], radius, cap)
+
+
+def boundary_radius(size, dilation_ratio=0.02):
+    """Boundary IoU's band width for a size = (H, W) image: max(1, round(dilation_ratio * diagonal)), Python's round on a
+    Python float, on the host (boundary-iou-api mask_to_boundary)"""
+    r = float(dilation_ratio)
+    if isinstance(dilation_ratio, bool) or not (r > 0 and math.isfinite(r)):
+        raise ValueError(f'dilation_ratio must be a positive finite number, got {dilation_ratio!r}')
+    H, W = int(size[0]), int(size[1])
+    return max(1, int(round(r * math.sqrt(H * H + W * W))))
+
+
 def runs_to_dicts(counts, n_host, size):
     """run table -> list of dict(size=[H, W], counts=list), the uncompressed form (HF `_mask_to_rle`).  n_host: the row
     lengths on the host (what fit_runs returned); one transfer, the table."""
