@@ -39,13 +39,14 @@ typedef void* rsp_stream_t;
 /* Library / build identification (also used by the "symbols load" CPU test).  This header is the ONLY declaration of   */
 /* the ABI: rsprompter_amd/_lib.py parses it at import into the ctypes prototypes, the descriptor structures and a table  */
 /* of the integer macros below (limits included), so keep to the C subset that parser reads (its docstring lists it).     */
-/* Still 5 with rsp_gemm_plan / RspGemmPlan (as with the run-table, polygon, simplification, oriented-box, component and   */
-/* rasterisation entry points): an                                                                                        */
-/* addition that leaves every earlier entry point, structure and macro as it was does not change the number.              */
+/* An addition that leaves every earlier entry point, structure and macro as it was does not change the number (under 5:  */
+/* rsp_gemm_plan and the run-table, polygon, simplification, oriented-box, component and rasterisation entry points).     */
+/* 6: rsp_run_pieces_count (was rsp_mask_polygon_pieces) and rsp_run_pieces write the column-piece table, which           */
+/* rsp_mask_polygon_edges and rsp_run_components_label read in place of counts / n / cap;                                 */
 /* 5: rsp_sam_fold_expand / rsp_sam_fold_gather; 4: rsp_sam_t2i_fold lost its `variant` argument, rsp_gemm_uses_pp;       */
 /* 3: RspBoxCoder in RspRpnDesc / rsp_bbox_post; 2: RspGemmDesc gained c_ncols / pl_col0, plane format words decode       */
 /* strictly.                                                                                                             */
-#define RSP_ABI_VERSION 5
+#define RSP_ABI_VERSION 6
 int rsp_abi_version(void);   /* = RSP_ABI_VERSION of the header the library was built from */
 const char* rsp_build_info(void);
 
@@ -753,24 +754,30 @@ int rsp_rle_intervals(const uint32_t* counts, const int32_t* n, int32_t k, int32
 /* reproduces that row bit for bit.                                                                                       */
 int rsp_rle_union(const int64_t* keys, const int32_t* ends, int64_t total, const int64_t* interval_offs, int32_t G, int32_t H,
                   int32_t W, uint32_t* counts_out, int32_t* n_out, int32_t cap_out, rsp_stream_t stream);
+/* The column-piece table of a run table (csrc/run_pieces.hip, DESIGN §14 "Its two intermediates"), which polygon export and   */
+/* the run-domain components below read.  counts [k, cap] / n [k] of k masks on ONE (H, W) canvas as above (a row with n <= 0   */
+/* has no pieces; n beyond cap is read up to cap); H * W >= 2^31 is refused (RSP_EINVAL).  A ones-run that crosses column ends  */
+/* is one piece (x, y0, y1), y0 < y1, per column.  No call reads the host, none uses atomics.  _count: piece_cnt int32 [k];     */
+/* the caller's exclusive sum is piece_offs int64 [k + 1], P = piece_offs[k] <= RSP_RUN_PIECES_MAX_PIECES (32-bit piece         */
+/* indices).  rsp_run_pieces writes pieces int32 [4, P] = the planes (x, y0, y1, instance), sorted by (instance, x, y0), with   */
+/* -1 as the instance of a slot that no row filled (a piece_offs that overstates a row).                                        */
+#define RSP_RUN_PIECES_MAX_PIECES 0x7fffff00LL
+int rsp_run_pieces_count(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                         int32_t* piece_cnt, rsp_stream_t stream);
+int rsp_run_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
+                   const int64_t* piece_offs, int64_t P, int32_t* pieces, rsp_stream_t stream);
 /* Polygon export (csrc/mask_polygons.hip): run tables -> exact rings on the pixel-corner lattice, replaces */
-/* decoding every instance to a dense H x W array on the host + cv2.findContours.  Input of the first two: counts [k, cap] */
-/* / n [k] of k masks on ONE (H, W) canvas as above (a row with n <= 0 has no pieces; n beyond cap is read up to cap).     */
-/* H * W >= 2^31 is refused (RSP_EINVAL).  The four calls are one pipeline; the caller reads two sizes in between and      */
-/* sorts the rings (rsprompter_amd/ops.py mask_polygons).  No call reads the host, none uses atomics.                      */
-/* 1. piece_cnt int32 [k]: the column pieces of each row (a ones-run crossing column ends is one piece per column).        */
-int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                            int32_t* piece_cnt, rsp_stream_t stream);
-/* 2. piece_offs int64 [k + 1] = exclusive sum of piece_cnt, P = piece_offs[k] <= RSP_MASK_POLYGON_MAX_PIECES (six edge     */
-/* slots per column piece, 32-bit slot numbers).  pieces int32 [4, P] =                                                     */
-/* (x, y0, y1, instance) per piece, sorted by (instance, x, y0).  Six edge slots per piece, E = 6 P: ekey int64 [E] = start */
-/* x * (H + 1) + start y of the directed boundary edge in the slot, INT64_MAX for an empty slot; eoth int32 [E] = the end   */
-/* vertex's other coordinate; succ int32 [E] = the slot of the next edge of the ring (saddles: foreground 8-connected).    */
+/* decoding every instance to a dense H x W array on the host + cv2.findContours.  Input: the piece table of k masks on    */
+/* ONE (H, W) canvas, pieces / piece_offs / P as rsp_run_pieces leaves them.  H * W >= 2^31 is refused (RSP_EINVAL).  The    */
+/* three calls are one pipeline after the table; the caller reads two sizes in between and sorts the rings                  */
+/* (rsprompter_amd/ops.py mask_polygons).  No call reads the host, none uses atomics.                                       */
+/* 1. P <= RSP_MASK_POLYGON_MAX_PIECES (six edge slots per column piece, 32-bit slot numbers), E = 6 P: ekey int64 [E] =     */
+/* start x * (H + 1) + start y of the directed boundary edge in the slot, INT64_MAX for an empty slot; eoth int32 [E] = the  */
+/* end vertex's other coordinate; succ int32 [E] = the slot of the next edge of the ring (saddles: foreground 8-connected). */
 #define RSP_MASK_POLYGON_MAX_PIECES (0x7fffffffLL / 6)
-int rsp_mask_polygon_edges(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                           const int64_t* piece_offs, int64_t P, int32_t* pieces, int64_t* ekey, int32_t* eoth, int32_t* succ,
-                           rsp_stream_t stream);
-/* 3. list ranking by pointer jumping, `rounds` launches per pass with 2^rounds >= the edges of the longest ring (6 x the   */
+int rsp_mask_polygon_edges(int32_t k, int32_t H, int32_t W, const int64_t* piece_offs, int64_t P, const int32_t* pieces,
+                           int64_t* ekey, int32_t* eoth, int32_t* succ, rsp_stream_t stream);
+/* 2. list ranking by pointer jumping, `rounds` launches per pass with 2^rounds >= the edges of the longest ring (6 x the   */
 /* largest piece_cnt bounds it).  ring_key int64 [E]: the smallest ekey of the edge's ring = its first vertex; flags uint8  */
 /* [E]: bit 0 the edge is its ring's first, bit 1 its start vertex is a corner; lastof int32 [E]: for a first edge the      */
 /* ring's last edge; corners int32 [E] / area2 int64 [E]: the corners and the doubled signed area (positive = clockwise on   */
@@ -780,7 +787,7 @@ int64_t rsp_mask_polygon_rank_workspace_bytes(int64_t P);
 int rsp_mask_polygon_rank(int64_t P, int32_t H, int32_t rounds, const int64_t* ekey, const int32_t* eoth, const int32_t* succ,
                           void* workspace, int64_t* ring_key, uint8_t* flags, int32_t* lastof, int32_t* corners, int64_t* area2,
                           rsp_stream_t stream);
-/* 4. ring_keys int64 [R] = instance << 33 | ring_key of the R rings, ascending; ring_offs int64 [R + 1] their vertex       */
+/* 3. ring_keys int64 [R] = instance << 33 | ring_key of the R rings, ascending; ring_offs int64 [R + 1] their vertex       */
 /* offsets, V = ring_offs[R]; ring_area2 int64 [R]; inst_ring_offs int64 [k + 1].  Writes verts int32 [V, 2] = (x, y), the   */
 /* corners of every ring from its smallest vertex on, and ring_parent int32 [R]: -1 for an outer ring, for a hole the index  */
 /* within its instance of the outer ring of the component around it (`rounds`: 2^rounds >= R; near_ws int32 [2 R]).         */
@@ -856,20 +863,18 @@ int rsp_hull_min_rect(const int32_t* hull_verts, const int64_t* hull_offs, int32
 /* Run-domain connected components (csrc/run_components.hip): the 8-connected components of every mask of a     */
 /* run table; replaces decoding every instance to a dense H x W array + cv2.connectedComponentsWithStats (segment-anything     */
 /* utils/amg.py remove_small_regions) and the dense labelling of rsp_mask_remove_small_regions where the masks live as runs.   */
-/* counts [k, cap] / n [k]: k masks on ONE (H, W) canvas as above (n <= 0: no pieces; n beyond cap is read up to cap).         */
+/* Input: the piece table of k masks on ONE (H, W) canvas, pieces / piece_offs / P as rsp_run_pieces leaves them.             */
 /* H * W >= 2^31 and P > RSP_RUN_COMPONENTS_MAX_PIECES (32-bit piece indices) are refused (RSP_EINVAL);                        */
 /* rsp_run_components_workspace_bytes(H, W, P) is -1 for what the calls refuse.  No call reads the host.  Atomics: integer     */
 /* min / max / add only, so a second launch gives the same bits.                                                              */
-/* 1. piece_offs int64 [k + 1] = exclusive sum of rsp_mask_polygon_pieces' piece_cnt, P = piece_offs[k].  Writes pieces int32   */
-/* [4, P] = (x, y0, y1, instance) sorted by (instance, x, y0) (-1 as the instance of a slot no row filled), label int32 [P] =  */
-/* the lowest piece index of the piece's component (pieces of columns x and x + 1 are joined iff their closed row ranges,       */
-/* widened by one row, overlap), root int32 [P] = 1 where label[p] == p.  status int32 [1], zeroed by the caller: set to 1      */
-/* when a find / union loop reached its step cap (the result is then invalid; a correct run never does).                       */
-#define RSP_RUN_COMPONENTS_MAX_PIECES 0x7fffff00LL
+/* 1. Writes label int32 [P] = the lowest piece index of the piece's component, -1 for a slot no row filled (pieces of columns  */
+/* x and x + 1 are joined iff their closed row ranges, widened by one row, overlap), root int32 [P] = 1 where label[p] == p.    */
+/* status int32 [1], zeroed by the caller: set to 1 when a find / union loop reached its step cap (the result is then invalid;  */
+/* a correct run never does).                                                                                                  */
+#define RSP_RUN_COMPONENTS_MAX_PIECES RSP_RUN_PIECES_MAX_PIECES
 int64_t rsp_run_components_workspace_bytes(int32_t H, int32_t W, int64_t P);
-int rsp_run_components_label(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                             const int64_t* piece_offs, int64_t P, int32_t* pieces, void* workspace, int32_t* label,
-                             int32_t* root, int32_t* status, rsp_stream_t stream);
+int rsp_run_components_label(int32_t k, int32_t H, int32_t W, const int64_t* piece_offs, int64_t P, const int32_t* pieces,
+                             void* workspace, int32_t* label, int32_t* root, int32_t* status, rsp_stream_t stream);
 /* 2. root_cum int64 [P] = the inclusive sum of root, C = root_cum[P - 1]: component c is the c-th root, which orders the       */
 /* components by (instance, label).  Writes piece_comp int32 [P] (-1 for an unfilled slot), comp_area int32 [C], comp_box       */
 /* int32 [C, 4] = (x0, y0, x1, y1) end-exclusive as rsp_rle_bbox, comp_first int32 [C] = the lowest row-major index y W + x of  */

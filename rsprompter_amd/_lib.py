@@ -35,8 +35,8 @@ _DECL = r"(?:const\s)?(\w+)\s*(\**)\s*(\w*)\s*(\[\s*\d*\s*\])?"      # one param
 def parse_header(text):
     """(structs, prototypes, constants) of a header in the C subset that include/rsp_hip.h keeps to:
       /* */ comments (a `//` outside a string is an error);
-      `#define NAME <integers, unary minus, ( ) << * / - +, suffixes u / L / LL>` (/ of non-negative values); function-like
-        macros, the include guard and every other directive are passed over;
+      `#define NAME <integers, RSP_* macros defined above it, unary minus, ( ) << * / - +, suffixes u / L / LL>` (/ of
+        non-negative values); function-like macros, the include guard and every other directive are passed over;
       `typedef struct [Name] { ... } Name;` of scalars, pointers, arrays `T x[4]` and earlier structs by value, several
         declarators (`int32_t M, N, K;`) or declarations on a line;
       prototypes of `rsp_*` functions over any number of lines, `(void)`, array parameters;
@@ -53,10 +53,11 @@ def parse_header(text):
 
     const = {}
     for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(?!\()[ \t]+(\S.*)$", code, re.M):
-        if not re.fullmatch(rf"(?:{_INT}|<<|[-+*/()\s])+", m.group(2)):
+        value = re.sub(r"\bRSP_\w+", lambda k: f"({const[k.group(0)]})" if k.group(0) in const else k.group(0), m.group(2))
+        if not re.fullmatch(rf"(?:{_INT}|<<|[-+*/()\s])+", value):
             fail("macro value is not an integer expression", m.group(0))
         try:
-            const[m.group(1)] = eval(re.sub(_INT, lambda k: str(int(k.group(1), 0)), m.group(2)).replace("/", "//"),
+            const[m.group(1)] = eval(re.sub(_INT, lambda k: str(int(k.group(1), 0)), value).replace("/", "//"),
                                      {"__builtins__": {}})
         except (SyntaxError, ValueError, ZeroDivisionError):
             fail("macro value does not evaluate", m.group(0))

@@ -171,8 +171,6 @@ __global__ __launch_bounds__(MO_THREADS) void mo_chain_kernel(const uint32_t* __
 }
 
 // ------------------------------------------------------------------------------------------------ the ring of one instance
-__device__ __forceinline__ int64_t mo_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 template <int T>
 __device__ __forceinline__ int64_t mo_block_sum64(int64_t v, int64_t* tmp) {
 #pragma unroll
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(MO_THREADS) void mo_write_kernel(const int32_t* __r
   int64_t off;
   const int64_t room = mo_slot_of(bound_offs, B, m, min(n_in[m], cap), &off);
   const int cu = chain_cnt[m], cl = chain_cnt[k + m];
-  const int64_t o0 = mo_clamp64(hull_offs[m], 0, Vh), o1 = mo_clamp64(hull_offs[m + 1], o0, Vh);
+  const int64_t o0 = rsp_clamp64(hull_offs[m], 0, Vh), o1 = rsp_clamp64(hull_offs[m + 1], o0, Vh);
   const bool ok = room > 0 && cu >= 2 && cl >= 2 && cu <= 2 * room && cl <= 2 * room && o1 - o0 == (int64_t)cu + cl;
   int64_t a2 = 0;
   if (ok) {                                                                 // uniform over the block
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(MO_THREADS) void mo_rect_kernel(const int32_t* __re
   __shared__ uint64_t w_phi[NW], w_plo[NW], w_L[NW];
   __shared__ int w_j[NW];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t s = mo_clamp64(offs[r], 0, Vh), e = mo_clamp64(offs[r + 1], s, Vh);
+  const int64_t s = rsp_clamp64(offs[r], 0, Vh), e = rsp_clamp64(offs[r + 1], s, Vh);
   const int64_t m64 = e - s;
   if (m64 < 1 || m64 > 0x7fffffffLL) {                                      // uniform over the block
     if (tid == 0) {

@@ -1,9 +1,8 @@
 // Polygon export: run tables -> exact vector rings on the pixel-corner lattice, in work proportional to
-// the number of runs.  Input: a run table as rsp_mask_rle / rsp_rle_shift / rsp_rle_union write it, read through
-// run_table.h; a row with n <= 0 has no rings.
+// the number of runs.  Input: the column-piece table of a run table (run_pieces.hip); a row with n <= 0 has no rings.
 //
-// PIECES.  A ones-run that crosses a column end is split into column pieces (x, y0, y1), y0 < y1; in stream order they
-// are sorted by (x, y0), and the pieces of one column neither overlap nor touch.
+// PIECES.  As rsp_run_pieces writes them: a ones-run cut at column ends, (x, y0, y1, instance), y0 < y1, sorted by
+// (instance, x, y0); the pieces of one column neither overlap nor touch.
 // EDGES.  Piece p owns six edge slots 6 p + j.  j = 0: its top side (x, y0) -> (x + 1, y0); j = 1: its bottom side
 // (x + 1, y1) -> (x, y1).  j = 2 + 2 side + end: the vertical edge on line X = x (side 0, neighbour column x - 1) or
 // X = x + 1 (side 1, neighbour x + 1) that begins at ya = y0 (end 0) or ya = y1 (end 1) and runs down to the next place yb
@@ -68,53 +67,6 @@ __device__ __forceinline__ void mp_col_state(const MpCol& P, int c, int y, bool*
     *fg = false;
     *next = more ? P.y0[q + 1] : MP_INF;
     *change_at = in_col && P.y1[q] == y;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------- pieces
-// One block per instance: the number of column pieces of its ones-runs.
-__global__ __launch_bounds__(MP_THREADS) void mp_count_kernel(const uint32_t* __restrict__ counts,
-                                                              const int32_t* __restrict__ n_in, int cap, int H,
-                                                              int32_t* __restrict__ piece_cnt) {
-  __shared__ int tmp[MP_THREADS / 64];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  int pieces = 0;
-  for (RspRunWalk<MP_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
-    if ((r.i & 1) && r.c > 0) {
-      const RspRunCols q = rsp_run_cols(r.s, r.c, H);
-      pieces += q.xb - q.xa + 1;
-    }
-  }
-  int total;
-  rsp_block_excl_scan<MP_THREADS>(pieces, tmp, &total);
-  if (tid == 0) piece_cnt[m] = total;
-}
-
-// One block per instance: its pieces, in stream order, into slots piece_offs[m] .. piece_offs[m + 1].
-__global__ __launch_bounds__(MP_THREADS) void mp_pieces_kernel(const uint32_t* __restrict__ counts,
-                                                               const int32_t* __restrict__ n_in, int cap, int H,
-                                                               const int64_t* __restrict__ piece_offs, int64_t P,
-                                                               int32_t* __restrict__ px, int32_t* __restrict__ py0,
-                                                               int32_t* __restrict__ py1, int32_t* __restrict__ pinst) {
-  __shared__ int tmp[MP_THREADS / 64];
-  const int m = blockIdx.x;
-  const int64_t base = piece_offs[m] < 0 ? 0 : piece_offs[m], end = piece_offs[m + 1] < P ? piece_offs[m + 1] : P;
-  int64_t carry_p = 0;
-  for (RspRunWalk<MP_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
-    const int ones = r.c & -(int)(r.i & 1);
-    const RspRunCols c = rsp_run_cols(r.s, ones, H);        // not used where ones == 0
-    const int np = ones > 0 ? c.xb - c.xa + 1 : 0;           // a mask and a select up to the second scan: run_table.h
-    int chunk_p;
-    const int64_t q0 = base + carry_p + rsp_block_excl_scan<MP_THREADS>(np, tmp, &chunk_p);
-    for (int j = 0; j < np; ++j) {
-      const int64_t q = q0 + j;
-      if (q < base || q >= end) break;
-      px[q] = c.xa + j;
-      py0[q] = j == 0 ? c.ra : 0;
-      py1[q] = j == np - 1 ? c.rb + 1 : H;
-      pinst[q] = m;
-    }
-    carry_p += chunk_p;
   }
 }
 
@@ -390,27 +342,14 @@ constexpr int64_t MP_MAX_PIECES = RSP_MASK_POLYGON_MAX_PIECES;
 
 }  // namespace
 
-extern "C" int rsp_mask_polygon_pieces(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                                       int32_t* piece_cnt, rsp_stream_t stream) {
-  if (!counts || !n || !piece_cnt || k < 0 || cap < 1 || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
-  if (k == 0) return RSP_OK;
-  hipLaunchKernelGGL(mp_count_kernel, dim3(k), dim3(MP_THREADS), 0, (hipStream_t)stream, counts, n, cap, H, piece_cnt);
-  RSP_CHECK_LAUNCH();
-  return RSP_OK;
-}
-
-extern "C" int rsp_mask_polygon_edges(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                                      const int64_t* piece_offs, int64_t P, int32_t* pieces, int64_t* ekey, int32_t* eoth,
-                                      int32_t* succ, rsp_stream_t stream) {
-  if (!counts || !n || !piece_offs || k < 0 || cap < 1 || P < 0 || P > MP_MAX_PIECES || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
+extern "C" int rsp_mask_polygon_edges(int32_t k, int32_t H, int32_t W, const int64_t* piece_offs, int64_t P, const int32_t* pieces,
+                                      int64_t* ekey, int32_t* eoth, int32_t* succ, rsp_stream_t stream) {
+  if (!piece_offs || k < 0 || P < 0 || P > MP_MAX_PIECES || !rsp_run_canvas_ok(H, W)) return RSP_EINVAL;
   if (P > 0 && (!pieces || !ekey || !eoth || !succ)) return RSP_EINVAL;
   if (k == 0 || P == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;
-  int32_t *px = pieces, *py0 = pieces + P, *py1 = pieces + 2 * P, *pinst = pieces + 3 * P;
-  if (hipMemsetAsync(pinst, 0xff, (size_t)P * sizeof(int32_t), s) != hipSuccess) return RSP_ELAUNCH;
+  const int32_t *px = pieces, *py0 = pieces + P, *py1 = pieces + 2 * P, *pinst = pieces + 3 * P;
   if (hipMemsetAsync(succ, 0xff, (size_t)(6 * P) * sizeof(int32_t), s) != hipSuccess) return RSP_ELAUNCH;
-  hipLaunchKernelGGL(mp_pieces_kernel, dim3(k), dim3(MP_THREADS), 0, s, counts, n, cap, H, piece_offs, P, px, py0, py1, pinst);
-  RSP_CHECK_LAUNCH();
   hipLaunchKernelGGL(mp_edges_kernel, dim3(mp_blocks(P)), dim3(MP_THREADS), 0, s, px, py0, py1, pinst, piece_offs, k, P, H, ekey,
                      eoth, succ);
   RSP_CHECK_LAUNCH();

@@ -1,9 +1,9 @@
 // Run-domain connected components: the 8-connected components of every mask of a run table, in work
-// proportional to the number of runs.  Input: a run table as rsp_mask_rle / rsp_rle_shift / rsp_rle_union write it, read
-// through run_table.h; a row with n <= 0 has no pieces.
+// proportional to the number of runs.  Input: the column-piece table of a run table (run_pieces.hip); a row with n <= 0 has
+// no pieces.
 //
-// PIECES.  As in mask_polygons.hip: a ones-run cut at column ends, (x, y0, y1, instance), y0 < y1, sorted by (instance, x, y0)
-// in stream order; the pieces of one column neither overlap nor touch.  No edge slots are made here.
+// PIECES.  As rsp_run_pieces writes them: a ones-run cut at column ends, (x, y0, y1, instance), y0 < y1, sorted by
+// (instance, x, y0) in stream order; the pieces of one column neither overlap nor touch.
 // ADJACENCY.  Pieces p of column x and q of column x + 1 of one instance are joined iff q.y0 <= p.y1 and q.y1 >= p.y0 (their
 // closed row ranges, widened by one row, overlap: a diagonal contact joins).  The pieces of column x + 1 lie behind p in the
 // sorted array; the first candidate is found by binary search on (x, y1), the rest follow it.  Two pieces of one ones-run
@@ -25,36 +25,7 @@ constexpr int RC_THREADS = 256;
 constexpr int RC_INF = 0x7fffffff;
 constexpr int64_t RC_MAX_PIECES = RSP_RUN_COMPONENTS_MAX_PIECES;
 
-__device__ __forceinline__ int64_t rc_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int rc_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// One block per instance: its pieces, in stream order, into slots piece_offs[m] .. piece_offs[m + 1] (mp_pieces_kernel's walk).
-__global__ __launch_bounds__(RC_THREADS) void rc_pieces_kernel(const uint32_t* __restrict__ counts,
-                                                               const int32_t* __restrict__ n_in, int cap, int H,
-                                                               const int64_t* __restrict__ piece_offs, int64_t P,
-                                                               int32_t* __restrict__ px, int32_t* __restrict__ py0,
-                                                               int32_t* __restrict__ py1, int32_t* __restrict__ pinst) {
-  __shared__ int tmp[RC_THREADS / 64];
-  const int m = blockIdx.x;
-  const int64_t base = rc_clamp64(piece_offs[m], 0, P), end = rc_clamp64(piece_offs[m + 1], base, P);
-  int64_t carry_p = 0;
-  for (RspRunWalk<RC_THREADS> r(rsp_run_row(counts, n_in, cap, m), tmp); r.next();) {
-    const int ones = r.c & -(int)(r.i & 1);
-    const RspRunCols c = rsp_run_cols(r.s, ones, H);        // not used where ones == 0
-    const int np = ones > 0 ? c.xb - c.xa + 1 : 0;           // a mask and a select up to the second scan: run_table.h
-    int chunk_p;
-    const int64_t q0 = base + carry_p + rsp_block_excl_scan<RC_THREADS>(np, tmp, &chunk_p);
-    for (int j = 0; j < np; ++j) {
-      const int64_t q = q0 + j;
-      if (q < base || q >= end) break;
-      px[q] = c.xa + j;
-      py0[q] = j == 0 ? c.ra : 0;
-      py1[q] = j == np - 1 ? c.rb + 1 : H;
-      pinst[q] = m;
-    }
-    carry_p += chunk_p;
-  }
-}
 
 __global__ __launch_bounds__(RC_THREADS) void rc_init_kernel(int P, int32_t* __restrict__ parent) {
   const int64_t p = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x;
@@ -99,7 +70,7 @@ __global__ __launch_bounds__(RC_THREADS) void rc_link_kernel(const int32_t* __re
   const int p = (int)p64;
   const int inst = pinst[p];
   if (inst < 0 || inst >= k) return;                                     // a slot no instance filled
-  const int hi = (int)rc_clamp64(piece_offs[inst + 1], 0, P);
+  const int hi = (int)rsp_clamp64(piece_offs[inst + 1], 0, P);
   const int64_t xn = (int64_t)px[p] + 1;
   const int a = py0[p], b = py1[p];
   // the first piece behind p that lies in column x + 1 and reaches row a - 1 (y1 >= a), or in a later column
@@ -188,7 +159,7 @@ __global__ __launch_bounds__(RC_THREADS) void rc_select_kernel(const int64_t* __
   __shared__ unsigned long long best[RC_THREADS];
   __shared__ int flags[RC_THREADS];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const int64_t c0 = rc_clamp64(comp_offs[i], 0, C), c1 = rc_clamp64(comp_offs[i + 1], c0, C);
+  const int64_t c0 = rsp_clamp64(comp_offs[i], 0, C), c1 = rsp_clamp64(comp_offs[i + 1], c0, C);
   unsigned long long mine = 0ull;
   int f = 0;                                                            // bit 0: a small component, bit 1: one that is not
   for (int64_t c = c0 + tid; c < c1; c += RC_THREADS) {
@@ -227,19 +198,15 @@ extern "C" int64_t rsp_run_components_workspace_bytes(int32_t H, int32_t W, int6
   return (P > 0 ? P : 1) * (int64_t)sizeof(int32_t);
 }
 
-extern "C" int rsp_run_components_label(const uint32_t* counts, const int32_t* n, int32_t k, int32_t cap, int32_t H, int32_t W,
-                                        const int64_t* piece_offs, int64_t P, int32_t* pieces, void* workspace, int32_t* label,
-                                        int32_t* root, int32_t* status, rsp_stream_t stream) {
-  if (!counts || !n || !piece_offs || k < 0 || cap < 1 || rsp_run_components_workspace_bytes(H, W, P) < 0) return RSP_EINVAL;
+extern "C" int rsp_run_components_label(int32_t k, int32_t H, int32_t W, const int64_t* piece_offs, int64_t P, const int32_t* pieces,
+                                        void* workspace, int32_t* label, int32_t* root, int32_t* status, rsp_stream_t stream) {
+  if (!piece_offs || k < 0 || rsp_run_components_workspace_bytes(H, W, P) < 0) return RSP_EINVAL;
   if (P > 0 && (!pieces || !workspace || !label || !root || !status)) return RSP_EINVAL;
   if (k == 0 || P == 0) return RSP_OK;
   hipStream_t s = (hipStream_t)stream;
-  int32_t *px = pieces, *py0 = pieces + P, *py1 = pieces + 2 * P, *pinst = pieces + 3 * P;
+  const int32_t *px = pieces, *py0 = pieces + P, *py1 = pieces + 2 * P, *pinst = pieces + 3 * P;
   int32_t* parent = static_cast<int32_t*>(workspace);
   const int steps = rc_step_cap(P);
-  if (hipMemsetAsync(pinst, 0xff, (size_t)P * sizeof(int32_t), s) != hipSuccess) return RSP_ELAUNCH;
-  hipLaunchKernelGGL(rc_pieces_kernel, dim3(k), dim3(RC_THREADS), 0, s, counts, n, cap, H, piece_offs, P, px, py0, py1, pinst);
-  RSP_CHECK_LAUNCH();
   hipLaunchKernelGGL(rc_init_kernel, dim3(rc_blocks(P)), dim3(RC_THREADS), 0, s, (int)P, parent);
   RSP_CHECK_LAUNCH();
   hipLaunchKernelGGL(rc_link_kernel, dim3(rc_blocks(P)), dim3(RC_THREADS), 0, s, px, py0, py1, pinst, piece_offs, k, (int)P,

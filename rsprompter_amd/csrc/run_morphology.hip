@@ -6,7 +6,7 @@
 // TABLES.  A table is a list of intervals (col, y0, y1), y0 < y1, sorted by (col, y0), the intervals of one column disjoint
 // and not touching; col = instance * Wt + X addresses column X of an instance on a strip of Wt columns, and a CSR array
 // offs int32 [k Wt + 1] (the caller's searchsorted over col) gives the intervals of each column.
-// LEVEL 1 (rsp_run_morph_pieces).  The column pieces of every ones-run (rc_pieces_kernel's cut), each shrunk to
+// LEVEL 1 (rsp_run_morph_pieces).  The column pieces of every ones-run (run_pieces.hip's cut), each shrunk to
 // [y0 + ry, y1 - ry); with border = 1 an end on the canvas edge stays, and `pad` full columns [0, H) stand on either side of
 // the canvas (Wt = W + 2 pad): the outside of the canvas counts as set.  Empty results are dropped.
 // JOIN (rsp_run_morph_join).  One lane per interval of the left table A at column X; its partner list is column X + shift of
@@ -26,8 +26,6 @@
 namespace {
 
 constexpr int RM_THREADS = 256;
-
-__device__ __forceinline__ int64_t rm_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------------------ level 1
 // the shrunk piece [a, b) of the piece [y0, y1)
@@ -51,8 +49,8 @@ __global__ __launch_bounds__(RM_THREADS) void rm_pieces_kernel(const uint32_t* _
   const int col0 = m * Wt;
   int64_t base = 0, end = 0;
   if (WRITE) {
-    base = rm_clamp64(piece_offs[m], 0, P);
-    end = rm_clamp64(piece_offs[m + 1], base, P);
+    base = rsp_clamp64(piece_offs[m], 0, P);
+    end = rsp_clamp64(piece_offs[m + 1], base, P);
   }
   int am, bm;                                              // a column the run covers from end to end
   rm_shrink(0, H, H, ry, border, am, bm);
@@ -120,8 +118,8 @@ __device__ __forceinline__ int rm_join_lane(const RmJoin& J, int op, int64_t i, 
   int lo = 0, hi = 0;
   if (have_b) {
     const int64_t bc = (int64_t)inst * J.Wb + XB;
-    lo = (int)rm_clamp64(J.b_offs[bc], 0, J.PB);
-    hi = (int)rm_clamp64(J.b_offs[bc + 1], lo, J.PB);
+    lo = (int)rsp_clamp64(J.b_offs[bc], 0, J.PB);
+    hi = (int)rsp_clamp64(J.b_offs[bc + 1], lo, J.PB);
   }
   // first = the first interval of the list that ends behind y0; last = the first at or behind it that starts at or behind y1
   int first = lo, up = hi;
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(RM_THREADS) void rm_join_write_kernel(const RmJoin 
                                                                    int64_t* __restrict__ keys, int32_t* __restrict__ ends) {
   const int64_t stride = (int64_t)gridDim.x * RM_THREADS;
   for (int64_t i = (int64_t)blockIdx.x * RM_THREADS + threadIdx.x; i < J.PA; i += stride) {
-    const int64_t q0 = rm_clamp64(offs[i], 0, total), q1 = rm_clamp64(offs[i + 1], q0, total);
+    const int64_t q0 = rsp_clamp64(offs[i], 0, total), q1 = rsp_clamp64(offs[i + 1], q0, total);
     int inst = 0, xo = 0;
     rm_join_lane(J, op, i, inst, xo, [&](int j, int s, int e) {
       const int64_t q = q0 + j;

@@ -11,6 +11,9 @@
 // The canvas of a run table: H * W fits COCO's 32-bit counts, and with them the int pixel starts of the walk.
 inline bool rsp_run_canvas_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffffLL; }
 
+// An offset of a caller's exclusive sum (piece_offs, interval_offs, ...) cut into [lo, hi], whatever the array holds.
+__device__ __forceinline__ int64_t rsp_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // Row m of a table: n is cut at the capacity, whatever the array holds.
 struct RspRunRow {
   const uint32_t* c;

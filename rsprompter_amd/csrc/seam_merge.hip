@@ -208,8 +208,8 @@ __global__ __launch_bounds__(SM_THREADS) void rle_union_kernel(const int64_t* __
                                                                int32_t* __restrict__ n_out, int cap_out) {
   __shared__ int tmp[SM_WAVES];
   const int g = blockIdx.x, tid = threadIdx.x;
-  const int64_t o0 = iv_offs[g], o1 = iv_offs[g + 1];                  // clamped into [0, total], whatever the array holds
-  const int64_t q0 = o0 < 0 ? 0 : (o0 > total ? total : o0), q1 = o1 < q0 ? q0 : (o1 > total ? total : o1);
+  // clamped into [0, total], whatever the array holds
+  const int64_t q0 = rsp_clamp64(iv_offs[g], 0, total), q1 = rsp_clamp64(iv_offs[g + 1], q0, total);
   uint32_t* out = counts_out + (int64_t)g * cap_out;
   int carry_max = 0;
   int64_t carry_slot = 0;

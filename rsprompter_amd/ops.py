@@ -1661,17 +1661,58 @@ def paste_tiles(masks, offsets, scene_hw):
 
 
 # ----------------------------------------------------------------------------- seam merge (csrc/seam_merge.hip)
-def _rle_rows(what, counts, n, H, W):
-    """the common checks of the run-domain entry points: counts int32 [k, cap] / n int32 [k] on one (H, W) canvas"""
-    H, W = int(H), int(W)
-    if H * W >= 2 ** 31:
-        raise ValueError(f'{what}: a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
-    if H < 1 or W < 1:
-        raise ValueError(f'{what}: an empty {H} x {W} canvas')
+def _rle_rows(what, counts, n, H=None, W=None):
+    """the common checks of the run-domain entry points: counts int32 [k, cap] / n int32 [k], on one (H, W) canvas where
+    the entry point takes one -> (counts, n, k, cap, H, W)"""
+    if H is not None:
+        H, W = int(H), int(W)
+        if H * W >= 2 ** 31:
+            raise ValueError(f'{what}: a {H} x {W} scene has {H * W} pixels; COCO run counts are 32-bit (< 2^31 pixels)')
+        if H < 1 or W < 1:
+            raise ValueError(f'{what}: an empty {H} x {W} canvas')
     if counts.dtype != torch.int32 or counts.dim() != 2 or n.dtype != torch.int32 or n.dim() != 1 \
             or n.shape[0] != counts.shape[0] or counts.shape[1] < 1 or n.device != counts.device:
         raise ValueError(f'{what}: expected counts int32 [k, cap >= 1] and n int32 [k] on one device')
     return counts.contiguous(), n.contiguous(), int(n.shape[0]), int(counts.shape[1]), H, W
+
+
+def _exclusive_total(cnt):
+    """counts along the last dimension -> (exclusive sum int64 [..., len + 1], its last entries still on the device)"""
+    offs = torch.cat([cnt.new_zeros(cnt.shape[:-1] + (1,), dtype=torch.int64), torch.cumsum(cnt, -1, dtype=torch.int64)], -1)
+    return offs.contiguous(), offs[..., -1]
+
+
+def _rle_intervals(lib, counts, n, k, cap, H, W, members, group_of, runs, total=None):
+    """rsp_rle_intervals: the ones-runs of M member rows (`runs` int64 [M] of them each) as (group << 31 | pixel start, end)
+    intervals -> (keys int64, ends int32, offs int64 [M + 1] = the first slot of every member, total).  total=None: their
+    number is read from the device (one host read); a bound given instead reads nothing.  total == 0: no launch, no arrays."""
+    ends_incl = torch.cumsum(runs, 0)
+    moff = (ends_incl - runs).contiguous()
+    offs = torch.cat([ends_incl.new_zeros((1,)), ends_incl]).contiguous()
+    total = int(ends_incl[-1].item()) if total is None else total
+    if total == 0:
+        return None, None, offs, 0
+    keys = torch.empty((total,), dtype=torch.int64, device=n.device)
+    ends = torch.empty((total,), dtype=torch.int32, device=n.device)
+    _lib.check(lib.rsp_rle_intervals(counts.data_ptr(), n.data_ptr(), k, cap, H, W, members.data_ptr(), group_of.data_ptr(),
+                                     moff.data_ptr(), int(members.shape[0]), total, keys.data_ptr(), ends.data_ptr(), _stream()),
+               "rsp_rle_intervals")
+    return keys, ends, offs, total
+
+
+def _intervals_to_runs(lib, keys, ends, total, iv_offs, G, H, W, cap_out):
+    """rsp_rle_union, the one step from intervals sorted by key to a run table: the first `total` of keys / ends (None
+    when there are none), iv_offs int64 [G + 1] -> (counts_out int32 [G, cap_out], n_out int32 [G]), n_out = -(needed) for
+    a row that does not fit (the protocol of fit_runs).  No host read."""
+    dev = iv_offs.device
+    out = torch.empty((G, int(cap_out)), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((G,), dtype=torch.int32, device=dev)
+    if G and total == 0:                                             # the entry point takes arrays of one slot at least
+        keys, ends = torch.empty((1,), dtype=torch.int64, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
+    if G:
+        _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), total, iv_offs.data_ptr(), G, H, W, out.data_ptr(),
+                                     n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_union")
+    return out, n_out
 
 
 def _rle_index(what, name, t, cols, dev):
@@ -1725,35 +1766,51 @@ def rle_union(counts, n, H, W, group_offs, members, cap_out):
     G, M = int(group_offs.shape[0]) - 1, int(members.shape[0])
     if G < 0 or int(cap_out) < 2:
         raise ValueError('rle_union: group_offs holds G + 1 entries and cap_out is at least 2')
-    out = torch.empty((max(G, 1), int(cap_out)), dtype=torch.int32, device=dev)
-    n_out = torch.zeros((max(G, 1),), dtype=torch.int32, device=dev)
-    if G == 0:
-        return out[:0], n_out[:0]
-    go = group_offs.to(torch.int64).clamp(0, M)
-    if M and k:
+    if G and M and k:
+        go = group_offs.to(torch.int64).clamp(0, M)
         inside = (members >= 0) & (members < k)
         runs = torch.where(inside, n[members.to(torch.int64).clamp(0, k - 1)].clamp(0, cap) // 2, 0).to(torch.int64)
-        ends_incl = torch.cumsum(runs, 0)
-        moff = (ends_incl - runs).contiguous()
-        total = int(ends_incl[-1].item())
         # the group of member mi: the last g with group_offs[g] <= mi (group_offs[0] = 0, group_offs[G] = M)
         group_of = torch.searchsorted(go[1:].contiguous(), torch.arange(M, dtype=torch.int64, device=dev), right=True)
         group_of = group_of.clamp(max=G - 1).to(torch.int32).contiguous()
-        iv_offs = torch.cat([moff, ends_incl[-1:]])[go].contiguous()
+        keys, ends, moffs, total = _rle_intervals(lib, counts, n, k, cap, H, W, members, group_of, runs)
+        iv_offs = moffs[go].contiguous()
+        if total:
+            keys, order = torch.sort(keys)
+            ends = ends[order].contiguous()
     else:
-        total = 0
-        iv_offs = torch.zeros((G + 1,), dtype=torch.int64, device=dev)
-    keys = torch.empty((max(total, 1),), dtype=torch.int64, device=dev)
-    ends = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
-    if total:
-        _lib.check(lib.rsp_rle_intervals(counts.data_ptr(), n.data_ptr(), k, cap, H, W, members.data_ptr(), group_of.data_ptr(),
-                                         moff.data_ptr(), M, total, keys.data_ptr(), ends.data_ptr(), _stream()),
-                   "rsp_rle_intervals")
-        keys, order = torch.sort(keys[:total])
-        ends = ends[:total][order].contiguous()
-    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), total, iv_offs.data_ptr(), G, H, W, out.data_ptr(),
-                                 n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_union")
-    return out, n_out
+        keys, ends, total, iv_offs = None, None, 0, torch.zeros((G + 1,), dtype=torch.int64, device=dev)
+    return _intervals_to_runs(lib, keys, ends, total, iv_offs, G, H, W, cap_out)
+
+
+# ----------------------------------------------------------------------------- column pieces (csrc/run_pieces.hip)
+RUN_PIECES_MAX_PIECES = CONST['RSP_RUN_PIECES_MAX_PIECES']          # column pieces of one call: 32-bit piece indices
+RunPieces = collections.namedtuple('RunPieces', 'pieces piece_offs P widest')
+
+
+def run_pieces(counts, n, H, W, *, what='run_pieces', limit=RUN_PIECES_MAX_PIECES):
+    """run table (counts int32 [k, cap], n int32 [k]: k masks on one (H, W) canvas) -> its column-piece table, which polygon
+    export and the components read, as RunPieces: pieces int32 [4, P] = (x, y0, y1, instance) of every ones-run
+    cut at column ends, sorted by (instance, x, y0); piece_offs int64 [k + 1]; on the host P and `widest`, the pieces of the
+    largest row.  A row with n <= 0 has none.  One device-to-host read (P with widest); k == 0 or P == 0 launches no write.
+    what, limit: the entry point that asks, for the messages, and the most pieces it takes in one call."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows(what, counts, n, H, W)
+    i32, i64 = dict(dtype=torch.int32, device=n.device), dict(dtype=torch.int64, device=n.device)
+    if k == 0:
+        return RunPieces(torch.zeros((4, 0), **i32), torch.zeros((1,), **i64), 0, 0)
+    piece_cnt = torch.zeros((k,), **i32)
+    _lib.check(lib.rsp_run_pieces_count(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_cnt.data_ptr(), _stream()),
+               "rsp_run_pieces_count")
+    piece_offs, total = _exclusive_total(piece_cnt)
+    P, widest = torch.stack([total, piece_cnt.max().to(torch.int64)]).tolist()                    # the read
+    if P > limit:
+        raise ValueError(f'{what}: {P} column pieces in one call; at most {limit} (split the rows)')
+    pieces = torch.empty((4, P), **i32)
+    if P:
+        _lib.check(lib.rsp_run_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_offs.data_ptr(), P, pieces.data_ptr(),
+                                      _stream()), "rsp_run_pieces")
+    return RunPieces(pieces, piece_offs, P, widest)
 
 
 # ----------------------------------------------------------------------------- polygon export (csrc/mask_polygons.hip)
@@ -1774,30 +1831,19 @@ def mask_polygons(counts, n, H, W):
     not repeat its first vertex.  A row with n <= 0 has no rings.  Three device-to-host reads, whatever k is: the pieces
     (total and largest row), the number of rings (inside torch.nonzero), the number of vertices."""
     lib = _lib.load()
-    counts, n, k, cap, H, W = _rle_rows('mask_polygons', counts, n, H, W)
-    dev = n.device
+    pieces, piece_offs, P, widest = run_pieces(counts, n, H, W, what='mask_polygons', limit=MASK_POLYGON_MAX_PIECES)   # read 1
+    k, H, W, dev = int(piece_offs.shape[0]) - 1, int(H), int(W), pieces.device
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
 
     def empty():
         return (torch.zeros((0, 2), **i32), torch.zeros((1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
                 torch.zeros((0,), **i64), torch.zeros((k + 1,), **i64))
-    if k == 0:
-        return empty()
-    piece_cnt = torch.zeros((k,), **i32)
-    _lib.check(lib.rsp_mask_polygon_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_cnt.data_ptr(), _stream()),
-               "rsp_mask_polygon_pieces")
-    piece_offs = torch.cat([piece_cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(piece_cnt, 0, dtype=torch.int64)])
-    P, widest = torch.stack([piece_offs[-1], piece_cnt.max().to(torch.int64)]).tolist()          # read 1
     if P == 0:
         return empty()
-    if P > MASK_POLYGON_MAX_PIECES:
-        raise ValueError(f'mask_polygons: {P} column pieces in one call; at most {MASK_POLYGON_MAX_PIECES} (split the rows)')
     E = 6 * P
-    pieces = torch.empty((4, P), **i32)
     ekey, eoth, succ = torch.empty((E,), **i64), torch.empty((E,), **i32), torch.empty((E,), **i32)
-    _lib.check(lib.rsp_mask_polygon_edges(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_offs.data_ptr(), P,
-                                          pieces.data_ptr(), ekey.data_ptr(), eoth.data_ptr(), succ.data_ptr(), _stream()),
-               "rsp_mask_polygon_edges")
+    _lib.check(lib.rsp_mask_polygon_edges(k, H, W, piece_offs.data_ptr(), P, pieces.data_ptr(), ekey.data_ptr(), eoth.data_ptr(),
+                                          succ.data_ptr(), _stream()), "rsp_mask_polygon_edges")
     ws = torch.empty((int(lib.rsp_mask_polygon_rank_workspace_bytes(P)) // 8 + 1,), **i64)
     ring_key, area2 = torch.empty((E,), **i64), torch.empty((E,), **i64)
     flags = torch.empty((E,), dtype=torch.uint8, device=dev)
@@ -1806,7 +1852,7 @@ def mask_polygons(counts, n, H, W):
                                          ws.data_ptr(), ring_key.data_ptr(), flags.data_ptr(), lastof.data_ptr(),
                                          corners.data_ptr(), area2.data_ptr(), _stream()), "rsp_mask_polygon_rank")
     # the rings = the edges that start one, sorted by (instance, first vertex); their sizes sit at each ring's last edge
-    first = torch.nonzero(flags & 1).view(-1)                                                     # read 2 (R)
+    first = (flags & 1).nonzero().view(-1)                                                        # read 2 (R)
     R = int(first.shape[0])
     if R == 0:
         return empty()
@@ -1815,9 +1861,9 @@ def mask_polygons(counts, n, H, W):
     ring_inst = ring_inst[order].contiguous()
     last = lastof[first[order]].to(torch.int64).clamp(min=0)
     ring_area2 = area2[last].contiguous()
-    ring_offs = torch.cat([last.new_zeros((1,)), torch.cumsum(corners[last].to(torch.int64), 0)]).contiguous()
+    ring_offs = _exclusive_total(corners[last])[0]
     inst_ring_offs = torch.searchsorted(ring_inst, torch.arange(k + 1, **i32)).to(torch.int64).contiguous()
-    V = int(ring_offs[-1])                                                                        # read 3
+    V = int(ring_offs[-1].item())                                                                 # read 3
     verts = torch.zeros((V, 2), **i32)
     ring_parent = torch.empty((R,), **i32)
     near_ws = torch.empty((2 * R,), **i32)
@@ -1932,8 +1978,8 @@ def mask_hull(counts, n, H, W, with_rounds=False):
     if k == 0:
         return empty()
     bound = 3 * (n.clamp(0, cap) // 2).to(torch.int64)
-    bound_offs = torch.cat([bound.new_zeros((1,)), torch.cumsum(bound, 0)]).contiguous()
-    B = int(bound_offs[-1])                                                                         # read 1
+    bound_offs, total = _exclusive_total(bound)
+    B = int(total.item())                                                                           # read 1
     if B == 0:
         return empty()
     if B > MASK_OBB_MAX_BOUND:
@@ -1943,8 +1989,8 @@ def mask_hull(counts, n, H, W, with_rounds=False):
     chain_cnt = torch.zeros((2, k), **i32)
     _lib.check(lib.rsp_mask_hull_chains(counts.data_ptr(), n.data_ptr(), k, cap, H, W, bound_offs.data_ptr(), B, ws.data_ptr(),
                                         chain_cnt.data_ptr(), rounds.data_ptr(), _stream()), "rsp_mask_hull_chains")
-    hull_offs = torch.cat([bound.new_zeros((1,)), torch.cumsum(chain_cnt.sum(0, dtype=torch.int64), 0)]).contiguous()
-    Vh = int(hull_offs[-1])                                                                         # read 2
+    hull_offs, total = _exclusive_total(chain_cnt.sum(0, dtype=torch.int64))
+    Vh = int(total.item())                                                                          # read 2
     verts, area2 = torch.zeros((Vh, 2), **i32), torch.zeros((k,), **i64)
     _lib.check(lib.rsp_mask_hull_write(n.data_ptr(), k, cap, bound_offs.data_ptr(), B, ws.data_ptr(), chain_cnt.data_ptr(),
                                        hull_offs.data_ptr(), Vh, verts.data_ptr(), area2.data_ptr(), _stream()),
@@ -2005,32 +2051,18 @@ def rle_components(counts, n, H, W):
     Components are numbered by (instance, first pixel in stream order).  A row with n <= 0 has none.  Two device-to-host
     reads, whatever k is: the pieces P, and the components C together with status (non-zero raises RuntimeError)."""
     lib = _lib.load()
-    counts, n, k, cap, H, W = _rle_rows('rle_components', counts, n, H, W)
-    dev = n.device
+    pieces, piece_offs, P, _ = run_pieces(counts, n, H, W, what='rle_components', limit=RUN_COMPONENTS_MAX_PIECES)     # read 1
+    k, H, W, dev = int(piece_offs.shape[0]) - 1, int(H), int(W), pieces.device
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
     status = torch.zeros((1,), **i32)
-
-    def empty(piece_offs):
-        return RunComponents(torch.zeros((k + 1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
-                             torch.zeros((0, 4), **i32), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
-                             torch.zeros((4, 0), **i32), piece_offs, status)
-    if k == 0:
-        return empty(torch.zeros((1,), **i64))
-    piece_cnt = torch.zeros((k,), **i32)
-    _lib.check(lib.rsp_mask_polygon_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_cnt.data_ptr(), _stream()),
-               "rsp_mask_polygon_pieces")
-    piece_offs = torch.cat([piece_cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(piece_cnt, 0, dtype=torch.int64)])
-    P = int(piece_offs[-1])                                                                         # read 1
     if P == 0:
-        return empty(piece_offs)
-    if P > RUN_COMPONENTS_MAX_PIECES:
-        raise ValueError(f'rle_components: {P} column pieces in one call; at most {RUN_COMPONENTS_MAX_PIECES} (split the rows)')
-    pieces = torch.empty((4, P), **i32)
+        return RunComponents(torch.zeros((k + 1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+                             torch.zeros((0, 4), **i32), torch.zeros((0,), **i32), torch.zeros((0,), **i32), pieces, piece_offs,
+                             status)
     ws = torch.empty((int(lib.rsp_run_components_workspace_bytes(H, W, P)) // 4,), **i32)
     label, root = torch.empty((P,), **i32), torch.empty((P,), **i32)
-    _lib.check(lib.rsp_run_components_label(counts.data_ptr(), n.data_ptr(), k, cap, H, W, piece_offs.data_ptr(), P,
-                                            pieces.data_ptr(), ws.data_ptr(), label.data_ptr(), root.data_ptr(),
-                                            status.data_ptr(), _stream()), "rsp_run_components_label")
+    _lib.check(lib.rsp_run_components_label(k, H, W, piece_offs.data_ptr(), P, pieces.data_ptr(), ws.data_ptr(), label.data_ptr(),
+                                            root.data_ptr(), status.data_ptr(), _stream()), "rsp_run_components_label")
     root_cum = torch.cumsum(root, 0, dtype=torch.int64)
     C, bad = torch.stack([root_cum[-1], status[0].to(torch.int64)]).tolist()                         # read 2
     check_components_status([bad])
@@ -2076,11 +2108,7 @@ def components_union(comps, H, W, cap_out, keep=None):
     G = C if keep is None else k
     if int(cap_out) < 2:
         raise ValueError('components_union: cap_out is at least 2')
-    out = torch.empty((max(G, 1), int(cap_out)), dtype=torch.int32, device=dev)
-    n_out = torch.zeros((max(G, 1),), dtype=torch.int32, device=dev)
-    if G == 0:
-        return out[:0], n_out[:0]
-    if P and C:
+    if G and P and C:
         pc = comps.piece_comp.to(torch.int64)
         x, y0, y1, inst = (comps.pieces[i].to(torch.int64) for i in range(4))
         live = pc >= 0
@@ -2093,11 +2121,8 @@ def components_union(comps, H, W, cap_out, keep=None):
         iv_offs = torch.searchsorted(keys, torch.arange(G + 1, dtype=torch.int64, device=dev) << 31).contiguous()
         total = P
     else:
-        keys, ends = torch.zeros((1,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
-        iv_offs, total = torch.zeros((G + 1,), dtype=torch.int64, device=dev), 0
-    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), total, iv_offs.data_ptr(), G, H, W, out.data_ptr(),
-                                 n_out.data_ptr(), int(cap_out), _stream()), "rsp_rle_union")
-    return out, n_out
+        keys, ends, total, iv_offs = None, None, 0, torch.zeros((G + 1,), dtype=torch.int64, device=dev)
+    return _intervals_to_runs(lib, keys, ends, total, iv_offs, G, H, W, cap_out)
 
 
 def rle_complement(counts, n):
@@ -2121,22 +2146,11 @@ def _canonical_rows(lib, counts, n, k, cap, H, W):
     """every row through a group-of-one rsp_rle_union: zero counts anywhere go, touching ones-runs merge, a row with n <= 0
     becomes the empty mask (one count H * W) -> (counts int32 [k, cap + 1], n int32 [k]).  The intervals of one row are in
     key order as rsp_rle_intervals writes them, so nothing is sorted; no host read."""
-    dev = n.device
     runs = (n.clamp(0, cap) // 2).to(torch.int64)
-    ends_incl = torch.cumsum(runs, 0)
-    moff = (ends_incl - runs).contiguous()
-    iv_offs = torch.cat([ends_incl.new_zeros((1,)), ends_incl]).contiguous()
-    bound = k * (cap // 2)                                      # the slots of all rows, without reading their sum
-    keys = torch.empty((max(bound, 1),), dtype=torch.int64, device=dev)
-    ends = torch.empty((max(bound, 1),), dtype=torch.int32, device=dev)
-    rows = torch.arange(k, dtype=torch.int32, device=dev)
-    _lib.check(lib.rsp_rle_intervals(counts.data_ptr(), n.data_ptr(), k, cap, H, W, rows.data_ptr(), rows.data_ptr(),
-                                     moff.data_ptr(), k, bound, keys.data_ptr(), ends.data_ptr(), _stream()), "rsp_rle_intervals")
-    out = torch.empty((k, cap + 1), dtype=torch.int32, device=dev)
-    n_out = torch.zeros((k,), dtype=torch.int32, device=dev)
-    _lib.check(lib.rsp_rle_union(keys.data_ptr(), ends.data_ptr(), bound, iv_offs.data_ptr(), k, H, W, out.data_ptr(),
-                                 n_out.data_ptr(), cap + 1, _stream()), "rsp_rle_union")
-    return out, n_out
+    rows = torch.arange(k, dtype=torch.int32, device=n.device)
+    # total: the slots of all rows, a bound that is known without reading their sum
+    keys, ends, iv_offs, total = _rle_intervals(lib, counts, n, k, cap, H, W, rows, rows, runs, total=k * (cap // 2))
+    return _intervals_to_runs(lib, keys, ends, total, iv_offs, k, H, W, cap + 1)
 
 
 class _RunIntervals:
@@ -2156,12 +2170,6 @@ class _RunIntervals:
         """int32 [k Wt + 1]: the first interval of every column"""
         cols = torch.arange(k * self.Wt + 1, dtype=torch.int32, device=self.col.device)
         return torch.searchsorted(self.col[:self.P], cols, out_int32=True).contiguous()
-
-
-def _exclusive_total(cnt):
-    """int32 counts -> (exclusive sum int64 [len + 1], its last entry still on the device)"""
-    offs = torch.cat([cnt.new_zeros((1,), dtype=torch.int64), torch.cumsum(cnt, 0, dtype=torch.int64)]).contiguous()
-    return offs, offs[-1]
 
 
 def _run_morph_join(lib, op, A, B, k, shift, span, out_shift, Wout, H, emit):
@@ -2211,8 +2219,8 @@ def _run_morph(what, counts, n, H, W, radius, border, band, cap):
     cnts = torch.zeros((len(shapes), k), dtype=torch.int32, device=dev)
     for i, s in enumerate(shapes):
         _lib.check(lib.rsp_run_morph_pieces_count(*args, *s, cnts[i].data_ptr(), _stream()), "rsp_run_morph_pieces_count")
-    offs = torch.cat([cnts.new_zeros((len(shapes), 1), dtype=torch.int64), torch.cumsum(cnts, 1, dtype=torch.int64)], 1).contiguous()
-    totals = offs[:, -1].tolist()                                                                    # read 1
+    offs, totals = _exclusive_total(cnts)
+    totals = totals.tolist()                                                                         # read 1
     if max(totals) >= 2 ** 31:
         raise ValueError(f'{what}: {max(totals)} column pieces in one call; at most 2^31 - 1 (split the rows)')
     tables = []
@@ -2231,13 +2239,7 @@ def _run_morph(what, counts, n, H, W, radius, border, band, cap):
         E = _run_morph_join(lib, 1, tables[1], E, k, 0, 1, 0, W, H, True)
     iv_offs = torch.searchsorted(E.keys[:E.P], torch.arange(k + 1, dtype=torch.int64, device=dev) << 31).contiguous()
 
-    def launch(cap):
-        out = torch.empty((k, cap), dtype=torch.int32, device=dev)
-        n_out = torch.zeros((k,), dtype=torch.int32, device=dev)
-        _lib.check(lib.rsp_rle_union(E.keys.data_ptr(), E.ends.data_ptr(), E.P, iv_offs.data_ptr(), k, H, W, out.data_ptr(),
-                                     n_out.data_ptr(), cap, _stream()), "rsp_rle_union")
-        return out, n_out
-    return fit_runs(launch, cap)
+    return fit_runs(lambda cap: _intervals_to_runs(lib, E.keys, E.ends, E.P, iv_offs, k, H, W, cap), cap)
 
 
 def rle_erode(counts, n, H, W, radius, border=0, cap=None):
@@ -2303,9 +2305,9 @@ def poly_raster_launcher(verts, ring_offs, ring_group, group_hw, compact=True):
     group_px = torch.zeros((max(G, 1),), **i64)
     _lib.check(lib.rsp_poly_raster_edges(verts.data_ptr(), ring_offs.data_ptr(), group_hw.data_ptr(), R, V, G, scaled.data_ptr(),
                                          edge_pts.data_ptr(), group_px.data_ptr(), _stream()), "rsp_poly_raster_edges")
-    edge_offs = torch.cat([edge_pts.new_zeros((1,)), torch.cumsum(edge_pts[:V], 0)]).contiguous()
+    edge_offs, total = _exclusive_total(edge_pts[:V])
     T, coord_max, pixels_max, bad_offs, bad_group = torch.stack(
-        [edge_offs[-1], scaled.abs().max().to(torch.int64), group_px.max(), bad_offs.to(torch.int64),
+        [total, scaled.abs().max().to(torch.int64), group_px.max(), bad_offs.to(torch.int64),
          bad_group.to(torch.int64)]).tolist()
     if bad_offs:
         raise ValueError('poly_raster: ring_offs must ascend from 0 to the number of vertices')
@@ -2508,13 +2510,6 @@ def coco_match(units, iou, gt_area, gt_crowd, gt_id, dt_area, area_rng, thrs, n_
 
 
 # ----------------------------------------------------------------------------- run-domain mask IoU (csrc/coco_iou_runs.hip)
-def _run_table(what, counts, n):
-    if counts.dtype != torch.int32 or counts.dim() != 2 or n.dtype != torch.int32 or n.dim() != 1 \
-            or n.shape[0] != counts.shape[0] or counts.shape[1] < 1 or n.device != counts.device:
-        raise ValueError(f'{what}: expected counts int32 [k, cap >= 1] and n int32 [k] on one device')
-    return counts.contiguous(), n.contiguous()
-
-
 def run_prefix(counts, n, check=True):
     """run table (counts int32 [k, cap], n int32 [k]; any canvas, any counts) -> (workspace int32 [k, cap]: ones pixels in
     front of each ones-run and the run's pixel start, area int64 [k] = rleArea, extent int32 [k, 2] = (first set pixel, one
@@ -2522,8 +2517,8 @@ def run_prefix(counts, n, check=True):
     row that did not fit its producer: ValueError (check=True: one device-to-host read; check=False leaves the test to the
     caller and reads nothing)."""
     lib = _lib.load()
-    counts, n = _run_table('run_prefix', counts, n)
-    k, cap, dev = int(n.shape[0]), int(counts.shape[1]), n.device
+    counts, n, k, cap = _rle_rows('run_prefix', counts, n)[:4]
+    dev = n.device
     if check and k and bool((n < 0).any()):
         raise ValueError('run_prefix: a row with negative n did not fit its producer (ops.fit_runs retries those)')
     ws = torch.empty((max(int(lib.rsp_run_prefix_workspace_bytes(k, cap)) // 4, 1),), dtype=torch.int32, device=dev)
@@ -2543,7 +2538,7 @@ def coco_iou_runs(units, n_iou, dt_runs, gt_runs, gt_crowd, dt_prefix=None, gt_p
     negative n (ValueError) next to it.  info (a dict) receives pairs / survivors."""
     lib = _lib.load()
     dev = units.device
-    (dc, dn), (gc, gn) = _run_table('coco_iou_runs', *dt_runs), _run_table('coco_iou_runs', *gt_runs)
+    (dc, dn), (gc, gn) = _rle_rows('coco_iou_runs', *dt_runs)[:2], _rle_rows('coco_iou_runs', *gt_runs)[:2]
     iou = torch.zeros((max(n_iou, 1),), dtype=torch.float64, device=dev)
     nu = units.numel() // COCO_UNIT_BYTES
     n_dt, n_gt = int(dn.shape[0]), int(gn.shape[0])

@@ -233,12 +233,128 @@ def check_refuses_bad_arguments(ops, dev, pytest):
         ops.mask_polygons(counts, n, 0, 4)
     lib = ops._lib.load()
     p = torch.zeros((64,), dtype=torch.int64, device=dev).data_ptr()
-    assert lib.rsp_mask_polygon_pieces(p, p, 1, 4, 65536, 32768, p, 0) != 0
-    assert lib.rsp_mask_polygon_edges(p, p, 1, 4, 65536, 32768, p, 1, p, p, p, p, 0) != 0
-    assert lib.rsp_mask_polygon_pieces(0, p, 1, 4, 4, 4, p, 0) != 0
-    assert lib.rsp_mask_polygon_edges(p, p, 1, 4, 4, 4, p, 2 ** 31 // 6 + 1, p, p, p, p, 0) != 0
+    assert lib.rsp_run_pieces_count(p, p, 1, 4, 65536, 32768, p, 0) != 0
+    assert lib.rsp_mask_polygon_edges(1, 65536, 32768, p, 1, p, p, p, p, 0) != 0
+    assert lib.rsp_run_pieces_count(0, p, 1, 4, 4, 4, p, 0) != 0
+    assert lib.rsp_mask_polygon_edges(1, 4, 4, p, 2 ** 31 // 6 + 1, p, p, p, p, 0) != 0
     assert lib.rsp_mask_polygon_rank(1, 4, 63, p, p, p, p, p, p, p, p, p, 0) != 0
     assert lib.rsp_mask_polygon_rank_workspace_bytes(-1) == 0 and lib.rsp_mask_polygon_rank_workspace_bytes(2) == 6 * 2 * 28
+
+
+# ---------------------------------------------------------------------------------------------------------- piece table
+def pieces_of_counts(rows, ns, cap, H):
+    """the column-piece table as a statement on the counts alone: every ones-run [s, e) of the first min(n, cap) counts of a
+    row, cut at the multiples of H -> ([(x, y0, y1, instance)] in stream order, piece_offs)"""
+    out, offs = [], [0]
+    for m, (row, n) in enumerate(zip(rows, ns)):
+        s = 0
+        for i in range(max(min(n, cap), 0)):
+            e = s + row[i]
+            if i & 1 and e > s:
+                out += [(x, max(s, x * H) - x * H, min(e, (x + 1) * H) - x * H, m) for x in range(s // H, (e - 1) // H + 1)]
+            s = e
+        offs.append(len(out))
+    return out, offs
+
+
+def piece_tables():
+    """[(H, W, rows, ns)]: per H in 1, 3, 7 a ones-run over four columns, rows with n = 0, n < 0 and n beyond the capacity,
+    a non-canonical row (zero counts between ones-runs, a ones-run of no pixel) and noise; the 24 x 24 checkerboard, whose 553
+    runs cross two chunks of the walk"""
+    rng = np.random.default_rng(41)
+    out = []
+    for H in (1, 3, 7):
+        W = 40
+        noise = [lref.rle_counts_np(rng.random((H, W)) < d) for d in (0.5, 0.3)]
+        rows = [[2, 3 * H + 1, H * W - 3 * H - 3], noise[1], noise[1], noise[0], [1, 2, 0, 3, 0, 0, 4, 1, 1, 0, 2, 2], noise[0], [H * W]]
+        cap = max(len(r) for r in rows)
+        ns = [len(r) for r in rows]
+        ns[1], ns[2], ns[3] = 0, -(cap + 5), cap + 7
+        rows[3] = (rows[3] + [1] * cap)[:cap]                  # every slot of the row that is read up to cap holds a count
+        out.append((H, W, rows, ns))
+    board = (np.add.outer(np.arange(24), np.arange(24)) & 1).astype(bool)
+    row = lref.rle_counts_np(board)
+    assert len(row) > 2 * 256
+    out.append((24, 24, [[5, 7, 564], row], [3, len(row)]))
+    return out
+
+
+def _table_on(rows, ns, dev):
+    counts, _ = seam_cases.rows_from_counts(rows, dev)
+    return counts, torch.tensor(ns, dtype=torch.int32).to(dev)
+
+
+def check_run_pieces(ops, dev):
+    """ops.run_pieces and the two C entries behind it against pieces_of_counts, everything by ==; the tables its two consumers
+    work on are the same bits; the documented host reads of the callers that share the run-domain intermediates"""
+    from _run_morphology_cases import ReadCounter
+    i32 = dict(dtype=torch.int32, device=dev)
+    lib = ops._lib.load()
+    for H, W, rows, ns in piece_tables():
+        counts, n = _table_on(rows, ns, dev)
+        cap = int(counts.shape[1])
+        want, want_offs = pieces_of_counts(rows, ns, cap, H)
+        assert max(x for x, _, _, _ in want) - min(x for x, _, _, _ in want[:4]) >= 3 or H == 24
+        got = ops.run_pieces(counts, n, H, W)
+        assert (got.P, got.widest) == (len(want), max(b - a for a, b in zip(want_offs, want_offs[1:])))
+        assert got.pieces.dtype == torch.int32 and got.piece_offs.dtype == torch.int64 and got.pieces.is_contiguous()
+        assert got.piece_offs.cpu().tolist() == want_offs
+        assert [tuple(p) for p in got.pieces.cpu().t().tolist()] == want, (H, W)
+        # the tables of the two consumers: the one mask_polygons works on (what its call of run_pieces returned) and the one
+        # rle_components returns
+        seen, inner = [], ops.run_pieces
+        ops.run_pieces = lambda *a, **kw: seen.append(inner(*a, **kw)) or seen[-1]
+        try:
+            ops.mask_polygons(counts, n, H, W)
+            comps = ops.rle_components(counts, n, H, W)
+        finally:
+            ops.run_pieces = inner
+        assert len(seen) == 2 and seen[1].pieces is comps.pieces and seen[1].piece_offs is comps.piece_offs
+        for t in seen:
+            assert torch.equal(t.pieces, got.pieces) and torch.equal(t.piece_offs, got.piece_offs) and t.P == got.P
+        # a piece_offs that overstates rows: the slots behind a row's pieces keep instance -1 and nothing else is written
+        k, pad, mark = len(rows), 5, 0x5a5a5a5a
+        cnt = torch.zeros((k,), **i32)
+        assert lib.rsp_run_pieces_count(counts.data_ptr(), n.data_ptr(), k, cap, H, W, cnt.data_ptr(), ops._stream()) == 0
+        assert cnt.cpu().tolist() == [b - a for a, b in zip(want_offs, want_offs[1:])]
+        extra = [(3 * m + 1) % 4 for m in range(k)]
+        offs = [0]
+        for c, x in zip(cnt.cpu().tolist(), extra):
+            offs.append(offs[-1] + c + x)
+        P = offs[-1]
+        buf = torch.full((4 * P + 2 * pad,), mark, **i32)
+        offs_t = torch.tensor(offs, dtype=torch.int64).to(dev)
+        assert lib.rsp_run_pieces(counts.data_ptr(), n.data_ptr(), k, cap, H, W, offs_t.data_ptr(), P, buf[pad:].data_ptr(),
+                                  ops._stream()) == 0
+        host = buf.cpu().tolist()
+        expect = [mark] * pad + [mark] * (3 * P) + [-1] * P + [mark] * pad
+        for m in range(k):
+            for j, p in enumerate(want[want_offs[m]:want_offs[m + 1]]):
+                for plane in range(4):
+                    expect[pad + plane * P + offs[m] + j] = p[plane]
+        assert host == expect, (H, W)
+    # no rows; rows without a piece
+    z = ops.run_pieces(torch.zeros((0, 4), **i32), torch.zeros((0,), **i32), 5, 6)
+    assert (z.P, z.widest, tuple(z.pieces.shape), z.piece_offs.cpu().tolist()) == (0, 0, (4, 0), [0])
+    counts, n = _table_on([[12], [3, 4, 5]], [1, -3], dev)
+    z = ops.run_pieces(counts, n, 3, 4)
+    assert (z.P, z.widest, tuple(z.pieces.shape), z.piece_offs.cpu().tolist()) == (0, 0, (4, 0), [0, 0, 0])
+    C = ops.CONST
+    assert C['RSP_RUN_COMPONENTS_MAX_PIECES'] == C['RSP_RUN_PIECES_MAX_PIECES'] == ops.RUN_PIECES_MAX_PIECES == 0x7fffff00
+    assert C['RSP_MASK_POLYGON_MAX_PIECES'] == (2 ** 31 - 1) // 6 < C['RSP_RUN_PIECES_MAX_PIECES'] and C['RSP_ABI_VERSION'] == 6
+    # host reads
+    H, W, rows, ns = piece_tables()[2]
+    counts, n = _table_on([rows[0], rows[3], rows[5]], [ns[0], len(rows[5]), ns[5]], dev)
+    reads = {}
+    for name, call in (('run_pieces', lambda: ops.run_pieces(counts, n, H, W)),
+                       ('mask_polygons', lambda: ops.mask_polygons(counts, n, H, W)),
+                       ('rle_components', lambda: ops.rle_components(counts, n, H, W)),
+                       ('mask_hull', lambda: ops.mask_hull(counts, n, H, W)),
+                       ('rle_union', lambda: ops.rle_union(counts, n, H, W, torch.tensor([0, 2, 3], **i32), torch.arange(3, **i32), 64))):
+        with ReadCounter(dev) as rc:
+            call()
+        reads[name] = rc.n
+    assert reads == dict(run_pieces=1, mask_polygons=3, rle_components=2, mask_hull=2, rle_union=1), reads
 
 
 # ------------------------------------------------------------------------------------------------------------------ API

@@ -460,13 +460,15 @@ def check_status_and_refusals(ops, rle, dev, pytest):
     assert lib.rsp_run_components_workspace_bytes(0, 4, 1) == -1
     p = torch.zeros((64,), dtype=torch.int64, device=dev).data_ptr()
     # a call without instances touches no array, so it is legal at the limit itself
-    assert lib.rsp_run_components_label(p, p, 0, 4, 2, 2, p, lim, p, p, p, p, p, 0) == OK
-    assert lib.rsp_run_components_label(p, p, 0, 4, 2, 2, p, lim + 1, p, p, p, p, p, 0) == EINVAL
-    assert lib.rsp_run_components_label(p, p, 0, 4, 46341, 46341, p, 1, p, p, p, p, p, 0) == EINVAL
-    assert lib.rsp_run_components_label(p, p, 0, 4, 46340, 46341, p, 1, p, p, p, p, p, 0) == OK
-    assert lib.rsp_run_components_label(0, p, 1, 4, 2, 2, p, 1, p, p, p, p, p, 0) == EINVAL
-    assert lib.rsp_run_components_label(p, p, 1, 0, 2, 2, p, 1, p, p, p, p, p, 0) == EINVAL
-    assert lib.rsp_run_components_label(p, p, 1, 4, 2, 2, p, 1, p, 0, p, p, p, 0) == EINVAL
+    assert lib.rsp_run_components_label(0, 2, 2, p, lim, p, p, p, p, p, 0) == OK
+    assert lib.rsp_run_components_label(0, 2, 2, p, lim + 1, p, p, p, p, p, 0) == EINVAL
+    assert lib.rsp_run_components_label(0, 46341, 46341, p, 1, p, p, p, p, p, 0) == EINVAL
+    assert lib.rsp_run_components_label(0, 46340, 46341, p, 1, p, p, p, p, p, 0) == OK
+    # the table's writer took the run table over, and with it the refusal of a missing one and of a capacity below 1
+    assert lib.rsp_run_pieces(0, p, 1, 4, 2, 2, p, 1, p, 0) == EINVAL
+    assert lib.rsp_run_pieces(p, p, 1, 0, 2, 2, p, 1, p, 0) == EINVAL
+    assert lib.rsp_run_components_label(1, 2, 2, p, 1, 0, p, p, p, p, 0) == EINVAL
+    assert lib.rsp_run_components_label(1, 2, 2, p, 1, p, 0, p, p, p, 0) == EINVAL
     assert lib.rsp_run_components_stats(p, 0, 2, 2, p, p, p, 0, p, p, p, p, p, 0) == OK
     assert lib.rsp_run_components_stats(p, lim + 1, 2, 2, p, p, p, 0, p, p, p, p, p, 0) == EINVAL
     assert lib.rsp_run_components_stats(p, 1, 2, 2, p, p, p, 2, p, p, p, p, p, 0) == EINVAL          # more components than pieces

@@ -24,7 +24,7 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f'{n} declared in include/rsp_hip.h but not exported'
     assert set(_lib.PROTOTYPES) <= set(names)
-    assert lib.rsp_abi_version() == 5
+    assert lib.rsp_abi_version() == 6
     assert b'gfx950' in lib.rsp_build_info()
 
 
@@ -329,7 +329,7 @@ def test_every_limit_refuses_one_past_it_on_the_emulator(emu_lib):
     pieces, ekey, eoth, succ = zeros(4, dtype=i32), zeros(6, dtype=i64), zeros(6, dtype=i32), zeros(6, dtype=i32)
 
     def edges(P):
-        return lib.rsp_mask_polygon_edges(_p(counts), _p(n), 0, 3, 2, 2, _p(offs), P, _p(pieces), _p(ekey), _p(eoth), _p(succ), None)
+        return lib.rsp_mask_polygon_edges(0, 2, 2, _p(offs), P, _p(pieces), _p(ekey), _p(eoth), _p(succ), None)
     assert edges(lim + 1) == EINVAL and edges(lim) == OK
     # polygon simplification: one square ring; both bounds are bounds on values, the call at the limit is as small
     side, tol = C['RSP_RING_SIMPLIFY_MAX_SIDE'], C['RSP_RING_SIMPLIFY_MAX_TOL2_Q8']

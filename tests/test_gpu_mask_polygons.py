@@ -59,6 +59,11 @@ def test_bad_arguments_are_refused(dev):
     cases.check_refuses_bad_arguments(ops, dev, pytest)
 
 
+def test_the_piece_table_its_two_consumers_and_their_host_reads(dev):
+    from rsprompter_amd import ops
+    cases.check_run_pieces(ops, dev)
+
+
 def test_masks_to_polygons_forms(dev):
     from rsprompter_amd import apis, rle
     cases.check_api_forms(apis, rle, dev)

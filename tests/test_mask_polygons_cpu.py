@@ -91,6 +91,10 @@ def test_bad_arguments_are_refused(emu):
     cases.check_refuses_bad_arguments(emu, CPU, pytest)
 
 
+def test_the_piece_table_its_two_consumers_and_their_host_reads(emu):
+    cases.check_run_pieces(emu, CPU)
+
+
 def test_rings_of_shifted_and_joined_run_tables(emu):
     """the tables rsp_rle_shift and rsp_rle_union write are input as well: tile rings + offset, rings of a union"""
     from rsprompter_amd import rle
