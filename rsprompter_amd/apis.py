@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, rle
 from .config import Config
 from .structures import DetDataSample
 
@@ -215,19 +215,12 @@ def remove_small_regions(masks, min_area, mode='both', device='cuda:0'):
     that small are removed; if all are, the largest stays) or 'both' (holes first).  Returns (masks bool of the input's
     shape, changed bool [k] or a bool).  One host read (the labelling's status).
     masks may also be a list of RLE dicts dict(size=[H, W], counts=...) of one size, compressed (bytes / str) or uncompressed
-    (list) counts as in masks_to_polygons: they are cleaned in the run domain (rle.clean_runs; `device` places
-    the run table) and come back as (RLE dicts of the input's counts form, changed bool [k] on the host)."""
+    (list) counts, canonical ones (rle.masks_to_runs): they are cleaned in the run domain (rle.clean_runs, DESIGN §14.10;
+    `device` places the run table) and come back as (RLE dicts of the input's counts form, changed bool [k] on the host)."""
     if not isinstance(masks, torch.Tensor):
-        from . import rle
-        masks = list(masks)
-        counts, n, size = _masks_to_runs(masks, device)
-        _check_canonical(counts, n, size)
+        counts, n, size, form = rle.masks_to_runs(masks, device, 'remove_small_regions', canonical=True)
         counts, n, n_host, _, changed = rle.clean_runs(counts, n, size, min_area, mode)
-        if isinstance(masks[0]['counts'], (bytes, str)):
-            out = rle.runs_to_strings(counts, n, size)
-        else:
-            out = rle.runs_to_dicts(counts, n_host, size)
-        return out, (changed != 0).any(1).cpu()
+        return rle.runs_to_masks(counts, n, size, form, n_host), (changed != 0).any(1).cpu()
     single = masks.dim() == 2
     out, info = ops.remove_small_regions(masks[None] if single else masks, min_area, mode)
     ops.check_region_status(info[:, 7].cpu().tolist())
@@ -235,70 +228,25 @@ def remove_small_regions(masks, min_area, mode='both', device='cuda:0'):
     return (out[0], bool(changed[0])) if single else (out, changed)
 
 
-# ------------------------------------------------------------------------------------------ polygon export
-POLYGON_FORMS = ('rings', 'coco', 'geojson')
-
-
-def _masks_to_runs(masks, device):
-    """the three mask forms of masks_to_polygons -> (counts, n, (H, W)) on the device"""
-    from . import rle
-    if isinstance(masks, torch.Tensor):
-        if masks.dim() != 3:
-            raise ValueError('masks_to_polygons: a mask tensor is bool [k, H, W]')
-        counts, n, _, _ = rle.encode_runs(masks.to(torch.bool))
-        return counts, n, (int(masks.shape[1]), int(masks.shape[2]))
-    masks = list(masks)
-    if not masks:
-        raise ValueError('masks_to_polygons: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
-    sizes = {(int(m['size'][0]), int(m['size'][1])) for m in masks}
-    if len(sizes) != 1:
-        raise ValueError(f'masks_to_polygons: the RLE dicts of one call share one size, got {sorted(sizes)}')
-    size = sizes.pop()
-    dev = torch.device(device)
-    ops.require_device(dev)
-    kinds = {isinstance(m['counts'], (bytes, str)) for m in masks}
-    if len(kinds) != 1:
-        raise ValueError('masks_to_polygons: compressed (bytes / str) and uncompressed (list) counts in one call')
-    if kinds.pop():
-        strings = [m['counts'].encode() if isinstance(m['counts'], str) else bytes(m['counts']) for m in masks]
-        offs = np.cumsum([0] + [len(s) for s in strings]).astype(np.int64)
-        flat = torch.from_numpy(np.frombuffer(b''.join(strings) or b'\0', dtype=np.uint8).copy()).to(dev)
-        counts, n = ops.rle_from_string(flat, torch.from_numpy(offs).to(dev))
-        return counts, n, size
-    width = max(max(len(m['counts']) for m in masks), 1)
-    table = np.zeros((len(masks), width), np.int64)
-    for i, m in enumerate(masks):
-        table[i, :len(m['counts'])] = m['counts']
-    if table.size and (int(table.max()) >= 2 ** 31 or int(table.min()) < 0):
-        raise ValueError('masks_to_polygons: not canonical COCO run counts: a count is negative or does not fit 32 bits')
-    n = torch.tensor([len(m['counts']) for m in masks], dtype=torch.int32)
-    return torch.from_numpy(table.astype(np.int32)).to(dev), n.to(dev), size
-
-
-def _masks_to_runs_mixed(masks, device):
-    """_masks_to_runs for lists whose dicts carry sizes of their own, compressed and uncompressed counts side by side ->
-    (counts, n, [(H, W)] per mask) on the device: one table, the rows in the order of the list (the run-domain IoU takes no
-    canvas size).  An empty list is an empty table."""
-    from . import rle
-    if isinstance(masks, torch.Tensor):
-        counts, n, size = _masks_to_runs(masks, device)
-        return counts, n, [size] * int(n.shape[0])
-    masks = list(masks)
-    dev = torch.device(device)
-    ops.require_device(dev)
-    if not masks:
-        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), []
-    sizes = [(int(m['size'][0]), int(m['size'][1])) for m in masks]
-    packed = [i for i, m in enumerate(masks) if isinstance(m['counts'], (bytes, str))]
-    plain = [i for i, m in enumerate(masks) if not isinstance(m['counts'], (bytes, str))]
-    tables, ns = [], []
-    for idx in (packed, plain):
-        if idx:                                               # one size for _masks_to_runs' sake: the sizes stay with us
-            c, n, _ = _masks_to_runs([dict(size=[1, 1], counts=masks[i]['counts']) for i in idx], dev)
-            tables.append(c)
-            ns.append(n)
-    back = torch.tensor(np.argsort(np.asarray(packed + plain, np.int64), kind='stable'), dtype=torch.int64, device=dev)
-    return rle.concat_runs(tables, rows=back).contiguous(), torch.cat(ns)[back].contiguous(), sizes
+# ------------------------------------------------------------------------------------------ run-domain IoU
+def _iou_sides(dt, gt, iscrowd, device, what):
+    """what mask_iou and boundary_iou do before their kernels: both sides as run tables, the refusals, the one unit of D x G
+    pairs and the crowd flags -> ((dt counts, n), (gt counts, n), D, G, the common size or None, units, g_crowd)"""
+    for t in (dt, gt):
+        if isinstance(t, torch.Tensor):
+            device = t.device
+    dc, dn, d_sizes, _ = rle.masks_to_runs(dt, device, what, one_size=False)
+    gc, gn, g_sizes, _ = rle.masks_to_runs(gt, device, what, one_size=False)
+    D, G = len(d_sizes), len(g_sizes)
+    sizes = set(d_sizes) | set(g_sizes)
+    if D and G and len(sizes) != 1:
+        raise ValueError(f'{what}: masks of different sizes in one call: {sorted(sizes)}')
+    crowd = np.zeros(G, np.uint8) if iscrowd is None else np.asarray(list(iscrowd)).astype(bool).astype(np.uint8).reshape(-1)
+    if crowd.shape[0] != G:
+        raise ValueError(f'{what}: iscrowd has {crowd.shape[0]} entries for {G} ground truths')
+    units = ops.coco_units([0], [0], [0], [D], [G], [0], dn.device)
+    g_crowd = torch.from_numpy(np.concatenate([crowd, [0]]).astype(np.uint8)).to(dn.device)
+    return (dc, dn), (gc, gn), D, G, sizes.pop() if D and G else None, units, g_crowd
 
 
 def mask_iou(dt, gt, iscrowd=None, device='cuda:0'):
@@ -309,34 +257,12 @@ def mask_iou(dt, gt, iscrowd=None, device='cuda:0'):
     No mask is expanded: scene-sized RLE costs its runs.  iscrowd: a bool per gt (None: none is).  Masks of different sizes
     in one call are refused (ValueError; cocoapi writes -1 there).  One device-to-host read (the pairs whose extents
     overlap), and the run capacity retry of bool tensors / compressed strings."""
-    for t in (dt, gt):
-        if isinstance(t, torch.Tensor):
-            device = t.device
-    dc, dn, d_sizes = _masks_to_runs_mixed(dt, device)
-    gc, gn, g_sizes = _masks_to_runs_mixed(gt, device)
-    D, G = len(d_sizes), len(g_sizes)
-    if D and G and len(set(d_sizes) | set(g_sizes)) != 1:
-        raise ValueError(f'mask_iou: masks of different sizes in one call: {sorted(set(d_sizes) | set(g_sizes))}')
-    crowd = np.zeros(G, np.uint8) if iscrowd is None else np.asarray(list(iscrowd)).astype(bool).astype(np.uint8).reshape(-1)
-    if crowd.shape[0] != G:
-        raise ValueError(f'mask_iou: iscrowd has {crowd.shape[0]} entries for {G} ground truths')
-    dev = dn.device
-    units = ops.coco_units([0], [0], [0], [D], [G], [0], dev)
-    g_crowd = torch.from_numpy(np.concatenate([crowd, [0]]).astype(np.uint8)).to(dev)
-    return ops.coco_iou_runs(units, D * G, (dc, dn), (gc, gn), g_crowd).view(D, G)
+    d_runs, g_runs, D, G, _, units, g_crowd = _iou_sides(dt, gt, iscrowd, device, 'mask_iou')
+    return ops.coco_iou_runs(units, D * G, d_runs, g_runs, g_crowd).view(D, G)
 
 
 # --------------------------------------------------------------------------------------- morphology, Boundary IoU (DESIGN §14.13)
 MORPHOLOGY_OPS = ('erode', 'dilate', 'open', 'close', 'boundary')
-
-
-def _runs_to_dense(counts, n, size):
-    """run table -> bool [k, H, W] on the device, through the bit planes of ops.rle_to_bits"""
-    (H, W), k, dev = size, int(n.shape[0]), n.device
-    nw = (H * W + 63) // 64
-    bits = ops.rle_to_bits(counts.contiguous(), n, torch.arange(k + 1, dtype=torch.int64, device=dev) * nw)[0]
-    px = (bits[:k * nw].view(torch.uint8).view(k, nw * 8, 1) >> torch.arange(8, dtype=torch.uint8, device=dev)) & 1
-    return px.view(k, nw * 64)[:, :H * W].reshape(k, W, H).transpose(1, 2).to(torch.bool).contiguous()
 
 
 def _morph_radius(radius):
@@ -345,24 +271,14 @@ def _morph_radius(radius):
     return int(radius)
 
 
-def _morphology(masks, op, radius, device):
-    from . import rle
+def _morphology(masks, op, radius, device, what):
     fn = dict(erode=rle.erode_runs, dilate=rle.dilate_runs, open=rle.open_runs, close=rle.close_runs,
               boundary=rle.boundary_runs)[op]
-    if isinstance(masks, torch.Tensor):
-        if masks.dim() != 3:
-            raise ValueError('mask_morphology: a mask tensor is bool [k, H, W]')
-        if masks.shape[0] == 0:
-            return masks.to(torch.bool).clone()
-        counts, n, size = _masks_to_runs(masks, masks.device)
-        counts, n, _, _ = fn(counts, n, size, radius)
-        return _runs_to_dense(counts, n, size)
-    masks = list(masks)
-    counts, n, size = _masks_to_runs(masks, device)
+    if isinstance(masks, torch.Tensor) and masks.dim() == 3 and masks.shape[0] == 0:
+        return masks.to(torch.bool).clone()
+    counts, n, size, form = rle.masks_to_runs(masks, device, what)
     counts, n, n_host, _ = fn(counts, n, size, radius)
-    if isinstance(masks[0]['counts'], (bytes, str)):
-        return rle.runs_to_strings(counts.contiguous(), n, size)
-    return rle.runs_to_dicts(counts, n_host, size)
+    return rle.runs_to_masks(counts, n, size, form, n_host)
 
 
 def mask_morphology(masks, op, radius, device='cuda:0'):
@@ -375,14 +291,13 @@ def mask_morphology(masks, op, radius, device='cuda:0'):
     pieces times log radius."""
     if op not in MORPHOLOGY_OPS:
         raise ValueError(f'mask_morphology: op must be one of {MORPHOLOGY_OPS}, got {op!r}')
-    return _morphology(masks, op, _morph_radius(radius), device)
+    return _morphology(masks, op, _morph_radius(radius), device, 'mask_morphology')
 
 
 def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0'):
     """The boundary band of Boundary IoU (Cheng et al., CVPR 2021; boundary-iou-api mask_to_boundary): the pixels of each
     mask within d of its outline or of the image border, d = rle.boundary_radius(size, dilation_ratio) = max(1, round(ratio *
     diagonal)) or `radius` when given.  Input and output forms as mask_morphology's."""
-    from . import rle
     if radius is None:
         size = tuple(masks.shape[1:]) if isinstance(masks, torch.Tensor) else None
         if size is None:
@@ -391,54 +306,26 @@ def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0'):
                 raise ValueError('mask_boundary: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
             size = masks[0]['size']
         radius = rle.boundary_radius(size, dilation_ratio)
-    return _morphology(masks, 'boundary', _morph_radius(radius), device)
+    return _morphology(masks, 'boundary', _morph_radius(radius), device, 'mask_boundary')
 
 
 def boundary_iou(dt, gt, iscrowd=None, dilation_ratio=0.02, radius=None, min_with_mask=False, device='cuda:0'):
     """Boundary IoU of every pair: mask_iou of the boundary bands (mask_boundary) -> float64 [D, G] on the device, with the
     inputs, conventions and refusals of mask_iou (0.0 without a common band pixel, / |dt band| for a crowd gt, masks of
     different sizes refused).  min_with_mask=True returns min(mask IoU, boundary IoU), what Boundary AP matches with."""
-    from . import rle
-    for t in (dt, gt):
-        if isinstance(t, torch.Tensor):
-            device = t.device
-    dc, dn, d_sizes = _masks_to_runs_mixed(dt, device)
-    gc, gn, g_sizes = _masks_to_runs_mixed(gt, device)
-    D, G = len(d_sizes), len(g_sizes)
-    sizes = set(d_sizes) | set(g_sizes)
-    if D and G and len(sizes) != 1:
-        raise ValueError(f'boundary_iou: masks of different sizes in one call: {sorted(sizes)}')
-    crowd = np.zeros(G, np.uint8) if iscrowd is None else np.asarray(list(iscrowd)).astype(bool).astype(np.uint8).reshape(-1)
-    if crowd.shape[0] != G:
-        raise ValueError(f'boundary_iou: iscrowd has {crowd.shape[0]} entries for {G} ground truths')
-    dev = dn.device
-    units = ops.coco_units([0], [0], [0], [D], [G], [0], dev)
-    g_crowd = torch.from_numpy(np.concatenate([crowd, [0]]).astype(np.uint8)).to(dev)
+    d_runs, g_runs, D, G, size, units, g_crowd = _iou_sides(dt, gt, iscrowd, device, 'boundary_iou')
     if not (D and G):
-        return torch.zeros((D, G), dtype=torch.float64, device=dev)
-    size = sizes.pop()
+        return torch.zeros((D, G), dtype=torch.float64, device=g_crowd.device)
     r = rle.boundary_radius(size, dilation_ratio) if radius is None else _morph_radius(radius)
-    db, gb = rle.boundary_runs(dc, dn, size, r)[:2], rle.boundary_runs(gc, gn, size, r)[:2]
+    db, gb = rle.boundary_runs(*d_runs, size, r)[:2], rle.boundary_runs(*g_runs, size, r)[:2]
     out = ops.coco_iou_runs(units, D * G, db, gb, g_crowd)
     if min_with_mask:
-        out = torch.minimum(out, ops.coco_iou_runs(units, D * G, (dc, dn), (gc, gn), g_crowd))
+        out = torch.minimum(out, ops.coco_iou_runs(units, D * G, d_runs, g_runs, g_crowd))
     return out.view(D, G)
 
 
-def _check_canonical(counts, n, size):
-    """RLE dicts come from outside: the tracer reads canonical COCO counts only (a zero count anywhere but in front would
-    make two runs of one value touch, counts that do not sum to H * W describe another canvas).  One device-to-host read."""
-    k, cap = int(counts.shape[0]), int(counts.shape[1])
-    if k == 0:
-        return
-    live = torch.arange(cap, device=counts.device)[None] < n[:, None]
-    c = torch.where(live, counts, 0).to(torch.int64)
-    bad = ((c[:, 1:] <= 0) & live[:, 1:]).any(1) | (c[:, :1] < 0).any(1) | ((c.sum(1) != size[0] * size[1]) & (n > 0))
-    rows = bad.nonzero().view(-1).tolist()
-    if rows:
-        raise ValueError(f'masks_to_polygons: the counts of mask {rows[0]} are not canonical COCO run counts of a '
-                         f'{size[0]} x {size[1]} canvas (a zero or negative count after the first, or a sum other than H * W)'
-                         + (f'; {len(rows)} masks in all' if len(rows) > 1 else ''))
+# ------------------------------------------------------------------------------------------ polygon export (DESIGN §14.7)
+POLYGON_FORMS = ('rings', 'coco', 'geojson')
 
 
 def rings_to_coco(rings):
@@ -501,7 +388,6 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tole
       (they may then cross); rings of less than min_ring_area pixels, rings that collapse, and the holes of a dropped outer
       ring are dropped -- a dropped hole is filled.  Both apply to all three forms; min_ring_area alone (tolerance=None)
       filters at tolerance 0, which keeps every vertex of the rings that stay."""
-    from . import rle
     if form not in POLYGON_FORMS:
         raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
     if transform is not None and form != 'geojson':
@@ -510,9 +396,7 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tole
     if simplify:                                                        # refused before anything runs
         rle.polygon_tolerance_q8(0 if tolerance is None else tolerance)
         rle.polygon_min_ring_area(min_ring_area)
-    counts, n, size = _masks_to_runs(masks, device)
-    if not isinstance(masks, torch.Tensor):
-        _check_canonical(counts, n, size)
+    counts, n, size, _ = rle.masks_to_runs(masks, device, 'masks_to_polygons', canonical=True)
     polys = rle.runs_to_polygons(counts, n, size)
     if simplify:
         polys, _ = rle.simplify_polygons(polys, size, 0 if tolerance is None else tolerance, min_ring_area)
@@ -582,7 +466,6 @@ def polygons_to_masks(polygons, size, form='rle', fill=None, transform=None, dev
     form='rle': list of dict(size=[H, W], counts=bytes), what every run-domain API here takes; 'runs': (counts int32
       [k, cap], n int32 [k]) on the device; 'dense': bool [k, H, W] on the device (refused above
       large_image.DENSE_MASK_LIMIT_BYTES)."""
-    from . import rle
     if form not in MASK_FORMS:
         raise ValueError(f'mask form {form!r}: one of {MASK_FORMS}')
     if fill is not None and fill not in rle.POLYGON_FILLS:
@@ -615,14 +498,7 @@ def polygons_to_masks(polygons, size, form='rle', fill=None, transform=None, dev
                                      torch.tensor([[H, W]] * k, dtype=torch.int32, device=dev).view(k, 2), fill=fill)
     if form == 'runs':
         return counts, n
-    if form == 'rle':
-        return rle.runs_to_strings(counts.contiguous(), n, (H, W))
-    nw = (H * W + 63) // 64
-    bits = ops.rle_to_bits(counts.contiguous(), n, torch.arange(k + 1, dtype=torch.int64, device=dev) * nw)[0]
-    # pixel j of the column-major stream is bit j & 7 of byte j >> 3 (little-endian words): one byte per pixel,
-    # then [W, H] -> [H, W]
-    px = (bits[:k * nw].view(torch.uint8).view(k, nw * 8, 1) >> torch.arange(8, dtype=torch.uint8, device=dev)) & 1
-    return px.view(k, nw * 64)[:, :H * W].reshape(k, W, H).transpose(1, 2).to(torch.bool).contiguous()
+    return rle.runs_to_masks(counts, n, (H, W), 'strings' if form == 'rle' else 'dense')
 
 
 # ------------------------------------------------------------------------------------------- oriented boxes
@@ -650,8 +526,8 @@ def obb_to_geojson(corners, transform=None):
 
 def masks_to_obb(masks, form='corners', transform=None, device='cuda:0', per_component=False):
     """Masks -> oriented boxes: the minimum-area rectangle around each mask (all its components together), exact on the
-    device in the run domain; what cv2.convexHull + cv2.minAreaRect give on a dense mask.  `masks` as in
-    masks_to_polygons (a bool [k, H, W] device tensor, or RLE dicts of one size with compressed or uncompressed counts).
+    device in the run domain; what cv2.convexHull + cv2.minAreaRect give on a dense mask.  `masks`: a
+    bool [k, H, W] device tensor, or RLE dicts of one size with compressed or uncompressed canonical counts (rle.masks_to_runs).
     form='corners': float64 [k, 4, 2], the corners in pixel-corner coordinates (pixel (x, y) covers [x, x + 1] x [y, y + 1]),
       clockwise on screen, the first side on a hull edge; NaN rows for empty masks.
     form='xywha': float64 [k, 5] = centre x, y, w >= h, angle of the w side in radians from +x towards +y in [-pi / 2, pi / 2).
@@ -661,15 +537,12 @@ def masks_to_obb(masks, form='corners', transform=None, device='cuda:0', per_com
       'xywha' (an affine map does not keep rectangles) and 'hull' (integer vertices).
     per_component=True: a list with one entry per instance, holding in the same form the boxes or hulls of its 8-connected
       components in component order (rle.split_runs); an empty mask has an empty entry."""
-    from . import rle
     if form not in OBB_FORMS:
         raise ValueError(f'oriented-box form {form!r}: one of {OBB_FORMS}')
     if transform is not None and form not in ('corners', 'geojson'):
         raise ValueError("transform applies to form='corners' and form='geojson' only: an affine map does not keep the "
                          "rectangle of 'xywha'")
-    counts, n, size = _masks_to_runs(masks, device)
-    if not isinstance(masks, torch.Tensor):
-        _check_canonical(counts, n, size)
+    counts, n, size, _ = rle.masks_to_runs(masks, device, 'masks_to_obb', canonical=True)
     if per_component:                                                   # one row per component, regrouped below
         counts, n, _, _, comp_offs = rle.split_runs(counts, n, size)
         co = comp_offs.tolist()
@@ -691,11 +564,9 @@ def masks_to_obb(masks, form='corners', transform=None, device='cuda:0', per_com
 def mask_components(masks, device='cuda:0'):
     """Masks -> per instance dict(count, areas int32 [c], bboxes int32 [c, 4] = (x0, y0, x1, y1) end-exclusive) of its
     8-connected components, ordered by their first pixel in column-major order; labelled on the device in the run domain
-    (rle.runs_components).  `masks` as in masks_to_polygons.  One transfer after the labelling's two reads."""
-    from . import rle
-    counts, n, size = _masks_to_runs(masks, device)
-    if not isinstance(masks, torch.Tensor):
-        _check_canonical(counts, n, size)
+    (rle.runs_components).  `masks` in the forms of rle.masks_to_runs.  One transfer after the labelling's two
+    reads."""
+    counts, n, size, _ = rle.masks_to_runs(masks, device, 'mask_components', canonical=True)
     comps = rle.runs_components(counts, n, size)
     k, C = int(n.shape[0]), int(comps.comp_area.shape[0])
     buf = torch.cat([comps.comp_offs, comps.comp_area.to(torch.int64), comps.comp_box.reshape(-1).to(torch.int64)]).cpu().numpy()

@@ -18,7 +18,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, rle
 from .datasets import ann_to_rle, anns_to_rle
 from .registry import Registry
 
@@ -41,44 +41,19 @@ def _np(x):
     return np.asarray(x)
 
 
-def _flat_strings(strings, device):
-    lens = np.fromiter((len(s) for s in strings), dtype=np.int64, count=len(strings))
-    offs = np.zeros(len(strings) + 1, dtype=np.int64)
-    np.cumsum(lens, out=offs[1:])
-    flat = np.frombuffer(b''.join(strings), dtype=np.uint8) if offs[-1] else np.zeros(1, dtype=np.uint8)
-    return torch.from_numpy(flat.copy()).to(device), torch.from_numpy(offs).to(device)
+def _segm_runs(segms, device):
+    """the run table (counts, n) of compressed segmentations, for masks of any size"""
+    return rle.strings_to_runs([s['counts'] for s in segms], device)
 
 
-def _masks_on_device(rles, device):
-    """compressed RLE dicts -> (bits, word_offs, area int64, wrange) on the device (rsp_rle_from_string + rsp_rle_to_bits)"""
-    strings = [r['counts'] if isinstance(r['counts'], bytes) else str(r['counts']).encode() for r in rles]
-    nwords = np.fromiter(((int(r['size'][0]) * int(r['size'][1]) + 63) // 64 for r in rles), dtype=np.int64,
-                         count=len(rles))
-    woff = np.zeros(len(rles) + 1, dtype=np.int64)
-    np.cumsum(nwords, out=woff[1:])
-    flat, offs = _flat_strings(strings, device)
-    counts, n = ops.rle_from_string(flat, offs)
-    woff_d = torch.from_numpy(woff).to(device)
-    bits, area, wrange = ops.rle_to_bits(counts, n, woff_d)
-    return bits, woff_d, area, wrange
-
-
-def _runs_on_device(rles, device):
-    """compressed RLE dicts -> the run table (counts, n) on the device (rsp_rle_from_string): _masks_on_device without the
-    bits, for masks of any size"""
-    strings = [r['counts'] if isinstance(r['counts'], bytes) else str(r['counts']).encode() for r in rles]
-    flat, offs = _flat_strings(strings, device)
-    return ops.rle_from_string(flat, offs)
+def _segm_sizes(segms):
+    return [s['size'] for s in segms]
 
 
 IOU_DOMAINS = ('bits', 'runs', 'auto')
 # iou_domain='auto': the run route when the bit words of one device_evaluate call (every dt and gt mask at one bit per
 # pixel) would pass this; one 8 192 x 9 000 mask is 9.2 MB of them
 BITS_BUDGET_BYTES = 1 << 30
-
-
-def _bits_bytes(rles):
-    return sum(8 * ((int(r['size'][0]) * int(r['size'][1]) + 63) // 64) for r in rles)
 
 
 class CocoEvalResult:
@@ -93,7 +68,6 @@ class CocoEvalResult:
 def _band_runs(runs, sizes, dilation_ratio):
     """the boundary bands of a run table whose rows lie on canvases of their own (sizes: (H, W) per row): the rows grouped
     by size, one rle.boundary_runs call per size with that size's radius, the groups put back in row order"""
-    from . import rle
     counts, n = runs
     groups = {}
     for i, s in enumerate(sizes):
@@ -118,14 +92,7 @@ def _band_iou(units, n_iou, d_runs, g_runs, d_sizes, g_sizes, g_crowd, dilation_
     d_band, g_band = _band_runs(d_runs, d_sizes, dilation_ratio), _band_runs(g_runs, g_sizes, dilation_ratio)
     if iou_domain == 'runs':
         return ops.coco_iou_runs(units, n_iou, d_band, g_band, g_crowd)
-    planes = []
-    for (counts, n), sizes in ((d_band, d_sizes), (g_band, g_sizes)):
-        woff = np.zeros(len(sizes) + 1, dtype=np.int64)
-        np.cumsum([(int(s[0]) * int(s[1]) + 63) // 64 for s in sizes], out=woff[1:])
-        woff_d = torch.from_numpy(woff).to(n.device)
-        bits, area, wrange = ops.rle_to_bits(counts, n, woff_d)
-        planes.append((bits, woff_d, area, wrange))
-    (db, dwo, da, dwr), (gb, gwo, ga, gwr) = planes
+    (db, dwo, da, dwr), (gb, gwo, ga, gwr) = rle.runs_to_bits(*d_band, d_sizes), rle.runs_to_bits(*g_band, g_sizes)
     return ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo, gt_woff=gwo,
                         dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
 
@@ -205,12 +172,12 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     g_area = dev([g['area'] for g in gts], np.float64)
     g_id = dev([g['id'] for g in gts], np.int64)
     t1 = time.perf_counter()
+    d_segm, g_segm = ([x['segmentation'] for x in dts], [x['segmentation'] for x in gts]) if segm else ([], [])
     if segm and iou_domain == 'auto':
-        iou_domain = 'runs' if _bits_bytes([d['segmentation'] for d in dts]) + \
-            _bits_bytes([g['segmentation'] for g in gts]) > BITS_BUDGET_BYTES else 'bits'
+        words = int(rle.word_offsets(_segm_sizes(d_segm))[-1] + rle.word_offsets(_segm_sizes(g_segm))[-1])
+        iou_domain = 'runs' if 8 * words > BITS_BUDGET_BYTES else 'bits'
     if segm and iou_domain == 'runs':
-        d_runs = _runs_on_device([d['segmentation'] for d in dts], device)
-        g_runs = _runs_on_device([g['segmentation'] for g in gts], device)
+        d_runs, g_runs = _segm_runs(d_segm, device), _segm_runs(g_segm, device)
         d_pre = ops.run_prefix(*d_runs, check=False)           # rle_from_string's retry left no negative n
         info = {}
         iou = ops.coco_iou_runs(units, n_iou, d_runs, g_runs, g_crowd, dt_prefix=d_pre, info=info)
@@ -218,8 +185,8 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         if timings is not None:
             timings.update(pairs=info['pairs'], survivors=info['survivors'])
     elif segm:
-        db, dwo, da, dwr = _masks_on_device([d['segmentation'] for d in dts], device)
-        gb, gwo, ga, gwr = _masks_on_device([g['segmentation'] for g in gts], device)
+        db, dwo, da, dwr = rle.runs_to_bits(*_segm_runs(d_segm, device), _segm_sizes(d_segm))
+        gb, gwo, ga, gwr = rle.runs_to_bits(*_segm_runs(g_segm, device), _segm_sizes(g_segm))
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
                            gt_woff=gwo, dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
         d_area = da.to(torch.float64) if n_dt else dev([0.0], np.float64)
@@ -231,10 +198,9 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     if iou_type == 'boundary' and n_iou:
         tb = time.perf_counter()
         if iou_domain != 'runs':
-            d_runs = _runs_on_device([d['segmentation'] for d in dts], device)
-            g_runs = _runs_on_device([g['segmentation'] for g in gts], device)
-        band = _band_iou(units, n_iou, d_runs, g_runs, [d['segmentation']['size'] for d in dts],
-                         [g['segmentation']['size'] for g in gts], g_crowd, dilation_ratio, iou_domain)
+            d_runs, g_runs = _segm_runs(d_segm, device), _segm_runs(g_segm, device)
+        band = _band_iou(units, n_iou, d_runs, g_runs, _segm_sizes(d_segm), _segm_sizes(g_segm), g_crowd, dilation_ratio,
+                         iou_domain)
         iou = torch.minimum(iou[:n_iou], band)
         if timings is not None:
             timings['band'] = timings.get('band', 0.0) + (time.perf_counter() - tb)     # inside 'device'

@@ -10,7 +10,14 @@ host and report a row that did not fit as n[i] = -(slots needed).  The retry on 
 string bytes (offs[k] > flat_cap: again with flat_cap = offs[k]) is `_string_bytes`; the features call the pipelines below
 and hold no capacity loop of their own.  The run table is also where the VECTOR form starts: runs_to_polygons
 turns it into exact rings on the device, simplify_polygons thins them there, polygons_to_lists brings them
-to the host in one transfer."""
+to the host in one transfer.
+
+The section "mask forms" below is the one home of the conversions between a CALLER'S masks (a dense bool tensor, RLE dicts
+with compressed or with uncompressed counts) and the run table, in both directions (DESIGN §14 "Mask forms"): masks_to_runs
+(over encode_runs, strings_to_runs, lists_to_runs, check_canonical) on the way in, runs_to_masks (over runs_to_dense,
+runs_to_strings, runs_to_dicts) on the way out, runs_to_bits for the bit planes of the COCO IoU.  The caller-facing
+functions of apis.py and evaluation.py check their own arguments and call these; ops.rle_from_string and ops.rle_to_bits
+have no other caller in the package."""
 import math
 
 import numpy as np
@@ -372,6 +379,130 @@ def runs_to_dicts(counts, n_host, size):
     lengths on the host (what fit_runs returned); one transfer, the table."""
     counts, n_host = counts.cpu().numpy(), n_host.tolist()
     return [dict(size=[int(size[0]), int(size[1])], counts=counts[i, :n_host[i]].tolist()) for i in range(len(n_host))]
+
+
+# ---------------------------------------------------------------------------------------------------- mask forms (DESIGN §14)
+# A caller's masks are a bool [k, H, W] tensor ('dense'), RLE dicts with compressed counts (bytes / str: 'strings') or with
+# uncompressed counts (list: 'lists').  Every conversion between these and the run table is here, in both directions.
+def strings_to_runs(strings, device, cap=1024):
+    """COCO's compressed counts (bytes as they are, str encoded) -> (counts, n) on `device` (ops.rle_from_string under
+    ops.fit_runs: one device-to-host read per attempt)"""
+    strings = [s if type(s) is bytes else s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+    offs = np.zeros(len(strings) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, strings), dtype=np.int64, count=len(strings)), out=offs[1:])
+    flat = np.frombuffer(b''.join(strings) or b'\0', dtype=np.uint8).copy()
+    return ops.rle_from_string(torch.from_numpy(flat).to(device), torch.from_numpy(offs).to(device), cap)
+
+
+def lists_to_runs(lists, device, what='lists_to_runs'):
+    """uncompressed counts -> (counts zero-padded, n) on `device`; no device-to-host read"""
+    table = np.zeros((len(lists), max([len(c) for c in lists] + [1])), np.int64)
+    for i, c in enumerate(lists):
+        table[i, :len(c)] = c
+    if table.size and (int(table.max()) >= 2 ** 31 or int(table.min()) < 0):
+        raise ValueError(f'{what}: not canonical COCO run counts: a count is negative or does not fit 32 bits')
+    n = torch.tensor([len(c) for c in lists], dtype=torch.int32)
+    return torch.from_numpy(table.astype(np.int32)).to(device), n.to(device)
+
+
+def check_canonical(counts, n, size, what):
+    """RLE dicts come from outside: the tracer reads canonical COCO counts only (a zero count anywhere but in front would
+    make two runs of one value touch, counts that do not sum to H * W describe another canvas).  One device-to-host read."""
+    k, cap = int(counts.shape[0]), int(counts.shape[1])
+    if k == 0:
+        return
+    live = torch.arange(cap, device=counts.device)[None] < n[:, None]
+    c = torch.where(live, counts, 0).to(torch.int64)
+    bad = ((c[:, 1:] <= 0) & live[:, 1:]).any(1) | (c[:, :1] < 0).any(1) | ((c.sum(1) != size[0] * size[1]) & (n > 0))
+    rows = bad.nonzero().view(-1).tolist()
+    if rows:
+        raise ValueError(f'{what}: the counts of mask {rows[0]} are not canonical COCO run counts of a '
+                         f'{size[0]} x {size[1]} canvas (a zero or negative count after the first, or a sum other than H * W)'
+                         + (f'; {len(rows)} masks in all' if len(rows) > 1 else ''))
+
+
+def masks_to_runs(masks, device, what, *, one_size=True, canonical=False, cap=None):
+    """A caller's masks -> (counts, n, size, form) on the device: a bool [k, H, W] tensor (form 'dense', on its own device;
+    encode_runs) or a list of RLE dicts dict(size=[H, W], counts=...) ('strings' / 'lists'; `device` places the table).
+    `what` names the public function that was called and heads every refusal.
+    one_size=True: the dicts share one size = (H, W) and one counts form; an empty list carries no size and is refused.
+    one_size=False: size is the list of every row's own (H, W); compressed and uncompressed counts may stand side by side
+      ('mixed'): one table, the rows in list order (the run-domain IoU takes no canvas size); an empty list is an empty table.
+    canonical=True: check_canonical on what came as dicts (one more read).  cap: the first run capacity of the producer."""
+    if isinstance(masks, torch.Tensor):
+        if masks.dim() != 3:
+            raise ValueError(f'{what}: a mask tensor is bool [k, H, W]')
+        counts, n, _, _ = encode_runs(masks.to(torch.bool), cap or 4096)
+        size = (int(masks.shape[1]), int(masks.shape[2]))
+        return counts, n, size if one_size else [size] * int(n.shape[0]), 'dense'
+    masks = list(masks)
+    sizes = [(int(m['size'][0]), int(m['size'][1])) for m in masks]
+    packed = [isinstance(m['counts'], (bytes, str)) for m in masks]
+    if one_size:
+        if not masks:
+            raise ValueError(f'{what}: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
+        if len(set(sizes)) != 1:
+            raise ValueError(f'{what}: the RLE dicts of one call share one size, got {sorted(set(sizes))}')
+        if len(set(packed)) != 1:
+            raise ValueError(f'{what}: compressed (bytes / str) and uncompressed (list) counts in one call')
+    dev = torch.device(device)
+    ops.require_device(dev)
+    if not masks:
+        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), [], 'lists'
+    form = 'mixed' if len(set(packed)) > 1 else 'strings' if packed[0] else 'lists'
+    order, tables, ns = [], [], []
+    for is_packed in (True, False):                                     # a table per counts form: the compressed rows first
+        idx = [i for i, p in enumerate(packed) if p == is_packed]
+        if idx:
+            rows = [masks[i]['counts'] for i in idx]
+            c, n = strings_to_runs(rows, dev, cap or 1024) if is_packed else lists_to_runs(rows, dev, what)
+            order, tables, ns = order + idx, tables + [c], ns + [n]
+    if one_size:                                                        # one counts form: its table as it is
+        if canonical:
+            check_canonical(tables[0], ns[0], sizes[0], what)
+        return tables[0], ns[0], sizes[0], form
+    back = torch.tensor(np.argsort(np.asarray(order, np.int64), kind='stable'), dtype=torch.int64, device=dev)
+    return concat_runs(tables, rows=back).contiguous(), torch.cat(ns)[back].contiguous(), sizes, form
+
+
+def word_offsets(sizes):
+    """(H, W) per mask -> int64 [k + 1] on the host: mask i holds words word_offsets[i] .. [i + 1] of the bit planes, one
+    bit per pixel in 64-bit words, every mask from a word of its own"""
+    offs = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(((int(h) * int(w) + 63) // 64 for h, w in sizes), dtype=np.int64, count=len(sizes)), out=offs[1:])
+    return offs
+
+
+def runs_to_bits(counts, n, sizes):
+    """run table, (H, W) per row -> (bits int64, word_offs int64 [k + 1], area int64 [k], wrange int32 [k, 2]) on the device:
+    the bit planes rsp_coco_iou reads (ops.rle_to_bits; one device-to-host read, the number of words)"""
+    word_offs = torch.from_numpy(word_offsets(sizes)).to(n.device)
+    bits, area, wrange = ops.rle_to_bits(counts, n, word_offs)
+    return bits, word_offs, area, wrange
+
+
+def runs_to_dense(counts, n, size):
+    """run table of k masks on one size = (H, W) canvas -> bool [k, H, W] on the device, through the bit planes of
+    ops.rle_to_bits (one size: the word offsets are made on the device)"""
+    (H, W), k, dev = size, int(n.shape[0]), n.device
+    nw = int(word_offsets([size])[1])
+    bits = ops.rle_to_bits(counts.contiguous(), n, torch.arange(k + 1, dtype=torch.int64, device=dev) * nw)[0]
+    # pixel j of the column-major stream is bit j & 7 of byte j >> 3 (little-endian words): one byte per pixel,
+    # then [W, H] -> [H, W]
+    px = (bits[:k * nw].view(torch.uint8).view(k, nw * 8, 1) >> torch.arange(8, dtype=torch.uint8, device=dev)) & 1
+    return px.view(k, nw * 64)[:, :H * W].reshape(k, W, H).transpose(1, 2).to(torch.bool).contiguous()
+
+
+def runs_to_masks(counts, n, size, form, n_host=None):
+    """run table -> the masks in the form they came in (masks_to_runs' `form`): 'dense' a bool [k, H, W] tensor, 'strings'
+    runs_to_strings (bytes, also for str input), 'lists' runs_to_dicts (n_host: the row lengths, where the host has them)"""
+    if form == 'dense':
+        return runs_to_dense(counts, n, size)
+    if form == 'strings':
+        return runs_to_strings(counts.contiguous(), n, size)
+    if form == 'lists':
+        return runs_to_dicts(counts, n.cpu() if n_host is None else n_host, size)
+    raise ValueError(f"mask form {form!r}: one of 'dense', 'strings', 'lists'")
 
 
 def encode_rle_strings(masks, cap=4096, flat_cap=None):

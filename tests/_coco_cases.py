@@ -85,7 +85,7 @@ def check_string_roundtrip(ops, dev, masks, cap=None):
 # ----------------------------------------------------------------------------- IoU
 def check_iou(ops, dev, rng, n_img, nd, ng, h, w, crowd_frac=0.2, mode='segm'):
     """rsp_coco_iou over a batch of images (one unit each), exactly equal to rleIou / bbIou of the restatement"""
-    from rsprompter_amd.evaluation import _masks_on_device
+    from rsprompter_amd import rle
     dt_rles, gt_rles, dt_box, gt_box, crowd, nds, ngs = [], [], [], [], [], [], []
     for i in range(n_img):
         a, b = int(rng.integers(0, nd + 1)) if i % 3 == 2 else nd, ng if i % 4 != 3 else int(rng.integers(0, ng + 1))
@@ -112,8 +112,8 @@ def check_iou(ops, dev, rng, n_img, nd, ng, h, w, crowd_frac=0.2, mode='segm'):
     units = ops.coco_units(dt0, gt0, out0, nd_a, ng_a, np.full(n_img, (h * w + 63) // 64), dev)
     g_crowd = torch.tensor(crowd + [0], dtype=torch.uint8, device=dev)
     if mode == 'segm':
-        db, dwo, da, dwr = _masks_on_device(dt_rles, dev)
-        gb, gwo, ga, gwr = _masks_on_device(gt_rles, dev)
+        db, dwo, da, dwr = rle.runs_to_bits(*rle.strings_to_runs([r['counts'] for r in dt_rles], dev), [r['size'] for r in dt_rles])
+        gb, gwo, ga, gwr = rle.runs_to_bits(*rle.strings_to_runs([r['counts'] for r in gt_rles], dev), [r['size'] for r in gt_rles])
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
                            gt_woff=gwo, dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
     else:

@@ -622,7 +622,8 @@ def check_mask_iou(apis, dev, pytest):
         assert apis.mask_iou(t[:0], t).shape == (0, 7)
     # sizes of their own: one table, the rows in the order of the list
     a, b = dict(size=[2, 3], counts=[1, 2, 3]), dict(size=[4, 1], counts=ref.rle_to_string([0, 3, 1]))
-    counts, n, sizes = apis._masks_to_runs_mixed([a, b, a], dev)
+    from rsprompter_amd import rle
+    counts, n, sizes, _ = rle.masks_to_runs([a, b, a], dev, 'mask_iou', one_size=False)
     assert sizes == [(2, 3), (4, 1), (2, 3)] and n.cpu().tolist() == [3, 3, 3]
     assert counts.cpu()[:, :3].tolist() == [[1, 2, 3], [0, 3, 1], [1, 2, 3]]
     with pytest.raises(ValueError, match='different sizes'):

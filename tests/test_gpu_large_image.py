@@ -144,6 +144,14 @@ def test_run_table_pipelines_retry_from_a_capacity_that_is_too_small(dev):
     cases.check_capacity_retries(ops, dev)
 
 
+def test_mask_forms_round_trip_through_the_run_table(dev):
+    """the conversions between a caller's masks and the run table (rsprompter_amd/rle.py "mask forms") on the device: exact
+    round trips, the bit planes, mixed sizes, k = 0, the capacity retry, the refusals and the host reads of every form"""
+    import _run_table_cases as cases
+    from rsprompter_amd import ops, rle
+    cases.check_mask_forms(ops, rle, dev, pytest)
+
+
 # --------------------------------------------------------------------------------------------------------- end to end
 def _cfg():
     from rsprompter_amd.config import Config

@@ -162,6 +162,14 @@ def test_run_table_pipelines_retry_from_a_capacity_that_is_too_small(emu):
     cases.check_capacity_retries(emu, torch.device('cpu'))
 
 
+def test_mask_forms_round_trip_through_the_run_table(emu):
+    """dense tensors, bytes / str dicts and list dicts to the run table and back (rsprompter_amd/rle.py "mask forms"): exact
+    round trips, the bit planes, mixed sizes, k = 0, the capacity retry, the refusals and the host reads of every form"""
+    import _run_table_cases as cases
+    from rsprompter_amd import rle
+    cases.check_mask_forms(emu, rle, torch.device('cpu'), pytest)
+
+
 # ---------------------------------------------------------------------------------------------------- tile front end
 @pytest.mark.parametrize('dtype', [np.uint8, np.float32])
 @pytest.mark.parametrize('norm', [False, True])

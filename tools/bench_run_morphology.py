@@ -66,11 +66,11 @@ def _rows_equal(a, b):
 def dense_bands(counts, n, size, d, chunk, encode=True):
     """the dense device route -> (counts, n) of the bands, rows in order; encode=False: the dense bands of the last chunk
     (rsp_mask_rle refuses a scene-sized dense mask: the route ends there)"""
-    from rsprompter_amd import apis, rle
+    from rsprompter_amd import rle
     import torch.nn.functional as F
     tables, ns = [], []
     for s in range(0, int(n.shape[0]), chunk):
-        m = apis._runs_to_dense(counts[s:s + chunk].contiguous(), n[s:s + chunk].contiguous(), size)
+        m = rle.runs_to_dense(counts[s:s + chunk].contiguous(), n[s:s + chunk].contiguous(), size)
         inv = 1 - F.pad(m.to(torch.float16), (d, d, d, d), value=0.0)[:, None]      # the outside of the image is background
         inv = F.max_pool2d(F.max_pool2d(inv, (2 * d + 1, 1), stride=1), (1, 2 * d + 1), stride=1)[:, 0]
         if not encode:
@@ -85,11 +85,11 @@ def dense_bands(counts, n, size, d, chunk, encode=True):
 def host_bands(counts, n, size, d, sample):
     """scipy on `sample` masks -> seconds per mask (decode and encode not counted)"""
     from scipy import ndimage as ndi
-    from rsprompter_amd import apis
+    from rsprompter_amd import rle
     idx = np.linspace(0, int(n.shape[0]) - 1, sample).astype(np.int64)
     sec = []
     for i in idx.tolist():
-        m = apis._runs_to_dense(counts[i:i + 1].contiguous(), n[i:i + 1].contiguous(), size)[0].cpu().numpy()
+        m = rle.runs_to_dense(counts[i:i + 1].contiguous(), n[i:i + 1].contiguous(), size)[0].cpu().numpy()
         t0 = time.perf_counter()
         m & ~ndi.binary_erosion(m, np.ones((3, 3), bool), iterations=d, border_value=0)
         sec.append(time.perf_counter() - t0)
@@ -98,9 +98,9 @@ def host_bands(counts, n, size, d, sample):
 
 def measure(a, gt, dts, dev, size, d, chunk, dense_sample, host_sample, radii=()):
     from rsprompter_amd import evaluation as E
-    from rsprompter_amd import ops
+    from rsprompter_amd import ops, rle
     segms = [x['segmentation'] for x in dts] + [g['segmentation'] for g in gt['annotations']]
-    counts, n = E._runs_on_device(segms, dev)
+    counts, n = rle.strings_to_runs([s['counts'] for s in segms], dev)
     k = int(n.shape[0])
     out = dict(masks=k, canvas=list(size), d=d, runs_per_mask=float(n.sum()) / k)
     band = lambda r=d: ops.rle_boundary(counts, n, size[0], size[1], r)[:2]         # noqa: E731
@@ -117,8 +117,7 @@ def measure(a, gt, dts, dev, size, d, chunk, dense_sample, host_sample, radii=()
         if encode:
             out['bands_equal_dense_route'] = _rows_equal((got[0][:ks], got[1][:ks]), want)
         else:                                                    # the last mask of the sample, pixel by pixel
-            from rsprompter_amd import apis
-            mine = apis._runs_to_dense(got[0][ks - 1:ks].contiguous(), got[1][ks - 1:ks].contiguous(), size)
+            mine = rle.runs_to_dense(got[0][ks - 1:ks].contiguous(), got[1][ks - 1:ks].contiguous(), size)
             out['bands_equal_dense_route'] = bool(torch.equal(mine, want))
             out['dense_route_ends_before_encode'] = True
         assert out['bands_equal_dense_route']
@@ -170,9 +169,8 @@ def large_instances(a, dev):
                                         band_runs_per_mask=float(got[1].sum()) / k, eroded_runs_per_mask=float(er[1].sum()) / k)
     if not a.no_baselines:                                       # one mask, pixel by pixel, at the widest band
         want = dense_bands(sc[:1].contiguous(), sn[:1].contiguous(), (H, W), 243, 1, encode=False)
-        from rsprompter_amd import apis
-        out['band_243_equal_dense_route'] = bool(torch.equal(apis._runs_to_dense(got[0][:1].contiguous(), got[1][:1].contiguous(),
-                                                                                 (H, W)), want))
+        mine = rle.runs_to_dense(got[0][:1].contiguous(), got[1][:1].contiguous(), (H, W))
+        out['band_243_equal_dense_route'] = bool(torch.equal(mine, want))
         assert out['band_243_equal_dense_route']
     return out
 
