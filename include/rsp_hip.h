@@ -922,6 +922,35 @@ int rsp_run_morph_join(int32_t op, const int32_t* a_col, const int32_t* a_y0, co
                        int32_t H, int32_t emit_keys, int32_t* o_col, int32_t* o_y0, int32_t* o_y1, int64_t* keys, int32_t* ends,
                        rsp_stream_t stream);
 
+/* Planar instance layers (csrc/run_flatten.hip): the k masks of a run table made pairwise disjoint by a         */
+/* priority, row i = M_i minus every M_j with rank[j] < rank[i]; replaces the per-pixel argmax over dense [k, H, W] masks of      */
+/* MaskFormerFusionHead.panoptic_postprocess (mmdet maskformer_fusion_head.py:70-104) for binary masks, and decode -> argmax ->  */
+/* encode on scene masks.  Input: the piece table of k masks on ONE (H, W) canvas, pieces int32 [4, P] / P as rsp_run_pieces      */
+/* leaves them (planes x, y0, y1, instance, sorted by (instance, x, y0)), and the caller's copy of it sorted by column: skeys     */
+/* int64 [P] = (x * H + y0) << 31 | piece index, ascending, cpieces int32 [4, P] = the same planes in that order.  rank int32 [k]: */
+/* a permutation of 0 .. k - 1, 0 wins (only compared: any values give SOME answer).  Refused with RSP_EINVAL: a null pointer      */
+/* where something is read or written, H * W >= 2^31, P > RSP_RUN_PIECES_MAX_PIECES, k < 0, total >= 2^31.  No call reads the      */
+/* host, none uses atomics, every output slot is stored once; offsets read from col_offs / out_offs are clamped into their         */
+/* arrays, whatever they hold.  No workspace.                                                                                     */
+/* 1. col_offs int32 [W + 1] = the first piece of every column in the sorted copy; reach int32 [P], reach[j] = the largest y1     */
+/* among the pieces of j's column at or before j (one wave per column, a max-scan with a carry).                                  */
+int rsp_run_flatten_columns(const int64_t* skeys, const int32_t* cpieces, int64_t P, int32_t H, int32_t W, int32_t* col_offs,
+                            int32_t* reach, rsp_stream_t stream);
+/* 2. One lane per piece: the parts of the piece that no piece of a smaller rank in its column covers.  _count: cnt int32 [P];    */
+/* the caller's exclusive sum is out_offs int64 [P + 1], total = out_offs[P].  _write stores them as rsp_rle_union's intervals,   */
+/* keys int64 [total] = instance << 31 | pixel start, ends int32 [total], in key order as they stand; the intervals of instance   */
+/* i are out_offs[piece_offs[i]] .. out_offs[piece_offs[i + 1]].  A piece whose instance is outside [0, k) has none.              */
+int rsp_run_flatten_count(const int32_t* pieces, const int32_t* cpieces, const int32_t* col_offs, const int32_t* reach,
+                          const int32_t* rank, int64_t P, int32_t k, int32_t H, int32_t W, int32_t* cnt, rsp_stream_t stream);
+int rsp_run_flatten_write(const int32_t* pieces, const int32_t* cpieces, const int32_t* col_offs, const int32_t* reach,
+                          const int32_t* rank, int64_t P, int32_t k, int32_t H, int32_t W, const int64_t* out_offs, int64_t total,
+                          int64_t* keys, int32_t* ends, rsp_stream_t stream);
+/* 3. The label map of DISJOINT masks given as intervals in that layout (any order): labels int32 [W, H] -- the column-major      */
+/* stream of the run counts, in which every interval is contiguous; the caller reads it transposed -- zeroed, then ids[instance]  */
+/* (ids int32 [k]) over every interval, one wave per interval.  Where intervals overlap a pixel takes one of their values.        */
+int rsp_run_flatten_paint(const int64_t* keys, const int32_t* ends, int64_t total, const int32_t* ids, int32_t k, int32_t H,
+                          int32_t W, int32_t* labels, rsp_stream_t stream);
+
 /* Polygon rasterisation (csrc/poly_raster.hip): rings of float64 vertices -> run tables; replaces cocoapi's    */
 /* maskApi.c rleFrPoly (one polygon at 5x resolution, its sort and its sequential run loop) per part, and with the caller's     */
 /* grouping rleMerge / COCO.annToRLE (rsprompter_amd/rle.py polygons_to_runs).  The result is rleFrPoly's, count for count.     */

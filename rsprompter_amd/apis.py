@@ -324,8 +324,68 @@ def boundary_iou(dt, gt, iscrowd=None, dilation_ratio=0.02, radius=None, min_wit
     return out.view(D, G)
 
 
+# ------------------------------------------------------------------------------------------ planar layers
+def _flatten(masks, scores, order, min_ratio, device, what):
+    """masks in the forms of rle.masks_to_runs -> (flattened counts, n, size, the form they came in, info)"""
+    rle._flatten_min_ratio(min_ratio)
+    if isinstance(masks, torch.Tensor):
+        device = masks.device
+    counts, n, size, came = rle.masks_to_runs(masks, device, what, canonical=False)
+    k = int(n.shape[0])
+    areas = ops.rle_bbox(counts, n, size[0], size[1])[1] if isinstance(order, str) and order == 'area' else None
+    rank = rle.flatten_rank(k, order, scores, areas)
+    counts, n, _, before, after, kept = rle.flatten_runs(counts, n, size, rank, min_ratio)
+    return counts, n, size, came, dict(area_before=before, area_after=after, kept=kept, rank=rank)
+
+
+def flatten_masks(masks, scores=None, order='score', min_ratio=0.0, form=None, device='cuda:0'):
+    """Overlapping instances -> a planar layer: every pixel stays with ONE of the instances that cover it, the one of highest
+    priority, so the results are pairwise disjoint and their union is the union of the inputs (csrc/run_flatten.hip, DESIGN
+    §14.14) -- the per-pixel argmax of score x mask of MaskFormerFusionHead.panoptic_postprocess for binary masks, in the run
+    domain: no mask is expanded.  masks: bool [k, H, W] on the device, or a list of RLE dicts dict(size=[H, W], counts=...) of
+    one size, compressed (bytes / str) or uncompressed (list) counts, zero counts anywhere allowed (`device` places the run
+    table).  order='score': the higher of `scores` wins, ties to the lower index (NaN refused); 'area': the smaller mask wins
+    (the usual way to paint SAM's everything output), ties to the lower index; or an explicit rank, a permutation of 0 ..
+    k - 1 where 0 wins.  min_ratio in [0, 1]: an instance that keeps less than that share of its pixels is emptied after the
+    partition is made (its pixels go to nobody; float64 comparison, rle.flatten_runs).
+    -> (masks, info): the masks in the form they came in, or form='rle' (compressed dicts) | 'runs' ((counts, n) on the
+    device) | 'dense' (bool [k, H, W], refused above large_image.DENSE_MASK_LIMIT_BYTES); an emptied instance is an empty
+    mask.  info = dict(area_before int32 [k], area_after int32 [k], kept bool [k] (device tensors), rank int32 numpy [k])."""
+    if form is not None and form not in MASK_FORMS:
+        raise ValueError(f'mask form {form!r}: one of {MASK_FORMS}')
+    counts, n, size, came, info = _flatten(masks, scores, order, min_ratio, device, 'flatten_masks')
+    if form == 'runs':
+        return (counts, n), info
+    out_form = came if form is None else 'strings' if form == 'rle' else 'dense'
+    if out_form == 'dense' and came != 'dense':
+        from .large_image import _check_dense
+        _check_dense(int(n.shape[0]), size[0], size[1])
+    return rle.runs_to_masks(counts, n, size, out_form), info
+
+
+def masks_to_label_map(masks, scores=None, order='score', ids=None, min_ratio=0.0, device='cuda:0'):
+    """Overlapping instances -> an instance-id raster: int32 [H, W] on the device, ids[i] (i + 1 when None) where instance i
+    wins under flatten_masks' rules (same masks, scores, order and min_ratio), 0 for the background and for the pixels of an
+    instance that min_ratio emptied.  Painted from the flattened run table (rle.runs_to_labels); 4 bytes per pixel, refused
+    above large_image.DENSE_MASK_LIMIT_BYTES."""
+    from .large_image import DENSE_MASK_LIMIT_BYTES
+    if isinstance(masks, torch.Tensor):
+        H, W = (int(s) for s in masks.shape[-2:])
+    else:
+        masks = list(masks)
+        if not masks:
+            raise ValueError('masks_to_label_map: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
+        H, W = int(masks[0]['size'][0]), int(masks[0]['size'][1])
+    need = 4 * H * W
+    if need > DENSE_MASK_LIMIT_BYTES:
+        raise ValueError(f'a label map of a {H} x {W} scene needs {need} bytes (limit large_image.DENSE_MASK_LIMIT_BYTES = '
+                         f'{DENSE_MASK_LIMIT_BYTES}): use flatten_masks(form="rle")')
+    counts, n, size, _, _ = _flatten(masks, scores, order, min_ratio, device, 'masks_to_label_map')
+    return rle.runs_to_labels(counts, n, size, ids)
+
+
 # ------------------------------------------------------------------------------------------ polygon export (DESIGN §14.7)
-POLYGON_FORMS = ('rings', 'coco', 'geojson')
+POLYGON_FORMS =('rings', 'coco', 'geojson')
 
 
 def rings_to_coco(rings):

@@ -156,14 +156,44 @@ def _clean_scene(counts, n, scene_hw, region):
     return counts, n
 
 
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None, region=None):
+def _check_flatten(flatten, min_ratio):
+    """flatten=False | 'score' | 'area' and flatten_min_ratio of inference_large_image -> (order or None, min_ratio)"""
+    if flatten is not False and flatten is not None and flatten not in rle.FLATTEN_ORDERS:
+        raise ValueError(f"flatten must be False, 'score' or 'area', got {flatten!r}")
+    ratio = rle._flatten_min_ratio(min_ratio)
+    if not flatten and ratio != 0.0:
+        raise ValueError("flatten_min_ratio applies with flatten='score' or flatten='area'")
+    return (flatten or None), ratio
+
+
+def _finish_scene(counts, n, scene_hw, region, planar):
+    """the scene run table before it takes any output form.  planar = (order, min_ratio, scores float [K], a list that receives
+    (kept bool [K], area int32 [K, 2])) or None: the instances made pairwise disjoint first (rle.flatten_runs),
+    so that the slivers a subtraction leaves are cleaned with everything else (_clean_scene).  Cleaning fills small holes, and
+    a hole of one instance may be where a better one lives: where both are asked for the cleaned table is flattened once
+    more, by the same rank, so the result is disjoint whatever was filled."""
+    if planar is None:
+        return _clean_scene(counts, n, scene_hw, region)
+    order, ratio, scores, out = planar
+    areas = ops.rle_bbox(counts, n, scene_hw[0], scene_hw[1])[1] if order == 'area' else None
+    rank = rle.flatten_rank(int(n.shape[0]), order, scores, areas)
+    counts, n, _, before, after, kept = rle.flatten_runs(counts, n, scene_hw, rank, ratio)
+    if region is not None:
+        counts, n = _clean_scene(counts, n, scene_hw, region)
+        counts, n, _, _, after, again = rle.flatten_runs(counts, n, scene_hw, rank)
+        kept = kept & again
+    out.append((kept, torch.stack([before, after], 1)))
+    return counts, n
+
+
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
         if obb_out is not None:
             obb_out.append(np.zeros((0, 4, 2), np.float64))
         return []
     sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
-    sc, sn = _clean_scene(sc, sn, scene_hw, region)
+    sc, sn = _finish_scene(sc, sn, scene_hw, region, planar)
     return _runs_out(sc, sn, scene_hw, polygons, obb_out)
 
 
@@ -292,7 +322,7 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
     return out, reps[keep_m], members, (flat, offs)
 
 
-def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None, region=None):
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None):
     """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
     (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
     flat, offs = groups
@@ -304,7 +334,7 @@ def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_
     sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
     members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
     uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
-    uc, un = _clean_scene(uc, un, scene_hw, region)
+    uc, un = _finish_scene(uc, un, scene_hw, region, planar)
     return _runs_out(uc, un, scene_hw, polygons, obb_out)
 
 
@@ -357,7 +387,8 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 @torch.no_grad()
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
                           batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
-                          polygon_min_ring_area=0, oriented_boxes=False, min_mask_region_area=0):
+                          polygon_min_ring_area=0, oriented_boxes=False, min_mask_region_area=0, flatten=False,
+                          flatten_min_ratio=0.0):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
@@ -370,7 +401,14 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     (masks='rle' or 'polygons'): holes and islands of fewer pixels than that are removed from every scene mask
     (segment-anything's remove_small_regions, 'both', in the run domain; with 'seam_mask' after the union), before strings,
     rings and oriented boxes are made; bboxes, scores and labels stay the detector's, no mask is emptied, and
-    pred_instances.region_changed is bool [K].  return_patches=True: (sample, per-tile samples,
+    pred_instances.region_changed is bool [K].  flatten='score' | 'area' (masks='rle' or 'polygons'): the scene
+    masks are made pairwise disjoint, a planar layer -- every pixel stays with the covering instance of highest score ('score',
+    ties to the lower index) or smallest scene mask ('area') -- on the scene run table, after the shift or union and before
+    the min_mask_region_area cleaning, strings, rings and oriented boxes; where the cleaning is on, the cleaned table is
+    flattened once more so that a filled hole cannot overlap the instance inside it.  flatten_min_ratio in [0, 1] empties an
+    instance that keeps less than that share of its pixels (apis.flatten_masks).  K, bboxes, scores and labels stay the
+    detector's; pred_instances.flatten_kept is bool [K] (False: the instance kept no pixel or was emptied) and flatten_area
+    int32 [K, 2], the pixels of each scene mask before and in the result.  return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -392,6 +430,11 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     if region is not None and masks == 'dense':                         # refused before the first tile runs
         raise ValueError("min_mask_region_area cleans the scene run table: use masks='rle' or masks='polygons' (dense masks "
                          'are cleaned by apis.remove_small_regions)')
+    flat_order, flat_ratio = _check_flatten(flatten, flatten_min_ratio)  # refused before the first tile runs
+    if flat_order is not None and masks == 'dense':
+        raise ValueError("flatten works on the scene run table: use masks='rle' or masks='polygons' (dense masks go through "
+                         'apis.flatten_masks)')
+    flat_out = []
     if polygon_tolerance is not None or polygon_min_ring_area != 0:
         if not poly:
             raise ValueError("polygon_tolerance and polygon_min_ring_area apply to masks='polygons'")
@@ -470,7 +513,8 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             tm = torch.cat(dense_tiles, 0) if dense_tiles else torch.zeros((0, th, tw), dtype=torch.bool, device=dev)
             out.masks = _seam_dense(tm, origin, groups, (H, W))
         else:
-            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region)
+            planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region, planar)
     else:
         keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
@@ -480,11 +524,16 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
             kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
-            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region)
+            planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region, planar)
     if obb:
         out.obb = obb[0]
     if region is not None:
         out.region_changed = region[1][0] if region[1] else torch.zeros((len(out.scores),), dtype=torch.bool, device=dev)
+    if flat_order is not None:
+        K = len(out.scores)
+        out.flatten_kept = flat_out[0][0] if flat_out else torch.zeros((K,), dtype=torch.bool, device=dev)
+        out.flatten_area = flat_out[0][1] if flat_out else torch.zeros((K, 2), dtype=torch.int32, device=dev)
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
@@ -620,6 +669,11 @@ def main(argv=None):
                     help='add "obb": the four corners of the minimum-area rectangle around each mask, made on the device')
     ap.add_argument('--min-mask-region-area', type=int, default=0, metavar='A',
                     help='remove holes and islands of less than A pixels from every scene mask, on the device')
+    ap.add_argument('--flatten', nargs='?', const='score', default=None, choices=('score', 'area'),
+                    help="make the instances of a scene pairwise disjoint, a planar layer: every pixel stays with the covering "
+                    "instance of highest score ('score', the default) or smallest mask ('area'), on the device")
+    ap.add_argument('--flatten-min-ratio', type=float, default=0.0, metavar='R',
+                    help='--flatten: empty an instance that keeps less than the share R of its pixels')
     a = ap.parse_args(argv)
     if a.geo_transform is not None and a.mask_format != 'geojson':
         ap.error('--geo-transform applies to --mask-format geojson')
@@ -630,6 +684,7 @@ def main(argv=None):
         rle.polygon_min_ring_area(a.min_ring_area)
         if a.min_mask_region_area < 0:
             raise ValueError(f'--min-mask-region-area must be a non-negative integer, got {a.min_mask_region_area}')
+        _check_flatten(a.flatten or False, a.flatten_min_ratio)
     except ValueError as e:
         ap.error(str(e))
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
@@ -639,7 +694,8 @@ def main(argv=None):
                                   a.batch_size, masks='rle' if a.mask_format == 'rle' else 'polygons',
                                   seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
                                   polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes,
-                                  min_mask_region_area=a.min_mask_region_area)
+                                  min_mask_region_area=a.min_mask_region_area, flatten=a.flatten or False,
+                                  flatten_min_ratio=a.flatten_min_ratio)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

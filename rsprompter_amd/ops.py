@@ -2263,6 +2263,83 @@ def rle_boundary(counts, n, H, W, radius, cap=None):
     return _run_morph('rle_boundary', counts, n, H, W, radius, 0, True, cap)
 
 
+# ----------------------------------------------------------------------------- planar layers (csrc/run_flatten.hip)
+def _flatten_rank(what, rank, k, dev):
+    if not isinstance(rank, torch.Tensor) or rank.dtype != torch.int32 or rank.dim() != 1 or rank.shape[0] != k \
+            or rank.device != dev:
+        raise ValueError(f'{what}: rank must be int32 [{k}] on the device of the counts')
+    return rank.contiguous()
+
+
+def rle_flatten(counts, n, H, W, rank, cap=None):
+    """the rows of a run table (counts int32 [k, cap_in], n int32 [k]: k masks on one (H, W) canvas) made pairwise disjoint
+    (DESIGN §14.14): rank int32 [k] on the device, a permutation of 0 .. k - 1 where 0 wins (rle.flatten_runs checks it;
+    here it is only compared); row i of the result is M_i minus every M_j with rank[j] < rank[i] -- the per-pixel argmax of
+    score x mask of MaskFormerFusionHead.panoptic_postprocess for binary masks, without a dense mask.  Zero counts anywhere
+    are legal input; a row with n <= 0 is the empty mask.  -> (counts int32 [k, cap'], n int32 [k], cap'), canonical COCO run
+    counts (an emptied row is one count H * W); cap: the first capacity (the input's plus two when None): a subtraction
+    splits runs, so a row may need more counts than it came with, and fit_runs grows the capacity.
+    Device-to-host reads, whatever k is: three -- the pieces (run_pieces), the survivors' total, and n per fit_runs attempt
+    (one more per retry); two when the table has no piece.  One device key sort (the column order of the pieces)."""
+    lib = _lib.load()
+    counts, n, k, cap_in, H, W = _rle_rows('rle_flatten', counts, n, H, W)
+    dev = n.device
+    rank = _flatten_rank('rle_flatten', rank, k, dev)
+    cap = max(int(cap), 2) if cap is not None else cap_in + 2
+    if k == 0:
+        return torch.zeros((0, cap), dtype=torch.int32, device=dev), n, cap
+    rp = run_pieces(counts, n, H, W, what='rle_flatten')                                              # read 1
+    P = rp.P
+    keys, ends, total = None, None, 0
+    iv_offs = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
+    if P:
+        px, py0 = rp.pieces[0].to(torch.int64), rp.pieces[1].to(torch.int64)
+        skeys = torch.sort(((px * H + py0) << 31) | torch.arange(P, dtype=torch.int64, device=dev))[0].contiguous()
+        cpieces = rp.pieces[:, skeys & 0x7fffffff].contiguous()
+        col_offs = torch.empty((W + 1,), dtype=torch.int32, device=dev)
+        reach = torch.empty((P,), dtype=torch.int32, device=dev)
+        _lib.check(lib.rsp_run_flatten_columns(skeys.data_ptr(), cpieces.data_ptr(), P, H, W, col_offs.data_ptr(),
+                                               reach.data_ptr(), _stream()), "rsp_run_flatten_columns")
+        head = (rp.pieces.data_ptr(), cpieces.data_ptr(), col_offs.data_ptr(), reach.data_ptr(), rank.data_ptr(), P, k, H, W)
+        cnt = torch.empty((P,), dtype=torch.int32, device=dev)
+        _lib.check(lib.rsp_run_flatten_count(*head, cnt.data_ptr(), _stream()), "rsp_run_flatten_count")
+        out_offs, total = _exclusive_total(cnt)
+        total = int(total.item())                                                                    # read 2
+        if total >= 2 ** 31:
+            raise ValueError(f'rle_flatten: {total} surviving intervals in one call; at most 2^31 - 1 (split the canvas)')
+        if total:
+            keys = torch.empty((total,), dtype=torch.int64, device=dev)
+            ends = torch.empty((total,), dtype=torch.int32, device=dev)
+            _lib.check(lib.rsp_run_flatten_write(*head, out_offs.data_ptr(), total, keys.data_ptr(), ends.data_ptr(), _stream()),
+                       "rsp_run_flatten_write")
+        iv_offs = out_offs[rp.piece_offs].contiguous()
+    out, n_out, _, cap = fit_runs(lambda cap: _intervals_to_runs(lib, keys, ends, total, iv_offs, k, H, W, cap), cap)
+    return out, n_out, cap
+
+
+def rle_label_map(counts, n, H, W, ids=None):
+    """the label map of a run table whose rows are pairwise DISJOINT (what rle_flatten returns): int32 [H, W] on the device,
+    ids[i] (int32 [k] on the device; i + 1 when None) on the pixels of row i, 0 elsewhere (rsp_run_flatten_paint).  The
+    kernel writes the column-major stream, int32 [W, H], in which every ones-run is contiguous; the result is its .T view.
+    Where rows overlap a pixel takes the id of one of them.  One device-to-host read (the number of ones-runs)."""
+    lib = _lib.load()
+    counts, n, k, cap, H, W = _rle_rows('rle_label_map', counts, n, H, W)
+    dev = n.device
+    if ids is None:
+        ids = torch.arange(1, k + 1, dtype=torch.int32, device=dev)
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or ids.shape[0] != k or ids.device != dev:
+        raise ValueError(f'rle_label_map: ids must be int32 [{k}] on the device of the counts')
+    ids = ids.contiguous()
+    labels = torch.empty((W, H), dtype=torch.int32, device=dev)
+    keys, ends, total = None, None, 0
+    if k:
+        rows = torch.arange(k, dtype=torch.int32, device=dev)
+        keys, ends, _, total = _rle_intervals(lib, counts, n, k, cap, H, W, rows, rows, (n.clamp(0, cap) // 2).to(torch.int64))
+    _lib.check(lib.rsp_run_flatten_paint(keys.data_ptr() if total else 0, ends.data_ptr() if total else 0, total, ids.data_ptr(),
+                                         k, H, W, labels.data_ptr(), _stream()), "rsp_run_flatten_paint")
+    return labels.t()
+
+
 # ----------------------------------------------------------------------------- polygon rasterisation (csrc/poly_raster.hip)
 POLY_RASTER_MAX_COORD = CONST['RSP_POLY_RASTER_MAX_COORD']        # |(int)(5 x + .5)| of every coordinate
 POLY_RASTER_MAX_POINTS = CONST['RSP_POLY_RASTER_MAX_POINTS']      # walk points of one call

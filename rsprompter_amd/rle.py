@@ -374,6 +374,83 @@ def boundary_radius(size, dilation_ratio=0.02):
     return max(1, int(round(r * math.sqrt(H * H + W * W))))
 
 
+FLATTEN_ORDERS = ('score', 'area')
+
+
+def _flatten_min_ratio(min_ratio):
+    r = min_ratio
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not 0.0 <= float(r) <= 1.0:
+        raise ValueError(f'min_ratio is a number in [0, 1], got {min_ratio!r}')
+    return float(r)
+
+
+def flatten_rank(k, order='score', scores=None, areas=None):
+    """the priority of planar layers -> rank int32 numpy [k], a permutation of 0 .. k - 1 where 0 wins, on the
+    host.  order='score': descending `scores`, ties to the lower index (the argmax of score x mask on torch CPU); NaN scores
+    are refused.  order='area': ascending `areas`, small masks on top, ties to the lower index.  Anything else is taken as
+    the rank itself and checked to be a permutation.  Tensors are brought to the host (a read where they are on the device)."""
+    def host(v, name):
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if v.reshape(-1).shape[0] != k:
+            raise ValueError(f'flatten: {name} has {v.reshape(-1).shape[0]} entries for {k} masks')
+        return v.reshape(-1)
+    if isinstance(order, str):
+        if order not in FLATTEN_ORDERS:
+            raise ValueError(f'flatten: order must be one of {FLATTEN_ORDERS} or a permutation, got {order!r}')
+        if order == 'score':
+            if scores is None:
+                raise ValueError("flatten: order='score' needs scores")
+            s = host(scores, 'scores').astype(np.float64)
+            if np.isnan(s).any():
+                raise ValueError('flatten: a score is NaN')
+            first = np.argsort(-s, kind='stable')
+        else:
+            first = np.argsort(host(areas, 'areas').astype(np.int64), kind='stable')
+        rank = np.empty(k, np.int32)
+        rank[first] = np.arange(k, dtype=np.int32)
+        return rank
+    r = host(order, 'rank')
+    if r.dtype.kind not in 'iu' or not np.array_equal(np.sort(r.astype(np.int64)), np.arange(k)):
+        raise ValueError(f'flatten: rank must be a permutation of 0 .. {k - 1} (integers, 0 wins)')
+    return r.astype(np.int32)
+
+
+def flatten_runs(counts, n, size, rank, min_ratio=0.0, cap=None):
+    """run table of k masks on one size = (H, W) canvas -> (counts, n, cap, area_before int32 [k], area_after int32 [k], kept
+    bool [k]), all on the device: the rows made pairwise disjoint, F_i = M_i minus every M_j with rank[j] < rank[i]
+    (ops.rle_flatten).  rank: a permutation of 0 .. k - 1, 0 wins -- a list, a numpy array or a tensor
+    (flatten_rank checks it on the host: a device tensor costs a read); any counts that describe the canvas are legal input.
+    min_ratio in [0, 1]: an instance with area(F_i) < min_ratio * area(M_i) is emptied AFTER the partition is made, so its
+    pixels are not handed to the instances below it (the iou_thr branch of panoptic_postprocess); the comparison is made in
+    float64 on the device (both areas are below 2^31, so only the product rounds).  kept[i] is False for such an instance
+    and for one whose F_i is empty; area_after is the area of the row that is returned.  Reads: those of ops.rle_flatten."""
+    k, dev = int(n.shape[0]), n.device
+    ratio = _flatten_min_ratio(min_ratio)
+    rank = torch.from_numpy(flatten_rank(k, rank)).to(dev)
+    H, W = int(size[0]), int(size[1])
+    out, n_out, cap = ops.rle_flatten(counts, n, H, W, rank, cap)
+    before, after = ops.rle_bbox(counts, n, H, W)[1], ops.rle_bbox(out, n_out, H, W)[1]
+    kept = (after > 0) & (after.to(torch.float64) >= ratio * before.to(torch.float64))
+    if k:
+        out[:, 0] = torch.where(kept, out[:, 0], torch.full_like(out[:, 0], H * W))
+        n_out = torch.where(kept, n_out, torch.ones_like(n_out))
+        after = torch.where(kept, after, torch.zeros_like(after))
+    return out, n_out, cap, before, after, kept
+
+
+def runs_to_labels(counts, n, size, ids=None):
+    """run table of k pairwise DISJOINT masks (flatten_runs) on one size = (H, W) canvas -> int32 [H, W] on the device: ids[i]
+    on the pixels of row i (i + 1 when None; a list, a numpy array or an int32 tensor), 0 for the background
+    (ops.rle_label_map: one device-to-host read)."""
+    k = int(n.shape[0])
+    if ids is not None:
+        ids = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.asarray(ids, np.int64).reshape(-1))
+        if ids.dim() != 1 or ids.shape[0] != k or ids.dtype.is_floating_point:
+            raise ValueError(f'runs_to_labels: ids holds one integer per mask ({k})')
+        ids = ids.to(device=n.device, dtype=torch.int32)
+    return ops.rle_label_map(counts, n, size[0], size[1], ids)
+
+
 def runs_to_dicts(counts, n_host, size):
     """run table -> list of dict(size=[H, W], counts=list), the uncompressed form (HF `_mask_to_rle`).  n_host: the row
     lengths on the host (what fit_runs returned); one transfer, the table."""
