@@ -829,6 +829,46 @@ int rsp_ring_simplify_write(const int32_t* verts, const int64_t* ring_offs, cons
                             int32_t* ring_parent_out, int64_t* ring_area2_out, int64_t* inst_ring_offs_out, int32_t* ring_src_out,
                             rsp_stream_t stream);
 
+/* Shared-border simplification (csrc/ring_coverage.hip): the rings of a PLANAR layer (a run table whose rows are */
+/* pairwise disjoint and canonical, what the rsp_run_flatten_* pipeline leaves) simplified so that a border between two          */
+/* instances keeps the same vertices on both sides; replaces shapely.coverage_simplify / GEOS CoverageSimplifier on the host.   */
+/* The table is read through the column-ordered pieces of rsp_run_flatten_columns: cpieces int32 [4, P] (x, y0, y1, instance     */
+/* sorted by (x, y0)) and col_offs int32 [W + 1]; owner(x, y) = the instance of the pixel, -1 for background and outside.        */
+/* Refused with RSP_EINVAL: H * W >= 2^31, a side above RSP_RING_COVERAGE_MAX_SIDE, P > RSP_RUN_PIECES_MAX_PIECES, negative      */
+/* sizes, a null pointer where something is read or written.  No call reads the host, none uses atomics, every output slot is   */
+/* stored once; every index read from an input array is clamped into the array it addresses.                                   */
+/* 1. bad int32 [P]: 1 where a piece overlaps its successor in the column (the rows are not disjoint: in a column sorted by y0   */
+/* any overlap shows there), 2 where two pieces of one instance touch (a zero count inside a row: not canonical), else 0.        */
+#define RSP_RING_COVERAGE_MAX_SIDE RSP_RING_SIMPLIFY_MAX_SIDE
+int rsp_ring_coverage_check(const int32_t* cpieces, int64_t P, int32_t H, int32_t W, int32_t* bad, rsp_stream_t stream);
+/* 2. The noded rings.  verts / ring_offs: the rings of rsp_mask_polygon_write on that table.  A lattice point is a NODE iff at  */
+/* least 3 of the 4 sides that meet in it separate different owners.  One lane per ring segment v_i -> v_{i+1}.  _count: cnt     */
+/* int32 [V] = 1 + the nodes strictly inside the segment (the change points of the far-side owner), first int32 [V] = where the  */
+/* segment's first node sits (0: v_i itself, 1: its first inner node, -1: none).  The caller's exclusive sum of cnt is noff      */
+/* int64 [V + 1], Vn = noff[V]; rot int64 [R] = the index within the noded ring of its first node visit (0 without one).         */
+/* _write: the noded rings, each rotated to begin at rot (ring r is noff[ring_offs[r]] .. noff[ring_offs[r + 1]]): nverts int32  */
+/* [Vn, 2], nflag uint8 [Vn] (1: node), nother int32 [Vn] = the owner on the far side of the unit step that leaves the vertex.   */
+int rsp_ring_coverage_nodes_count(const int32_t* verts, const int64_t* ring_offs, int64_t R, int64_t V, const int32_t* cpieces,
+                                  const int32_t* col_offs, int64_t P, int32_t k, int32_t H, int32_t W, int32_t* cnt,
+                                  int32_t* first, rsp_stream_t stream);
+int rsp_ring_coverage_nodes_write(const int32_t* verts, const int64_t* ring_offs, int64_t R, int64_t V, const int32_t* cpieces,
+                                  const int32_t* col_offs, int64_t P, int32_t k, int32_t H, int32_t W, const int64_t* noff,
+                                  const int64_t* rot, int64_t Vn, int32_t* nverts, uint8_t* nflag, int32_t* nother,
+                                  rsp_stream_t stream);
+/* 3. rsp_ring_simplify_mark on the noded rings with three changes: `keep` is read as well as written -- a vertex whose byte is */
+/* not 0 (a node) is kept from the start, with index 0; among equal distances the vertex with the smallest (x, y) wins; a chain  */
+/* whose two ends are the same point splits without the tolerance test.  All three are symmetric under reversal of a chain, so   */
+/* the two rings along a border keep the same vertices.  Arguments, limits, outputs and variants as rsp_ring_simplify_mark;      */
+/* rsp_ring_simplify_survive (min_ring_area 0) and rsp_ring_simplify_write follow on the noded layout.                           */
+int rsp_ring_coverage_mark(const int32_t* verts, const int64_t* ring_offs, int64_t R, int64_t V, int64_t tol2_q8, int32_t H,
+                           int32_t W, int32_t variant, uint8_t* keep, int32_t* pos, int32_t* kept_cnt, int64_t* area2,
+                           int32_t* rounds, rsp_stream_t stream);
+/* 4. nother compacted like the vertices: other_out int32 [V2], with keep / pos of the mark and sums / csum / V2 as               */
+/* rsp_ring_simplify_write takes them (ring_offs / R / V: the noded rings).                                                      */
+int rsp_ring_coverage_other(const int64_t* ring_offs, int64_t R, int64_t V, const uint8_t* keep, const int32_t* pos,
+                            const int64_t* sums, const int64_t* csum, int64_t V2, const int32_t* nother, int32_t* other_out,
+                            rsp_stream_t stream);
+
 /* Oriented boxes (csrc/mask_obb.hip): the convex hull and the minimum-area rectangle of every mask of a run    */
 /* table, exact in integers; replaces decoding every instance to a dense H x W array on the host + cv2.convexHull +           */
 /* cv2.minAreaRect.  Pixel (x, y) covers [x, x + 1] x [y, y + 1]; an instance is the union of the squares of ALL its pixels.  */

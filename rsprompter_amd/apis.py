@@ -431,7 +431,8 @@ def format_polygons(per_instance, form='rings', transform=None):
     raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
 
 
-def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tolerance=None, min_ring_area=0):
+def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tolerance=None, min_ring_area=0,
+                      topology='rings'):
     """Masks -> exact vector rings on the pixel-corner lattice, traced on the device in the run domain.
     masks: a bool [k, H, W] device tensor, or a list of RLE dicts dict(size=[H, W], counts=...) of one size with compressed
     counts (bytes / str, what `encode_mask_results` returns) or uncompressed ones (list, what `generate_masks` returns);
@@ -447,11 +448,21 @@ def masks_to_polygons(masks, form='rings', transform=None, device='cuda:0', tole
       it reaches the host: a dropped vertex lies within `tolerance` of the kept outline; rings are simplified independently
       (they may then cross); rings of less than min_ring_area pixels, rings that collapse, and the holes of a dropped outer
       ring are dropped -- a dropped hole is filled.  Both apply to all three forms; min_ring_area alone (tolerance=None)
-      filters at tolerance 0, which keeps every vertex of the rings that stay."""
+      filters at tolerance 0, which keeps every vertex of the rings that stay.
+    topology='shared' (DESIGN §14.15; the masks must be pairwise disjoint, what flatten_masks returns, and min_ring_area 0;
+      a tolerance is required, 0 is legal): a border between two instances is simplified once, to the same vertices in both
+      rings, so neighbouring features share their border coordinates exactly -- no gaps, no slivers.  Every node (a T-junction,
+      a point where three or four regions or two and the canvas border meet, a saddle) becomes a vertex, also on a straight
+      wall, and a ring begins at its first node, not at its smallest vertex.  Different borders may still cross each other
+      at large tolerances.  Overlapping masks are refused."""
     if form not in POLYGON_FORMS:
         raise ValueError(f'polygon form {form!r}: one of {POLYGON_FORMS}')
     if transform is not None and form != 'geojson':
         raise ValueError("transform applies to form='geojson' only")
+    if rle.polygon_topology(topology, tolerance, min_ring_area):        # refused before anything runs
+        counts, n, size, _ = rle.masks_to_runs(masks, device, 'masks_to_polygons', canonical=True)
+        polys, _, _ = rle.simplify_coverage(counts, n, size, tolerance)
+        return format_polygons(rle.polygons_to_lists(*polys), form, transform)
     simplify = tolerance is not None or min_ring_area != 0
     if simplify:                                                        # refused before anything runs
         rle.polygon_tolerance_q8(0 if tolerance is None else tolerance)

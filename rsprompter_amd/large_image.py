@@ -133,11 +133,14 @@ def _check_dense(k, H, W):
 # ------------------------------------------------------------------------------------------------------------- pipeline
 def _runs_out(counts, n, scene_hw, polygons, obb_out=None):
     """the scene run table in the form the caller asked for: COCO strings (rsp_rle_to_string), or with polygons (True, or
-    (tolerance, min_ring_area) to simplify them on the device) the per-instance ring lists of DESIGN §14.7
+    (tolerance, min_ring_area) to simplify them on the device, DESIGN §14.8, or (tolerance, 0, 'shared') to simplify the
+    shared borders of a flattened table once) the per-instance ring lists of DESIGN §14.7
     (csrc/mask_polygons.hip), traced on the table before any string is made.  obb_out: a list that receives the oriented
     boxes of the table, float64 [k, 4, 2] (csrc/mask_obb.hip), made from the same table first"""
     if obb_out is not None:
         obb_out.append(rle.obb_to_numpy(*rle.runs_to_obb(counts, n, scene_hw)[3:], form='corners'))
+    if polygons is not True and polygons and len(polygons) == 3:        # (tolerance, 0, 'shared'): DESIGN §14.15
+        return rle.polygons_to_lists(*rle.simplify_coverage(counts, n, scene_hw, polygons[0])[0])
     if polygons:
         polys = rle.runs_to_polygons(counts, n, scene_hw)
         if polygons is not True:
@@ -388,14 +391,17 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
                           batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
                           polygon_min_ring_area=0, oriented_boxes=False, min_mask_region_area=0, flatten=False,
-                          flatten_min_ratio=0.0):
+                          flatten_min_ratio=0.0, polygon_topology='rings'):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
     (masks='rle'), a bool [K, H, W] device tensor (masks='dense'), or per instance the list of (ring int32 [m, 2], parent,
     area2) of DESIGN §14.7 (masks='polygons': traced on the device from the scene run table; polygon_tolerance in pixels and
     polygon_min_ring_area in pixels simplify the rings there first, DESIGN §14.8 -- apis.masks_to_polygons says how; they
-    apply to masks='polygons' only).  oriented_boxes=True (masks='rle' or 'polygons'): pred_instances.obb is float64 numpy
+    apply to masks='polygons' only; polygon_topology='shared', DESIGN §14.15, simplifies every border between two instances
+    once, to the same vertices in both rings: it requires masks='polygons', flatten on, a polygon_tolerance -- 0 is legal --
+    and polygon_min_ring_area 0; with min_mask_region_area the last step is a flatten, so the table is disjoint).
+    oriented_boxes=True (masks='rle' or 'polygons'): pred_instances.obb is float64 numpy
     [K, 4, 2], the corners of the minimum-area rectangle around each instance's scene mask (clockwise on screen,
     NaN for an empty mask), made on the device from the scene run table before any string is made.  min_mask_region_area > 0
     (masks='rle' or 'polygons'): holes and islands of fewer pixels than that are removed from every scene mask
@@ -441,6 +447,13 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
         poly = (0 if polygon_tolerance is None else polygon_tolerance, polygon_min_ring_area)
         rle.polygon_tolerance_q8(poly[0])                               # refused before the first tile runs
         rle.polygon_min_ring_area(poly[1])
+    if rle.polygon_topology(polygon_topology, polygon_tolerance if poly else 0, polygon_min_ring_area if poly else 0):
+        if not poly:                                                    # refused before the first tile runs
+            raise ValueError("polygon_topology='shared' applies to masks='polygons'")
+        if flat_order is None:
+            raise ValueError("polygon_topology='shared' needs pairwise disjoint instances: turn flatten on (flatten='score' "
+                             "or flatten='area')")
+        poly = (polygon_tolerance, 0, 'shared')
     ph_, pw_ = (int(patch_size), int(patch_size)) if isinstance(patch_size, (int, float)) else (int(patch_size[0]), int(patch_size[1]))
     if pw_ > MAX_PATCH_WIDTH:
         raise ValueError(f'a patch {pw_} pixels wide: the tile RLE kernel is specified for widths up to {MAX_PATCH_WIDTH}')
@@ -669,6 +682,9 @@ def main(argv=None):
                     help='add "obb": the four corners of the minimum-area rectangle around each mask, made on the device')
     ap.add_argument('--min-mask-region-area', type=int, default=0, metavar='A',
                     help='remove holes and islands of less than A pixels from every scene mask, on the device')
+    ap.add_argument('--simplify-topology', default='rings', choices=rle.POLYGON_TOPOLOGIES,
+                    help="'shared': simplify every border between two instances once, to the same vertices on both sides "
+                         '(needs --flatten, --simplify-tolerance and --mask-format polygons or geojson; DESIGN 14.15)')
     ap.add_argument('--flatten', nargs='?', const='score', default=None, choices=('score', 'area'),
                     help="make the instances of a scene pairwise disjoint, a planar layer: every pixel stays with the covering "
                     "instance of highest score ('score', the default) or smallest mask ('area'), on the device")
@@ -685,6 +701,11 @@ def main(argv=None):
         if a.min_mask_region_area < 0:
             raise ValueError(f'--min-mask-region-area must be a non-negative integer, got {a.min_mask_region_area}')
         _check_flatten(a.flatten or False, a.flatten_min_ratio)
+        if rle.polygon_topology(a.simplify_topology, a.simplify_tolerance, a.min_ring_area):
+            if a.mask_format == 'rle':
+                raise ValueError('--simplify-topology shared applies to --mask-format polygons and geojson')
+            if not a.flatten:
+                raise ValueError('--simplify-topology shared needs pairwise disjoint instances: add --flatten')
     except ValueError as e:
         ap.error(str(e))
     model = init_detector(a.config, None if a.checkpoint in ('', 'none', 'None') else a.checkpoint, device=a.device)
@@ -695,7 +716,7 @@ def main(argv=None):
                                   seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
                                   polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes,
                                   min_mask_region_area=a.min_mask_region_area, flatten=a.flatten or False,
-                                  flatten_min_ratio=a.flatten_min_ratio)
+                                  flatten_min_ratio=a.flatten_min_ratio, polygon_topology=a.simplify_topology)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

@@ -1830,8 +1830,13 @@ def mask_polygons(counts, n, H, W):
     Rings are ordered by (instance, first vertex); a ring starts at its smallest vertex by (x, y), holds corners only and does
     not repeat its first vertex.  A row with n <= 0 has no rings.  Three device-to-host reads, whatever k is: the pieces
     (total and largest row), the number of rings (inside torch.nonzero), the number of vertices."""
+    return _trace_pieces(run_pieces(counts, n, H, W, what='mask_polygons', limit=MASK_POLYGON_MAX_PIECES), H, W)   # read 1
+
+
+def _trace_pieces(rp, H, W):
+    """mask_polygons after its piece table (reads 2 and 3)"""
     lib = _lib.load()
-    pieces, piece_offs, P, widest = run_pieces(counts, n, H, W, what='mask_polygons', limit=MASK_POLYGON_MAX_PIECES)   # read 1
+    pieces, piece_offs, P, widest = rp
     k, H, W, dev = int(piece_offs.shape[0]) - 1, int(H), int(W), pieces.device
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
 
@@ -1948,6 +1953,102 @@ def ring_simplify(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_rin
                                            out_inst.data_ptr(), out_parent.data_ptr(), out_area2.data_ptr(),
                                            out_inst_offs.data_ptr(), out_src.data_ptr(), _stream()), "rsp_ring_simplify_write")
     out = (out_verts, out_offs, out_inst, out_parent, out_area2, out_inst_offs, out_src)
+    return out + (rounds,) if with_rounds else out
+
+
+# ----------------------------------------------------------------------------- shared borders (csrc/ring_coverage.hip)
+RING_COVERAGE_MAX_SIDE = CONST['RSP_RING_COVERAGE_MAX_SIDE']         # the coordinate bound of the 128-bit distance, as above
+
+
+def ring_coverage(counts, n, H, W, tol2_q8, with_rounds=False, variant=0):
+    """Shared-border simplification of a planar layer: counts int32 [k, cap] / n int32 [k], k masks on one
+    (H, W) canvas whose rows are pairwise DISJOINT and canonical (what rle_flatten returns), H W < 2^31, max(H, W) <= 2^20 ->
+    the rings of mask_polygons with every node inserted (a lattice point where at least 3 of the 4 sides around it separate
+    different owners: T-junctions, points where 3 or 4 regions meet or two meet the canvas border, saddles), each ring rotated
+    to begin at its first node visit (a ring without a node stays at its smallest vertex), and every arc between two node
+    visits simplified by Douglas-Peucker at tol2_q8 = round(256 tolerance^2) with rules that do not depend on the direction
+    or the start of the walk -- so the two rings along a border keep the same vertices.  Every node is kept; tol2_q8 = 0 keeps
+    every vertex.  A ring is dropped when fewer than 3 vertices are kept, when its new doubled area is 0 or changed sign, or
+    when it is a hole whose outer ring was dropped.  Returns the six arrays of the surviving rings in the layout of
+    ring_simplify, ring_src int32 [R'] and vert_other int32 [V']: the owner on the far side of the edge that leaves every
+    output vertex (-1: background or the canvas border); with_rounds=True appends rounds int32 [R] of every traced ring.
+    Rows that overlap, or that hold a zero count inside, are refused (ValueError).
+    Five device-to-host reads, whatever k is: the pieces, the rings and the vertices of the trace (mask_polygons), the
+    noded vertices together with the disjointness flags, the survivors (R' and V' together); one when the table has no
+    piece.  `variant`: the launch alternatives of rsp_ring_coverage_mark (measurement only)."""
+    lib = _lib.load()
+    if isinstance(tol2_q8, bool) or not isinstance(tol2_q8, int) or not 0 <= tol2_q8 <= RING_SIMPLIFY_MAX_TOL2_Q8:
+        raise ValueError(f'ring_coverage: tol2_q8 is an integer in [0, 2^40], got {tol2_q8!r}')
+    if max(int(H), int(W)) > RING_COVERAGE_MAX_SIDE:
+        raise ValueError(f'ring_coverage: a {int(H)} x {int(W)} canvas; the sides are at most 2^20')
+    rp = run_pieces(counts, n, H, W, what='ring_coverage', limit=MASK_POLYGON_MAX_PIECES)                 # read 1
+    k, H, W, dev, P = int(rp.piece_offs.shape[0]) - 1, int(H), int(W), rp.pieces.device, rp.P
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    rounds = torch.zeros((0,), **i32)
+
+    def nothing():
+        out = (torch.zeros((0, 2), **i32), torch.zeros((1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32),
+               torch.zeros((0,), **i64), torch.zeros((k + 1,), **i64), torch.zeros((0,), **i32), torch.zeros((0,), **i32))
+        return out + (rounds,) if with_rounds else out
+    if P == 0:
+        return nothing()
+    cpieces, col_offs, _ = _column_pieces(lib, rp, H, W)
+    bad = torch.empty((P,), **i32)
+    _lib.check(lib.rsp_ring_coverage_check(cpieces.data_ptr(), P, H, W, bad.data_ptr(), _stream()), "rsp_ring_coverage_check")
+    verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs = _trace_pieces(rp, H, W)        # reads 2, 3
+    R, V = int(ring_inst.shape[0]), int(verts.shape[0])
+    cnt, first = torch.ones((max(V, 1),), **i32), torch.full((max(V, 1),), -1, **i32)
+    table = (cpieces.data_ptr(), col_offs.data_ptr(), P, k, H, W)
+    _lib.check(lib.rsp_ring_coverage_nodes_count(verts.data_ptr(), ring_offs.data_ptr(), R, V, *table, cnt.data_ptr(),
+                                                 first.data_ptr(), _stream()), "rsp_ring_coverage_nodes_count")
+    noff, total = _exclusive_total(cnt[:V])
+    Vn, worst = torch.stack([total, bad.max().to(torch.int64)]).tolist()                                  # read 4
+    if worst == 1:
+        raise ValueError('ring_coverage: the rows of the table overlap; shared borders exist between disjoint instances only '
+                         '(make them disjoint first: apis.flatten_masks / rle.flatten_runs)')
+    if worst:
+        raise ValueError('ring_coverage: a row of the table is not canonical (a zero count inside it: two ones-runs touch); '
+                         'rle.flatten_runs returns canonical rows')
+    if R == 0:
+        return nothing()
+    # every ring's first node visit: the first segment at or behind the ring's start that holds a node, and where in it
+    has = (first[:V] >= 0).to(torch.int64)
+    seen = torch.cumsum(has, 0)
+    start = ring_offs[:-1]
+    j = torch.searchsorted(seen, (seen - has)[start.clamp(max=V - 1)] + 1).clamp(max=V - 1)
+    found = (j < ring_offs[1:]) & (has[j] > 0)
+    rot = torch.where(found, noff[j] + first[j].clamp(min=0) - noff[start], torch.zeros_like(start)).contiguous()
+    n_offs = noff[ring_offs].contiguous()
+    nverts, nother = torch.empty((Vn, 2), **i32), torch.empty((Vn,), **i32)
+    keep = torch.empty((Vn,), dtype=torch.uint8, device=dev)
+    _lib.check(lib.rsp_ring_coverage_nodes_write(verts.data_ptr(), ring_offs.data_ptr(), R, V, *table, noff.data_ptr(),
+                                                 rot.data_ptr(), Vn, nverts.data_ptr(), keep.data_ptr(), nother.data_ptr(),
+                                                 _stream()), "rsp_ring_coverage_nodes_write")
+    pos = torch.empty((Vn,), **i32)
+    kept_cnt, area2, sums = torch.empty((R,), **i32), torch.empty((R,), **i64), torch.empty((2, R), **i64)
+    rounds = torch.empty((R,), **i32)
+    _lib.check(lib.rsp_ring_coverage_mark(nverts.data_ptr(), n_offs.data_ptr(), R, Vn, tol2_q8, H, W, int(variant),
+                                          keep.data_ptr(), pos.data_ptr(), kept_cnt.data_ptr(), area2.data_ptr(),
+                                          rounds.data_ptr(), _stream()), "rsp_ring_coverage_mark")
+    _lib.check(lib.rsp_ring_simplify_survive(ring_inst.data_ptr(), ring_parent.data_ptr(), ring_area2.data_ptr(),
+                                             inst_ring_offs.data_ptr(), R, k, 0, kept_cnt.data_ptr(), area2.data_ptr(),
+                                             sums.data_ptr(), _stream()), "rsp_ring_simplify_survive")
+    csum = torch.cumsum(sums, 1)
+    R2, V2 = csum[:, -1].tolist()                                                                         # read 5
+    if R2 == 0:
+        return nothing()
+    out_verts, out_other = torch.zeros((V2, 2), **i32), torch.empty((V2,), **i32)
+    out_offs, out_area2, out_inst_offs = torch.empty((R2 + 1,), **i64), torch.empty((R2,), **i64), torch.empty((k + 1,), **i64)
+    out_inst, out_parent, out_src = torch.empty((R2,), **i32), torch.empty((R2,), **i32), torch.empty((R2,), **i32)
+    _lib.check(lib.rsp_ring_simplify_write(nverts.data_ptr(), n_offs.data_ptr(), ring_inst.data_ptr(), ring_parent.data_ptr(),
+                                           inst_ring_offs.data_ptr(), R, Vn, k, keep.data_ptr(), pos.data_ptr(), area2.data_ptr(),
+                                           sums.data_ptr(), csum.data_ptr(), R2, V2, out_verts.data_ptr(), out_offs.data_ptr(),
+                                           out_inst.data_ptr(), out_parent.data_ptr(), out_area2.data_ptr(),
+                                           out_inst_offs.data_ptr(), out_src.data_ptr(), _stream()), "rsp_ring_simplify_write")
+    _lib.check(lib.rsp_ring_coverage_other(n_offs.data_ptr(), R, Vn, keep.data_ptr(), pos.data_ptr(), sums.data_ptr(),
+                                           csum.data_ptr(), V2, nother.data_ptr(), out_other.data_ptr(), _stream()),
+               "rsp_ring_coverage_other")
+    out = (out_verts, out_offs, out_inst, out_parent, out_area2, out_inst_offs, out_src, out_other)
     return out + (rounds,) if with_rounds else out
 
 
@@ -2271,6 +2372,20 @@ def _flatten_rank(what, rank, k, dev):
     return rank.contiguous()
 
 
+def _column_pieces(lib, rp, H, W):
+    """the column-ordered copy of a piece table with P > 0 pieces (one device key sort, rsp_run_flatten_columns) ->
+    (cpieces int32 [4, P] sorted by (x, y0), col_offs int32 [W + 1], reach int32 [P]).  No host read."""
+    P, dev = rp.P, rp.pieces.device
+    px, py0 = rp.pieces[0].to(torch.int64), rp.pieces[1].to(torch.int64)
+    skeys = torch.sort(((px * H + py0) << 31) | torch.arange(P, dtype=torch.int64, device=dev))[0].contiguous()
+    cpieces = rp.pieces[:, skeys & 0x7fffffff].contiguous()
+    col_offs = torch.empty((W + 1,), dtype=torch.int32, device=dev)
+    reach = torch.empty((P,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_run_flatten_columns(skeys.data_ptr(), cpieces.data_ptr(), P, H, W, col_offs.data_ptr(),
+                                           reach.data_ptr(), _stream()), "rsp_run_flatten_columns")
+    return cpieces, col_offs, reach
+
+
 def rle_flatten(counts, n, H, W, rank, cap=None):
     """the rows of a run table (counts int32 [k, cap_in], n int32 [k]: k masks on one (H, W) canvas) made pairwise disjoint
     (DESIGN §14.14): rank int32 [k] on the device, a permutation of 0 .. k - 1 where 0 wins (rle.flatten_runs checks it;
@@ -2293,14 +2408,8 @@ def rle_flatten(counts, n, H, W, rank, cap=None):
     keys, ends, total = None, None, 0
     iv_offs = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
     if P:
-        px, py0 = rp.pieces[0].to(torch.int64), rp.pieces[1].to(torch.int64)
-        skeys = torch.sort(((px * H + py0) << 31) | torch.arange(P, dtype=torch.int64, device=dev))[0].contiguous()
-        cpieces = rp.pieces[:, skeys & 0x7fffffff].contiguous()
-        col_offs = torch.empty((W + 1,), dtype=torch.int32, device=dev)
-        reach = torch.empty((P,), dtype=torch.int32, device=dev)
-        _lib.check(lib.rsp_run_flatten_columns(skeys.data_ptr(), cpieces.data_ptr(), P, H, W, col_offs.data_ptr(),
-                                               reach.data_ptr(), _stream()), "rsp_run_flatten_columns")
-        head = (rp.pieces.data_ptr(), cpieces.data_ptr(), col_offs.data_ptr(), reach.data_ptr(), rank.data_ptr(), P, k, H, W)
+        cpieces, col_offs, reach = _column_pieces(lib, rp, H, W)
+        head =(rp.pieces.data_ptr(), cpieces.data_ptr(), col_offs.data_ptr(), reach.data_ptr(), rank.data_ptr(), P, k, H, W)
         cnt = torch.empty((P,), dtype=torch.int32, device=dev)
         _lib.check(lib.rsp_run_flatten_count(*head, cnt.data_ptr(), _stream()), "rsp_run_flatten_count")
         out_offs, total = _exclusive_total(cnt)

@@ -159,6 +159,39 @@ def simplify_polygons(polys, size, tolerance, min_ring_area=0):
     return out[:6], out[6]
 
 
+POLYGON_TOPOLOGIES = ('rings', 'shared')
+
+
+def polygon_topology(topology, tolerance, min_ring_area):
+    """the `topology` of the polygon outputs with the options that go with it -> True for 'shared' (DESIGN §14.15), which
+    requires a tolerance (0 is legal: the noded exact rings) and min_ring_area == 0"""
+    if topology not in POLYGON_TOPOLOGIES:
+        raise ValueError(f'polygon topology {topology!r}: one of {POLYGON_TOPOLOGIES}')
+    if topology == 'rings':
+        return False
+    if tolerance is None:
+        raise ValueError("topology='shared' simplifies shared borders and requires a tolerance (0 gives the exact rings "
+                         'with their nodes)')
+    polygon_tolerance_q8(tolerance)
+    if polygon_min_ring_area(min_ring_area) != 0:
+        raise ValueError("topology='shared' requires min_ring_area == 0: a ring dropped by its area would leave its pixels "
+                         'to nobody, and the layer would have a gap again')
+    return True
+
+
+def simplify_coverage(counts, n, size, tolerance):
+    """run table of k masks on one size = (H, W) canvas whose rows are pairwise disjoint and canonical (what flatten_runs
+    returns) -> (the six arrays of the simplified rings, ring_src int32 [R'], vert_other int32 [V']) on the device:
+    shared-border simplification at `tolerance` pixels (ops.ring_coverage).  A border between two instances
+    keeps the same vertices in both rings, every node (T-junctions, points where three or four regions or two and the canvas
+    border meet, saddles) is a vertex, and a ring begins at its first node visit, not at its smallest vertex (a ring without a
+    node stays there).  vert_other[v] = the instance on the far side of the edge that leaves vertex v, -1 for background.
+    Arcs of different borders may still cross each other at large tolerances.  Overlapping or non-canonical rows raise
+    ValueError.  Five device-to-host reads (one when the table has no piece)."""
+    out = ops.ring_coverage(counts, n, size[0], size[1], polygon_tolerance_q8(tolerance))
+    return out[:6], out[6], out[7]
+
+
 def polygons_to_lists(verts, ring_offs, ring_inst, ring_parent, ring_area2, inst_ring_offs):
     """what runs_to_polygons returns -> per instance a list of (ring int32 ndarray [m, 2] = (x, y), parent, area2) on the
     host, after ONE transfer (the five arrays that are read, packed into one int64 buffer)."""
