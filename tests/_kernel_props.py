@@ -332,7 +332,8 @@ def check_query_topk(ops, dev, B, Nq, nc, k, seed):
 
 def check_roi_align(ops, dev, K, P, seed):
     """RoIAlign with RoIs that are tiny, huge, partly or wholly outside the image, on every pyramid level, against the C
-    restatement of mmcv RoIAlign"""
+    restatement of mmcv RoIAlign
+    (samples exactly on the cuts, the last row and the level thresholds: check_exact_roi_align, tests/_sampler_props.py)"""
     import torch_ops_mock as mock
     g = torch.Generator().manual_seed(seed)
     B, C = 2, 8
@@ -362,7 +363,8 @@ def check_msdeform_attn(ops, dev, L, hd, seed):
 
 def check_resample(ops, dev, B, h, w, ho, wo, seed):
     """bilinear resizing up and down, GroupNorm with add / ReLU, the query prompter's attention-mask rule incl. a fully
-    blocked row"""
+    blocked row
+    (dyadic ratios, from and to 1 x 1 and logits that tie with the threshold: check_exact_interp, tests/_sampler_props.py)"""
     import torch_ops_mock as mock
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, h, w, 128, generator=g)

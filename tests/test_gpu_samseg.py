@@ -25,9 +25,13 @@ def test_paste_masks_kernel_matches_reference_vectors(dev):
         h, w = c['masks'].shape[-2:]
         got = ops.paste_masks(c['logits'].permute(0, 2, 3, 1).contiguous().to(dev), c['labels'].to(dev),
                               c['boxes_out'].to(dev), (h, w), 0.5)
-        mism = float((got.cpu() != c['masks']).float().mean())
+        diff = got.cpu() != c['masks']
+        mism = float(diff.float().mean())
         print(f'paste {meta}: mismatch {mism:.2e}')
         assert mism < 1e-4          # pixels whose pasted probability sits within fp32 noise of the threshold
+        # ... and only those: the real file's own soft byte of every mismatching pixel is 127 or 128 (p * 255 = 127.5)
+        at = c['masks_soft'][diff].int()
+        assert bool(((at == 127) | (at == 128)).all()), ('a mismatch away from the threshold', meta, at.unique().tolist())
         # mask_thr_binary < 0 (fcn_mask_head.py:390-394): the probabilities as uint8, against the real file's output
         soft = ops.paste_masks(c['logits'].permute(0, 2, 3, 1).contiguous().to(dev), c['labels'].to(dev),
                                c['boxes_out'].to(dev), (h, w), -1.0).cpu()

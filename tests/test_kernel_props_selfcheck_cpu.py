@@ -163,3 +163,98 @@ def test_exact_field_check_rejects(mutation):
         for hw in mf.crop_groups(_MF_CASES):
             with pytest.raises(AssertionError):
                 mf.check_exact_crops(fake, 'cpu', hw, seed=101, cases=_MF_CASES)
+
+
+# ---------------------------------------------------------------------------------------------------------- the sampler checks
+import _sampler_props as sp  # noqa: E402
+
+# sampler -> (mutations, the exact-tier bodies that must show them, their cases); rsp_resize_pad's siblings share its family
+_SAMPLERS = {
+    'roi_align': (sp.ROI_MUTATIONS, ((sp.check_exact_roi_align, sp.ROI_EXACT),)),
+    'paste_masks': (sp.PASTE_MUTATIONS, ((sp.check_exact_paste, sp.PASTE_EXACT),)),
+    'resize_pad': (sp.RESIZE_MUTATIONS, ((sp.check_exact_resize_pad, sp.RESIZE_EXACT), (sp.check_exact_windows, sp.WINDOW_EXACT))),
+    'interpolate': (sp.INTERP_MUTATIONS, ((sp.check_exact_interp, sp.INTERP_EXACT),)),
+    'msdeform_attn': (sp.MSDA_MUTATIONS, ((sp.check_exact_msdeform, sp.MSDA_EXACT),)),
+}
+
+
+def test_sampler_fake_reproduces_the_oracles():
+    """the unmutated stand-in (the fp32 restatements) passes every exact case of the five conventions -- so an
+    AssertionError under a mutation below comes from the comparison with `ops`, not from a precondition of the case, which
+    never looks at `ops` -- and the fp64 restatements agree with the independent statements this suite already has: the C
+    restatement of mmcv RoIAlign, mmdet's mask paste and the cv2 restatement"""
+    fake = sp.FakeOps()
+    for muts, bodies in _SAMPLERS.values():
+        assert len(muts) >= 4
+        for body, cases in bodies:
+            for c in cases:
+                body(fake, 'cpu', c)
+    import torch_ops_mock as mock
+    case = sp.ROI_TOL[0]
+    feats, pes, rois = sp.roi_tol_inputs(case)
+    a = sp.roi_align_ref(feats, pes, rois, case.P, [4, 8, 16, 32])
+    assert float((a - mock.roi_align(feats, pes, rois, case.P, [4, 8, 16, 32]).double()).abs().max()) < 1e-4
+    pc = sp.PASTE_TOL[1]
+    logits, labels, boxes = sp.paste_tol_inputs(pc)
+    field, region = sp.paste_field(logits, labels, boxes, pc.img)
+    d = sp.paste_bytes(field, region, -1.0).int() - mock.paste_masks(logits, labels, boxes, pc.img, -1.0).int()
+    assert int(d.abs().max()) <= 1 and float((d != 0).float().mean()) < 2e-3
+    g = torch.Generator().manual_seed(3)
+    img = torch.randint(0, 256, (37, 53, 3), generator=g).to(torch.uint8)
+    b = sp.resize_pad_ref(img, (50, 71), (64, 72), (1.0, 2.0, 3.0))
+    assert float((b - mock.resize_pad(img, (50, 71), (64, 72), (1.0, 2.0, 3.0)).double()).abs().max()) < 1e-3
+
+
+def _sampler_check_rejects(sampler, mutation):
+    fake = sp.FakeOps(mutation)
+    rejected = 0
+    for body, cases in _SAMPLERS[sampler][1]:
+        for c in cases:
+            try:
+                body(fake, 'cpu', c)
+            except AssertionError:
+                rejected += 1
+    assert rejected, (sampler, mutation)
+
+
+@pytest.mark.parametrize('mutation', sp.ROI_MUTATIONS)
+def test_exact_roi_align_check_rejects(mutation):
+    """check_exact_roi_align raises AssertionError on at least one exact case: no -0.5, an inclusive cut at H or at -1, the
+    low clamp missing, the top index unclamped, a fixed 2 x 2 grid, a level one too low at an exact power of two, the PE skipped"""
+    _sampler_check_rejects('roi_align', mutation)
+
+
+@pytest.mark.parametrize('mutation', sp.PASTE_MUTATIONS)
+def test_exact_paste_masks_check_rejects(mutation):
+    """check_exact_paste: `>` for `>=`, align_corners=True, border padding, the soft mode's region without its margin, the
+    label ignored, an infinite coordinate not zeroed, rounding for truncation"""
+    _sampler_check_rejects('paste_masks', mutation)
+
+
+@pytest.mark.parametrize('mutation', sp.RESIZE_MUTATIONS)
+def test_exact_resize_pad_check_rejects(mutation):
+    """check_exact_resize_pad / check_exact_windows: no half pixel, the right and bottom edge unclamped, padding not
+    normalised, the mean indexed before the swap, the scale taken from the canvas, a window's origin read as (y, x)"""
+    _sampler_check_rejects('resize_pad', mutation)
+
+
+@pytest.mark.parametrize('mutation', sp.INTERP_MUTATIONS)
+def test_exact_interpolate_check_rejects(mutation):
+    """check_exact_interp: align_corners=True, no half pixel, `<=` for `<` at the threshold, the fully blocked row kept, the
+    blocked-row rule taken over the batch"""
+    _sampler_check_rejects('interpolate', mutation)
+
+
+@pytest.mark.parametrize('mutation', sp.MSDA_MUTATIONS)
+def test_exact_msdeform_attn_check_rejects(mutation):
+    """check_exact_msdeform: x and y swapped, a level read from the next map's start, border padding, a softmax over the
+    points of one level only, align_corners=True, offsets divided by the first level's size"""
+    _sampler_check_rejects('msdeform_attn', mutation)
+
+
+def test_roi_align_tolerance_check_rejects_a_dropped_level_epsilon():
+    """the 1e-6 of floor(log2(sqrt(w h) / 56 + 1e-6)) moves a roi only when sqrt(w h) / 56 is within 1e-6 below a power of
+    two, which no dyadic roi is: the tolerance tier carries two such rois, and its body rejects a stand-in without the epsilon"""
+    sp.check_roi_align_tolerance(sp.FakeOps(), 'cpu', report=lambda line: None)
+    with pytest.raises(AssertionError):
+        sp.check_roi_align_tolerance(sp.FakeOps('level_epsilon_dropped'), 'cpu', report=lambda line: None)
