@@ -948,7 +948,8 @@ int rsp_run_morph_pieces(const uint32_t* counts, const int32_t* n, int32_t k, in
                          rsp_stream_t stream);
 /* 2. Join, one lane per interval of table A (PA intervals on strips of Wa columns) against column X + shift of table B (PB      */
 /* intervals, strips of Wb columns, b_offs int32 [k Wb + 1] = the first interval of every column): op 0 = the intersections,     */
-/* none when X + span > Wa or X + shift is outside B's strip; op 1 = A minus B (all of A where B has no such column).  The       */
+/* none when X + span > Wa or X + shift is outside B's strip; op 1 = A minus B (all of A where B has no such column; shift may  */
+/* be negative there, op 0 takes shift >= 0).  The                                                                              */
 /* output column is X + out_shift on strips of Wout columns; an interval whose output column falls outside writes nothing.       */
 /* _count: cnt int32 [PA]; the caller's exclusive sum is out_offs int64 [PA + 1], total = out_offs[PA] < 2^31.  emit_keys = 0:    */
 /* the result as a table (o_col, o_y0, o_y1 [total]); emit_keys = 1: as rsp_rle_union's intervals on the (H, Wout) canvas,       */
@@ -961,6 +962,24 @@ int rsp_run_morph_join(int32_t op, const int32_t* a_col, const int32_t* a_y0, co
                        int32_t shift, int32_t span, const int64_t* out_offs, int64_t total, int32_t out_shift, int32_t Wout,
                        int32_t H, int32_t emit_keys, int32_t* o_col, int32_t* o_y0, int32_t* o_y1, int64_t* keys, int32_t* ends,
                        rsp_stream_t stream);
+
+/* Euclidean buffers (csrc/run_disc.hip): dilation of every mask of a run table by the exact disc dx^2 + dy^2 <=  */
+/* r2 or the diamond; replaces scipy.ndimage.binary_dilation / distance_transform_edt on dense masks and the buffer step of a      */
+/* GIS after vector export.  The structuring element is hh int32 [R + 1]: hh[dx] = the rows it reaches above and below its         */
+/* centre at column offset dx, NON-INCREASING, filled on the host (isqrt(r2 - dx^2), or r - dx), entries cut into [0, H]; R <=     */
+/* W - 1.  One lane per (interval of a TABLE of rsp_run_morph_pieces / rsp_run_morph_join on strips of W columns, dx) stores one   */
+/* interval of rsp_rle_union on the (H, W) canvas, keys = instance << 31 | pixel start, the interval [y0, y1) grown to             */
+/* [max(y0 - hh[dx], 0), min(y1 + hh[dx], H)) in column X + dir * dx.  dir = 0: dx = 0 only, slot base + i for interval i.  dir =  */
+/* +1 / -1: dx = 1 .. R, targets outside [0, W) are skipped, slots base + slot_offs[i] .. base + slot_offs[i + 1] in the order of  */
+/* dx, slot_offs int64 [P + 1] = the caller's exclusive sum of min(R, W - 1 - X) / min(R, X).  total = the length of keys / ends;  */
+/* slots at or beyond it are not written.  The intervals are NOT in key order: the caller sorts them before rsp_rle_union.  With   */
+/* the table = the pieces for dir 0 and the pieces minus those of the next / previous column (rsp_run_morph_join, op 1, shift      */
+/* +1 / -1) for dir +1 / -1, the union of the three calls is the dilation.  No host read, no atomics, every slot stored once.      */
+/* Refused with RSP_EINVAL: H * W >= 2^31, k * W >= 2^31, P or total >= 2^31, R < 0 or R > W - 1, dir outside -1 .. 1, base        */
+/* outside [0, total], a null pointer where something is read or written.                                                         */
+int rsp_run_disc_emit(const int32_t* col, const int32_t* y0, const int32_t* y1, int64_t P, int32_t k, int32_t H, int32_t W,
+                      const int32_t* hh, int32_t R, int32_t dir, const int64_t* slot_offs, int64_t base, int64_t total,
+                      int64_t* keys, int32_t* ends, rsp_stream_t stream);
 
 /* Planar instance layers (csrc/run_flatten.hip): the k masks of a run table made pairwise disjoint by a         */
 /* priority, row i = M_i minus every M_j with rank[j] < rank[i]; replaces the per-pixel argmax over dense [k, H, W] masks of      */

@@ -271,33 +271,63 @@ def _morph_radius(radius):
     return int(radius)
 
 
-def _morphology(masks, op, radius, device, what):
+MORPHOLOGY_ELEMENTS = rle.MORPHOLOGY_ELEMENTS
+
+
+def _morph_element(what, element, radius):
+    """element and its radius: an integer for the square and the diamond, a non-negative real number for the disc"""
+    if element not in MORPHOLOGY_ELEMENTS:
+        raise ValueError(f'{what}: element must be one of {MORPHOLOGY_ELEMENTS}, got {element!r}')
+    if element != 'disc':
+        return _morph_radius(radius)
+    rle.disc_r2(radius)                                     # refuses what is not a non-negative finite real number
+    return radius
+
+
+def _morphology(masks, op, radius, device, what, element='square'):
     fn = dict(erode=rle.erode_runs, dilate=rle.dilate_runs, open=rle.open_runs, close=rle.close_runs,
-              boundary=rle.boundary_runs)[op]
+              boundary=rle.boundary_runs, buffer=rle.buffer_runs)[op]
     if isinstance(masks, torch.Tensor) and masks.dim() == 3 and masks.shape[0] == 0:
         return masks.to(torch.bool).clone()
     counts, n, size, form = rle.masks_to_runs(masks, device, what)
-    counts, n, n_host, _ = fn(counts, n, size, radius)
+    counts, n, n_host, _ = fn(counts, n, size, radius, **({} if element == 'square' else dict(element=element)))
     return rle.runs_to_masks(counts, n, size, form, n_host)
 
 
-def mask_morphology(masks, op, radius, device='cuda:0'):
+def buffer_masks(masks, distance, device='cuda:0'):
+    """The GIS buffer in the run domain (csrc/run_disc.hip): distance > 0 grows every mask to the pixels whose
+    Euclidean distance to it is at most `distance` (the exact disc dx^2 + dy^2 <= floor(distance^2), clipped to the canvas);
+    distance < 0 shrinks it to the pixels farther than |distance| from its outside, the outside of the canvas counting as set
+    (the edge of a scene is not an object boundary) -- the usual way to pull touching footprints apart; 0 returns the masks
+    in canonical form.  distance is a real number in pixels (metres divided by the pixel size), squared in exact arithmetic.
+    Input and output forms as mask_morphology's; no mask is expanded."""
+    rle._exact_fraction(distance, 'buffer_masks: distance')
+    return _morphology(masks, 'buffer', distance, device, 'buffer_masks')
+
+
+def mask_morphology(masks, op, radius, device='cuda:0', element='square'):
     """Morphology by the (2 radius + 1)^2 square in the run domain (csrc/run_morphology.hip): op 'erode'
     (outside the canvas counts as background), 'dilate', 'open' (erode, then dilate), 'close' (dilate, then erode with the
     outside set) or 'boundary' (the mask minus its erosion) -- cv2.erode / cv2.dilate / cv2.morphologyEx with a square kernel,
     scipy.ndimage.binary_erosion(M, ones((3, 3)), iterations=radius).  masks: bool [k, H, W] on the device -> bool [k, H, W];
     or a list of RLE dicts dict(size=[H, W], counts=...) of one size, compressed (bytes / str) or uncompressed (list) ->
     RLE dicts of the same counts form, never a dense mask (`device` places the run table); the cost is the masks' column
-    pieces times log radius."""
+    pieces times log radius.  element (MORPHOLOGY_ELEMENTS): 'square'; 'disc', the exact Euclidean disc dx^2 + dy^2 <=
+    floor(radius^2), radius a non-negative real number (scipy.ndimage with that footprint, the distance transform thresholded;
+    not cv2's MORPH_ELLIPSE); 'diamond', |dx| + |dy| <= radius (csrc/run_disc.hip, DESIGN §14.16: the cost grows linearly
+    with the radius, never with the area)."""
     if op not in MORPHOLOGY_OPS:
         raise ValueError(f'mask_morphology: op must be one of {MORPHOLOGY_OPS}, got {op!r}')
-    return _morphology(masks, op, _morph_radius(radius), device, 'mask_morphology')
+    return _morphology(masks, op, _morph_element('mask_morphology', element, radius), device, 'mask_morphology', element)
 
 
-def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0'):
+def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0', element='square'):
     """The boundary band of Boundary IoU (Cheng et al., CVPR 2021; boundary-iou-api mask_to_boundary): the pixels of each
     mask within d of its outline or of the image border, d = rle.boundary_radius(size, dilation_ratio) = max(1, round(ratio *
-    diagonal)) or `radius` when given.  Input and output forms as mask_morphology's."""
+    diagonal)) or `radius` when given.  Input and output forms as mask_morphology's.  element: as mask_morphology's (the
+    published metric is the square)."""
+    if element not in MORPHOLOGY_ELEMENTS:
+        raise ValueError(f'mask_boundary: element must be one of {MORPHOLOGY_ELEMENTS}, got {element!r}')
     if radius is None:
         size = tuple(masks.shape[1:]) if isinstance(masks, torch.Tensor) else None
         if size is None:
@@ -306,7 +336,7 @@ def mask_boundary(masks, dilation_ratio=0.02, radius=None, device='cuda:0'):
                 raise ValueError('mask_boundary: an empty list carries no canvas size; pass a bool [0, H, W] tensor instead')
             size = masks[0]['size']
         radius = rle.boundary_radius(size, dilation_ratio)
-    return _morphology(masks, 'boundary', _morph_radius(radius), device, 'mask_boundary')
+    return _morphology(masks, 'boundary', _morph_element('mask_boundary', element, radius), device, 'mask_boundary', element)
 
 
 def boundary_iou(dt, gt, iscrowd=None, dilation_ratio=0.02, radius=None, min_with_mask=False, device='cuda:0'):

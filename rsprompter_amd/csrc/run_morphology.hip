@@ -199,8 +199,9 @@ inline bool rm_pieces_args_ok(const void* counts, const void* n, int32_t k, int3
 inline bool rm_join_args_ok(int32_t op, const void* a_col, const void* a_y0, const void* a_y1, int64_t PA, int32_t Wa,
                             const void* b_offs, const void* b_y0, const void* b_y1, int64_t PB, int32_t k, int32_t Wb,
                             int32_t shift, int32_t span) {
-  if ((op != 0 && op != 1) || PA < 0 || PB < 0 || PA > 0x7fffffffLL || PB > 0x7fffffffLL || k < 0 || shift < 0 || span < 1)
-    return false;
+  // a negative shift: the difference with a column to the left (op 1, the E- of run_disc.hip); op 0's windows grow to the right
+  if ((op != 0 && op != 1) || PA < 0 || PB < 0 || PA > 0x7fffffffLL || PB > 0x7fffffffLL || k < 0 || span < 1) return false;
+  if (shift < 0 && op != 1) return false;
   if (!rm_strip_ok(k > 0 ? k : 1, Wa) || !rm_strip_ok(k > 0 ? k : 1, Wb)) return false;
   if (PA > 0 && (!a_col || !a_y0 || !a_y1 || !b_offs)) return false;
   return PB == 0 || (b_y0 && b_y1);

@@ -169,12 +169,27 @@ def _check_flatten(flatten, min_ratio):
     return (flatten or None), ratio
 
 
-def _finish_scene(counts, n, scene_hw, region, planar):
-    """the scene run table before it takes any output form.  planar = (order, min_ratio, scores float [K], a list that receives
+def _check_buffer(buffer):
+    """buffer of inference_large_image: a signed finite real number of pixels -> it, or None for 0"""
+    try:
+        d = rle._exact_fraction(buffer, 'buffer')
+    except ValueError:
+        raise ValueError(f'buffer must be a finite real number of pixels (signed), got {buffer!r}') from None
+    return buffer if d != 0 else None
+
+
+def _finish_scene(counts, n, scene_hw, region, planar, buf=None):
+    """the scene run table before it takes any output form.  buf = (distance, a list that receives area int32 [K, 2]) or
+    None: every mask buffered by the signed distance first (rle.buffer_runs) -- growth may create overlaps,
+    which the flatten below resolves, so a planar layer stays planar.  planar = (order, min_ratio, scores float [K], a list that receives
     (kept bool [K], area int32 [K, 2])) or None: the instances made pairwise disjoint first (rle.flatten_runs),
     so that the slivers a subtraction leaves are cleaned with everything else (_clean_scene).  Cleaning fills small holes, and
     a hole of one instance may be where a better one lives: where both are asked for the cleaned table is flattened once
     more, by the same rank, so the result is disjoint whatever was filled."""
+    if buf is not None:
+        area0 = ops.rle_bbox(counts, n, scene_hw[0], scene_hw[1])[1]
+        counts, n, _, _ = rle.buffer_runs(counts, n, scene_hw, buf[0])
+        buf[1].append(torch.stack([area0, ops.rle_bbox(counts, n, scene_hw[0], scene_hw[1])[1]], 1))
     if planar is None:
         return _clean_scene(counts, n, scene_hw, region)
     order, ratio, scores, out = planar
@@ -189,14 +204,14 @@ def _finish_scene(counts, n, scene_hw, region, planar):
     return counts, n
 
 
-def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None):
+def _scene_rle(counts, n, offsets, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None, buf=None):
     """tile run counts of the kept instances -> list of dict(size=[H, W], counts=bytes) (rsp_rle_shift, rsp_rle_to_string)"""
     if int(n.shape[0]) == 0:
         if obb_out is not None:
             obb_out.append(np.zeros((0, 4, 2), np.float64))
         return []
     sc, sn, _, _ = rle.shift_runs(counts, n, offsets, tile_hw, scene_hw)
-    sc, sn = _finish_scene(sc, sn, scene_hw, region, planar)
+    sc, sn = _finish_scene(sc, sn, scene_hw, region, planar, buf)
     return _runs_out(sc, sn, scene_hw, polygons, obb_out)
 
 
@@ -325,7 +340,8 @@ def _seam_merge(boxes, scores, labels, tile_of, tile_rects, counts, n, tile_hw, 
     return out, reps[keep_m], members, (flat, offs)
 
 
-def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None):
+def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_out=None, region=None, planar=None,
+              buf=None):
     """the merged instances' scene RLE: the members' tile runs shifted into the scene (rsp_rle_shift), joined per group
     (rsp_rle_union) and written as strings (rsp_rle_to_string)"""
     flat, offs = groups
@@ -337,7 +353,7 @@ def _seam_rle(counts, n, origin, groups, tile_hw, scene_hw, polygons=False, obb_
     sc, sn, _, _ = rle.shift_runs(counts[flat], n[flat].contiguous(), origin[flat].contiguous(), tile_hw, scene_hw)
     members = torch.arange(flat.shape[0], dtype=torch.int32, device=flat.device)
     uc, un, _, _ = rle.union_runs(sc, sn, scene_hw, offs, members)
-    uc, un = _finish_scene(uc, un, scene_hw, region, planar)
+    uc, un = _finish_scene(uc, un, scene_hw, region, planar, buf)
     return _runs_out(uc, un, scene_hw, polygons, obb_out)
 
 
@@ -391,7 +407,7 @@ def _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr
 def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, merge_iou_thr=0.25, merge_nms_type='nms',
                           batch_size=1, masks='rle', return_patches=False, seam_iou_thr=0.5, polygon_tolerance=None,
                           polygon_min_ring_area=0, oriented_boxes=False, min_mask_region_area=0, flatten=False,
-                          flatten_min_ratio=0.0, polygon_topology='rings'):
+                          flatten_min_ratio=0.0, polygon_topology='rings', buffer=0.0):
     """demo/large_image_demo.py:105-170 as one call.  img: path, ndarray or tensor [H, W, 3] (BGR like TestPipeline);
     patch_size: int or (h, w).  Returns a DetDataSample with ori_shape = (H, W) and pred_instances.{bboxes, scores,
     labels} on the device in batched_nms' keep order; pred_instances.masks is a list of dict(size=[H, W], counts=bytes)
@@ -414,7 +430,12 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     flattened once more so that a filled hole cannot overlap the instance inside it.  flatten_min_ratio in [0, 1] empties an
     instance that keeps less than that share of its pixels (apis.flatten_masks).  K, bboxes, scores and labels stay the
     detector's; pred_instances.flatten_kept is bool [K] (False: the instance kept no pixel or was emptied) and flatten_area
-    int32 [K, 2], the pixels of each scene mask before and in the result.  return_patches=True: (sample, per-tile samples,
+    int32 [K, 2], the pixels of each scene mask before and in the result.  buffer (masks='rle' or 'polygons'): a
+    signed real number of pixels; every scene mask is grown (> 0) or shrunk (< 0, the outside of the scene counting as set) by
+    the exact Euclidean disc (apis.buffer_masks) as the first step on the scene run table, before flatten and cleaning, so
+    overlaps that growth creates are resolved by flatten; bboxes, scores and labels stay the detector's, polygons, oriented
+    boxes and strings are made from the buffered table, and pred_instances.buffer_area is int32 [K, 2] (before, after).
+    return_patches=True: (sample, per-tile samples,
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
@@ -441,6 +462,11 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
         raise ValueError("flatten works on the scene run table: use masks='rle' or masks='polygons' (dense masks go through "
                          'apis.flatten_masks)')
     flat_out = []
+    buf_dist = _check_buffer(buffer)                                    # refused before the first tile runs
+    if buf_dist is not None and masks == 'dense':
+        raise ValueError("buffer works on the scene run table: use masks='rle' or masks='polygons' (dense masks go through "
+                         'apis.buffer_masks)')
+    buf = (buf_dist, []) if buf_dist is not None else None
     if polygon_tolerance is not None or polygon_min_ring_area != 0:
         if not poly:
             raise ValueError("polygon_tolerance and polygon_min_ring_area apply to masks='polygons'")
@@ -527,7 +553,7 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             out.masks = _seam_dense(tm, origin, groups, (H, W))
         else:
             planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
-            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region, planar)
+            out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region, planar, buf)
     else:
         keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
@@ -538,7 +564,8 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
         elif runs:
             kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
             planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
-            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region, planar)
+            out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region, planar,
+                                   buf)
     if obb:
         out.obb = obb[0]
     if region is not None:
@@ -547,6 +574,8 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
         K = len(out.scores)
         out.flatten_kept = flat_out[0][0] if flat_out else torch.zeros((K,), dtype=torch.bool, device=dev)
         out.flatten_area = flat_out[0][1] if flat_out else torch.zeros((K, 2), dtype=torch.int32, device=dev)
+    if buf is not None:
+        out.buffer_area = buf[1][0] if buf[1] else torch.zeros((len(out.scores), 2), dtype=torch.int32, device=dev)
     sample = DetDataSample(metainfo=dict(img_path=img_path, ori_shape=(H, W), img_shape=(H, W), img_id=0))
     sample.pred_instances = out
     sample.keep = keep                                                  # indices into the tile-ordered concatenation
@@ -690,6 +719,9 @@ def main(argv=None):
                     "instance of highest score ('score', the default) or smallest mask ('area'), on the device")
     ap.add_argument('--flatten-min-ratio', type=float, default=0.0, metavar='R',
                     help='--flatten: empty an instance that keeps less than the share R of its pixels')
+    ap.add_argument('--buffer', type=float, default=0.0, metavar='D',
+                    help='grow (D > 0) or shrink (D < 0) every scene mask by the Euclidean disc of |D| pixels, on the device, '
+                         'before --flatten and the cleaning (DESIGN 14.16)')
     a = ap.parse_args(argv)
     if a.geo_transform is not None and a.mask_format != 'geojson':
         ap.error('--geo-transform applies to --mask-format geojson')
@@ -701,6 +733,7 @@ def main(argv=None):
         if a.min_mask_region_area < 0:
             raise ValueError(f'--min-mask-region-area must be a non-negative integer, got {a.min_mask_region_area}')
         _check_flatten(a.flatten or False, a.flatten_min_ratio)
+        _check_buffer(a.buffer)
         if rle.polygon_topology(a.simplify_topology, a.simplify_tolerance, a.min_ring_area):
             if a.mask_format == 'rle':
                 raise ValueError('--simplify-topology shared applies to --mask-format polygons and geojson')
@@ -716,7 +749,8 @@ def main(argv=None):
                                   seam_iou_thr=a.seam_iou_thr, polygon_tolerance=a.simplify_tolerance,
                                   polygon_min_ring_area=a.min_ring_area, oriented_boxes=a.oriented_boxes,
                                   min_mask_region_area=a.min_mask_region_area, flatten=a.flatten or False,
-                                  flatten_min_ratio=a.flatten_min_ratio, polygon_topology=a.simplify_topology)
+                                  flatten_min_ratio=a.flatten_min_ratio, polygon_topology=a.simplify_topology,
+                                  buffer=a.buffer)
         geo = a.mask_format == 'geojson'
         dst = os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ('.geojson' if geo else '.json'))
         with open(dst, 'w') as f:

@@ -2364,6 +2364,226 @@ def rle_boundary(counts, n, H, W, radius, cap=None):
     return _run_morph('rle_boundary', counts, n, H, W, radius, 0, True, cap)
 
 
+# ----------------------------------------------------------------------------- Euclidean buffers (csrc/run_disc.hip)
+# The most intervals one pass of rle_dilate_disc / rle_erode_disc emits and sorts: 12 bytes each as written
+# (int64 key, int32 end), 32 while the sort holds its sorted copy, the permutation and the gathered ends -- 2 GiB at the limit.
+# Above it the rows are processed in chunks; a single row above it is refused.
+DISC_MAX_INTERVALS = 1 << 26
+
+
+def _disc_hh(what, hh, H, W):
+    """the half-heights of a structuring element as the kernels take them -> (hh cut to R_eff + 1 = min(R, W - 1) + 1 entries
+    and to H, R_eff, the frame (columns, rows) an erosion with border 0 loses: (min(R, W), min(hh[0], H)))"""
+    try:
+        hh = [int(v) for v in hh]
+        ok = len(hh) >= 1 and all(v >= 0 for v in hh) and all(a >= b for a, b in zip(hh, hh[1:]))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what}: hh must be a non-empty list of non-negative, non-increasing integers (rle.half_heights)')
+    R = len(hh) - 1
+    Re = min(R, W - 1)
+    return [min(v, H) for v in hh[:Re + 1]], Re, (min(R, W), min(hh[0], H))
+
+
+def _disc_frame(k, H, W, fc, fr, dev):
+    """the complement of the rectangle [fc, W - fc) x [fr, H - fr) of every row as intervals of rsp_rle_union: what the outside
+    of the canvas, read as background, takes from an erosion.  In the column-major stream the bottom of one column and the top
+    of the next are one interval: W - 2 fc + 1 intervals per row, one where the rectangle is empty -> (keys int64, ends int32)"""
+    i64 = dict(dtype=torch.int64, device=dev)
+    if fc == 0 and fr == 0:
+        return torch.zeros((0,), **i64), torch.zeros((0,), dtype=torch.int32, device=dev)
+    if 2 * fc >= W or 2 * fr >= H:
+        starts, stops = torch.zeros((1,), **i64), torch.full((1,), H * W, **i64)
+    else:
+        xs = torch.arange(fc, W - fc, **i64)
+        starts = torch.cat([torch.zeros((1,), **i64), xs * H + (H - fr)])
+        stops = torch.cat([xs * H + fr, torch.full((1,), H * W, **i64)])
+        if fr == 0:                                                # nothing between two columns: the side strips alone
+            starts, stops = starts[[0, -1]], stops[[0, -1]]
+    inst = torch.arange(k, **i64)[:, None] << 31
+    return (inst | starts[None, :]).reshape(-1), stops.to(torch.int32).repeat(k)
+
+
+def _disc_frame_count(H, W, fc, fr):
+    if fc == 0 and fr == 0:
+        return 0
+    if 2 * fc >= W or 2 * fr >= H:
+        return 1
+    return W - 2 * fc + 1 if fr > 0 else 2
+
+
+def _disc_dilate(what, lib, cc, cn, k, cap_c, H, W, hh, R, frame, cap, row0):
+    """canonical rows -> (counts, n, n on the host, cap) of their dilation united with the frame, or the list of row ranges to
+    process one by one when the intervals exceed DISC_MAX_INTERVALS"""
+    dev = cn.device
+    args = (cc.data_ptr(), cn.data_ptr(), k, cap_c, H, W)
+    pcnt = torch.zeros((k,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_run_morph_pieces_count(*args, 0, 0, 0, pcnt.data_ptr(), _stream()), "rsp_run_morph_pieces_count")
+    poffs, _ = _exclusive_total(pcnt)
+    per_row = pcnt.tolist()                                                                          # read 1
+    P = sum(per_row)
+    if P >= 2 ** 31:
+        raise ValueError(f'{what}: {P} column pieces in one call; at most 2^31 - 1 (split the rows)')
+    n_frame = _disc_frame_count(H, W, *frame)
+    T = _RunIntervals(P, W, dev)
+    if P:
+        _lib.check(lib.rsp_run_morph_pieces(*args, 0, 0, 0, poffs.data_ptr(), P, T.col.data_ptr(), T.y0.data_ptr(),
+                                            T.y1.data_ptr(), _stream()), "rsp_run_morph_pieces")
+    sides, n_side, n_emit = [], [0, 0], [0, 0]
+    if P and R:
+        b_offs = T.offs(k)
+        X = T.col[:P] % W
+        reach = (torch.clamp(W - 1 - X, max=R).to(torch.int64), torch.clamp(X, max=R).to(torch.int64))
+        for d, shift in enumerate((1, -1)):                  # E+ = T(X) - T(X + 1), E- = T(X) - T(X - 1): the count passes
+            head = (1, T.col.data_ptr(), T.y0.data_ptr(), T.y1.data_ptr(), P, W, b_offs.data_ptr(), T.y0.data_ptr(),
+                    T.y1.data_ptr(), P, k, W, shift, 1)
+            cnt = torch.zeros((P,), dtype=torch.int32, device=dev)
+            _lib.check(lib.rsp_run_morph_join_count(*head, 0, W, cnt.data_ptr(), _stream()), "rsp_run_morph_join_count")
+            sides.append((head, cnt))
+        # per row: the parts of E+, of E-, and the intervals they emit (the pieces themselves come on top)
+        per_piece = torch.stack([sides[0][1].to(torch.int64), sides[1][1].to(torch.int64),
+                                 sides[0][1] * reach[0], sides[1][1] * reach[1]])
+        csum = torch.cat([per_piece.new_zeros((4, 1)), torch.cumsum(per_piece, 1)], 1)
+        rows = (csum[:, poffs[1:]] - csum[:, poffs[:-1]]).tolist()                                   # read 2
+        n_side, n_emit = [sum(rows[0]), sum(rows[1])], [sum(rows[2]), sum(rows[3])]
+        per_row = [p + a + b for p, a, b in zip(per_row, rows[2], rows[3])]
+    per_row = [p + n_frame for p in per_row]
+    total = sum(per_row)
+    if max(n_side) >= 2 ** 31:
+        raise ValueError(f'{what}: {max(n_side)} exposed pieces in one call; at most 2^31 - 1 (split the rows)')
+    if total > DISC_MAX_INTERVALS:
+        worst = per_row.index(max(per_row))
+        if per_row[worst] > DISC_MAX_INTERVALS:
+            raise ValueError(f'{what}: row {row0 + worst} alone emits {per_row[worst]} intervals; at most '
+                             f'{DISC_MAX_INTERVALS} in one pass (ops.DISC_MAX_INTERVALS)')
+        chunks, a, acc = [], 0, 0
+        for i, v in enumerate(per_row):
+            if acc + v > DISC_MAX_INTERVALS:
+                chunks.append((a, i))
+                a, acc = i, 0
+            acc += v
+        return chunks + [(a, k)]
+    keys = torch.empty((max(total, 1),), dtype=torch.int64, device=dev)
+    ends = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
+    hh_t = torch.tensor(hh, dtype=torch.int32, device=dev)
+
+    def emit(t, direction, slot_offs, base):
+        _lib.check(lib.rsp_run_disc_emit(t.col.data_ptr(), t.y0.data_ptr(), t.y1.data_ptr(), t.P, k, H, W, hh_t.data_ptr(), R,
+                                         direction, slot_offs.data_ptr() if slot_offs is not None else 0, base, total,
+                                         keys.data_ptr(), ends.data_ptr(), _stream()), "rsp_run_disc_emit")
+    emit(T, 0, None, 0)
+    base = P
+    for d, (head, cnt) in enumerate(sides):
+        offs, _ = _exclusive_total(cnt)
+        E = _RunIntervals(n_side[d], W, dev)
+        _lib.check(lib.rsp_run_morph_join(*head, offs.data_ptr(), E.P, 0, W, H, 0, E.col.data_ptr(), E.y0.data_ptr(),
+                                          E.y1.data_ptr(), 0, 0, _stream()), "rsp_run_morph_join")
+        XE = E.col[:E.P] % W
+        slots, _ = _exclusive_total(torch.clamp(W - 1 - XE if d == 0 else XE, max=R))
+        emit(E, 1 if d == 0 else -1, slots, base)
+        base += n_emit[d]
+    if n_frame:
+        fk, fe = _disc_frame(k, H, W, frame[0], frame[1], dev)
+        keys[total - k * n_frame:], ends[total - k * n_frame:] = fk, fe
+    iv_offs = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
+    if total:
+        keys, order = torch.sort(keys[:total])
+        ends = ends[:total][order].contiguous()
+        iv_offs = torch.searchsorted(keys, torch.arange(k + 1, dtype=torch.int64, device=dev) << 31).contiguous()
+    return fit_runs(lambda cap: _intervals_to_runs(lib, keys, ends, total, iv_offs, k, H, W, cap), cap)
+
+
+def _run_disc(what, counts, n, H, W, hh, erode, border, cap, row0=0):
+    lib = _lib.load()
+    counts, n, k, cap_in, H, W = _rle_rows(what, counts, n, H, W)
+    if border not in (0, 1):
+        raise ValueError(f'{what}: border must be 0 or 1, got {border!r}')
+    hh_cut, R, frame = _disc_hh(what, hh, H, W)
+    dev = n.device
+    cap = max(int(cap), 2) if cap is not None else cap_in + 2
+    if k == 0:
+        return torch.zeros((0, cap), dtype=torch.int32, device=dev), n, n.cpu(), cap
+    if k * W >= 2 ** 31:
+        raise ValueError(f'{what}: {k} rows x {W} columns; column numbers are 32-bit (< 2^31; split the rows)')
+    cc, cn = _canonical_rows(lib, counts, n, k, cap_in, H, W)
+    if erode:                        # the complement of a canonical row is canonical; a row with n <= 0 is the empty mask by now
+        cc, cn = rle_complement(cc, cn)
+    out = _disc_dilate(what, lib, cc, cn, k, int(cc.shape[1]), H, W, hh_cut, R, frame if erode and not border else (0, 0), cap,
+                       row0)
+    if isinstance(out, list):                                    # too many intervals for one pass: row chunks, each on its own
+        from .rle import concat_runs
+        parts = [_run_disc(what, counts[a:b], n[a:b], H, W, hh, erode, border, cap, row0 + a) for a, b in out]
+        c = concat_runs([p[0] for p in parts])
+        return c, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), int(c.shape[1])
+    if not erode:
+        return out
+    c, m = rle_complement(out[0], out[1])
+    return c, m, m.cpu(), int(c.shape[1])
+
+
+def rle_dilate_disc(counts, n, H, W, hh, cap=None):
+    """dilation of every row of a run table (counts int32 [k, cap_in], n int32 [k]: k masks on one (H, W) canvas) by the
+    structuring element whose half-heights are `hh` (rle.half_heights: hh[dx] = the rows it reaches above and below its centre
+    at column offset dx, non-increasing; the exact disc dx^2 + dy^2 <= r2, or the diamond): a pixel is set iff
+    the element centred on it meets the mask, clipped to the canvas -- scipy.ndimage.binary_dilation(M, footprint), the
+    squared Euclidean distance to the mask <= r2.  Zero counts anywhere are legal input; a row with n <= 0 is the empty mask;
+    hh = [0] returns the canonical form of the rows; columns of hh beyond W - 1 are not read.  -> (counts int32 [k, cap'],
+    n int32 [k], n on the host, cap') under fit_runs, canonical COCO run counts; cap: the first capacity (the input's plus two
+    when None).  Intervals emitted and sorted: the column pieces + R (|E+| + |E-|), E+- the parts of the pieces with no set
+    pixel beside them: linear in R, never in the area.  More than DISC_MAX_INTERVALS: the rows go in chunks, each with the
+    reads of a call of its own after the two that found it out; a single row above it is refused (ValueError).
+    Device-to-host reads, whatever k is: 2 + one per fit_runs attempt (the pieces per row; the exposed parts and their
+    intervals per row); 1 + ... for a table without pieces or with hh = [0]; k = 0 launches nothing and reads nothing."""
+    return _run_disc('rle_dilate_disc', counts, n, H, W, hh, False, 1, cap)
+
+
+def rle_erode_disc(counts, n, H, W, hh, border=0, cap=None):
+    """erosion of every row by the same structuring element: a pixel stays iff every pixel of the element centred on it is set,
+    the outside of the canvas counting as `border` (0 or 1) -- scipy.ndimage.binary_erosion(M, footprint,
+    border_value=border).  It is the complement (rle_complement) of the dilation of the complement; with border 0 the outside
+    takes exactly the frame of len(hh) - 1 columns and hh[0] rows, which joins the dilation as W - 2 R + 1 intervals per row
+    before the sort (no dense mask; the empty mask where the canvas is no larger than two frames).  Input, result and chunking
+    as rle_dilate_disc's.  Device-to-host reads: rle_dilate_disc's and one more (n of the complemented result)."""
+    return _run_disc('rle_erode_disc', counts, n, H, W, hh, True, border, cap)
+
+
+def rle_minus(counts_a, n_a, counts_b, n_b, H, W, cap=None):
+    """row i of table A minus row i of table B, both on one (H, W) canvas (the band M - erode(M) of DESIGN §14.16): the column
+    pieces of both (rsp_run_morph_pieces), rsp_run_morph_join's op 1 emitting keys, rsp_rle_union.  Zero counts anywhere are
+    legal; a row with n <= 0 is the empty mask.  -> (counts, n, n on the host, cap) under fit_runs.  Device-to-host reads: 2 +
+    one per fit_runs attempt (the pieces of both tables, the total of the difference); k = 0 reads nothing."""
+    lib = _lib.load()
+    counts_a, n_a, k, cap_a, H, W = _rle_rows('rle_minus', counts_a, n_a, H, W)
+    counts_b, n_b, kb, cap_b, _, _ = _rle_rows('rle_minus', counts_b, n_b, H, W)
+    if kb != k or n_b.device != n_a.device:
+        raise ValueError(f'rle_minus: {k} rows minus {kb} rows; the tables pair row by row on one device')
+    dev = n_a.device
+    cap = max(int(cap), 2) if cap is not None else cap_a + 2
+    if k == 0:
+        return torch.zeros((0, cap), dtype=torch.int32, device=dev), n_a, n_a.cpu(), cap
+    if k * W >= 2 ** 31:
+        raise ValueError(f'rle_minus: {k} rows x {W} columns; column numbers are 32-bit (< 2^31; split the rows)')
+    sides = [(_canonical_rows(lib, c, m, k, cp, H, W), cp + 1) for c, m, cp in ((counts_a, n_a, cap_a), (counts_b, n_b, cap_b))]
+    cnts = torch.zeros((2, k), dtype=torch.int32, device=dev)
+    for i, ((c, m), cp) in enumerate(sides):
+        _lib.check(lib.rsp_run_morph_pieces_count(c.data_ptr(), m.data_ptr(), k, cp, H, W, 0, 0, 0, cnts[i].data_ptr(),
+                                                  _stream()), "rsp_run_morph_pieces_count")
+    offs, totals = _exclusive_total(cnts)
+    totals = totals.tolist()                                                                         # read 1
+    if max(totals) >= 2 ** 31:
+        raise ValueError(f'rle_minus: {max(totals)} column pieces in one call; at most 2^31 - 1 (split the rows)')
+    tables = []
+    for i, ((c, m), cp) in enumerate(sides):
+        t = _RunIntervals(totals[i], W, dev)
+        _lib.check(lib.rsp_run_morph_pieces(c.data_ptr(), m.data_ptr(), k, cp, H, W, 0, 0, 0, offs[i].data_ptr(), t.P,
+                                            t.col.data_ptr(), t.y0.data_ptr(), t.y1.data_ptr(), _stream()), "rsp_run_morph_pieces")
+        tables.append(t)
+    E = _run_morph_join(lib, 1, tables[0], tables[1], k, 0, 1, 0, W, H, True)                        # read 2
+    iv_offs = torch.searchsorted(E.keys[:E.P], torch.arange(k + 1, dtype=torch.int64, device=dev) << 31).contiguous()
+    return fit_runs(lambda cap: _intervals_to_runs(lib, E.keys, E.ends, E.P, iv_offs, k, H, W, cap), cap)
+
+
 # ----------------------------------------------------------------------------- planar layers (csrc/run_flatten.hip)
 def _flatten_rank(what, rank, k, dev):
     if not isinstance(rank, torch.Tensor) or rank.dtype != torch.int32 or rank.dim() != 1 or rank.shape[0] != k \

@@ -362,15 +362,88 @@ def clean_runs(counts, n, size, min_area, mode='both', cap=None):
     return counts, n, n.cpu(), int(counts.shape[1]), changed
 
 
-def erode_runs(counts, n, size, radius, border=0, cap=None):
+MORPHOLOGY_ELEMENTS = ('square', 'disc', 'diamond')
+
+
+def _exact_fraction(x, what):
+    """a real number as the exact fractions.Fraction of what the caller wrote: an int, a Fraction, a Decimal, a string, or a
+    float through its shortest repr (1.1 is 11/10, not the binary fraction next to it)"""
+    import decimal
+    import fractions
+    if isinstance(x, bool) or x is None:
+        raise ValueError(f'{what} must be a real number, got {x!r}')
+    try:
+        if isinstance(x, (int, fractions.Fraction, decimal.Decimal)):
+            f = fractions.Fraction(x)
+        elif isinstance(x, str):
+            f = fractions.Fraction(x.strip())
+        else:
+            x = float(x)
+            if not math.isfinite(x):
+                raise ValueError
+            f = fractions.Fraction(repr(x))
+    except (ValueError, TypeError, ZeroDivisionError, OverflowError):
+        raise ValueError(f'{what} must be a finite real number, got {x!r}') from None
+    return f
+
+
+def disc_r2(radius):
+    """a real radius d >= 0 in pixels -> the squared radius floor(d^2) of the exact disc, in exact arithmetic (1.5 -> 2, 2.9 -> 8)"""
+    f = _exact_fraction(radius, 'radius')
+    if f < 0:
+        raise ValueError(f'radius must be non-negative, got {radius!r}')
+    return math.floor(f * f)
+
+
+def half_heights(element, radius=None, r2=None, size=None):
+    """the structuring element of the Euclidean buffers -> (hh, R): hh a list of R + 1 ints, hh[dx] = the rows
+    the element reaches above and below its centre at column offset dx, non-increasing, hh[0] = R.  element='disc': the exact
+    disc dx^2 + dy^2 <= r2, hh[dx] = isqrt(r2 - dx^2), R = isqrt(r2); give an integer r2 >= 0, or a real radius >= 0 for r2 =
+    floor(radius^2) (disc_r2).  element='diamond': |dx| + |dy| <= radius, an integer, hh[dx] = radius - dx.  size = (H, W):
+    r2 is cut at H^2 + W^2 (the diamond's radius at H + W), beyond which nothing changes on that canvas."""
+    if element == 'disc':
+        if (radius is None) == (r2 is None):
+            raise ValueError("half_heights: 'disc' takes a radius or r2, one of them")
+        if r2 is None:
+            r2 = disc_r2(radius)
+        elif isinstance(r2, bool) or not isinstance(r2, (int, np.integer)) or int(r2) < 0:
+            raise ValueError(f'half_heights: r2 must be a non-negative integer, got {r2!r}')
+        r2 = int(r2)
+        if size is not None:
+            r2 = min(r2, int(size[0]) ** 2 + int(size[1]) ** 2)
+        R = math.isqrt(r2)
+        return [math.isqrt(r2 - dx * dx) for dx in range(R + 1)], R
+    if element == 'diamond':
+        if r2 is not None or radius is None or isinstance(radius, bool) or int(radius) != radius or int(radius) < 0:
+            raise ValueError(f"half_heights: 'diamond' takes a non-negative integer radius, got {radius!r}")
+        R = int(radius) if size is None else min(int(radius), int(size[0]) + int(size[1]))
+        return [R - dx for dx in range(R + 1)], R
+    raise ValueError(f"half_heights: element must be 'disc' or 'diamond', got {element!r}")
+
+
+def _element(element, radius, size):
+    """element, radius of the *_runs below -> None for the square (the code of DESIGN §14.13), else the half-heights"""
+    if element not in MORPHOLOGY_ELEMENTS:
+        raise ValueError(f'element must be one of {MORPHOLOGY_ELEMENTS}, got {element!r}')
+    return None if element == 'square' else half_heights(element, radius, size=size)[0]
+
+
+def erode_runs(counts, n, size, radius, border=0, cap=None, element='square'):
     """run table of k masks on one size = (H, W) canvas -> (counts, n, n on the host, cap): every mask eroded by the
-    (2 radius + 1)^2 square, the outside of the canvas counting as `border` (ops.rle_erode)"""
+    (2 radius + 1)^2 square, the outside of the canvas counting as `border` (ops.rle_erode); element='disc'
+    (radius a real number: the exact disc of floor(radius^2)) or 'diamond': ops.rle_erode_disc, DESIGN §14.16"""
+    hh = _element(element, radius, size)
+    if hh is not None:
+        return ops.rle_erode_disc(counts, n, size[0], size[1], hh, border, cap)
     return ops.rle_erode(counts, n, size[0], size[1], radius, border, cap)
 
 
-def dilate_runs(counts, n, size, radius, cap=None):
+def dilate_runs(counts, n, size, radius, cap=None, element='square'):
     """every mask dilated by the square: the complement of the erosion of the complement with the outside set.  A row with
-    n <= 0 stays the empty mask."""
+    n <= 0 stays the empty mask.  element='disc' | 'diamond': ops.rle_dilate_disc."""
+    hh = _element(element, radius, size)
+    if hh is not None:
+        return ops.rle_dilate_disc(counts, n, size[0], size[1], hh, cap)
     live = n > 0
     c, m, _, cap = ops.rle_erode(*ops.rle_complement(counts, n), size[0], size[1], radius, 1, cap)
     c, m = ops.rle_complement(c, m)
@@ -380,21 +453,35 @@ def dilate_runs(counts, n, size, radius, cap=None):
     return c, m, m.cpu(), int(c.shape[1])
 
 
-def open_runs(counts, n, size, radius, cap=None):
-    """opening: dilation of the erosion (border 0); removes what the square does not fit into"""
-    c, m, _, cap = erode_runs(counts, n, size, radius, 0, cap)
-    return dilate_runs(c, m, size, radius, cap)
+def open_runs(counts, n, size, radius, cap=None, element='square'):
+    """opening: dilation of the erosion (border 0); removes what the element does not fit into"""
+    c, m, _, cap = erode_runs(counts, n, size, radius, 0, cap, element)
+    return dilate_runs(c, m, size, radius, cap, element)
 
 
-def close_runs(counts, n, size, radius, cap=None):
-    """closing: erosion (border 1) of the dilation; fills what the square does not fit into"""
-    c, m, _, cap = dilate_runs(counts, n, size, radius, cap)
-    return erode_runs(c, m, size, radius, 1, cap)
+def close_runs(counts, n, size, radius, cap=None, element='square'):
+    """closing: erosion (border 1) of the dilation; fills what the element does not fit into"""
+    c, m, _, cap = dilate_runs(counts, n, size, radius, cap, element)
+    return erode_runs(c, m, size, radius, 1, cap, element)
 
 
-def boundary_runs(counts, n, size, radius, cap=None):
-    """the boundary band of every mask, M & ~erode(M, radius) (ops.rle_boundary): Boundary IoU's G_d & G"""
+def boundary_runs(counts, n, size, radius, cap=None, element='square'):
+    """the boundary band of every mask, M & ~erode(M, radius) (ops.rle_boundary): Boundary IoU's G_d & G; with
+    element='disc' | 'diamond' the mask minus its erosion by that element (ops.rle_erode_disc, ops.rle_minus)"""
+    if _element(element, radius, size) is not None:
+        c, m, _, cap = erode_runs(counts, n, size, radius, 0, cap, element)
+        return ops.rle_minus(counts, n, c, m, size[0], size[1], cap)
     return ops.rle_boundary(counts, n, size[0], size[1], radius, cap)
+
+
+def buffer_runs(counts, n, size, distance, cap=None):
+    """the GIS buffer of every mask by a signed real distance in pixels: > 0 the dilation by the exact disc
+    of floor(distance^2), < 0 the erosion by the disc of |distance| with the outside of the canvas set (the edge of a scene is
+    not an object boundary), 0 the canonical rows -> (counts, n, n on the host, cap)"""
+    d = _exact_fraction(distance, 'distance')
+    if d < 0:
+        return erode_runs(counts, n, size, -d, 1, cap, 'disc')
+    return dilate_runs(counts, n, size, d, cap, 'disc')
 
 
 def boundary_radius(size, dilation_ratio=0.02):
