@@ -563,6 +563,24 @@ int rsp_query_mask_post(const float* low_res, const int32_t* qidx, const float* 
                         int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h, int32_t crop_w, int32_t out_h,
                         int32_t out_w, void* stats_ws, uint8_t* out_mask, float* out_logits, float* det_score,
                         float* bboxes, rsp_stream_t stream);
+/* maskformer_fusion_head.py:41-106 (panoptic_postprocess) behind models.py:698-701 / maskformer_fusion_head.py:253-256   */
+/* (csrc/panoptic_fuse.hip), one image: cls [Nq, nc + 1] class logits, low_res [Nq, h, w]; the geometry is      */
+/* rsp_query_mask_post's.  score, label = softmax(cls).max(-1) (lowest class on a tie); kept = label != nc && score >      */
+/* object_mask_thr, in query order; per output pixel the kept query with the largest score * sigmoid(field) wins (lowest    */
+/* kept index on a tie); mask_area = pixels won, original_area = pixels with sigmoid(field) >= 0.5; a kept query paints its  */
+/* pixels (with filter_low_score: those whose sigmoid >= 0.5) unless an area is 0 or (double)mask_area / original_area <     */
+/* iou_thr; a stuff class (label >= num_things) paints label, a thing label + 1000 * instance id, ids from 1 in kept order   */
+/* over the things that paint; every other pixel is nc.  Writes sem_seg int32 [out_h, out_w] and, per query [Nq]: segment    */
+/* (the id painted, -1: none), mask_area, original_area (0 for a query not kept), score fp32.  Nothing is read by the host:  */
+/* the kept count stays on the device, so the limit is on Nq.  RSP_EINVAL: Nq > RSP_PANOPTIC_MAX_QUERIES (the bins of the    */
+/* kernel's LDS histograms), an invalid geometry, num_things > nc.  workspace: rsp_panoptic_workspace_bytes() bytes, 16-byte */
+/* aligned.  Integer atomics only: bit-reproducible.                                                                        */
+#define RSP_PANOPTIC_MAX_QUERIES 1024
+int64_t rsp_panoptic_workspace_bytes(void);
+int rsp_panoptic_fuse(const float* cls, const float* low_res, int32_t Nq, int32_t nc, int32_t num_things, int32_t h,
+                      int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w,
+                      float object_mask_thr, double iou_thr, int32_t filter_low_score, void* workspace, int32_t* sem_seg,
+                      int32_t* segment, int32_t* mask_area, int32_t* original_area, float* score, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Data movement                                                              */

@@ -23,7 +23,7 @@ import torch
 
 from . import ops, rle
 from .config import Config
-from .structures import DetDataSample
+from .structures import DetDataSample, PixelData
 
 _SKIPPED = ('LoadAnnotations', 'mmdet.LoadAnnotations')
 
@@ -183,11 +183,19 @@ class DetInferencer:
         return list(inputs) if isinstance(inputs, (list, tuple)) else [inputs]
 
     def pred2dict(self, sample, with_rle=True):
+        """labels / scores / bboxes as lists (+ masks as COCO RLE) when the sample has `pred_instances` -- a detector with the
+        reference's default test_cfg (panoptic_on, no instance_on) has none --, and `panoptic_seg` when it has
+        `pred_panoptic_seg`: unlike the lists, that entry is the PixelData itself with its device tensors, untouched (mmdet
+        writes a PNG there, which is not built; `panoptic_to_coco` turns it into the image and segments_info)."""
         from .rle import encode_mask_results
-        p = sample.pred_instances
-        out = dict(labels=p.labels.tolist(), scores=p.scores.tolist(), bboxes=p.bboxes.tolist())
-        if with_rle and hasattr(p, 'masks') and p.masks is not None:
-            out['masks'] = encode_mask_results(p.masks) if len(p.labels) else []
+        out = {}
+        p = sample.get('pred_instances')
+        if p is not None:
+            out.update(labels=p.labels.tolist(), scores=p.scores.tolist(), bboxes=p.bboxes.tolist())
+            if with_rle and hasattr(p, 'masks') and p.masks is not None:
+                out['masks'] = encode_mask_results(p.masks) if len(p.labels) else []
+        if sample.get('pred_panoptic_seg') is not None:
+            out['panoptic_seg'] = sample.pred_panoptic_seg
         return out
 
     @torch.no_grad()
@@ -673,3 +681,34 @@ def mask_components(masks, device='cuda:0'):
     buf = torch.cat([comps.comp_offs, comps.comp_area.to(torch.int64), comps.comp_box.reshape(-1).to(torch.int64)]).cpu().numpy()
     o, area, box = buf[:k + 1].tolist(), buf[k + 1:k + 1 + C].astype(np.int32), buf[k + 1 + C:].astype(np.int32).reshape(-1, 4)
     return [dict(count=o[i + 1] - o[i], areas=area[o[i]:o[i + 1]], bboxes=box[o[i]:o[i + 1]]) for i in range(k)]
+
+
+def panoptic_to_coco(pan, num_things_classes, void=None):
+    """A panoptic map -- PixelData with sem_seg [1, H, W] (a detector's `pred_panoptic_seg`), or an int tensor [H, W] /
+    [1, H, W] -- in COCO's panoptic form: (uint8 [H, W, 3] on the host, segments_info).  The colour of id is panopticapi's
+    id2rgb (id % 256, id // 256 % 256, id // 65536), VOID pixels are (0, 0, 0); segments_info is a list of dict(id,
+    category_id = id % 1000, isthing, area) in ascending id without the void id.  `void`: the id of unpainted pixels
+    (num_classes); by default the `void` field the fusion head sets on its PixelData.  A plain tensor, or a PixelData without
+    that field, needs the argument: a ValueError otherwise (the void id would come out as a segment).  Areas come from one device unique /
+    count (plumbing)."""
+    sem = pan.sem_seg if hasattr(pan, 'sem_seg') else pan
+    sem = torch.as_tensor(sem)
+    if sem.dim() == 3:
+        sem = sem[0]
+    if sem.dim() != 2 or sem.dtype not in (torch.int32, torch.int64):
+        raise ValueError('panoptic_to_coco expects an int32 / int64 map [H, W] or [1, H, W]')
+    if void is None and isinstance(pan, PixelData):
+        void = pan.get('void')
+    if void is None:
+        raise ValueError('panoptic_to_coco needs the void id (num_classes): pass void=, or a PixelData that carries it')
+    ids, counts = torch.unique(sem, return_counts=True)
+    sem64 = sem.to(torch.int64)
+    rgb = torch.stack((sem64 % 256, sem64 // 256 % 256, sem64 // 65536), -1).to(torch.uint8)
+    rgb[sem64 == void] = 0                              # VOID is colour (0, 0, 0) in COCO's PNGs
+    segments = []
+    for i, a in zip(ids.tolist(), counts.tolist()):
+        if i == void:
+            continue
+        cat = i % 1000
+        segments.append(dict(id=i, category_id=cat, isthing=bool(cat < num_things_classes), area=a))
+    return rgb.cpu().numpy(), segments

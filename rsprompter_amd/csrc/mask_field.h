@@ -165,3 +165,63 @@ __device__ __forceinline__ void mask_each_strip(const float* __restrict__ low, c
     if (ONCE) break;
   }
 }
+
+// ---- every pixel x every listed mask (panoptic_fuse.hip): the traversal of the fields of `n` masks of one [*, h, w] logit
+// tensor, mask j = plane list[j], by the blocks blockIdx.x of a grid.  A work item is a GROUP of R x C pixels, and a thread
+// sees all n fields of its group before it moves on:
+//   MASK_STRIP               R = ROWS rows of one column quad (C = 4) through MaskStrip -- the x coefficients once per group,
+//                            the source-row pair once per mask and change of pair;
+//   MASK_GENERIC, QUAD       one row of a quad (R = 1, C = 4) through mask_pixel<false>, (ow & 3) == 0;
+//   MASK_IDENT / MASK_GENERIC, !QUAD   one pixel through mask_pixel<IDENT>.
+// Per group: f(j, v[R * C], live) for j = 0 .. n - 1 in list order (v[r * C + e] = the field of mask j at row oy0 + r, column
+// ox + e), then done(oy0, ox, live).  Bit r of `live` says that row r of the group exists.  EVERY lane of a block takes every
+// step: a lane past the last group evaluates the last group with live == 0, and a row past the last row evaluates the last row
+// with its bit clear, so that f may hold wave ballots and done a block barrier.  The values are those of mask_stage1 /
+// mask_pixel, as in the traversals of one mask above.
+template <MaskForm FORM, bool QUAD, int ROWS>
+struct MaskGroup {
+  static constexpr int R = FORM == MASK_STRIP ? ROWS : 1;
+  static constexpr int C = (FORM == MASK_STRIP || QUAD) ? 4 : 1;
+  static_assert(FORM != MASK_IDENT || !QUAD, "an identity geometry of whole quads is a MASK_STRIP one");
+  static __host__ __device__ inline int64_t items(int oh, int ow) { return (int64_t)((oh + R - 1) / R) * (C == 4 ? ow >> 2 : ow); }
+};
+
+template <MaskForm FORM, bool QUAD, int ROWS, typename F, typename D>
+__device__ __forceinline__ void mask_each_group_of_list(const float* __restrict__ low_all, const int32_t* __restrict__ list,
+                                                        int n, const MaskGeom& g, F&& f, D&& done) {
+  typedef MaskGroup<FORM, QUAD, ROWS> G;
+  constexpr int R = G::R, C = G::C;
+  const MaskScales sc = mask_scales(g);
+  const int per_row = C == 4 ? g.ow >> 2 : g.ow;
+  const int64_t nitem = G::items(g.oh, g.ow);
+  const int64_t plane = (int64_t)g.h * g.w;
+  for (int64_t base = (int64_t)blockIdx.x * MASK_BLOCK; base < nitem; base += (int64_t)gridDim.x * MASK_BLOCK) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t ii = i < nitem ? i : nitem - 1;
+    const int ty = (int)(ii / per_row), ox = (int)(ii - (int64_t)ty * per_row) * C;
+    const int oy0 = ty * R;
+    unsigned live = 0;
+    int oy[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      live |= (i < nitem && oy0 + r < g.oh ? 1u : 0u) << r;
+      oy[r] = min(oy0 + r, g.oh - 1);
+    }
+    MaskStrip st;
+    if (FORM == MASK_STRIP) st.init(g, sc, ox);
+    for (int j = 0; j < n; ++j) {
+      const float* low = low_all + (int64_t)list[j] * plane;
+      float v[R * C];
+      if (FORM == MASK_STRIP) {
+        st.r0 = -1; st.r1 = -1;          // the cached rows are another mask's
+#pragma unroll
+        for (int r = 0; r < R; ++r) st.row(low, g, sc, oy[r], v + r * C);
+      } else {
+#pragma unroll
+        for (int e = 0; e < C; ++e) v[e] = mask_pixel<FORM == MASK_IDENT>(low, g, sc, oy[0], ox + e);
+      }
+      f(j, v, live);
+    }
+    done(oy0, ox, live);
+  }
+}

@@ -3073,3 +3073,34 @@ def query_mask_post(low_res, qidx, cls_score, batch_input_shape, crop_hw, out_hw
                                                       masks.data_ptr(), _ptr(logits), det.data_ptr(), boxes.data_ptr(),
                                                       _stream()), "rsp_query_mask_post"))
     return (masks, det, boxes, logits) if want_logits else (masks, det, boxes)
+
+
+PANOPTIC_MAX_QUERIES = _lib.CONST['RSP_PANOPTIC_MAX_QUERIES']
+
+
+def panoptic_fuse(cls, low_res, batch_input_shape, crop_hw, out_hw, num_things_classes, num_classes, object_mask_thr=0.8,
+                  iou_thr=0.8, filter_low_score=False):
+    """MaskFormerFusionHead.panoptic_postprocess (maskformer_fusion_head.py:41-106) of one image on the mask field of
+    query_mask_post: cls [Nq, nc + 1] class logits, low_res [Nq, h, w] logits -> (sem_seg int32 [oh, ow], info) with info =
+    dict(segment, mask_area, original_area: int32 [Nq]; score: fp32 [Nq]) -- the id every query painted (-1: none) and its two
+    areas (0 for a query that was not kept).  Nothing is read back: four launches on the current stream."""
+    lib = _lib.load()
+    Nq, h, w = _mask_logits(low_res, "panoptic_fuse")
+    _chk_f32(cls, "cls")
+    dev = low_res.device
+    if cls.dim() != 2 or not cls.is_contiguous() or cls.device != dev or cls.shape[0] != Nq or cls.shape[1] != num_classes + 1:
+        raise ValueError("panoptic_fuse expects contiguous fp32 cls [Nq, num_classes + 1] on the device of low_res")
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    sem = torch.empty((max(oh, 0), max(ow, 0)), dtype=torch.int32, device=dev)
+    info = {k: torch.empty((Nq,), dtype=torch.int32, device=dev) for k in ('segment', 'mask_area', 'original_area')}
+    info['score'] = torch.empty((Nq,), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.rsp_panoptic_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    _timed('panoptic_fuse_kernel', 0, 4.0 * low_res.numel() + 4.0 * sem.numel(),
+           lambda: _lib.check(lib.rsp_panoptic_fuse(cls.data_ptr(), low_res.data_ptr(), Nq, int(num_classes),
+                                                    int(num_things_classes), h, w,
+                                                    *_mask_geometry(batch_input_shape, crop_hw, out_hw),
+                                                    float(object_mask_thr), float(iou_thr), int(bool(filter_low_score)),
+                                                    ws.data_ptr(), sem.data_ptr(), info['segment'].data_ptr(),
+                                                    info['mask_area'].data_ptr(), info['original_area'].data_ptr(),
+                                                    info['score'].data_ptr(), _stream()), "rsp_panoptic_fuse"))
+    return sem, info

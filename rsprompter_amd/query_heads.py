@@ -24,7 +24,7 @@ from .detectors import BaseDetectorHIP
 from .necks import conv3x3_weight
 from .nnutil import HIPModule, add_param, nchw_view, nhwc_view
 from .registry import MODELS
-from .structures import InstanceData
+from .structures import InstanceData, PixelData
 
 
 def _g(root, dotted):
@@ -541,18 +541,23 @@ class RSMaskFormerFusionHead(HIPModule):
         self.test_cfg = test_cfg or {}
 
     def predict(self, mask_cls_results, mask_pred_results, batch_data_samples, rescale=False, **kwargs):
-        """models.py:662-715 + instance_postprocess (maskformer_fusion_head.py:126-182)."""
+        """models.py:662-715 + instance_postprocess (maskformer_fusion_head.py:126-182) + panoptic_postprocess (:41-106).
+        `panoptic_on` (the reference's default) adds result['pan_results']: PixelData(sem_seg int32 [1, oh, ow]) with
+        query_segment / mask_area / original_area int32 [Nq] for callers, as query_indices is on the instance results."""
         metas = _metas_of(batch_data_samples)
         cfg = self.test_cfg
-        if cfg.get('panoptic_on', True) or cfg.get('semantic_on', False):
-            raise NotImplementedError('only instance_on (the RSPrompter test_cfg) is implemented')
+        if cfg.get('semantic_on', False):
+            raise NotImplementedError('semantic_on is not implemented (the reference asserts against it: models.py:675)')
         if not isinstance(mask_pred_results, LazyUpsampledMasks):
             raise TypeError('expected the LazyUpsampledMasks returned by RSMask2FormerHead.predict')
+        panoptic_on = cfg.get('panoptic_on', True)
+        instance_on = cfg.get('instance_on', False) or not panoptic_on
         low = mask_pred_results.low_res
         B, Nq = mask_cls_results.shape[:2]                  # maskformer_fusion_head.py:143 `num_queries = mask_cls.shape[0]`
         nc = self.num_classes
-        k = min(cfg.get('max_per_image', 100), Nq * nc)
-        scores, flat = ops.query_topk(mask_cls_results.contiguous(), k)
+        if instance_on:
+            k = min(cfg.get('max_per_image', 100), Nq * nc)
+            scores, flat = ops.query_topk(mask_cls_results.contiguous(), k)
         results = []
         for b, meta in enumerate(metas):
             oh, ow = meta['ori_shape'][:2]
@@ -560,12 +565,22 @@ class RSMaskFormerFusionHead(HIPModule):
             Hb, Wb = mask_pred_results.size
             crop = (min(int(oh * sf[1]), Hb), min(int(ow * sf[0]), Wb))
             out_hw = (oh, ow) if rescale else crop
-            labels = torch.remainder(flat[b], nc)            # index arithmetic on 100 ints (plumbing)
-            qidx = torch.div(flat[b], nc, rounding_mode='floor').to(torch.int32).contiguous()
-            masks, det, boxes = ops.query_mask_post(low[b].contiguous(), qidx, scores[b].contiguous(), (Hb, Wb), crop, out_hw)
-            r = InstanceData(bboxes=boxes, labels=labels.to(torch.long), scores=det, masks=masks)
-            r.query_indices = qidx
-            results.append(dict(ins_results=r))
+            result = {}
+            if panoptic_on:
+                sem, info = ops.panoptic_fuse(mask_cls_results[b].contiguous(), low[b].contiguous(), (Hb, Wb), crop, out_hw,
+                                              self.num_things_classes, nc, cfg.get('object_mask_thr', 0.8),
+                                              cfg.get('iou_thr', 0.8), cfg.get('filter_low_score', False))
+                pan = PixelData(sem_seg=sem[None], void=nc)
+                pan.query_segment, pan.mask_area, pan.original_area = info['segment'], info['mask_area'], info['original_area']
+                result['pan_results'] = pan
+            if instance_on:
+                labels = torch.remainder(flat[b], nc)            # index arithmetic on 100 ints (plumbing)
+                qidx = torch.div(flat[b], nc, rounding_mode='floor').to(torch.int32).contiguous()
+                masks, det, boxes = ops.query_mask_post(low[b].contiguous(), qidx, scores[b].contiguous(), (Hb, Wb), crop, out_hw)
+                r = InstanceData(bboxes=boxes, labels=labels.to(torch.long), scores=det, masks=masks)
+                r.query_indices = qidx
+                result['ins_results'] = r
+            results.append(result)
         return results
 
 
@@ -622,6 +637,8 @@ class RSPrompterQuery(BaseDetectorHIP):
         self._last_head_out = debug.keep((cls, masks))     # parity tests only (rsprompter_amd/debug.py)
         results = self.panoptic_fusion_head.predict(cls, masks, batch_data_samples, rescale=rescale)
         for s, r in zip(batch_data_samples, results):       # maskformer.py:112-152
+            if 'pan_results' in r:                          # maskformer.py:141-146
+                s.pred_panoptic_seg = r['pan_results']
             if 'ins_results' in r:
                 s.pred_instances = r['ins_results']
         return batch_data_samples
@@ -681,6 +698,8 @@ class SAMSegMask2Former(BaseDetectorHIP):
         self._last_head_out = debug.keep((cls, masks))
         results = self.panoptic_fusion_head.predict(cls, masks, batch_data_samples, rescale=rescale)
         for s, r in zip(batch_data_samples, results):
+            if 'pan_results' in r:                          # maskformer.py:141-146
+                s.pred_panoptic_seg = r['pan_results']
             if 'ins_results' in r:
                 s.pred_instances = r['ins_results']
         return batch_data_samples
