@@ -80,6 +80,7 @@ def assert_exact(got, ref, what):
 
 class Report:
     """value outputs of the tolerance tier: err <= max(F, 2 E32) per case; all cases are printed, then asserted"""
+    prefix = 'sampler'
 
     def __init__(self, family, report=print):
         self.family, self.rows, self.bad, self.report = family, [], [], report
@@ -90,7 +91,7 @@ class Report:
         floor = 4 * _ulp32(float(ref.abs().max()))
         bound = max(floor, 2.0 * e32)
         ok = err <= bound                                       # NaN fails
-        self.report(f'sampler {self.family} {case}: err {err:.3e} E32 {e32:.3e} F {floor:.3e} bound {bound:.3e}{"" if ok else "  <-- FAIL"}')
+        self.report(f'{self.prefix} {self.family} {case}: err {err:.3e} E32 {e32:.3e} F {floor:.3e} bound {bound:.3e}{"" if ok else "  <-- FAIL"}')
         self.rows.append((case, err, e32, bound))
         if not ok:
             self.bad.append((case, err, e32, bound))

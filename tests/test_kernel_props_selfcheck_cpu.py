@@ -258,3 +258,113 @@ def test_roi_align_tolerance_check_rejects_a_dropped_level_epsilon():
     sp.check_roi_align_tolerance(sp.FakeOps(), 'cpu', report=lambda line: None)
     with pytest.raises(AssertionError):
         sp.check_roi_align_tolerance(sp.FakeOps('level_epsilon_dropped'), 'cpu', report=lambda line: None)
+
+
+# ------------------------------------------------------------------------------------------------ the detection selection checks
+import _det_props as dp  # noqa: E402
+
+# family -> (mutations, the exact- and sequence-tier bodies that must show them, their cases).  The 4300-row walk and the
+# 16384 / 16385-row capacities repeat what smaller cases show: they are left to the device
+_DET_NMS = tuple(c for c in dp.nms_cases() if c.emu)
+_DET = {
+    'nms': (dp.NMS_MUTATIONS, ((dp.check_nms, _DET_NMS), (dp.check_nms_flat, _DET_NMS))),
+    'decode': (dp.DECODE_MUTATIONS, ((dp.check_decode, dp.decode_cases()),)),
+    'bbox_post': (dp.POST_MUTATIONS, ((dp.check_post, dp.post_cases()),)),
+    'rpn_topk': (dp.TOPK_MUTATIONS, ((dp.check_exact_rpn_topk, dp.RPN_TOPK),)),
+    'query_topk': (dp.QUERY_MUTATIONS, ((dp.check_exact_query_topk, dp.QUERY_EXACT), (dp.check_seq_query_topk, dp.QUERY_SEQ))),
+}
+
+
+def test_det_fake_reproduces_the_restatements():
+    """the unmutated stand-in (the fp32 sequence) passes every exact and sequence body of the five entry points -- so an
+    AssertionError under a mutation below comes from the comparison with `ops`, not from a precondition of the case, which
+    never looks at `ops` -- and the tolerance bodies"""
+    fake = dp.FakeOps()
+    for muts, bodies in _DET.values():
+        for body, cases in bodies:
+            for c in cases:
+                body(fake, 'cpu', c)
+    quiet = lambda line: None
+    for body in (dp.check_decode_tolerance, dp.check_post_tolerance, dp.check_rpn_topk_tolerance, dp.check_query_topk_tolerance):
+        body(fake, 'cpu', quiet)
+
+
+def _det_check_rejects(family, mutation):
+    """-> the names of the cases whose body raises AssertionError under the mutation"""
+    fake = dp.FakeOps(mutation)
+    rejected = []
+    for body, cases in _DET[family][1]:
+        for c in cases:
+            try:
+                body(fake, 'cpu', c)
+            except AssertionError:
+                rejected.append((body.__name__, getattr(c, 'name', c)))
+    assert rejected, (family, mutation)
+    return rejected
+
+
+@pytest.mark.parametrize('mutation', dp.NMS_MUTATIONS)
+def test_nms_check_rejects(mutation):
+    """check_nms / check_nms_flat: `>=` at the IoU threshold, inter > thr * union, the IoU in fp64, a contracted id * unit + box,
+    the unit without its + 1, the max taken over the capacity rows, the count ignored, ties by descending index, a suppressed box
+    that suppresses, max_out counting visited rows, 0 / 0 read as suppressed -- and every case that names the mutation rejects it"""
+    rejected = {name for body, name in _det_check_rejects('nms', mutation) if body == 'check_nms'}
+    named = {c.name for c in _DET_NMS if mutation in c.kills}
+    assert named and named <= rejected, (mutation, sorted(named - rejected))
+    if mutation in ('iou_fp64', 'iou_cross_multiplied', 'offset_contracted'):   # value-preserving on dyadic inputs: the sequence tier's
+        assert all(dp.nms_case(n).tier == 'seq' for n in rejected), (mutation, rejected)
+
+
+@pytest.mark.parametrize('mutation', dp.DECODE_MUTATIONS)
+def test_rpn_decode_check_rejects(mutation):
+    """check_decode: contracted d * std + mean and pw * dx + px, the size clamped from both sides under add_ctr_clamp, the centre
+    clamp skipped, a clip to size - 1, `>=` at min_bbox_size, min_bbox_size = 0 read as off"""
+    rejected = {name for _, name in _det_check_rejects('decode', mutation)}
+    named = {c.name for c in dp.decode_cases() if mutation in c.kills}
+    assert named and named <= rejected, (mutation, sorted(named - rejected))
+    if mutation in ('delta_contracted', 'centre_contracted'):
+        assert all(dp.decode_case(n).tier == 'seq' for n in rejected), (mutation, rejected)
+
+
+@pytest.mark.parametrize('mutation', dp.POST_MUTATIONS + ('iou_ge', 'ties_by_index_descending'))
+def test_bbox_post_check_rejects(mutation):
+    """check_post: `>=` at score_thr, the background column as a candidate, a softmax without its max, a division by the scale
+    factor, a reciprocal that is not rounded to nearest; and two mistakes of the NMS behind it -- every case that names the mutation
+    rejects it"""
+    rejected = {name for _, name in _det_check_rejects('bbox_post', mutation)}
+    named = {c.name for c in dp.post_cases() if mutation in c.kills}
+    assert named and named <= rejected, (mutation, sorted(named - rejected))
+
+
+@pytest.mark.parametrize('mutation', dp.TOPK_MUTATIONS)
+def test_rpn_topk_check_rejects(mutation):
+    """check_exact_rpn_topk: a -0.0 logit ranked below +0.0, ties by descending index, the ties with the k-th score taken from
+    the end, a sorted level although n <= nms_pre -- every case that names the mutation (dp.topk_kills) rejects it"""
+    rejected = {name for _, name in _det_check_rejects('rpn_topk', mutation)}
+    named = {c.name for c in dp.RPN_TOPK if mutation in dp.topk_kills(c)}
+    assert named and named <= rejected, (mutation, sorted(named - rejected))
+
+
+@pytest.mark.parametrize('mutation', dp.QUERY_MUTATIONS)
+def test_query_topk_check_rejects(mutation):
+    """check_exact_query_topk: ties by descending index, the ties with the k-th score taken from the end, a class-major flat index;
+    check_seq_query_topk: a reciprocal that is not rounded to nearest -- every case that names the mutation rejects it"""
+    by_body = _det_check_rejects('query_topk', mutation)
+    exact = {name for body, name in by_body if body == 'check_exact_query_topk'}
+    if mutation == 'division_by_truncated_reciprocal':
+        named, rejected = set(dp.QUERY_SEQ), {name for body, name in by_body if body == 'check_seq_query_topk'}
+        assert not exact                                                     # 1 / 2^k is exact under any reciprocal: the exact tier cannot see it
+    else:
+        named, rejected = {c for c in dp.QUERY_EXACT if mutation in dp.query_kills(c)}, exact
+    assert named and named <= rejected, (mutation, named - rejected)
+
+
+def test_det_tolerance_checks_reject_what_only_real_arithmetic_shows():
+    """the upper size clamp and the expf path are tolerance-tier only (dw != 0 has no exact form): a stand-in that clamps the size
+    from both sides under add_ctr_clamp fails check_decode_tolerance on the case with dw far below -max_ratio; the tolerance
+    tier's exact ties (a duplicated query) still hold the index order"""
+    quiet = lambda line: None
+    with pytest.raises(AssertionError):
+        dp.check_decode_tolerance(dp.FakeOps('size_clamped_from_both_sides_under_ctr_clamp'), 'cpu', quiet, cases=dp.DECODE_TOL[1:2])
+    with pytest.raises(AssertionError):
+        dp.check_query_topk_tolerance(dp.FakeOps('ties_by_index_descending'), 'cpu', quiet)
