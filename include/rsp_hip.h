@@ -581,6 +581,40 @@ int rsp_panoptic_fuse(const float* cls, const float* low_res, int32_t Nq, int32_
                       int32_t w, int32_t Hb, int32_t Wb, int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w,
                       float object_mask_thr, double iou_thr, int32_t filter_low_score, void* workspace, int32_t* sem_seg,
                       int32_t* segment, int32_t* mask_area, int32_t* original_area, float* score, rsp_stream_t stream);
+/* Panoptic quality of one image: pq_compute_single_core (mmdet/evaluation/functional/panoptic_utils.py:60-169) on the maps as  */
+/* CocoPanopticMetric hands them over (coco_panoptic_metric.py:270-297, :309-387), csrc/panoptic_quality.hip, DESIGN 16.1.       */
+/* pred int32 [H, W]: id = label + 1000 * instance; a pixel is void when id % 1000 is num_classes or ignore_index.  The ground   */
+/* truth is EITHER gt_rgb uint8 [H, W, 3] (id = R + 256 G + 65536 B) OR gt_map int32 [H, W]; the other pointer is null.          */
+/* tables (device int32, written by the host): gt id ascending [G] | category index [G] | iscrowd [G] | area [G] (negative:     */
+/* count the pixels) | category index of label 0..999 [1000] (-1: none) | crowd_of [n_cat] = the slot, in the ascending order,   */
+/* of the LAST crowd segment of the category in JSON order (-1: none).  Listed gt ids are distinct and positive.  The predicted  */
+/* segments are the distinct non-void ids ascending (np.unique); TP: iou = inter / (area_pred + area_gt - inter - void overlap)  */
+/* as one double division, iou > 0.5; FN: every unmatched non-crowd gt segment; FP: an unmatched predicted segment unless        */
+/* 2 * (void overlap + crowd overlap) > area_pred (the integer form of the reference's `> 0.5`).  Writes per category [n_cat]:   */
+/* tp, fp, fn int32 and iou_sum double (summed in ascending gt id), status (0, or RSP_PQ_STATUS_* bits: the row is then zero),   */
+/* n_pred = P and, [RSP_PQ_MAX_SEGMENTS] each, the predicted ids, their category indices and areas (-1, -1, 0 beyond P).  Five   */
+/* launches, nothing read by the host; integer atomics only: bit-reproducible.  RSP_EINVAL: H * W >= 2^31, G >                   */
+/* RSP_PQ_MAX_SEGMENTS, n_cat > RSP_PQ_MAX_CATEGORIES, both or neither gt pointer, a null pointer, a map or the workspace not    */
+/* 16-byte aligned.  workspace: rsp_pq_workspace_bytes(G) bytes (-1 for a G the call would refuse).                              */
+#define RSP_PQ_MAX_SEGMENTS 1024
+#define RSP_PQ_MAX_PRED_ID (1 << 21)
+#define RSP_PQ_MAX_CATEGORIES 1024
+#define RSP_PQ_STATUS_TOO_MANY_SEGMENTS 1   /* more than RSP_PQ_MAX_SEGMENTS distinct predicted ids                      */
+#define RSP_PQ_STATUS_PRED_ID_RANGE 2       /* a predicted id below 0 or at / above RSP_PQ_MAX_PRED_ID                   */
+#define RSP_PQ_STATUS_PRED_ID_ZERO 4        /* predicted id 0 that is not void: it collides with VOID in the PNG encoding */
+#define RSP_PQ_STATUS_PRED_CATEGORY 8       /* a predicted label without a category (the reference raises KeyError)      */
+#define RSP_PQ_STATUS_GT_AREA 16            /* a listed non-crowd gt area below the segment's pixels in the map: a union  */
+                                            /* can then be 0 and one segment can match twice                             */
+int64_t rsp_pq_workspace_bytes(int32_t G);
+int rsp_pq_image(const int32_t* pred, const uint8_t* gt_rgb, const int32_t* gt_map, int32_t H, int32_t W,
+                 int32_t num_classes, int32_t ignore_index, const int32_t* tables, int32_t G, int32_t n_cat, void* workspace,
+                 int32_t* tp, int32_t* fp, int32_t* fn, double* iou_sum, int32_t* status, int32_t* n_pred,
+                 int32_t* pred_ids, int32_t* pred_cat, int32_t* pred_area, rsp_stream_t stream);
+/* PQStat.__iadd__ over n_img rows in order (coco_panoptic_metric.py:529-531): tp, fp, fn int32 [n_img, n_cat], iou_sum double  */
+/* [n_img, n_cat], status int32 [n_img] -> out int64 [4 n_cat + n_img]: the sums of tp | fp | fn | the bits of the double sum   */
+/* ((0 + s1) + s2) + ... | the statuses, so one read serves compute_metrics.                                                     */
+int rsp_pq_reduce(const int32_t* tp, const int32_t* fp, const int32_t* fn, const double* iou_sum, const int32_t* status,
+                  int32_t n_img, int32_t n_cat, int64_t* out, rsp_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Data movement                                                              */

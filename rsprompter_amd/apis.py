@@ -712,3 +712,60 @@ def panoptic_to_coco(pan, num_things_classes, void=None):
         cat = i % 1000
         segments.append(dict(id=i, category_id=cat, isthing=bool(cat < num_things_classes), area=a))
     return rgb.cpu().numpy(), segments
+
+
+def write_panoptic_png(pan, path, void=None):
+    """Write a panoptic map -- PixelData with sem_seg [1, H, W], or an int tensor [H, W] / [1, H, W], on any device -- as the
+    PNG mmdet's CocoPanopticMetric writes (coco_panoptic_metric.py:295-300): the colour of id is id2rgb (id % 256, id // 256
+    % 256, id // 65536), and every pixel whose label id % 1000 is a void label is black.  `void`: a label or several
+    (num_classes, ignore_index); by default the `void` field of the PixelData.  Returns the uint8 [H, W, 3] image written."""
+    from PIL import Image
+    sem = torch.as_tensor(pan.sem_seg if hasattr(pan, 'sem_seg') else pan)
+    if sem.dim() == 3:
+        sem = sem[0]
+    if sem.dim() != 2 or sem.dtype not in (torch.int32, torch.int64):
+        raise ValueError('write_panoptic_png expects an int32 / int64 map [H, W] or [1, H, W]')
+    if void is None and isinstance(pan, PixelData):
+        void = pan.get('void')
+    if void is None:
+        raise ValueError('write_panoptic_png needs the void label (num_classes): pass void=, or a PixelData that carries it')
+    sem64 = sem.to(torch.int64)
+    if bool((sem64 < 0).any()) or bool((sem64 >= 1 << 24).any()):
+        raise ValueError('write_panoptic_png: ids must be in [0, 2^24)')
+    for v in (void if isinstance(void, (tuple, list, set)) else (void,)):
+        sem64 = torch.where(sem64 % 1000 == int(v), torch.zeros_like(sem64), sem64)
+    rgb = torch.stack((sem64 % 256, sem64 // 256 % 256, sem64 // 65536), -1).to(torch.uint8).cpu().numpy()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    Image.fromarray(rgb, 'RGB').save(path, format='PNG')
+    return rgb
+
+
+def panoptic_quality(preds, gts, gt_segments, classes, thing_classes=None, ignore_index=None, device=None):
+    """PQ / SQ / RQ of lists of maps without a metric object: the computation of evaluation.CocoPanopticMetric (per image
+    ops.pq_image on the device, one ops.pq_reduce in list order, one host read, PQStat.pq_average).  preds[i]: int map [H, W]
+    or [1, H, W] or PixelData, id = label + 1000 * instance, void where id % 1000 is len(classes) (or ignore_index); gts[i]:
+    uint8 [H, W, 3] (a panoptic PNG's pixels) or an int id map; gt_segments[i]: that image's segments_info -- dicts of id,
+    category_id (the class index), iscrowd, area (None or absent: counted).  Returns the nine numbers of parse_pq_results
+    (PQ, SQ, RQ, *_th, *_st, each x 100), `n` per group and `classwise`: {class: dict(tp, fp, fn, iou, pq, sq, rq)}."""
+    from .evaluation import parse_pq_results, pq_results, pq_stat_from_packed
+    if not (len(preds) == len(gts) == len(gt_segments)) or len(preds) == 0:
+        raise ValueError('panoptic_quality expects three lists of one length, not empty')
+    classes = list(classes)
+    things = set(classes if thing_classes is None else thing_classes)
+    categories = {i: dict(id=i, name=n, isthing=1 if n in things else 0) for i, n in enumerate(classes)}
+    rows = []
+    for p, g, segs in zip(preds, gts, gt_segments):
+        sem = torch.as_tensor(p.sem_seg if hasattr(p, 'sem_seg') else p)
+        sem = sem[0] if sem.dim() == 3 else sem
+        dev = torch.device(device) if device is not None else (sem.device if ops._is_device(sem) else torch.device('cuda', torch.cuda.current_device()))
+        ops.require_device(dev)
+        row = ops.pq_image(sem.to(device=dev, dtype=torch.int32).contiguous(), torch.as_tensor(g).to(dev), segs, categories,
+                           len(classes), ignore_index=ignore_index)
+        rows.append({k: row[k] for k in ('tp', 'fp', 'fn', 'iou', 'status')})
+    stat = pq_stat_from_packed(ops.pq_reduce(rows)['packed'], list(categories))
+    res = pq_results(stat, categories)
+    out = parse_pq_results(res)
+    out['n'] = {g: res[g]['n'] for g in ('All', 'Things', 'Stuff')}
+    out['classwise'] = {classes[c]: dict(tp=stat[c][0], fp=stat[c][1], fn=stat[c][2], iou=stat[c][3], **res['classwise'][c])
+                        for c in categories}
+    return out

@@ -10,6 +10,9 @@ Both ground-truth paths of the reference work and give the reference's (differen
   * no `ann_file` (every RSPrompter config): the ground truth of the data samples, converted as `gt_to_coco_json` does
     (annotation ids from 1, category ids 0..C-1, every instance non-crowd, area = float32 box area w * h);
   * `ann_file`: the JSON as it is (crowd flags, the JSON's areas and annotation ids).
+
+`CocoPanopticMetric` (mmdet/evaluation/metrics/coco_panoptic_metric.py) is at the end: PQ / SQ / RQ of panoptic maps with
+the per-image confusion and matching on the device (csrc/panoptic_quality.hip), without panopticapi.
 """
 import json
 import os
@@ -585,3 +588,245 @@ class CocoMetric:
                 lines.append(f' {title:<18} {typ} @[ IoU={iou:<9} | area={area:>6s} | '
                              f'maxDets={self.proposal_nums[mi]:>3d} ] = {v:0.3f}')
         return '\n'.join(lines)
+
+
+# ------------------------------------------------------------------------------------------------------------ panoptic
+PQ_KEYS = ('PQ', 'SQ', 'RQ', 'PQ_th', 'SQ_th', 'RQ_th', 'PQ_st', 'SQ_st', 'RQ_st')
+
+
+def pq_average(stat, categories, isthing=None):
+    """panopticapi's PQStat.pq_average on stat = {category id: (tp, fp, fn, iou_sum)}, categories = {id: dict(isthing=...)}:
+    (dict(pq, sq, rq, n), per class).  A category with tp + fp + fn == 0 is not counted.  A group without a counted
+    category gives pq = sq = rq = 0.0, n = 0 (panopticapi divides by n; every RSPrompter dataset has no stuff class, so the
+    Stuff group would fail there every time: DESIGN §16.1)."""
+    pq = sq = rq = 0.0
+    n = 0
+    per_class = {}
+    for c, info in categories.items():
+        if isthing is not None and isthing != (info['isthing'] == 1):
+            continue
+        tp, fp, fn, iou = stat[c]
+        if tp + fp + fn == 0:
+            per_class[c] = dict(pq=0.0, sq=0.0, rq=0.0)
+            continue
+        n += 1
+        pq_c = iou / (tp + 0.5 * fp + 0.5 * fn)
+        sq_c = iou / tp if tp != 0 else 0
+        rq_c = tp / (tp + 0.5 * fp + 0.5 * fn)
+        per_class[c] = dict(pq=pq_c, sq=sq_c, rq=rq_c)
+        pq, sq, rq = pq + pq_c, sq + sq_c, rq + rq_c
+    if n == 0:
+        return dict(pq=0.0, sq=0.0, rq=0.0, n=0), per_class
+    return dict(pq=pq / n, sq=sq / n, rq=rq / n, n=n), per_class
+
+
+def pq_results(stat, categories):
+    """{'All' | 'Things' | 'Stuff': dict(pq, sq, rq, n), 'classwise': per class of All} (coco_panoptic_metric.py:533-540)"""
+    out = {}
+    for name, isthing in (('All', None), ('Things', True), ('Stuff', False)):
+        out[name], per_class = pq_average(stat, categories, isthing)
+        if name == 'All':
+            out['classwise'] = per_class
+    return out
+
+
+def parse_pq_results(res):
+    """coco_panoptic_metric.py:556-575"""
+    return {k.upper() + s: 100 * res[g][k] for g, s in (('All', ''), ('Things', '_th'), ('Stuff', '_st')) for k in ('pq', 'sq', 'rq')}
+
+
+def _text_table(rows):
+    width = [max(len(str(r[i])) for r in rows) for i in range(len(rows[0]))]
+    line = '+' + '+'.join('-' * (w + 2) for w in width) + '+'
+    body = ['| ' + ' | '.join(str(v).ljust(w) for v, w in zip(r, width)) + ' |' for r in rows]
+    return '\n'.join([line, body[0], line] + body[1:] + [line])
+
+
+def panoptic_table(res, classwise=None):
+    """print_panoptic_table (coco_panoptic_metric.py:578-618) as plain text"""
+    rows = [['', 'PQ', 'SQ', 'RQ', 'categories']]
+    for name in ('All', 'Things', 'Stuff'):
+        rows.append([name] + [f'{res[name][k] * 100:0.3f}' for k in ('pq', 'sq', 'rq')] + [res[name]['n']])
+    text = 'Panoptic Evaluation Results:\n' + _text_table(rows)
+    if classwise is not None:
+        rows = [['category', 'PQ', 'SQ', 'RQ']] + [[name] + [f'{m[k] * 100:0.3f}' for k in ('pq', 'sq', 'rq')]
+                                                  for name, m in classwise.items()]
+        text += '\nClasswise Panoptic Evaluation Results:\n' + _text_table(rows)
+    return text
+
+
+def pq_stat_from_packed(packed, cat_ids, names=None):
+    """the one host read of ops.pq_reduce -> {category id: (tp, fp, fn, iou_sum)}; a row with a status raises, naming it"""
+    buf = packed.cpu().numpy()
+    n = len(cat_ids)
+    for k, st in enumerate(buf[4 * n:].tolist()):
+        if st:
+            who = names[k] if names is not None else k
+            raise RuntimeError(f'panoptic quality: image {who!r} was refused: {ops.pq_status_text(st)} (status {st})')
+    iou = buf[3 * n:4 * n].view(np.float64)
+    return {c: (int(buf[i]), int(buf[n + i]), int(buf[2 * n + i]), float(iou[i])) for i, c in enumerate(cat_ids)}
+
+
+def _segments_as_json(segments_info, categories):
+    """segments_info in the JSON's form: the dataset's form (id, category, is_thing) converted as
+    coco_panoptic_metric.py:355-372 does -- iscrowd = a thing class whose segment is not a thing; the area is counted"""
+    out = []
+    for s in segments_info:
+        if 'category_id' in s:
+            out.append(dict(id=int(s['id']), category_id=s['category_id'], iscrowd=int(s.get('iscrowd', 0)), area=s.get('area')))
+        else:
+            label = s['category']
+            crowd = 1 if categories[label]['isthing'] and not s['is_thing'] else 0
+            out.append(dict(id=int(s['id']), category_id=label, iscrowd=crowd, area=None))
+    return out
+
+
+@METRICS.register_module()
+class CocoPanopticMetric:
+    """mmdet CocoPanopticMetric (mmdet/evaluation/metrics/coco_panoptic_metric.py): PQ / SQ / RQ of `pred_panoptic_seg`
+    with the per-image work -- void mapping, np.unique, the confusion of the two maps, matching -- on the device
+    (ops.pq_image, csrc/panoptic_quality.hip): the predicted map is never copied to the host or written to a
+    file to be scored.  `process` keeps one small row per image; `compute_metrics` reduces them on the device in processing
+    order, reads the host once and averages as PQStat.pq_average.  Needs neither panopticapi nor terminaltables.
+
+    The ground truth of a sample comes from, in this order: an in-memory id map `gt_panoptic` with `segments_info`; with
+    `ann_file` the JSON's segments_info (areas as listed) and the PNG `seg_prefix/<name>.png`; else the sample's
+    `segments_info` with `seg_map_path` (or `seg_prefix/<name>.png`), areas counted.  `outfile_prefix` additionally writes
+    `<prefix>.panoptic/<name>.png` and `<prefix>.panoptic.json` (`format_only`: only that); PQ itself always comes from the
+    maps.  `nproc` is accepted and ignored: the sums are the in-order ones."""
+    default_prefix = 'coco_panoptic'
+
+    def __init__(self, ann_file=None, seg_prefix=None, classwise=False, format_only=False, outfile_prefix=None, nproc=32,
+                 file_client_args=None, backend_args=None, collect_device='cpu', prefix=None, device=None):
+        if file_client_args is not None:
+            raise RuntimeError('The `file_client_args` is deprecated, please use `backend_args` instead')
+        if backend_args is not None:
+            raise NotImplementedError('backend_args: only local files are supported (backend_args=None)')
+        self.classwise = classwise
+        self.format_only = format_only
+        if format_only:
+            assert outfile_prefix is not None, 'outfile_prefix must be not None when format_only is True'
+        self.outfile_prefix = outfile_prefix
+        self.seg_out_dir = None if outfile_prefix is None else f'{outfile_prefix}.panoptic'
+        self.nproc = nproc
+        self.seg_prefix = seg_prefix
+        self.collect_device = collect_device
+        self.prefix = prefix or self.default_prefix
+        self.device = device
+        self._coco_api = None
+        self.categories = None
+        if ann_file:
+            with open(ann_file) as f:
+                self._coco_api = json.load(f)
+            self.categories = {c['id']: c for c in self._coco_api['categories']}
+            self._img_to_segments = {a['image_id']: a['segments_info'] for a in self._coco_api.get('annotations', [])}
+        self._dataset_meta = None
+        self.results = []
+        self.pq_results = None
+        self.table = None
+
+    @property
+    def dataset_meta(self):
+        return self._dataset_meta
+
+    @dataset_meta.setter
+    def dataset_meta(self, meta):
+        self._dataset_meta = meta
+
+    def _categories(self):
+        """(categories, label2cat) as coco_panoptic_metric.py:316-327: without an ann_file the labels are the ids; with
+        one, label i is the i-th JSON category whose name is a class (get_cat_ids keeps the JSON's order)"""
+        classes = list(self.dataset_meta['classes'])
+        if self._coco_api is None:
+            things = set(self.dataset_meta.get('thing_classes', classes))
+            return {i: dict(id=i, name=n, isthing=1 if n in things else 0) for i, n in enumerate(classes)}, None
+        cat_ids = [c['id'] for c in self._coco_api['categories'] if c['name'] in classes]
+        return self.categories, {i: c for i, c in enumerate(cat_ids)}
+
+    @staticmethod
+    def _read_png(path, device):
+        from PIL import Image
+        with Image.open(path) as im:
+            return torch.from_numpy(np.array(im.convert('RGB'), dtype=np.uint8)).to(device)
+
+    def process(self, data_batch, data_samples):
+        device = torch.device(self.device) if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        ops.require_device(device)                          # the kernels have no CPU form: refused before a map is moved
+        categories, label2cat = self._categories()
+        num_classes = len(self.dataset_meta['classes'])
+        for s in data_samples:
+            pred = _get(s, 'pred_panoptic_seg')
+            sem = torch.as_tensor(_get(pred, 'sem_seg'))
+            sem = (sem[0] if sem.dim() == 3 else sem).to(device=device, dtype=torch.int32).contiguous()
+            ignore_index = _get(pred, 'ignore_index', num_classes)
+            img_id = _get(s, 'img_id')
+            name = os.path.basename(_get(s, 'img_path') or f'{img_id}.png').replace('jpg', 'png')
+            gt_map = _get(s, 'gt_panoptic')
+            if gt_map is not None:
+                gt = torch.as_tensor(gt_map).to(device)
+                segments = _segments_as_json(_get(s, 'segments_info'), categories)
+            elif self._coco_api is not None:
+                gt = self._read_png(os.path.join(self.seg_prefix, name), device)
+                segments = self._img_to_segments[img_id]
+            else:
+                path = _get(s, 'seg_map_path') or os.path.join(self.seg_prefix, name)
+                gt = self._read_png(path, device)
+                segments = _segments_as_json(_get(s, 'segments_info'), categories)
+            try:
+                row = ops.pq_image(sem, gt, segments, categories, num_classes, ignore_index=ignore_index, label2cat=label2cat)
+            except ValueError as e:
+                raise ValueError(f'CocoPanopticMetric: image {name!r}: {e}') from e
+            kept = dict(name=name, img_id=img_id, row={k: row[k] for k in ('tp', 'fp', 'fn', 'iou', 'status')})
+            if self.outfile_prefix is not None:
+                kept['annotation'] = self._write_prediction(sem, row, name, img_id, categories, num_classes, ignore_index)
+            self.results.append(kept)
+
+    def _write_prediction(self, sem, row, name, img_id, categories, num_classes, ignore_index):
+        """_parse_predictions' file (coco_panoptic_metric.py:295-305) and result2json's entry (:231-242); this path reads
+        the segment list of the image from the device, and with it the status: a refused image raises here, before a file
+        with an empty segment list is written (format_only never reaches the check of compute_metrics)"""
+        from .apis import write_panoptic_png
+        status, n = torch.cat([row['status'], row['n_pred']]).cpu().tolist()
+        if status:
+            raise RuntimeError(f'panoptic quality: image {name!r} was refused: {ops.pq_status_text(status)} (status {status})')
+        os.makedirs(self.seg_out_dir, exist_ok=True)
+        write_panoptic_png(sem, os.path.join(self.seg_out_dir, name), void=(num_classes, ignore_index))
+        cat_ids = list(categories)
+        ids, cats, areas = (row[k][:n].cpu().tolist() for k in ('pred_ids', 'pred_cat', 'pred_area'))
+        info = [dict(id=i, category_id=cat_ids[c], area=a, isthing=categories[cat_ids[c]]['isthing'])
+                for i, c, a in zip(ids, cats, areas) if c >= 0]
+        return dict(image_id=img_id, segments_info=info, file_name=name)
+
+    def evaluate(self, size):
+        results = self.results[:size]
+        metrics = self.compute_metrics(results)
+        self.results = []
+        return {f'{self.prefix}/{k}': v for k, v in metrics.items()}
+
+    def compute_metrics(self, results):
+        import logging
+        logger = logging.getLogger('rsprompter_amd')
+        if self.outfile_prefix is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(self.outfile_prefix)), exist_ok=True)
+            with open(f'{self.outfile_prefix}.panoptic.json', 'w') as f:
+                json.dump(dict(annotations=[r['annotation'] for r in results]), f)
+            if self.format_only:
+                logger.info(f'results are saved in {os.path.dirname(self.outfile_prefix)}')
+                return dict()
+        categories, _ = self._categories()
+        self.categories = categories
+        cat_ids = list(categories)
+        if results:
+            red = ops.pq_reduce([r['row'] for r in results])
+            stat = pq_stat_from_packed(red['packed'], cat_ids, [r['name'] for r in results])
+        else:
+            stat = {c: (0, 0, 0, 0.0) for c in cat_ids}
+        self.pq_stat = stat
+        res = pq_results(stat, categories)
+        classwise = None
+        if self.classwise:
+            classwise = {k: v for k, v in zip(self.dataset_meta['classes'], res['classwise'].values())}
+        self.pq_results, self.classwise_results = res, classwise
+        self.table = panoptic_table(res, classwise)
+        logger.info(self.table)
+        return parse_pq_results(res)

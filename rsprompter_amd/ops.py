@@ -3104,3 +3104,133 @@ def panoptic_fuse(cls, low_res, batch_input_shape, crop_hw, out_hw, num_things_c
                                                     info['mask_area'].data_ptr(), info['original_area'].data_ptr(),
                                                     info['score'].data_ptr(), _stream()), "rsp_panoptic_fuse"))
     return sem, info
+
+
+PQ_MAX_SEGMENTS = _lib.CONST['RSP_PQ_MAX_SEGMENTS']
+PQ_MAX_PRED_ID = _lib.CONST['RSP_PQ_MAX_PRED_ID']
+PQ_MAX_CATEGORIES = _lib.CONST['RSP_PQ_MAX_CATEGORIES']
+PQ_STATUS = {v: k[len('RSP_PQ_STATUS_'):].lower() for k, v in _lib.CONST.items() if k.startswith('RSP_PQ_STATUS_')}
+_PQ_LABELS = 1000                       # INSTANCE_OFFSET (panoptic_utils.py:18)
+
+
+def pq_status_text(status):
+    """the names of the RSP_PQ_STATUS_* bits of a row's status"""
+    return ', '.join(name for bit, name in sorted(PQ_STATUS.items()) if status & bit) or 'ok'
+
+
+def pq_image(pred, gt, gt_segments, categories, num_classes, ignore_index=None, label2cat=None):
+    """pq_compute_single_core (panoptic_utils.py:60-169) of one image on the maps CocoPanopticMetric hands it
+    (coco_panoptic_metric.py:270-297), csrc/panoptic_quality.hip.  pred int32 [H, W] on the device: id = label + 1000 *
+    instance, void where id % 1000 is num_classes or ignore_index (default num_classes).  gt uint8 [H, W, 3] (a panoptic PNG:
+    id = R + 256 G + 65536 B) or an int32 / int64 id map [H, W], on the device of pred (an int64 map is narrowed to int32 on
+    the device without a look at its values: it must hold ids below 2^31, or a larger one wraps onto a small one).  gt_segments: the image's
+    segments_info in JSON order, dicts with id, category_id, iscrowd and area (None or absent: the pixels are counted, as the
+    dataset path does).  categories: the category ids, in the order of the result's columns (a dict: its keys).  label2cat:
+    label -> category id (None: the label is the category id).
+
+    Returns a row of device tensors: tp, fp, fn int32 [n_cat], iou float64 [n_cat], status int32 [1] (0, or RSP_PQ_STATUS_*
+    bits -- what only the map can tell: too many segments, an id out of range, a predicted id 0 that is not void, a predicted
+    label without a category, a listed non-crowd gt area below the segment's pixels in the map; the row is then zero), n_pred int32 [1] and pred_ids, pred_cat (an index into categories),
+    pred_area int32 [PQ_MAX_SEGMENTS].  Nothing is read back.  What the arguments alone tell raises ValueError before a launch."""
+    if not isinstance(pred, torch.Tensor) or pred.dtype != torch.int32 or pred.dim() != 2 or not pred.is_contiguous() \
+            or pred.numel() == 0:
+        raise ValueError("pq_image expects pred as a contiguous int32 map [H, W]")
+    if not _is_device(pred):
+        raise ValueError(f"pq_image expects the maps on the HIP device, got pred on {pred.device}")
+    lib = _lib.load()
+    H, W = int(pred.shape[0]), int(pred.shape[1])
+    dev = pred.device
+    if not isinstance(gt, torch.Tensor) or gt.device != dev:
+        raise ValueError("pq_image expects gt on the device of pred")
+    rgb = gt.dtype == torch.uint8
+    if rgb:
+        if gt.dim() != 3 or gt.shape[2] != 3:
+            raise ValueError("pq_image expects a uint8 gt as [H, W, 3]")
+    elif gt.dtype not in (torch.int32, torch.int64) or gt.dim() != 2:
+        raise ValueError("pq_image expects gt as uint8 [H, W, 3] or an int32 / int64 map [H, W]")
+    if tuple(gt.shape[:2]) != (H, W):
+        raise ValueError(f"pq_image: the maps differ in size: pred {(H, W)}, gt {tuple(gt.shape[:2])}")
+    if H * W >= 2 ** 31:
+        raise ValueError("pq_image: H * W >= 2^31")
+    gt = gt.contiguous() if rgb else gt.to(torch.int32).contiguous()
+    if pred.data_ptr() % 16 or gt.data_ptr() % 16:
+        raise ValueError("pq_image: the maps must start at 16-byte aligned addresses")
+    cat_ids = list(categories.keys() if isinstance(categories, dict) else categories)
+    n_cat, G = len(cat_ids), len(gt_segments)
+    if not 1 <= n_cat <= PQ_MAX_CATEGORIES or len(set(cat_ids)) != n_cat:
+        raise ValueError(f"pq_image: categories must be 1 .. {PQ_MAX_CATEGORIES} distinct ids")
+    if G > PQ_MAX_SEGMENTS:
+        raise ValueError(f"pq_image: {G} ground-truth segments, at most {PQ_MAX_SEGMENTS}")
+    num_classes = int(num_classes)
+    ignore_index = num_classes if ignore_index is None else int(ignore_index)
+    if num_classes < 0:
+        raise ValueError("pq_image: num_classes < 0")
+    index = {c: i for i, c in enumerate(cat_ids)}
+    ids = [int(s['id']) for s in gt_segments]
+    if len(set(ids)) != G:
+        raise ValueError("pq_image: duplicate ground-truth segment ids")
+    if any(not 0 < i < 2 ** 31 for i in ids):
+        raise ValueError("pq_image: ground-truth segment ids must be in [1, 2^31) (0 is VOID)")
+    order = sorted(range(G), key=lambda k: ids[k])
+    slot = {ids[k]: j for j, k in enumerate(order)}
+    area = []
+    for k in order:
+        a = gt_segments[k].get('area')
+        if a is not None and not 0 <= int(a) < 2 ** 31:
+            raise ValueError("pq_image: a ground-truth area outside [0, 2^31)")
+        area.append(-1 if a is None else int(a))
+    # a gt category outside `categories` takes part in nothing (the reference counts it where pq_average never looks)
+    gcat = [index.get(gt_segments[k]['category_id'], -1) for k in order]
+    crowd = [1 if int(gt_segments[k].get('iscrowd', 0)) == 1 else 0 for k in order]
+    crowd_of = [-1] * n_cat
+    for s in gt_segments:                                  # JSON order: the last crowd segment of a category stays
+        if int(s.get('iscrowd', 0)) == 1 and s['category_id'] in index:
+            crowd_of[index[s['category_id']]] = slot[int(s['id'])]
+    if label2cat is None:
+        label_cat = [index.get(l, -1) for l in range(_PQ_LABELS)]
+    else:
+        label_cat = [-1] * _PQ_LABELS
+        for l, c in label2cat.items():
+            if not 0 <= int(l) < _PQ_LABELS:
+                raise ValueError(f"pq_image: label {l} outside [0, {_PQ_LABELS})")
+            if c not in index:
+                raise ValueError(f"pq_image: label {l} maps to category {c}, which is not in categories")
+            label_cat[int(l)] = index[c]
+    tables = torch.tensor([ids[k] for k in order] + gcat + crowd + area + label_cat + crowd_of, dtype=torch.int32).to(dev)
+    # two buffers: a caller that keeps the statistics of many images (CocoPanopticMetric) drops the segment list
+    ints = torch.empty((3 * n_cat + 2,), dtype=torch.int32, device=dev)
+    segs = torch.empty((3, PQ_MAX_SEGMENTS), dtype=torch.int32, device=dev)
+    row = dict(tp=ints[:n_cat], fp=ints[n_cat:2 * n_cat], fn=ints[2 * n_cat:3 * n_cat], status=ints[3 * n_cat:3 * n_cat + 1],
+               n_pred=ints[3 * n_cat + 1:], iou=torch.empty((n_cat,), dtype=torch.float64, device=dev),
+               pred_ids=segs[0], pred_cat=segs[1], pred_area=segs[2])
+    ws = torch.empty((lib.rsp_pq_workspace_bytes(G),), dtype=torch.uint8, device=dev)
+    _timed('pq_image_kernel', 0, (8.0 + (6.0 if rgb else 8.0)) * H * W,
+           lambda: _lib.check(lib.rsp_pq_image(pred.data_ptr(), gt.data_ptr() if rgb else 0, 0 if rgb else gt.data_ptr(), H, W,
+                                               num_classes, ignore_index, tables.data_ptr(), G, n_cat, ws.data_ptr(),
+                                               row['tp'].data_ptr(), row['fp'].data_ptr(), row['fn'].data_ptr(),
+                                               row['iou'].data_ptr(), row['status'].data_ptr(), row['n_pred'].data_ptr(),
+                                               row['pred_ids'].data_ptr(), row['pred_cat'].data_ptr(),
+                                               row['pred_area'].data_ptr(), _stream()), "rsp_pq_image"))
+    return row
+
+
+def pq_reduce(rows):
+    """PQStat.__iadd__ over the rows of pq_image in order (coco_panoptic_metric.py:529-531), on the device: dict(tp, fp, fn
+    int64 [n_cat], iou float64 [n_cat] = ((0 + s1) + s2) + ..., status int32-valued int64 [n_img]) as views of ONE device
+    buffer `packed` int64 [4 n_cat + n_img], so a caller reads the host once."""
+    rows = list(rows)
+    if not rows:
+        raise ValueError("pq_reduce: no rows")
+    if not isinstance(rows[0]['tp'], torch.Tensor) or not _is_device(rows[0]['tp']):
+        raise ValueError("pq_reduce expects rows of ops.pq_image on the HIP device")
+    lib = _lib.load()
+    n_cat = rows[0]['tp'].numel()
+    if any(r['tp'].numel() != n_cat or r['tp'].device != rows[0]['tp'].device for r in rows):
+        raise ValueError("pq_reduce: rows of different categories or devices")
+    n_img = len(rows)
+    tp, fp, fn, iou, st = (torch.stack([r[k].reshape(-1) for r in rows]).contiguous() for k in ('tp', 'fp', 'fn', 'iou', 'status'))
+    out = torch.empty((4 * n_cat + n_img,), dtype=torch.int64, device=tp.device)
+    _lib.check(lib.rsp_pq_reduce(tp.data_ptr(), fp.data_ptr(), fn.data_ptr(), iou.data_ptr(), st.data_ptr(), n_img, n_cat,
+                                 out.data_ptr(), _stream()), "rsp_pq_reduce")
+    return dict(packed=out, tp=out[:n_cat], fp=out[n_cat:2 * n_cat], fn=out[2 * n_cat:3 * n_cat],
+                iou=out[3 * n_cat:4 * n_cat].view(torch.float64), status=out[4 * n_cat:])
