@@ -952,6 +952,36 @@ int rsp_mask_hull_write(const int32_t* n, int32_t k, int32_t cap, const int64_t*
 int rsp_hull_min_rect(const int32_t* hull_verts, const int64_t* hull_offs, int32_t k, int64_t Vh, int32_t* edge, int64_t* q,
                       rsp_stream_t stream);
 
+/* Oriented-box comparison (csrc/obb_iou.hip): rotated IoU and mmcv's nms_rotated.  A box is a convex          */
+/* quadrilateral, double [4][2] = (x, y) of its corners in order, in pixel coordinates: the corner form of                   */
+/* rle.obb_to_numpy (clockwise on screen, sum x_i y_{i+1} - x_{i+1} y_i > 0); the opposite orientation is accepted and        */
+/* normalised by the sign of the doubled area.  A box with a non-finite coordinate or zero area is DEGENERATE: its IoU with   */
+/* everything is 0.0, it suppresses nothing and the NMS keeps it (the NaN row of an empty mask takes this path).  No atomics; */
+/* a second launch gives the same bits.                                                                                      */
+/* rsp_obb_corners: edge int32 [k] / q int64 [k, 6] as rsp_hull_min_rect writes them, offset int32 [k, 2] = (ox, oy) or NULL  */
+/* -> corners double [k, 4, 2].  The offset moves q in integers first (a += ox ex + oy ey, b += -ox ey + oy ex); a corner is  */
+/* then ((a ex - b ey) / L, (a ey + b ex) / L) in fp64 with one division: the bits of rle.obb_to_numpy(form='corners') of the */
+/* shifted table.  edge = -1 gives a NaN row.                                                                                 */
+int rsp_obb_corners(const int32_t* edge, const int64_t* q, const int32_t* offset, int32_t k, double* corners,
+                    rsp_stream_t stream);
+/* IoU blocks of n_units units, as rsp_coco_iou takes them (units: DEVICE array, nwords ignored): iou[out0 + d * ng + g] of   */
+/* dt_quad [n_dt, 4, 2] and gt_quad [n_gt, 4, 2], one lane per pair, in fp64: inter / (area_d + area_g - inter), inter /      */
+/* area_d for a crowd gt, 0.0 when inter <= 0 or the union is not positive.  The intersection is a closed polygon: the gt     */
+/* box clipped successively by the four half-planes of the dt box, both translated by the dt box's centre, one shoelace sum.  */
+/* Pairs whose axis-aligned bounds do not overlap write 0.0 without clipping.  A unit that reaches outside n_dt, n_gt or      */
+/* n_iou writes nothing.                                                                                                      */
+int rsp_obb_iou(const RspCocoUnit* units, int32_t n_units, const double* dt_quad, int64_t n_dt, const double* gt_quad,
+                int64_t n_gt, const uint8_t* gt_crowd, double* iou, int64_t n_iou, rsp_stream_t stream);
+/* mmcv.ops.nms_rotated on flat arrays: quad double [n, 4, 2], scores float [n], labels int32 [n].  Order: score descending,  */
+/* original position ascending; box j is suppressed by a KEPT box i ahead of it iff they share a label (or class_agnostic !=  */
+/* 0) and iou(i, j) > iou_thr (strict; iou_thr >= 0).  keep int32 [n] = indices into the input in kept order, keep_cnt int32  */
+/* [1].  n <= RSP_OBB_NMS_MAX (the n x ceil(n / 64) word suppression mask is 128 MiB there); beyond it RSP_EINVAL, and        */
+/* rsp_obb_nms_workspace_bytes is -1.                                                                                         */
+#define RSP_OBB_NMS_MAX 32768
+int64_t rsp_obb_nms_workspace_bytes(int32_t n);
+int rsp_obb_nms(const double* quad, const float* scores, const int32_t* labels, int32_t n, double iou_thr,
+                int32_t class_agnostic, void* workspace, int32_t* keep, int32_t* keep_cnt, rsp_stream_t stream);
+
 /* Run-domain connected components (csrc/run_components.hip): the 8-connected components of every mask of a     */
 /* run table; replaces decoding every instance to a dense H x W array + cv2.connectedComponentsWithStats (segment-anything     */
 /* utils/amg.py remove_small_regions) and the dense labelling of rsp_mask_remove_small_regions where the masks live as runs.   */

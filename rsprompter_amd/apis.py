@@ -670,6 +670,86 @@ def masks_to_obb(masks, form='corners', transform=None, device='cuda:0', per_com
     return [out[co[i]:co[i + 1]] for i in range(len(co) - 1)] if per_component else out
 
 
+def xywha_to_corners(xywha):
+    """float64 [k, 5] = (cx, cy, w, h, angle) in the convention rle.obb_to_numpy(form='xywha') writes (angle of the w side in
+    radians from +x towards +y) -> float64 numpy [k, 4, 2], corners clockwise on screen from (-w / 2, -h / 2) in the box's
+    frame.  Made on the host in float64: one cos / sin away from exact, where the corner form of a mask's rectangle is one
+    division away."""
+    b = np.asarray(xywha, np.float64).reshape(-1, 5)
+    ux, uy = np.cos(b[:, 4]), np.sin(b[:, 4])
+    hw, hh = b[:, 2] / 2, b[:, 3] / 2
+    sa, sb = np.array([-1.0, 1.0, 1.0, -1.0]), np.array([-1.0, -1.0, 1.0, 1.0])
+    x = b[:, None, 0] + sa * (hw * ux)[:, None] - sb * (hh * uy)[:, None]
+    y = b[:, None, 1] + sa * (hw * uy)[:, None] + sb * (hh * ux)[:, None]
+    return np.stack([x, y], 2)
+
+
+def _as_obb_corners(boxes, device, who):
+    """oriented boxes in any accepted form -> float64 [k, 4, 2] on `device`: corners [k, 4, 2], xywha [k, 5] (tensor, array or
+    nested list), or masks in the forms of masks_to_obb (a bool [k, H, W] device tensor, RLE dicts of one size), reduced to
+    their rectangles on the device"""
+    dev = torch.device(device)
+    masks = (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.bool) or \
+        (isinstance(boxes, (list, tuple)) and len(boxes) > 0 and isinstance(boxes[0], dict))
+    if masks:
+        counts, n, size, _ = rle.masks_to_runs(boxes, dev, who, canonical=True)
+        return rle.runs_to_obb_corners(counts, n, size)
+    if isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float64 and boxes.device == dev and boxes.dim() == 3 \
+            and tuple(boxes.shape[1:]) == (4, 2):
+        return boxes.contiguous()                                       # corners on the device already: no copy, no read
+    t = boxes.detach().to(torch.float64).cpu().numpy() if isinstance(boxes, torch.Tensor) else np.asarray(boxes, np.float64)
+    if t.size == 0 and t.ndim < 3:
+        t = t.reshape(0, 4, 2)
+    if t.ndim == 2 and t.shape[1] == 5:
+        t = xywha_to_corners(t)
+    if t.ndim != 3 or t.shape[1:] != (4, 2):
+        raise ValueError(f'{who}: oriented boxes are corners [k, 4, 2], xywha [k, 5] or masks; got an array of shape '
+                         f'{tuple(t.shape)}')
+    return torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+
+
+def obb_iou(a, b, iscrowd=None, device='cuda:0'):
+    """The IoU of every oriented box of `a` with every one of `b` -> float64 [D, G] on the device (ops.obb_iou, DESIGN
+    §14.17): inter / union in fp64 with the intersection clipped as a closed polygon; a column g with iscrowd[g] set holds
+    inter / area(a[d]), as COCO's crowd regions.  `a`, `b`: corners [k, 4, 2] (either orientation), xywha [k, 5] in the
+    convention of masks_to_obb(form='xywha') (xywha_to_corners: one cos / sin away from exact), or masks in the forms of
+    masks_to_obb, reduced to their rectangles on the device.  Degenerate boxes (NaN, zero area: empty masks) have IoU 0."""
+    dev = torch.device(device)
+    qa, qb = _as_obb_corners(a, dev, 'obb_iou'), _as_obb_corners(b, dev, 'obb_iou')
+    D, G = int(qa.shape[0]), int(qb.shape[0])
+    crowd = torch.zeros((G,), dtype=torch.uint8, device=dev) if iscrowd is None else \
+        (_flat(iscrowd, dev) != 0).to(torch.uint8)
+    if crowd.shape[0] != G:
+        raise ValueError(f'obb_iou: iscrowd has {crowd.shape[0]} entries for {G} boxes')
+    if D == 0 or G == 0:
+        return torch.zeros((D, G), dtype=torch.float64, device=dev)
+    # one unit per row of `a`: a unit is one block of the kernel, so a single [D] x [G] unit would run on one CU
+    d = np.arange(D, dtype=np.int64)
+    units = ops.coco_units(d, np.zeros(D, np.int64), d * G, np.ones(D, np.int64), np.full(D, G, np.int64),
+                           np.zeros(D, np.int64), dev)
+    return ops.obb_iou(units, D * G, qa, qb, crowd).view(D, G)
+
+
+def nms_rotated(obb, scores, labels=None, iou_thr=0.5, device='cuda:0'):
+    """mmcv.ops.nms_rotated: greedy suppression by rotated IoU > iou_thr (strict) in descending score order (ties by
+    position), between boxes of one label when `labels` is given, between all otherwise -> keep int64 [m] on the device,
+    indices into the input in kept order (ops.obb_nms).  `obb` in the forms of obb_iou; degenerate boxes are
+    kept and suppress nothing."""
+    dev = torch.device(device)
+    quad = _as_obb_corners(obb, dev, 'nms_rotated')
+    n = int(quad.shape[0])
+    s = _flat(scores, dev).to(torch.float32)
+    lab = torch.zeros((n,), dtype=torch.int32, device=dev) if labels is None else _flat(labels, dev).to(torch.int32)
+    if s.shape[0] != n or lab.shape[0] != n:
+        raise ValueError(f'nms_rotated: {n} boxes, {s.shape[0]} scores and {lab.shape[0]} labels')
+    return ops.obb_nms(quad, s, lab, iou_thr, class_agnostic=labels is None)
+
+
+def _flat(x, dev):
+    """a tensor, array or list -> a flat tensor on `dev`"""
+    return (x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))).reshape(-1).to(dev)
+
+
 def mask_components(masks, device='cuda:0'):
     """Masks -> per instance dict(count, areas int32 [c], bboxes int32 [c, 4] = (x0, y0, x1, y1) end-exclusive) of its
     8-connected components, ordered by their first pixel in column-major order; labelled on the device in the run domain

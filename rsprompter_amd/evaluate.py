@@ -94,7 +94,7 @@ def _scene_predictions(model, ds, mine, large_image):
 
 @torch.no_grad()
 def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_ann_file=None, device=None,
-             verbose=True, gt_raster=None, large_image=None, iou_domain=None, boundary=False, dilation_ratio=None):
+             verbose=True, gt_raster=None, large_image=None, iou_domain=None, boundary=False, dilation_ratio=None, obb=False):
     """Run the test set of `cfg` through `model` on this rank's shard; on rank 0 return the metrics dict (mmdet's keys),
     elsewhere None.  `metric_ann_file` sets CocoMetric's ann_file (the ground-truth JSON path of the reference's metric);
     by default the metric converts the dataset's ground truth as every RSPrompter config does.  `gt_raster` ('host' /
@@ -102,7 +102,8 @@ def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_
     `large_image`: a dict of inference_large_image keywords (LARGE_IMAGE_KEYS; {} for its defaults) -- every dataset item
     is then a scene, and the metric's iou_domain is 'runs' unless `iou_domain` ('bits' / 'runs' / 'auto') or the config says
     otherwise.  `iou_domain` alone overrides CocoMetric's on the tile path.  `boundary` appends 'boundary' (Boundary AP,
-    DESIGN §14.13) to the metric list; `dilation_ratio` sets its band width and is refused without it."""
+    DESIGN §14.13) to the metric list; `dilation_ratio` sets its band width and is refused without it.  `obb` appends 'obb'
+    (oriented-box AP, DESIGN §14.17: segm with the IoU of the masks' minimum-area rectangles)."""
     import torch.distributed as dist
     if dilation_ratio is not None and not boundary:
         raise ValueError('evaluate: dilation_ratio applies to boundary=True')
@@ -157,6 +158,10 @@ def evaluate(model, cfg, data_root=None, ann_file=None, out_prefix=None, metric_
         ev_cfg['metric'] = listed + [m for m in ('boundary',) if m not in listed]
         if dilation_ratio is not None:
             ev_cfg['dilation_ratio'] = dilation_ratio
+    if obb:
+        listed = ev_cfg.get('metric', 'bbox')
+        listed = list(listed) if isinstance(listed, (list, tuple)) else [listed]
+        ev_cfg['metric'] = listed + [m for m in ('obb',) if m not in listed]
     metric = METRICS.build(ev_cfg)
     metric.dataset_meta = ds.dataset_meta
     metric.device = str(dev)
@@ -205,12 +210,15 @@ def main(argv=None):
                     help="adds Boundary AP (metric 'boundary': min(mask IoU, Boundary IoU) per pair) to the metric list")
     ap.add_argument('--dilation-ratio', type=float, default=None,
                     help='--boundary: the band width as a fraction of the image diagonal (default 0.02)')
+    ap.add_argument('--obb', action='store_true',
+                    help="adds oriented-box AP (metric 'obb': the IoU of the masks' minimum-area rectangles per pair) to the "
+                         'metric list')
     ap.add_argument('--large-image', action='store_true',
                     help='every image of the dataset is a scene: sliced inference (inference_large_image) instead of test_step')
     ap.add_argument('--patch-size', type=int, default=None, help='--large-image: tile side in pixels')
     ap.add_argument('--patch-overlap-ratio', type=float, default=None)
     ap.add_argument('--merge-iou-thr', type=float, default=None)
-    ap.add_argument('--merge-nms-type', choices=('nms', 'seam_mask'), default=None)
+    ap.add_argument('--merge-nms-type', choices=('nms', 'seam_mask', 'nms_rotated'), default=None)
     ap.add_argument('--seam-iou-thr', type=float, default=None)
     ap.add_argument('--batch-size', type=int, default=None, help='--large-image: tiles per forward pass')
     ap.add_argument('--min-mask-region-area', type=int, default=None)
@@ -227,7 +235,7 @@ def main(argv=None):
     model = init_detector(cfg, args.checkpoint, device=f'cuda:{local}')
     res = evaluate(model, cfg, args.data_root, args.ann_file, args.out_prefix, verbose=rank == 0, gt_raster=args.gt_raster,
                    large_image=given if args.large_image else None, iou_domain=args.iou_domain, boundary=args.boundary,
-                   dilation_ratio=args.dilation_ratio)
+                   dilation_ratio=args.dilation_ratio, obb=args.obb)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

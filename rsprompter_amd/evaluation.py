@@ -89,6 +89,21 @@ def _band_runs(runs, sizes, dilation_ratio):
     return rle.concat_runs(tables, rows=back).contiguous(), torch.cat(ns)[back].contiguous()
 
 
+def _obb_quads(runs, sizes):
+    """the oriented boxes of a run table whose rows lie on canvases of their own (sizes: (H, W) per row): the rows grouped by
+    size as in _band_runs, one rle.runs_to_obb_corners call per size -> float64 [k, 4, 2] on the device, in row order (NaN
+    rows for empty masks)"""
+    counts, n = runs
+    out = torch.full((len(sizes), 4, 2), float('nan'), dtype=torch.float64, device=n.device)
+    groups = {}
+    for i, s in enumerate(sizes):
+        groups.setdefault((int(s[0]), int(s[1])), []).append(i)
+    for size, idx in groups.items():
+        sel = torch.tensor(idx, dtype=torch.int64, device=n.device)
+        out[sel] = rle.runs_to_obb_corners(counts[sel].contiguous(), n[sel].contiguous(), size)
+    return out
+
+
 def _band_iou(units, n_iou, d_runs, g_runs, d_sizes, g_sizes, g_crowd, dilation_ratio, iou_domain):
     """the IoU blocks of the boundary bands, through the route the mask IoU took: the bit route gets its words from the band
     tables"""
@@ -113,9 +128,12 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     iou_type 'boundary'  is 'segm' with the IoU of every pair replaced by min(mask IoU, Boundary IoU): the
     bands M & ~erode(M, d) of detections and ground truths are made in the run domain (one rle.boundary_runs call per image
     size, d = rle.boundary_radius(size, dilation_ratio)) and their IoU goes through the same route as the mask IoU; areas,
-    crowds, matching and accumulation are segm's."""
+    crowds, matching and accumulation are segm's.
+    iou_type 'obb'  is 'segm' with the IoU of every pair replaced by the IoU of the masks' minimum-area
+    rectangles (rle.runs_to_obb_corners per image size, ops.obb_iou); areas (the mask areas), crowds, area ranges, matching
+    and accumulation are segm's, so the two APs differ by the IoU alone.  It reads the run tables (iou_domain is not used)."""
     import time
-    segm = iou_type in ('segm', 'boundary')
+    segm = iou_type in ('segm', 'boundary', 'obb')
     if iou_domain not in IOU_DOMAINS:
         raise ValueError(f'device_evaluate: iou_domain {iou_domain!r}: one of {IOU_DOMAINS}')
     t0 = time.perf_counter()
@@ -176,10 +194,11 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
     g_id = dev([g['id'] for g in gts], np.int64)
     t1 = time.perf_counter()
     d_segm, g_segm = ([x['segmentation'] for x in dts], [x['segmentation'] for x in gts]) if segm else ([], [])
-    if segm and iou_domain == 'auto':
+    by_mask = segm and iou_type != 'obb'                       # the IoU reads the masks themselves
+    if by_mask and iou_domain == 'auto':
         words = int(rle.word_offsets(_segm_sizes(d_segm))[-1] + rle.word_offsets(_segm_sizes(g_segm))[-1])
         iou_domain = 'runs' if 8 * words > BITS_BUDGET_BYTES else 'bits'
-    if segm and iou_domain == 'runs':
+    if by_mask and iou_domain == 'runs':
         d_runs, g_runs = _segm_runs(d_segm, device), _segm_runs(g_segm, device)
         d_pre = ops.run_prefix(*d_runs, check=False)           # rle_from_string's retry left no negative n
         info = {}
@@ -187,12 +206,18 @@ def device_evaluate(gt, dt, iou_type, img_ids, cat_ids, iou_thrs, max_dets, devi
         d_area = d_pre[1].to(torch.float64) if n_dt else dev([0.0], np.float64)
         if timings is not None:
             timings.update(pairs=info['pairs'], survivors=info['survivors'])
-    elif segm:
+    elif by_mask:
         db, dwo, da, dwr = rle.runs_to_bits(*_segm_runs(d_segm, device), _segm_sizes(d_segm))
         gb, gwo, ga, gwr = rle.runs_to_bits(*_segm_runs(g_segm, device), _segm_sizes(g_segm))
         iou = ops.coco_iou(units, n_iou, ops.COCO_IOU_SEGM, gt_crowd=g_crowd, dt_bits=db, gt_bits=gb, dt_woff=dwo,
                            gt_woff=gwo, dt_wrange=dwr, gt_wrange=gwr, dt_area=da, gt_area=ga)
         d_area = da.to(torch.float64) if n_dt else dev([0.0], np.float64)
+    elif segm:                                                 # 'obb': the rectangles of the run tables, segm's areas
+        iou_domain = 'runs'
+        d_runs, g_runs = _segm_runs(d_segm, device), _segm_runs(g_segm, device)
+        d_area = ops.run_prefix(*d_runs, check=False)[1].to(torch.float64) if n_dt else dev([0.0], np.float64)
+        iou = ops.obb_iou(units, n_iou, _obb_quads(d_runs, _segm_sizes(d_segm)), _obb_quads(g_runs, _segm_sizes(g_segm)),
+                          g_crowd[:n_gt])
     else:
         d_box = dev(np.asarray([d['bbox'] for d in dts], np.float64).reshape(-1, 4), np.float64)
         g_box = dev(np.asarray([g['bbox'] for g in gts], np.float64).reshape(-1, 4), np.float64)
@@ -333,7 +358,9 @@ GT_RASTERS = ('host', 'device')
 class CocoMetric:
     """mmdet CocoMetric (bbox / segm) -- `process`, `compute_metrics`, `evaluate(size)`, `dataset_meta`.  metric 'boundary'
     adds Boundary AP (LVIS iouType='boundary', boundary-iou-api): segm with min(mask IoU, Boundary IoU) per pair, band width
-    dilation_ratio * the image diagonal; keys boundary_mAP, boundary_mAP_50, ...."""
+    dilation_ratio * the image diagonal; keys boundary_mAP, boundary_mAP_50, ....  metric 'obb' adds
+    oriented-box AP: segm with the IoU of the masks' minimum-area rectangles per pair; keys obb_mAP, obb_mAP_50, ... (DESIGN
+    §14.17)."""
     default_prefix = 'coco'
 
     def __init__(self, ann_file=None, metric='bbox', classwise=False, proposal_nums=(100, 300, 1000), iou_thrs=None,
@@ -344,7 +371,7 @@ class CocoMetric:
         for m in self.metrics:
             if m in ('proposal', 'proposal_fast'):
                 raise NotImplementedError(f'CocoMetric: metric {m!r} is not implemented (bbox and segm are)')
-            if m not in ('bbox', 'segm', 'boundary'):
+            if m not in ('bbox', 'segm', 'boundary', 'obb'):
                 raise KeyError(f"metric should be one of 'bbox', 'segm', 'proposal', 'proposal_fast', but got {m}.")
         if file_client_args is not None:
             raise RuntimeError('The `file_client_args` is deprecated, please use `backend_args` instead')
@@ -529,7 +556,7 @@ class CocoMetric:
         names = {n: i for i, n in enumerate(STAT_NAMES)}
         gt_rle = None
         for metric in self.metrics:
-            masks = metric in ('segm', 'boundary')          # 'boundary' reads the segm results and ground-truth RLEs
+            masks = metric in ('segm', 'boundary', 'obb')   # 'boundary' and 'obb' read the segm results and ground-truth RLEs
             preds_m = result_lists.get('segm' if masks else metric)
             if preds_m is None:
                 raise KeyError(f'{metric} is not in results')

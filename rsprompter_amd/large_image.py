@@ -99,9 +99,9 @@ def _check_nms_cfg(nms_cfg):
     """-> (type, box IoU threshold, seam IoU threshold)"""
     cfg = dict(nms_cfg)
     typ = cfg.pop('type', 'nms')
-    if typ not in ('nms', 'seam_mask'):
-        raise NotImplementedError(f"merge nms type {typ!r}: only 'nms' (mmcv.ops.nms through batched_nms) and 'seam_mask' "
-                                  'are implemented')
+    if typ not in ('nms', 'seam_mask', 'nms_rotated'):
+        raise NotImplementedError(f"merge nms type {typ!r}: only 'nms' (mmcv.ops.nms through batched_nms), 'seam_mask' and "
+                                  "'nms_rotated' are implemented")
     if cfg.get('class_agnostic', False):
         raise NotImplementedError('class_agnostic merging is not implemented')
     return typ, float(cfg.get('iou_threshold', cfg.get('iou_thr', 0.5))), float(cfg.get('seam_iou_threshold', 0.5))
@@ -112,15 +112,40 @@ def merge_results_by_nms(results, offsets, src_image_shape, nms_cfg):
     DetDataSample with the metainfo of results[0] and the kept instances in batched_nms' order (descending score).
     nms_cfg = dict(type='seam_mask', iou_threshold=..., seam_iou_threshold=...): fragments of one object are first joined
     by their mask IoU at the tile seams (the tile size is the masks' shape, as in shift_predictions); the
-    sample then also carries `keep` and `members` like inference_large_image's."""
+    sample then also carries `keep` and `members` like inference_large_image's.
+    nms_cfg = dict(type='nms_rotated', iou_threshold=...): mmcv.ops.nms_rotated in place of the box NMS, on the minimum-area
+    rectangles of the patch masks moved to their place in the scene; every patch result needs masks, the
+    boxes stay axis-aligned."""
     typ, thr, seam_thr = _check_nms_cfg(nms_cfg)
     if typ == 'seam_mask':
         return _merge_results_by_seam_mask(results, offsets, src_image_shape, thr, seam_thr)
+    if typ == 'nms_rotated':
+        insts = [s.pred_instances for s in results]
+        if not insts or not all('masks' in p and p.masks is not None for p in insts):
+            raise ValueError("merge type 'nms_rotated' compares the masks' rectangles: every patch result needs "
+                             'pred_instances.masks')
     inst = shift_predictions(results, offsets, src_image_shape)
-    keep = ops.nms_flat(inst.bboxes, inst.scores, inst.labels, thr)
+    if typ == 'nms_rotated':
+        tile = torch.cat([p.masks for p in insts], 0).to(torch.bool)
+        off = _offsets_tensor(offsets, [len(p.scores) for p in insts], tile.device)
+        counts, n, _, _ = rle.encode_runs(tile)
+        keep = _rotated_keep(counts, n, tuple(tile.shape[1:]), off, inst.scores, inst.labels, thr)
+    else:
+        keep = ops.nms_flat(inst.bboxes, inst.scores, inst.labels, thr)
     merged = DetDataSample(metainfo=results[0].metainfo)
     merged.pred_instances = inst[keep]
     return merged
+
+
+def _rotated_keep(counts, n, tile_hw, offsets, scores, labels, thr):
+    """merge type 'nms_rotated' (DESIGN §14.17): the minimum-area rectangle of every tile instance from the tile run table,
+    moved by its tile origin in integers (offsets int32 [k, 2] = (ox, oy)), then ONE rotated NMS over the scene -> keep int64,
+    indices in kept order like ops.nms_flat's.  An instance with an empty mask has no rectangle: it suppresses nothing and
+    is kept."""
+    if int(n.shape[0]) == 0:
+        return torch.zeros((0,), dtype=torch.int64, device=n.device)
+    quad = rle.runs_to_obb_corners(counts, n, tile_hw, offsets.to(torch.int32).contiguous())
+    return ops.obb_nms(quad, scores.to(torch.float32), labels.to(torch.int32), thr)
 
 
 def _check_dense(k, H, W):
@@ -439,12 +464,25 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
     starting_pixels).  merge_nms_type='seam_mask' (DESIGN §14.6): instances of different tiles with one label whose masks
     agree inside the tiles' common rectangle (IoU there >= seam_iou_thr) are fragments of one object and come back as ONE
     instance -- mask = the union, score = the maximum, box = the hull of the members' boxes -- before the same box NMS;
-    `sample.keep` then holds the representatives (the best-scored member) and `sample.members` the index lists."""
+    `sample.keep` then holds the representatives (the best-scored member) and `sample.members` the index lists.
+    merge_nms_type='nms_rotated' (masks='rle' or 'polygons'): the merge suppresses by the IoU of the instances'
+    ORIENTED boxes -- the minimum-area rectangle of every tile instance, from the tile run tables the loop makes, moved by its
+    tile origin in integers -- with mmcv.ops.nms_rotated's rule at merge_iou_thr (two ships moored side by side at 45 degrees
+    overlap as axis-aligned boxes and not at all as oriented ones); everything downstream of `keep` is 'nms''s,
+    pred_instances.bboxes stay axis-aligned and oriented_boxes=True still reports the scene-table rectangles.  One rotated NMS
+    holds ops.OBB_NMS_MAX = 32 768 boxes (its suppression mask has n^2 / 8 bytes): a scene whose tiles return more instances
+    than that in all is refused with a ValueError when the merge starts, after the tiles have run -- raise the detector's score
+    threshold or lower its max_per_img, or merge with 'nms'."""
     from .apis import TestPipeline, get_test_pipeline_cfg
-    if merge_nms_type not in ('nms', 'seam_mask'):
-        raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms' and 'seam_mask' are implemented (soft_nms "
-                                  'and the other mmcv variants are not)')
+    if merge_nms_type not in ('nms', 'seam_mask', 'nms_rotated'):
+        raise NotImplementedError(f"merge_nms_type {merge_nms_type!r}: only 'nms', 'seam_mask' and 'nms_rotated' are "
+                                  'implemented (soft_nms and the other mmcv variants are not)')
     seam = merge_nms_type == 'seam_mask'
+    rotated = merge_nms_type == 'nms_rotated'
+    if rotated and masks == 'dense':                                    # refused before the first tile runs
+        raise ValueError("merge_nms_type='nms_rotated' reads the tile run tables: use masks='rle' or masks='polygons'")
+    if rotated and getattr(model, 'with_mask', True) is False:          # refused before the first tile runs
+        raise ValueError("merge_nms_type='nms_rotated' compares the masks' rectangles: the detector returns no masks")
     if masks not in ('rle', 'dense', 'polygons'):
         raise ValueError("masks must be 'rle', 'dense' or 'polygons'")
     poly = masks == 'polygons'
@@ -531,6 +569,8 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             del bm
         elif seam:
             raise ValueError("merge_nms_type='seam_mask' compares masks: the detector returned none")
+        elif rotated:
+            raise ValueError("merge_nms_type='nms_rotated' compares the masks' rectangles: the detector returned none")
         if return_patches:
             patch_samples.extend(res)
         del res, insts
@@ -555,14 +595,20 @@ def inference_large_image(model, img, patch_size=640, patch_overlap_ratio=0.25, 
             planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
             out.masks = _seam_rle(ac, an, origin, groups, (th, tw), (H, W), poly, obb, region, planar, buf)
     else:
-        keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
+        all_runs = None
+        if rotated:
+            all_runs = rle.concat_runs(runs, device=dev)                # every tile instance's runs: the rectangles read them
+            keep = _rotated_keep(all_runs, cat(run_n, torch.int32), (th, tw), off_all, all_scores, all_labels, merge_iou_thr)
+        else:
+            keep = ops.nms_flat(all_boxes, all_scores, all_labels, merge_iou_thr)
         out = InstanceData(bboxes=all_boxes[keep], scores=all_scores[keep], labels=all_labels[keep])
         koff = off_all[keep].to(torch.int32).contiguous()
         if masks == 'dense' and dense_tiles:
             _check_dense(keep.shape[0], H, W)
             out.masks = ops.paste_tiles(torch.cat(dense_tiles, 0)[keep], koff, (H, W))
         elif runs:
-            kc = rle.concat_runs(runs, keep)                            # only the kept instances' runs are gathered
+            # only the kept instances' runs are gathered ('nms_rotated' has the whole table already)
+            kc = rle.concat_runs(runs, keep) if all_runs is None else all_runs[keep].contiguous()
             planar = (flat_order, flat_ratio, out.scores, flat_out) if flat_order else None
             out.masks = _scene_rle(kc, torch.cat(run_n, 0)[keep].contiguous(), koff, (th, tw), (H, W), poly, obb, region, planar,
                                    buf)
@@ -692,8 +738,9 @@ def main(argv=None):
     ap.add_argument('--patch-size', type=int, default=640, help='The size of patches')
     ap.add_argument('--patch-overlap-ratio', type=float, default=0.25, help='Ratio of overlap between two patches')
     ap.add_argument('--merge-iou-thr', type=float, default=0.25, help='IoU threshould for merging results')
-    ap.add_argument('--merge-nms-type', default='nms', help="NMS type for merging results: 'nms', or 'seam_mask' to join "
-                    'the fragments of objects cut by tile seams first')
+    ap.add_argument('--merge-nms-type', default='nms', help="NMS type for merging results: 'nms', 'seam_mask' to join "
+                    "the fragments of objects cut by tile seams first, or 'nms_rotated' to suppress by the IoU of the "
+                    "instances' oriented boxes")
     ap.add_argument('--seam-iou-thr', type=float, default=0.5, help="mask IoU inside the tiles' overlap above which two "
                     "fragments are one object (--merge-nms-type seam_mask)")
     ap.add_argument('--batch-size', type=int, default=1, help='Batch size of patches')

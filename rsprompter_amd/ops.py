@@ -2128,6 +2128,98 @@ def hull_min_rect(hull_verts, hull_offs):
     return edge, q
 
 
+# ----------------------------------------------------------------------------- oriented-box comparison (csrc/obb_iou.hip)
+OBB_NMS_MAX = CONST['RSP_OBB_NMS_MAX']                        # boxes of one obb_nms: an n x ceil(n / 64) word suppression mask
+
+
+def _chk_quad(what, name, t, dev=None):
+    """a box array: float64 [n, 4, 2] on the HIP device -> (contiguous tensor, n)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 3 or tuple(t.shape[1:]) != (4, 2):
+        raise ValueError(f'{what}: {name} must be a float64 tensor [n, 4, 2] (four corners (x, y) per box)')
+    if not _is_device(t):
+        raise ValueError(f'{what}: {name} lives on the HIP device')
+    if dev is not None and t.device != dev:
+        raise ValueError(f'{what}: {name} must be on the device of the other arrays')
+    return t.contiguous(), int(t.shape[0])
+
+
+def _chk_vec(what, name, t, dtype, n, dev, cols=None):
+    shape = (n,) if cols is None else (n, cols)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+        raise ValueError(f'{what}: {name} must be a {dtype} tensor {list(shape)} on the device of the other arrays')
+    return t.contiguous()
+
+
+def obb_corners(edge, q, offsets=None):
+    """(edge int32 [k], q int64 [k, 6]) as hull_min_rect returns them, offsets int32 [k, 2] = (ox, oy) or None -> float64
+    [k, 4, 2] on the device: the corners of rle.obb_to_numpy(form='corners'), bit for bit, of the rectangles moved by their
+    offsets in integers first; NaN rows where edge is -1 (rsp_obb_corners).  No device-to-host read."""
+    lib = _lib.load()
+    if not isinstance(edge, torch.Tensor) or edge.dtype != torch.int32 or edge.dim() != 1:
+        raise ValueError('obb_corners: edge must be an int32 tensor [k]')
+    if not _is_device(edge):
+        raise ValueError('obb_corners: the rectangles live on the HIP device')
+    k, dev = int(edge.shape[0]), edge.device
+    q = _chk_vec('obb_corners', 'q', q, torch.int64, k, dev, 6)
+    if offsets is not None:
+        offsets = _chk_vec('obb_corners', 'offsets', offsets, torch.int32, k, dev, 2)
+    out = torch.empty((k, 4, 2), dtype=torch.float64, device=dev)
+    if k:
+        _lib.check(lib.rsp_obb_corners(edge.contiguous().data_ptr(), q.data_ptr(), _ptr(offsets), k, out.data_ptr(), _stream()),
+                   "rsp_obb_corners")
+    return out
+
+
+def obb_iou(units, n_iou, dt_quad, gt_quad, gt_crowd):
+    """IoU blocks of the units (`coco_units`, ascending in out0; nwords is not read) between oriented boxes dt_quad float64
+    [n_dt, 4, 2] and gt_quad float64 [n_gt, 4, 2], gt_crowd uint8 [n_gt] -> float64 [n_iou] (rsp_obb_iou):
+    inter / union in fp64, inter / area_dt for a crowd gt, the intersection clipped as a closed polygon.  A degenerate box
+    (a non-finite coordinate, zero area) has IoU 0.0 with everything.  No device-to-host read."""
+    lib = _lib.load()
+    dt_quad, n_dt = _chk_quad('obb_iou', 'dt_quad', dt_quad)
+    dev = dt_quad.device
+    gt_quad, n_gt = _chk_quad('obb_iou', 'gt_quad', gt_quad, dev)
+    gt_crowd = _chk_vec('obb_iou', 'gt_crowd', gt_crowd, torch.uint8, n_gt, dev)
+    if not isinstance(units, torch.Tensor) or units.dtype != torch.uint8 or units.dim() != 1 or units.device != dev or \
+            units.numel() % COCO_UNIT_BYTES:
+        raise ValueError('obb_iou: units must be the uint8 tensor of coco_units on the device of the boxes')
+    n_iou = int(n_iou)
+    if n_iou < 0:
+        raise ValueError('obb_iou: n_iou is negative')
+    iou = torch.zeros((max(n_iou, 1),), dtype=torch.float64, device=dev)
+    nu = units.numel() // COCO_UNIT_BYTES
+    if nu and n_iou:
+        _lib.check(lib.rsp_obb_iou(_units_ptr(units.contiguous()), nu, dt_quad.data_ptr(), n_dt, gt_quad.data_ptr(), n_gt,
+                                   gt_crowd.data_ptr(), iou.data_ptr(), n_iou, _stream()), "rsp_obb_iou")
+    return iou[:n_iou]
+
+
+def obb_nms(quad, scores, labels, iou_thr, class_agnostic=False):
+    """mmcv.ops.nms_rotated on flat device tensors (rsp_obb_nms): quad float64 [n, 4, 2], scores float32 [n],
+    labels int32 [n] -> keep int64 [m], indices into the inputs in kept order.  Order: score descending, original position
+    ascending; a box is suppressed by a kept box ahead of it with the same label (any label with class_agnostic) and
+    IoU > iou_thr (strict).  Degenerate boxes (NaN rows of empty masks) suppress nothing and are kept.  n <= OBB_NMS_MAX.
+    One host read (the number kept)."""
+    lib = _lib.load()
+    quad, n = _chk_quad('obb_nms', 'quad', quad)
+    dev = quad.device
+    scores = _chk_vec('obb_nms', 'scores', scores, torch.float32, n, dev)
+    labels = _chk_vec('obb_nms', 'labels', labels, torch.int32, n, dev)
+    iou_thr = float(iou_thr)
+    if not iou_thr >= 0.0:
+        raise ValueError(f'obb_nms: iou_thr = {iou_thr}; it must be >= 0')
+    if n > OBB_NMS_MAX:
+        raise ValueError(f'obb_nms: {n} boxes, rsp_obb_nms holds {OBB_NMS_MAX} at most (its suppression mask has n^2 / 8 bytes)')
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.int64, device=dev)
+    ws = torch.empty((int(lib.rsp_obb_nms_workspace_bytes(n)) // 8,), dtype=torch.int64, device=dev)
+    keep = torch.zeros((n,), dtype=torch.int32, device=dev)
+    cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.rsp_obb_nms(quad.data_ptr(), scores.data_ptr(), labels.data_ptr(), n, iou_thr, int(bool(class_agnostic)),
+                               ws.data_ptr(), keep.data_ptr(), cnt.data_ptr(), _stream()), "rsp_obb_nms")
+    return keep[:int(cnt.item())].to(torch.int64)
+
+
 # ----------------------------------------------------------------------------- run-domain components (csrc/run_components.hip)
 RUN_COMPONENTS_MAX_PIECES = CONST['RSP_RUN_COMPONENTS_MAX_PIECES']      # column pieces of one call: 32-bit piece indices
 RunComponents = collections.namedtuple('RunComponents', 'comp_offs piece_comp comp_area comp_box comp_first comp_inst pieces '

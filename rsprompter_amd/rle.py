@@ -272,6 +272,16 @@ def runs_to_obb(counts, n, size):
     return hull_verts, hull_offs, hull_area2, edge, q
 
 
+def runs_to_obb_corners(counts, n, size, offsets=None):
+    """run table of k masks on one size = (H, W) canvas -> float64 [k, 4, 2] ON THE DEVICE: the corners of every mask's
+    minimum-area rectangle, the doubles of obb_to_numpy(form='corners') bit for bit, NaN rows for empty masks
+    (ops.obb_corners).  offsets int32 [k, 2] = (ox, oy): each rectangle moved by its offset in integers first
+    (a tile's rectangle at its place in the scene: the rectangle of the shifted table).  The two device-to-host reads of
+    runs_to_hulls; the rectangles themselves stay on the device."""
+    edge, q = runs_to_obb(counts, n, size)[3:]
+    return ops.obb_corners(edge, q, offsets)
+
+
 OBB_FORMS = ('corners', 'xywha')
 
 
