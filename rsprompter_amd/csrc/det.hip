@@ -7,37 +7,13 @@
 //   BBoxHead._predict_by_feat_single + multiclass_nms      bbox_head.py:476-571, bbox_nms.py:12-105
 //   mmcv.ops.nms / batched_nms (un-vendored): stable score-descending order,
 //   suppress when IoU > thr (strict), boxes_for_nms = boxes + id * (max_coord + 1) in fp32.
-// Canonical tie order everywhere: score descending, original position ascending.
+// Canonical tie order everywhere: score descending, original position ascending.  The key that holds it, the sort
+// network and the greedy walk over the suppression mask are nms_core.h's, shared with query.hip and obb_iou.hip.
 // Compiled with -ffp-contract=off so that box / IoU arithmetic matches the scalar CPU code.
 #include "rsp_common.h"
+#include "nms_core.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t f2ord(float f) {  // order-preserving float -> uint
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-  const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  return __uint_as_float(u);
-}
-
-// In-LDS bitonic sort of n (power of two) 64-bit keys, DESCENDING, by all threads of the block.
-__device__ void bitonic_sort_desc(unsigned long long* keys, int n) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], b = keys[ixj];
-          const bool desc = ((i & k) == 0);
-          if (desc ? (a < b) : (a > b)) { keys[i] = b; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -87,9 +63,9 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
         raw[u] = base[(int64_t)pos * p.ld + (cc - pos * A)];
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) f(c + u * TK_THREADS, f2ord(sigmoidf_(raw[u])));
+      for (int u = 0; u < U; ++u) f(c + u * TK_THREADS, nms_f2ord(sigmoidf_(raw[u])));
     }
-    for (; c < n; c += TK_THREADS) f(c, f2ord(score_at(c)));
+    for (; c < n; c += TK_THREADS) f(c, nms_f2ord(score_at(c)));
   };
   if (n <= k) {  // nms_pre >= n: keep everything in natural order (rpn_head.py:205)
     for (int c = tid; c < n; c += TK_THREADS) { out_idx[c] = c; out_score[c] = score_at(c); }
@@ -130,7 +106,7 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
   scan_keys([&](int c, uint32_t u) {
     if (u > kth) {
       const unsigned int s = atomicAdd(&s_gt_slot, 1u);
-      skeys[s] = ((unsigned long long)u << 32) | (uint32_t)(0xffffffffu - (uint32_t)c);
+      skeys[s] = nms_key_ord(u, c);
     } else if (u == kth) {
       const unsigned int s = atomicAdd(&s_eq_cnt, 1u);
       if (s < (unsigned)TK_MAXK) eq_list[s] = c;
@@ -144,8 +120,7 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
       const int c = eq_list[i];
       int rank = 0;
       for (int j = 0; j < n_eq; ++j) rank += (eq_list[j] < c);
-      if (rank < n_eq_take)
-        skeys[n_gt + rank] = ((unsigned long long)kth << 32) | (uint32_t)(0xffffffffu - (uint32_t)c);
+      if (rank < n_eq_take) skeys[n_gt + rank] = nms_key_ord(kth, c);
     }
   } else {
     // many ties (saturated scores): take the first n_eq_take tied candidates in index order with a block-wide
@@ -159,7 +134,7 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
       const unsigned int taken = s_taken;
       if ((int)taken >= n_eq_take) break;
       const int c = c0 + tid;
-      const bool flag = c < n && f2ord(score_at(c)) == kth;
+      const bool flag = c < n && nms_f2ord(score_at(c)) == kth;
       const unsigned long long bal = __ballot(flag);
       if (lane == 0) wcnt[wave] = (unsigned int)__popcll(bal);
       __syncthreads();
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
       if (flag) {
         const unsigned int rank = off + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
         if ((int)rank < n_eq_take)
-          skeys[n_gt + rank] = ((unsigned long long)kth << 32) | (uint32_t)(0xffffffffu - (uint32_t)c);
+          skeys[n_gt + rank] = nms_key_ord(kth, c);
       }
       __syncthreads();
       if (tid == 0) s_taken = taken + total;
@@ -180,11 +155,11 @@ __global__ __launch_bounds__(TK_THREADS) void rpn_topk_kernel(const TopkP p) {
   }
   for (int i = k + tid; i < TK_MAXK; i += TK_THREADS) skeys[i] = 0ull;
   __syncthreads();
-  bitonic_sort_desc(skeys, TK_MAXK);
+  nms_sort_desc(skeys, TK_MAXK);
   for (int i = tid; i < k; i += TK_THREADS) {
     const unsigned long long key = skeys[i];
-    out_idx[i] = (int32_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
-    out_score[i] = ord2f((uint32_t)(key >> 32));
+    out_idx[i] = nms_key_pos(key);
+    out_score[i] = nms_key_score(key);
   }
   if (tid == 0) p.sel_cnt[b * p.num_levels + lvl] = k;
 }
@@ -384,7 +359,8 @@ __global__ __launch_bounds__(1024) void bbox_post_kernel(const BboxPostP p) {
 
 // ---------------------------------------------------------------------------------------
 // Batched NMS (three kernels): prepare (max coordinate, stable sort, id offsets) ->
-// 64x64 IoU bit-mask tiles -> sequential greedy reduction by one wave per image.
+// 64x64 IoU bit-mask tiles -> sequential greedy reduction by one wave per image
+// (nms_core.h: nms_walk_kernel reads mask, sorder, cnt, cap, words, max_out, keep and keep_cnt of NmsP).
 // ---------------------------------------------------------------------------------------
 struct NmsP {
   const float* boxes; const float* scores; const int32_t* ids; const int32_t* cnt;
@@ -421,16 +397,12 @@ __global__ __launch_bounds__(1024) void nms_prepare_kernel(const NmsP p) {
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mm = fmaxf(mm, red[w]);
     s_max = mm;
   }
-  for (int i = tid; i < p.nsort; i += blockDim.x) {
-    unsigned long long key = 0ull;
-    if (i < n) key = ((unsigned long long)f2ord(scores[i]) << 32) | (uint32_t)(0xffffffffu - (uint32_t)i);
-    skeys_dyn[i] = key;
-  }
+  for (int i = tid; i < p.nsort; i += blockDim.x) skeys_dyn[i] = i < n ? nms_key(scores[i], i) : 0ull;
   __syncthreads();
-  bitonic_sort_desc(skeys_dyn, p.nsort);
+  nms_sort_desc(skeys_dyn, p.nsort);
   const float off_unit = s_max + 1.0f;  // max_coordinate + 1
   for (int i = tid; i < n; i += blockDim.x) {
-    const int src = (int)(0xffffffffu - (uint32_t)(skeys_dyn[i] & 0xffffffffull));
+    const int src = nms_key_pos(skeys_dyn[i]);
     const float off = (float)ids[src] * off_unit;
     float* sb = p.sboxes + ((int64_t)b * p.cap + i) * 4;
     sb[0] = boxes[src * 4 + 0] + off; sb[1] = boxes[src * 4 + 1] + off;
@@ -473,90 +445,6 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const NmsP p) {
       p.mask[((int64_t)b * p.cap + ri) * p.words + cb] = bits;
     }
   }
-}
-
-// NMS_MAXW removal words per lane: 64 lanes * NMS_MAXW words * 64 bits candidates (4: 16384, the RSPrompter sizes; 32: 131072)
-constexpr int NMS_MAXW_LARGE = RSP_NMS_MAX_CANDIDATES / (64 * 64);
-template <int NMS_MAXW>
-__global__ __launch_bounds__(64) void nms_reduce_kernel(const NmsP p) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = p.cnt[b];
-  const int nblk = (n + 63) / 64;
-  unsigned long long remv[NMS_MAXW];
-#pragma unroll
-  for (int i = 0; i < NMS_MAXW; ++i) remv[i] = 0ull;
-  const unsigned long long* mask = p.mask + (int64_t)b * p.cap * p.words;
-  const int32_t* sorder = p.sorder + (int64_t)b * p.cap;
-  int32_t* keep = p.keep + (int64_t)b * p.max_out;
-  int kept = 0;
-  // A block's inputs -- its diagonal mask word and its sort-order entry per row -- are requested one block AHEAD, and the
-  // rows a block keeps are propagated four at a time with their loads in flight together: the walk is serial by nature
-  // (one wave per image), and round 5's counters showed it 81 % of its cycles waiting for one load after the other.
-  auto load_blk = [&](int bk, unsigned long long& dm, int& so) {
-    const int r = bk * 64 + lane;
-    const bool ok = bk < nblk && r < n;
-    dm = ok ? mask[(int64_t)r * p.words + bk] : 0ull;
-    so = ok ? sorder[r] : 0;
-  };
-  unsigned long long dmask;
-  int sord;
-  load_blk(0, dmask, sord);
-  for (int blk = 0; blk < nblk && kept < p.max_out; ++blk) {
-    unsigned long long dnext;
-    int snext;
-    load_blk(blk + 1, dnext, snext);
-    // removal word of this block lives in lane (blk & 63), slot (blk >> 6)
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int i = 0; i < NMS_MAXW; ++i) if (i == (blk >> 6)) mine = remv[i];
-    const unsigned int lo = __shfl((unsigned int)(mine & 0xffffffffull), blk & 63, 64);
-    const unsigned int hi = __shfl((unsigned int)(mine >> 32), blk & 63, 64);
-    unsigned long long cur = ((unsigned long long)hi << 32) | lo;
-    const int rows_here = min(64, n - blk * 64);
-    unsigned long long kept_bits = 0ull;
-    for (int t = 0; t < rows_here; ++t) {
-      const unsigned int dlo = __shfl((unsigned int)(dmask & 0xffffffffull), t, 64);
-      const unsigned int dhi = __shfl((unsigned int)(dmask >> 32), t, 64);
-      const int so = __shfl(sord, t, 64);
-      if (!((cur >> t) & 1ull)) {
-        if (kept < p.max_out) {
-          kept_bits |= (1ull << t);
-          if (lane == 0) keep[kept] = so;
-          ++kept;
-          cur |= ((unsigned long long)dhi << 32) | dlo;
-        }
-      }
-    }
-    if (kept >= p.max_out) break;
-    // propagate the kept rows of this block to all later words
-    constexpr int CH = NMS_MAXW <= 4 ? 4 : 1;              // rows per batch of loads (register budget of the large form)
-    unsigned long long kb = kept_bits;
-    while (kb) {
-      int tt[CH];
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        tt[j] = -1;
-        if (kb) { tt[j] = __builtin_ctzll(kb); kb &= kb - 1ull; }
-      }
-      unsigned long long v[CH][NMS_MAXW];
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        const unsigned long long* mrow = mask + (int64_t)(blk * 64 + max(tt[j], 0)) * p.words;
-#pragma unroll
-        for (int i = 0; i < NMS_MAXW; ++i) {
-          const int w = lane + 64 * i;
-          v[j][i] = (tt[j] >= 0 && w > blk && w < nblk) ? mrow[w] : 0ull;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int i = 0; i < NMS_MAXW; ++i) remv[i] |= v[j][i];
-    }
-    dmask = dnext;
-    sord = snext;
-  }
-  if (lane == 0) p.keep_cnt[b] = kept;
 }
 
 // out rows gathered from candidate arrays through keep lists
@@ -685,8 +573,7 @@ extern "C" int rsp_batched_nms(const float* boxes, const float* scores, const in
   hipLaunchKernelGGL(nms_prepare_kernel, dim3(B), dim3(1024), smem, s, p);
   const int gw = p.words < 256 ? p.words : 256;
   hipLaunchKernelGGL(nms_mask_kernel, dim3(gw, gw, B), dim3(64), 0, s, p);
-  if (p.words <= 64 * 4) hipLaunchKernelGGL(nms_reduce_kernel<4>, dim3(B), dim3(64), 0, s, p);
-  else hipLaunchKernelGGL(nms_reduce_kernel<NMS_MAXW_LARGE>, dim3(B), dim3(64), 0, s, p);
+  nms_walk_launch(p, B, s);
   hipLaunchKernelGGL(nms_gather_kernel, dim3(B), dim3(256), 0, s, boxes, scores, ids, src, cap, keep, keep_cnt,
                      max_out, out_boxes, out_scores, out_ids, out_src);
   RSP_CHECK_LAUNCH();

@@ -18,20 +18,23 @@
 // l at [vertex][l], so a wave's access is 64 consecutive doubles); a run-time indexed register array would go to scratch.
 // A lane touches its own slots only: no barrier.  No atomics, no inline assembly; the library is built with -ffp-contract=off.
 //
-// NMS.  obn_sort_kernel: one block, bitonic sort in memory of (ordered score << 32 | ~position), the canonical order of
-// det.hip: score descending, original position ascending.  obn_gather_kernel: boxes and labels in that order.
-// obn_pair_kernel: one wave per (row i, word w) of the n x ceil(n / 64) suppression mask, upper triangle only; lane l is box
-// j = 64 w + l, its bit is set iff j > i, the labels agree (or class_agnostic) and iou(i, j) > iou_thr (strict); the word is
-// the wave's ballot.  obn_walk_kernel: one wave walks the rows in order, `removed` in LDS.  A second launch gives the same
-// bits: every word that is read was written by exactly one wave of this launch.
+// NMS.  The key, the sort network and the greedy walk are nms_core.h's, shared with det.hip and query.hip.  obn_sort_kernel:
+// one block sorts the keys in memory into the canonical order, score descending, original position ascending.
+// obn_gather_kernel: boxes and labels in that order.  obn_pair_kernel: one wave per (row i, word w) of the n x ceil(n / 64)
+// suppression mask, upper triangle only; lane l is box j = 64 w + l, its bit is set iff j > i, the labels agree (or
+// class_agnostic) and iou(i, j) > iou_thr (strict); the word is the wave's ballot: the mask contract of nms_core.h.
+// nms_walk_kernel: the greedy walk of box NMS, one wave, launched by nms_walk_launch on one candidate set whose size the sort
+// kernel has written to the workspace.  A second launch gives the same bits: every word that is read was written by exactly
+// one wave of this launch.
 #include "rsp_common.h"
+#include "nms_core.h"
 
 namespace {
 
 constexpr int OI_THREADS = 128;
 constexpr int OI_MAXV = 8;
 constexpr int OBN_SORT_THREADS = 1024;
-constexpr int OBN_MAX_WORDS = RSP_OBB_NMS_MAX / 64;
+static_assert(RSP_OBB_NMS_MAX <= RSP_NMS_MAX_CANDIDATES, "the large form of nms_walk holds every rotated candidate set");
 
 struct OiBox {
   double x[4], y[4];
@@ -190,30 +193,12 @@ __global__ __launch_bounds__(OI_THREADS) void obb_iou_kernel(const RspCocoUnit* 
 }
 
 // ----------------------------------------------------------------------------------------------------------------- NMS
-__device__ __forceinline__ uint32_t obn_f2ord(float f) {  // order-preserving float -> uint (det.hip)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(OBN_SORT_THREADS) void obn_sort_kernel(const float* __restrict__ scores, int n, int nsort,
-                                                                    unsigned long long* keys) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < nsort; i += OBN_SORT_THREADS)
-    keys[i] = i < n ? ((unsigned long long)obn_f2ord(scores[i]) << 32) | (uint32_t)(0xffffffffu - (uint32_t)i) : 0ull;
+                                                                    unsigned long long* keys, int32_t* cnt) {
+  if (threadIdx.x == 0) *cnt = n;                          // the walk reads the size of its candidate set from memory
+  for (int i = threadIdx.x; i < nsort; i += OBN_SORT_THREADS) keys[i] = i < n ? nms_key(scores[i], i) : 0ull;
   __syncthreads();
-  for (int k = 2; k <= nsort; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < nsort; i += OBN_SORT_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], b = keys[ixj];
-          const bool desc = ((i & k) == 0);
-          if (desc ? (a < b) : (a > b)) { keys[i] = b; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  nms_sort_desc(keys, nsort);
 }
 
 __global__ __launch_bounds__(256) void obn_gather_kernel(const unsigned long long* __restrict__ keys,
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(256) void obn_gather_kernel(const unsigned long lon
                                                          int32_t* __restrict__ order) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  int src = (int)(0xffffffffu - (uint32_t)(keys[i] & 0xffffffffull));
+  int src = nms_key_pos(keys[i]);
   src = src < 0 ? 0 : (src >= n ? n - 1 : src);          // (a real key always is in range)
   order[i] = src;
   slab[i] = labels[src];
@@ -247,28 +232,8 @@ __global__ __launch_bounds__(OI_THREADS) void obn_pair_kernel(const double* __re
   if (row && lane == 0 && w >= (i >> 6)) mask[(int64_t)i * W + w] = word;    // every word the walk reads, the diagonal one too
 }
 
-__global__ __launch_bounds__(64) void obn_walk_kernel(const unsigned long long* __restrict__ mask,
-                                                      const int32_t* __restrict__ order, int n, int W,
-                                                      int32_t* __restrict__ keep, int32_t* __restrict__ keep_cnt) {
-  __shared__ unsigned long long removed[OBN_MAX_WORDS];
-  const int lane = threadIdx.x;
-  for (int w = lane; w < W && w < OBN_MAX_WORDS; w += 64) removed[w] = 0ull;
-  RSP_WAVE_LOCKSTEP();
-  int cnt = 0;
-  for (int i = 0; i < n; ++i) {
-    const int wi = i >> 6;
-    if (!((removed[wi] >> (i & 63)) & 1ull)) {                              // uniform over the wave: row i only adds bits j > i
-      if (lane == 0) keep[cnt] = order[i];
-      ++cnt;
-      for (int w = wi + lane; w < W; w += 64) removed[w] |= mask[(int64_t)i * W + w];
-    }
-    RSP_WAVE_LOCKSTEP();
-  }
-  if (lane == 0) *keep_cnt = cnt;
-}
-
 struct ObnLayout {
-  int64_t nsort, keys, squad, slab, order, mask, total;
+  int64_t nsort, keys, squad, slab, order, mask, cnt, total;
   int W;
 };
 inline bool obn_layout(int64_t n, ObnLayout* L) {
@@ -282,7 +247,8 @@ inline bool obn_layout(int64_t n, ObnLayout* L) {
   L->slab = L->squad + 64 * n;
   L->order = L->slab + n8;
   L->mask = L->order + n8;
-  L->total = L->mask + 8 * n * L->W + 256;
+  L->cnt = L->mask + 8 * n * L->W;                                           // one int32: n, for the walk
+  L->total = L->cnt + 8 + 256;
   return true;
 }
 
@@ -320,24 +286,27 @@ extern "C" int rsp_obb_nms(const double* quad, const float* scores, const int32_
   ObnLayout L;
   if (!obn_layout(n, &L) || !(iou_thr >= 0.0) || !keep_cnt) return RSP_EINVAL;
   if (n > 0 && (!quad || !scores || !labels || !workspace || !keep)) return RSP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0)                                                                // nothing to walk, and there may be no workspace
+    return hipMemsetAsync(keep_cnt, 0, sizeof(int32_t), s) == hipSuccess ? RSP_OK : RSP_ELAUNCH;
   char* ws = (char*)workspace;
   unsigned long long* keys = (unsigned long long*)(ws + L.keys);
   double* squad = (double*)(ws + L.squad);
   int32_t* slab = (int32_t*)(ws + L.slab);
   int32_t* order = (int32_t*)(ws + L.order);
   unsigned long long* mask = (unsigned long long*)(ws + L.mask);
-  if (n > 0) {
-    hipLaunchKernelGGL(obn_sort_kernel, dim3(1), dim3(OBN_SORT_THREADS), 0, (hipStream_t)stream, scores, (int)n, (int)L.nsort,
-                       keys);
-    RSP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(obn_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys, quad, labels,
-                       (int)n, squad, slab, order);
-    RSP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(obn_pair_kernel, dim3((unsigned)L.W, (unsigned)((n + OI_THREADS / 64 - 1) / (OI_THREADS / 64))),
-                       dim3(OI_THREADS), 0, (hipStream_t)stream, squad, slab, (int)n, L.W, iou_thr, (int)class_agnostic, mask);
-    RSP_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(obn_walk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, mask, order, (int)n, L.W, keep, keep_cnt);
+  int32_t* cnt = (int32_t*)(ws + L.cnt);
+  hipLaunchKernelGGL(obn_sort_kernel, dim3(1), dim3(OBN_SORT_THREADS), 0, s, scores, (int)n, (int)L.nsort, keys, cnt);
+  RSP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(obn_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, quad, labels, (int)n, squad, slab,
+                     order);
+  RSP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(obn_pair_kernel, dim3((unsigned)L.W, (unsigned)((n + OI_THREADS / 64 - 1) / (OI_THREADS / 64))),
+                     dim3(OI_THREADS), 0, s, squad, slab, (int)n, L.W, iou_thr, (int)class_agnostic, mask);
+  RSP_CHECK_LAUNCH();
+  // one candidate set of n boxes, n rows to a set, every kept box put out
+  const NmsWalkP p = {mask, order, cnt, (int)n, L.W, (int)n, keep, keep_cnt};
+  nms_walk_launch(p, 1, s);
   RSP_CHECK_LAUNCH();
   return RSP_OK;
 }

@@ -8,6 +8,7 @@
 // All HBM / latency bound; fp32 arithmetic.
 #include "rsp_common.h"
 #include "mask_field.h"
+#include "nms_core.h"
 
 namespace {
 
@@ -301,11 +302,6 @@ __global__ __launch_bounds__(256) void mask_embed_kernel(const MaskEmbP p) {
 }
 
 // ------------------------------------------------------------------------------------ fusion head
-__device__ __forceinline__ uint32_t f2ord_(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // per image: softmax over nc+1 logits, drop the background column, top-k of the Nq*nc scores with
 // (score desc, flat index asc) ties (maskformer_fusion_head.py:149-162)
 __global__ __launch_bounds__(1024) void query_topk_kernel(const float* __restrict__ cls, int Nq, int nc, int k, int nsort,
@@ -323,29 +319,16 @@ __global__ __launch_bounds__(1024) void query_topk_kernel(const float* __restric
       float s = 0.f;
       for (int j = 0; j <= nc; ++j) s += expf(row[j] - m);
       const float sc = expf(row[c] - m) / s;
-      key = ((unsigned long long)f2ord_(sc) << 32) | (uint32_t)(0xffffffffu - (uint32_t)i);
+      key = nms_key(sc, i);
     }
     keys[i] = key;
   }
   __syncthreads();
-  for (int kk = 2; kk <= nsort; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < nsort; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], c = keys[ixj];
-          const bool desc = ((i & kk) == 0);
-          if (desc ? (a < c) : (a > c)) { keys[i] = c; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  nms_sort_desc(keys, nsort);
   for (int i = threadIdx.x; i < k; i += blockDim.x) {
     const unsigned long long key = keys[i];
-    const uint32_t o = (uint32_t)(key >> 32);
-    const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    out_score[(int64_t)b * k + i] = __uint_as_float(u);
-    out_flat[(int64_t)b * k + i] = (int32_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
+    out_score[(int64_t)b * k + i] = nms_key_score(key);
+    out_flat[(int64_t)b * k + i] = nms_key_pos(key);
   }
 }
 

@@ -319,6 +319,63 @@ def check_nms_sizes(ops, dev, sizes=NMS_SIZES):
     return kept
 
 
+# Sizes the exact reference cannot reach (it is quadratic in fractions): a construction whose keep lists are known in O(n).
+# n = 4097 is 65 mask words, a second removal word per lane of the walk; n = 16449 is 258 > 256 words, the large form
+# (csrc/nms_core.h).
+NMS_GRID_SIZES = (4097, 16449)
+NMS_GRID_TAIL = 100
+
+
+@functools.lru_cache(maxsize=None)
+def nms_grid_case(n, m=None):
+    """(quads, scores, labels, keep class-aware, keep class-agnostic).  Positions 0 .. m - 1 (the head, m = n - 100) are the
+    same box in distinct cells of a grid of pitch 100, position i >= m (the tail) is the box of i - m again: two boxes are
+    identical or their bounds are disjoint, so every IoU is 0 or 1.  Scores do not increase with the position, in plateaus of
+    130 equal values (ties across mask-word edges); a tail box scores below its twin.  Labels are i % 3 in the head; in the
+    tail an even i has its twin's label and is suppressed, an odd i another one and is kept unless class_agnostic.  More
+    than half of all boxes are kept, so every block of the walk propagates, and the last words of the mask hold kept boxes
+    beside boxes that a box of the first two words suppresses."""
+    m = n - NMS_GRID_TAIL if m is None else m
+    assert NMS_GRID_TAIL <= m < n <= 2 * m
+    head = np.stack([box(100.0 * (k % 128) + 50.0, 100.0 * (k // 128) + 50.0, 40, 16, 0.3) for k in range(m)])
+    pos = np.arange(n)
+    q = np.concatenate([head, head[:n - m]])
+    scores = (1.0 - (pos // 130) / 256.0).astype(np.float32)
+    assert n // 130 < 256 and m > 130                       # positive, exact in float32; a twin is on a lower plateau
+    labels = (pos % 3).astype(np.int32)
+    tail = pos[m:]
+    labels[m:] = np.where(tail % 2 == 0, labels[tail - m], (labels[tail - m] + 1) % 3)
+    aware = list(range(m)) + [int(i) for i in tail if i % 2 == 1]
+    return q, scores, labels, aware, list(range(m))
+
+
+def nms_grid_permuted(n, m=None, seed=5):
+    """the same case with one fixed permutation applied to the inputs, so that the sort does the ordering: new position j
+    holds old position perm[j]; the kept set is mapped through it and put into the canonical order of the new inputs"""
+    q, s, lab, aware, agnostic = nms_grid_case(n, m)
+    perm = np.random.default_rng(seed).permutation(n)
+    inv = np.empty(n, np.int64)
+    inv[perm] = np.arange(n)
+    s2 = s[perm]
+
+    def mapped(keep):
+        new = inv[np.asarray(keep, np.int64)]
+        return [int(j) for j in new[np.lexsort((new, -s2[new].astype(np.float64)))]]
+    return q[perm], s2, lab[perm], mapped(aware), mapped(agnostic)
+
+
+def check_nms_grid(ops, dev, n):
+    """both input orders, both thresholds, both label modes against the known keep lists"""
+    for q, s, lab, aware, agnostic in (nms_grid_case(n), nms_grid_permuted(n)):
+        assert 2 * len(agnostic) > n and len(aware) == len(agnostic) + NMS_GRID_TAIL // 2
+        for thr in NMS_THRS:
+            got = run_nms(ops, dev, q, s, lab, thr, False)
+            assert got == aware, (n, thr, len(got), len(aware), [(a, b) for a, b in zip(got, aware) if a != b][:5])
+            got = run_nms(ops, dev, q, s, lab, thr, True)
+            assert got == agnostic, (n, thr, len(got), len(agnostic), [(a, b) for a, b in zip(got, agnostic) if a != b][:5])
+    return len(aware), len(agnostic)
+
+
 def check_nms_rules(ops, dev):
     S = sq(0, 0, 4, 4)
     one = np.zeros(8, np.int32)

@@ -49,6 +49,14 @@ def test_nms_sizes_across_mask_word_edges(dev):
     print(cases.check_nms_sizes(ops, dev))
 
 
+@pytest.mark.parametrize('n', cases.NMS_GRID_SIZES)
+def test_nms_grid_beyond_one_removal_word_a_lane(dev, n):
+    """65 and 258 mask words: a second removal word per lane, and the large form of the walk (the keep lists are the
+    construction's, pinned to the exact reference at n = 260 by tests/test_obb_iou_cpu.py)"""
+    from rsprompter_amd import ops
+    print(n, cases.check_nms_grid(ops, dev, n))
+
+
 def test_nms_rules(dev):
     from rsprompter_amd import ops
     cases.check_nms_rules(ops, dev)

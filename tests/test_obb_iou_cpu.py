@@ -75,6 +75,19 @@ def test_no_exact_iou_of_a_decision_case_is_near_a_threshold():
     assert cases.BOUND < cases.DECISION_MARGIN / 100
 
 
+def test_the_grid_construction_is_the_reference_nms():
+    """the keep lists that the sizes beyond the exact reference's reach are compared with (cases.nms_grid_case) are the
+    reference's on exact IoUs where it can be run: n = 260, m = 160, both input orders; no product code runs here"""
+    for q, s, lab, aware, agnostic in (cases.nms_grid_case(260, 160), cases.nms_grid_permuted(260, 160)):
+        iou = ref.exact_iou_matrix(q, q)
+        assert all(e is ref.ZERO or e == 1 for row in iou for e in row)           # nothing is near a threshold
+        assert sum(1 for row in iou for e in row if e == 1) == 260 + 2 * cases.NMS_GRID_TAIL
+        for thr in cases.NMS_THRS:
+            assert ref.nms(q, s, lab, thr, False, iou) == aware
+            assert ref.nms(q, s, lab, thr, True, iou) == agnostic
+        assert len(aware) == 210 and len(agnostic) == 160 and aware != agnostic
+
+
 # ------------------------------------------------------------------------------------------------------------ kernels
 def test_exact_answers(emu):
     assert cases.check_exact_table(emu, CPU) > 100
@@ -96,6 +109,14 @@ def test_corners_are_bit_equal_with_obb_to_numpy(emu):
 
 def test_nms_sizes_across_mask_word_edges(emu):
     print(cases.check_nms_sizes(emu, CPU, EMU_NMS_SIZES))
+
+
+def test_nms_grid_with_a_second_removal_word_a_lane(emu):
+    """n = 4097, 65 mask words.  The eight runs of cases.check_nms_grid take 21 s on the emulator against 3.3 s of this
+    file's slowest test, so they are the device tier's (tests/test_gpu_obb_iou.py, with n = 16449); here one of them, 2.6 s:
+    the permuted inputs, class-aware, so that the sort orders and the tail is kept in part"""
+    q, s, lab, aware, _ = cases.nms_grid_permuted(cases.NMS_GRID_SIZES[0])
+    assert cases.run_nms(emu, CPU, q, s, lab, cases.NMS_THRS[-1], False) == aware
 
 
 def test_nms_rules(emu):
